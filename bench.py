@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: lit Mpixels/s of the fused deferred-lighting + GI pass at 4K on MI355X (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR] [--full]
 
 A step = one Lighting pass (default workload: sun CSM + LPV GI gather + AO + emissive + sky, SURVEY.md §8 a0-a3,a6) over one
 synthetic 3840x2160 G-buffer already resident in HBM.  N > 1 (launched by torch.distributed.run, one rank per GPU): the
@@ -14,9 +14,13 @@ chain of androidrenderer_amd/chain.py: every rank shades its rows (+ halo), redu
 exchange the quarter-resolution mip 1, build the smaller mips redundantly, composite their rows of the final image and exchange the
 RGBA8 rows — in reversed rank order, because the composite samples the scene upside down.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including `roofline` (dominant kernel vs HBM peak,
-kernel time measured with HIP events on the launch stream) and, at N = 1, `cpu_baseline` (the CPU oracle, OpenMP, -O3
--march=native, median of 5 repetitions of a bounded row band of the same frame).
+Prints ONE JSON line on rank 0 including `roofline` (dominant kernel vs HBM peak, kernel time measured with HIP events on the
+launch stream).  A plain run sets up, warms up, times the K steps and prints that line: nothing else.  `--full` adds everything else the
+benchmark measures and checks, each outside the timed region: at N = 1 `cpu_baseline` (the CPU oracle, OpenMP, -O3 -march=native,
+median of 5 repetitions of a bounded row band of the same frame), the same loop over 200 steps, the LPV pass with its gather copy
+rebuilt every step, the light statistics, the per-part timings of the LPV frame and the RTGI generator; at N > 1 the same workload
+unsharded on one GPU, the pre-flight and final checks of the sharded frames against it, and the exchange alone.
+`--dump-outputs DIR` writes what the timed path computed in its last step (see dump_outputs) after the timed steps.
 """
 import argparse
 import ctypes as C
@@ -233,9 +237,15 @@ def parse_args(argv=None):
                     "kernel is launched before the timed passes (diagnostic: profiles/README.md \"8K under --pmc\" — the fault it was added for turned out to be "
                     "the light statistics' 16,384 outstanding dispatches, not the input synthesis)")
     ap.add_argument("--no-light-stats", action="store_true", help="light workloads: skip the lights-per-tile / per-pixel statistics (torch kernels on full-frame tensors)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU-oracle baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target duration of the CPU-oracle sample")
+    ap.add_argument("--full", action="store_true", help="besides the headline, everything else the benchmark measures and checks (module docstring); "
+                    "a plain run does only what its headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last step "
+                    "as DIR/<name>.npy (float32; a fixed, seeded sample of the pixels when the image is larger than the budget)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.repack_lpv:
         args.lpv_copy, args.probe_copy = "rebuild", "rebuild"
     return args
@@ -514,7 +524,8 @@ def setup_lpv_frame(R):
         propagate()
     fr.lpv_generation = _abi.GENERATION_TRACKED
     parts = {}
-    for name, fn in (("clear", clear), ("rsm_render", render_rsm), ("extract_inject_x4", inject), (f"propagate_x{steps}", propagate), ("upkeep", upkeep)):
+    timed_parts = (("clear", clear), ("rsm_render", render_rsm), ("extract_inject_x4", inject), (f"propagate_x{steps}", propagate), ("upkeep", upkeep))
+    for name, fn in timed_parts if R.args.full else ():
         for _ in range(3):
             upkeep()
         torch.cuda.synchronize()
@@ -533,7 +544,8 @@ def setup_lpv_frame(R):
     R.keep_lpv_frame = (geo, rsm_t, scratch, vpls, count, vd, sd, rsm)
     R.lpv_frame = dict(parts, propagation_steps=steps, triangles=int(mesh.atrium(R.args.atrium_subdiv).arrays()["indices"].size // 3) if False else None,
                        rsm="4 cascades x 128 x 128", non_zero_cells_rgb=lit_cells,
-                       note="each part timed on its own (20 calls back to back) before the timed region; `upkeep` = one frame's clear + RSM + inject + propagate")
+                       note="--full: each part timed on its own (20 calls back to back) before the timed region; `upkeep` = one frame's clear + RSM + inject + "
+                            "propagate")
     R.lpv_frame.pop("triangles")
 
 
@@ -601,9 +613,9 @@ def setup_traced(R):
     e[5].record()
     ctx.probe_update(atlases, pt.trace_results, probe_ids.data_ptr(), n_probes)
     e[6].record()
-    # (not part of this workload's frame — the RTGI mode's generator, one GI ray per pixel — timed once for the record)
-    ctx.rtgi_trace(fr.view.gpu_data, fr.sun.constants, sky_luts, planes_rt[0], planes_rt[1], planes_rt[2],
-                   images.plane(rtgi_rb, _abi.FORMAT_R16G16B16A16_SFLOAT), images.plane(rtgi_ri, _abi.FORMAT_R16G16B16A16_SFLOAT))
+    if args.full:  # (not part of this workload's frame — the RTGI mode's generator, one GI ray per pixel — timed once for the record)
+        ctx.rtgi_trace(fr.view.gpu_data, fr.sun.constants, sky_luts, planes_rt[0], planes_rt[1], planes_rt[2],
+                       images.plane(rtgi_rb, _abi.FORMAT_R16G16B16A16_SFLOAT), images.plane(rtgi_ri, _abi.FORMAT_R16G16B16A16_SFLOAT))
     e[7].record()
     torch.cuda.synchronize()
     tr_dist = trace_results.view(torch.float16)[..., 3].float()
@@ -611,14 +623,14 @@ def setup_traced(R):
     R.traced = {"triangles": rt_stats[0], "levels": rt_stats[2], "gi_bounces": args.rt_bounces, "rt_build_ms": round(e[0].elapsed_time(e[1]), 4), "rtao_ms": round(e[2].elapsed_time(e[3]), 4),
                 "sun_shadow_mask_ms": round(e[3].elapsed_time(e[4]), 4), "probe_trace_ms": round(e[4].elapsed_time(e[5]), 4),
                 "probe_update_ms": round(e[5].elapsed_time(e[6]), 4), "probes_per_frame": n_probes,
-                "rtgi_trace_ms_not_in_frame": round(e[6].elapsed_time(e[7]), 4),
+                "rtgi_trace_ms_not_in_frame": round(e[6].elapsed_time(e[7]), 4) if args.full else None,
                 "shadow_samples": float(fr.sun.constants.num_shadow_samples), "ao_unoccluded_fraction": round(float((d_arr["ao"] == 1).float().mean()), 4),
                 "mask_lit_fraction": round(float(d_arr["shadow_mask"].mean()), 4),
                 "mask_pixels_0_between_1": [round(float((d_arr["shadow_mask"] == 0).float().mean()), 4),
                                             round(float(((d_arr["shadow_mask"] > 0) & (d_arr["shadow_mask"] < 1)).float().mean()), 4),
                                             round(float((d_arr["shadow_mask"] == 1).float().mean()), 4)],
                 "probe_rays_hit_front_back_miss": [round(float((tr_dist > 0).float().mean()), 4), round(float((tr_dist < 0).float().mean()), 4)],
-                "rtgi_rays_hit_fraction": round(float((rtgi_rb.view(torch.float16)[..., 3].float() != 0).float().mean()), 4)}
+                "rtgi_rays_hit_fraction": round(float((rtgi_rb.view(torch.float16)[..., 3].float() != 0).float().mean()), 4) if args.full else None}
 
 
 def frame_maintenance(R):
@@ -777,7 +789,7 @@ def time_unsharded(R):
     torch, ctx, fr, d_arr, W, H = R.torch, R.ctx, R.fr, R.d_arr, R.W, R.H
     R.beat("unsharded reference")
     R.single_gpu = R.ref_image = None
-    if not (R.world > 1 or R.args.force_gather):
+    if not (R.world > 1 or R.args.force_gather) or not R.args.full:  # (no reference image: preflight() and verify() then check nothing)
         return
     if R.chain:
         ref = chain_mod.ShardedChain(ctx, fr, d_arr, 0, 1, tonemap_flags=R.tm_flags)
@@ -960,7 +972,7 @@ def time_longer_run(R):
     driver's K steps, the same loop over at least 200 steps (GPU time between two events, after the timed region): what the K-step number is good
     for can be read off the two."""
     torch = R.torch
-    if not (R.world == 1 and not R.exchange and R.args.steps < 200):
+    if not (R.args.full and R.world == 1 and not R.exchange and R.args.steps < 200):
         return None
     n = 200
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -982,7 +994,7 @@ def time_exchange_only(R):
     compute beside them — what the frame rate cannot exceed whatever the kernels do (the sharded loop overlaps them with compute: frame time =
     max(compute, exchange)).  EVERY rank runs it (the gathers are collective), the same fixed number of times; outside the timed region.
     Returns the report's dict or None."""
-    if not (R.world > 1 and R.pipelined and R.gather and R.lib_gather and R.pc is not None and not R.failure):
+    if not (R.args.full and R.world > 1 and R.pipelined and R.gather and R.lib_gather and R.pc is not None and not R.failure):
         return None
     torch, ctx = R.torch, R.ctx
     sc = R.pc.sets[0]
@@ -1022,7 +1034,7 @@ def time_with_rebuild(R):
     frame pays when its volumes are rewritten by a pass that is not the library's.  Outside the timed region; returns the report's dict or None."""
     from androidrenderer_amd import _abi
     torch, ctx, fr, d_arr = R.torch, R.ctx, R.fr, R.d_arr
-    if not (R.world == 1 and R.gi_kind == _abi.GI_LPV and not R.chain and not R.exchange and R.args.lpv_copy == "propagate"):
+    if not (R.args.full and R.world == 1 and R.gi_kind == _abi.GI_LPV and not R.chain and not R.exchange and R.args.lpv_copy == "propagate"):
         return None
     saved = fr.lpv_generation
     fr.lpv_generation = 0
@@ -1046,6 +1058,35 @@ def time_with_rebuild(R):
     return {"ms_per_step": round(ms, 5), "value": round(R.W * R.H / (ms * 1e-3) / 1e6, 1), "unit": "Mpixels/s", "steps": n,
             "gather_copy_rebuilds_during_it": ctx.copy_rebuilds()[0] - before,
             "note": "the same pass with lpv_generation 0 (k_lpv_pack + the pass in every step), GPU time between two events, after the timed region"}
+
+
+DUMP_MAX_PIXELS = 1 << 21  # 16 bytes per RGBA pixel in float32: 32 MiB per image at most
+DUMP_SEED = 20261016
+
+
+def dump_outputs(R):
+    """--dump-outputs DIR, rank 0, right after the timed region: the image the timed path's last step handed its caller, as float32 RGBA —
+    `lit.npy` (the Lighting pass's R16G16B16A16_SFLOAT target, widened exactly) or, for chain workloads, `final_image.npy` (the R8G8B8A8 codes
+    of the composite, as numbers 0..255).  An image of at most DUMP_MAX_PIXELS pixels is written whole, shaped (H, W, 4); a larger one as the
+    pixels at a fixed set of flat indices (row * W + column), shaped (DUMP_MAX_PIXELS, 4): the first DUMP_MAX_PIXELS of a permutation of all
+    the pixels drawn by numpy's default generator seeded with DUMP_SEED, sorted.  The inputs are seeded, so two runs with the same arguments
+    (and two builds of the project) can be compared file for file."""
+    torch, args = R.torch, R.args
+    if R.pc is not None:
+        img, name = R.pc.image(R.pc.submitted - 1), "final_image"
+    elif R.chain:
+        img, name = R.sc.out, "final_image"
+    else:
+        img, name = R.bufs[(args.steps - 1) % len(R.bufs)]["lit"].view(torch.float16), "lit"
+    img = img.float()
+    h, w, c = img.shape
+    if h * w > DUMP_MAX_PIXELS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).permutation(h * w)[:DUMP_MAX_PIXELS])
+        img = img.reshape(h * w, c)[torch.from_numpy(idx).to(img.device)]
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    path = os.path.join(args.dump_outputs, name + ".npy")
+    np.save(path, np.ascontiguousarray(img.cpu().numpy(), dtype=np.float32))
+    print(f"[bench] wrote {path} {tuple(img.shape)} float32", file=sys.stderr, flush=True)
 
 
 def metric_name(workload, chain, W, H):
@@ -1152,9 +1193,9 @@ def report(R):
     if R.failure:
         out["error"] = R.failure
         out["measured_but_invalid_Mpixels_per_s"] = round(value, 1)
-    if R.n_lights and not args.no_light_stats:
+    if args.full and R.n_lights and not args.no_light_stats:
         out["config"].update(light_stats(R.torch, R.fr, R.d_arr, R.lights, R.dev))
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(R.fr, args.cpu_seconds)
     if R.saved_stdout is not None:
         sys.stdout.flush()
@@ -1185,6 +1226,8 @@ def main(argv=None):
     time_unsharded(R)
     preflight(R)
     run_timed(R)
+    if args.dump_outputs and R.rank == 0:
+        dump_outputs(R)
     verify(R)
     R.exchange_only = time_exchange_only(R)
     R.longer_run = time_longer_run(R) if R.rank == 0 and not R.failure else None

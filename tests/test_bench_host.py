@@ -91,3 +91,50 @@ def test_a_launcher_with_another_world_size_is_refused():
     out = subprocess.run([sys.executable, os.path.join(bench.ROOT, "bench.py"), "--gpus", "4"], env=dict(os.environ, WORLD_SIZE="2", RANK="0"),
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert out.returncode != 0 and "WORLD_SIZE is 2" in out.stderr
+
+
+def test_a_plain_run_is_lean_and_full_is_an_option():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    b = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert b.full is True and b.dump_outputs == "out"
+    import pytest
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def _dump(tmp_path, img, chain=False, steps=5):
+    import torch
+    R = bench.Run()
+    R.torch, R.pc, R.chain = torch, None, chain
+    R.args = bench.parse_args(["--steps", str(steps), "--dump-outputs", str(tmp_path)])
+    if chain:
+        R.sc = type("Chain", (), {"out": img})()
+    else:
+        R.bufs = [{"lit": torch.zeros_like(img)}, {"lit": img}]  # two lit targets, used in turn: step i wrote bufs[i % 2]
+    bench.dump_outputs(R)
+    import numpy as np
+    return np.load(tmp_path / ("final_image.npy" if chain else "lit.npy"))
+
+
+def test_dump_outputs_writes_the_last_steps_image_as_float32(tmp_path, monkeypatch):
+    """--dump-outputs: the Lighting target of the last timed step widened from fp16 exactly (whole when small, a seeded sample of pixels when large),
+    the chain's RGBA8 codes as numbers"""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(3)
+    h = rng.standard_normal((6, 10, 4)).astype(np.float16)
+    h[0, 0, 0], h[1, 1, 1] = np.inf, np.nan
+    lit = torch.from_numpy(h.view(np.int16).copy())
+    whole = _dump(tmp_path / "a", lit, steps=6)  # step 5 wrote bufs[1]
+    assert whole.dtype == np.float32 and whole.shape == (6, 10, 4)
+    assert np.array_equal(whole.view(np.uint32), h.astype(np.float32).view(np.uint32))
+    assert not _dump(tmp_path / "b", lit, steps=5).any()  # step 4 wrote bufs[0]
+    monkeypatch.setattr(bench, "DUMP_MAX_PIXELS", 16)
+    s1, s2 = _dump(tmp_path / "c", lit, steps=6), _dump(tmp_path / "d", lit, steps=6)
+    assert s1.shape == (16, 4) and np.array_equal(s1.view(np.uint32), s2.view(np.uint32))
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).permutation(60)[:16])
+    assert np.array_equal(s1.view(np.uint32), h.astype(np.float32).reshape(60, 4)[idx].view(np.uint32))
+    codes = torch.from_numpy(rng.integers(0, 256, (5, 3, 4), dtype=np.uint8))
+    fin = _dump(tmp_path / "e", codes, chain=True)
+    assert fin.dtype == np.float32 and np.array_equal(fin, codes.numpy().astype(np.float32))

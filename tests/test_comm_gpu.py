@@ -207,7 +207,7 @@ def test_bench_rehearsal_of_two_ranks_verifies_its_frames(tmp_path, fail_preflig
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **({"SAH_BENCH_FAIL_PREFLIGHT": "1"} if fail_preflight else {}))
     port += 7 if fail_preflight else 0
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--rehearse-on-one-gpu"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--rehearse-on-one-gpu", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -229,7 +229,7 @@ def test_bench_reports_a_failed_verification_as_a_failure(tmp_path):
     port = 29950 + (os.getpid() % 40)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", SAH_BENCH_FAIL_VERIFY="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--rehearse-on-one-gpu", "--ramp-ms", "0"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--rehearse-on-one-gpu", "--ramp-ms", "0", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode != 0, out.stdout[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -244,7 +244,7 @@ def test_bench_gpus_2_without_a_launcher_starts_its_own_ranks(tmp_path):
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--rehearse-on-one-gpu", "--ramp-ms", "0"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--rehearse-on-one-gpu", "--ramp-ms", "0", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
