@@ -241,6 +241,8 @@ void sah_destroy(sah_ctx* ctx) {
     if (ctx->state) (void)hipFree(ctx->state);
     if (ctx->list) (void)hipFree(ctx->list);
     if (ctx->lpv_packed) (void)hipFree(ctx->lpv_packed);
+    if (ctx->gv_keys) (void)hipFree(ctx->gv_keys);
+    if (ctx->gv_factors) (void)hipFree(ctx->gv_factors);
     if (ctx->irr32) (void)hipFree(ctx->irr32);
     if (ctx->colx_table) (void)hipFree(ctx->colx_table);
     if (ctx->tm_thresholds) (void)hipFree(ctx->tm_thresholds);

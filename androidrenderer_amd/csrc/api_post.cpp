@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "../../include/sah_hip.h"
+#include "../../include/sah_lpv_gv.h"
 #include "ctx.hpp"
 #include "post_args.hpp"
 
@@ -24,7 +25,13 @@ hipError_t launch_tonemap(const TonemapArgs& t, hipStream_t st);
 hipError_t launch_tonemap_tol(const TonemapArgs& t, hipStream_t st);
 hipError_t launch_tonemap_axis_tables(const TonemapArgs& t, TmAxis* out, hipStream_t st);
 hipError_t launch_lpv_clear(const VolumeArg* vols, int n, uint32_t num_cascades, hipStream_t st);
-hipError_t launch_lpv_propagate(const VolumeArg src[3], const VolumeArg dst[3], uint32_t num_cascades, const LpvPackEmit* emit, int mode, hipStream_t st);
+hipError_t launch_lpv_propagate(const VolumeArg src[3], const VolumeArg dst[3], uint32_t num_cascades, const LpvPackEmit* emit, int mode, hipStream_t st,
+                                const LpvGvStep* gv = nullptr);
+hipError_t launch_lpv_gv_factors(const VolumeArg& gv, void* factors, uint32_t num_cascades, hipStream_t st);
+hipError_t launch_gv_inject_rsm(const VolumeArg& normals, const VolumeArg& depth, const sah_lpv_cascade_matrices* cascades, uint32_t first_cascade,
+                                uint32_t cascade_count, uint32_t num_cascades, const VolumeArg& gv, uint32_t* keys, hipStream_t st);
+hipError_t launch_gv_inject_scene(const PlaneArg& depth, const PlaneArg& normals, uint32_t width, uint32_t height, const sah_view_data& view,
+                                  const sah_lpv_cascade_matrices* cascades, uint32_t num_cascades, const VolumeArg& gv, uint32_t* keys, hipStream_t st);
 hipError_t launch_lpv_build_tables(hipStream_t st, bool* hot_structure);
 hipError_t launch_sky_luts(const PlaneArg& transmittance, const PlaneArg& multiscattering, const PlaneArg& sky_view, const float light_vector[3], hipStream_t st);
 hipError_t launch_fill_r32f(const PlaneArg& dst, uint32_t w, uint32_t h, float value, hipStream_t st);
@@ -388,9 +395,33 @@ int sah_lpv_clear(sah_ctx* ctx, const sah_volume* red, const sah_volume* green, 
     return SAH_OK;
 }
 
-int sah_lpv_propagate(sah_ctx* ctx, const sah_volume a_rgb[3], const sah_volume b_rgb[3], uint32_t num_cascades, uint32_t steps) {
-    SAH_RANGE();
+}  // extern "C"
+
+namespace {
+// a device buffer of the context that only grows (the GV scratch): synchronises only when it has to free a smaller one
+hipError_t grow_scratch(sah_ctx* ctx, void** ptr, size_t* bytes, size_t need) {
+    if (*bytes >= need) return hipSuccess;
+    if (*ptr) {
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return e;
+        (void)hipFree(*ptr);
+    }
+    *ptr = nullptr;
+    *bytes = 0;
+    const hipError_t e = hipMalloc(ptr, need);
+    if (e == hipSuccess) *bytes = need;
+    return e;
+}
+bool gv_volume_ok(const sah_volume* v, uint32_t num_cascades) {
+    return lpv_vol_ok(v) && v->width >= 32 * num_cascades && v->height >= 32 && v->depth >= 32 && (uint64_t)v->width * v->height * v->depth <= (1ull << 26) &&
+           (uint64_t)v->slice_pitch_bytes * v->depth < (1ull << 32);
+}
+// sah_lpv_propagate, with use_gv = 1 when `geometry` is not null (sah_lpv_propagate_gv)
+int lpv_propagate(sah_ctx* ctx, const sah_volume a_rgb[3], const sah_volume b_rgb[3], const sah_volume* geometry, uint32_t num_cascades, uint32_t steps) {
     if (!ctx || !a_rgb || !b_rgb || num_cascades == 0 || num_cascades > 4) return SAH_ERR_INVALID_ARGUMENT;
+    if (geometry && (!lpv_vol_ok(geometry) || !geometry->width || !geometry->height || !geometry->depth ||
+                     (uint64_t)geometry->slice_pitch_bytes * geometry->depth >= (1ull << 32)))
+        return fail(ctx, SAH_ERR_UNSUPPORTED_FORMAT, "the geometry volume must be an RGBA16F volume under 4 GiB, 8-byte aligned");
     sah::VolumeArg a[3], b[3];
     for (int i = 0; i < 3; i++) {
         if (!lpv_vol_ok(&a_rgb[i]) || !lpv_vol_ok(&b_rgb[i])) return fail(ctx, SAH_ERR_UNSUPPORTED_FORMAT, "LPV volumes must be RGBA16F");
@@ -438,10 +469,24 @@ int sah_lpv_propagate(sah_ctx* ctx, const sah_volume a_rgb[3], const sah_volume 
         if (emits) HIP_TRY(ctx, sah_lpv_pack_borders_for(ctx, last[0].width, last[0].height, last[0].depth, pk.total));
         emit = {ctx->lpv_packed, pk.row_pitch, pk.slice_pitch, ctx->state};
     }
+    // use_gv = 1: the GV does not change during the steps, so its 30 factors per cell are computed once, ahead of them, and every step
+    // reads them (64 bytes per cell); SAH_LPV_GV_MODE=2 samples the GV in every step instead (the other variant: DESIGN.md §5i, §7)
+    sah::LpvGvStep gv = {};
+    if (geometry && steps > 0) {
+        static const int env_gv = getenv("SAH_LPV_GV_MODE") ? atoi(getenv("SAH_LPV_GV_MODE")) : 1;  // experiments: 1 precomputed, 2 sampled per step
+        gv.gv = varg(*geometry);
+        gv.mode = env_gv == 2 ? 2 : 1;
+        if (gv.mode == 1) {
+            HIP_TRY(ctx, grow_scratch(ctx, &ctx->gv_factors, &ctx->gv_factors_bytes, (size_t)4 * 16 * 32768 * 4));
+            gv.factors = ctx->gv_factors;
+            HIP_TRY(ctx, sah::launch_lpv_gv_factors(gv.gv, gv.factors, num_cascades, ctx->stream));
+        }
+    }
+    const sah::LpvGvStep* g = geometry ? &gv : nullptr;
     for (uint32_t s = 0; s < steps; s++) {
         const sah::LpvPackEmit* e = (emits && s + 1 == steps) ? &emit : nullptr;
-        if ((s & 1) == 0) HIP_TRY(ctx, sah::launch_lpv_propagate(a, b, num_cascades, e, mode, ctx->stream));
-        else HIP_TRY(ctx, sah::launch_lpv_propagate(b, a, num_cascades, e, mode, ctx->stream));
+        if ((s & 1) == 0) HIP_TRY(ctx, sah::launch_lpv_propagate(a, b, num_cascades, e, mode, ctx->stream, g));
+        else HIP_TRY(ctx, sah::launch_lpv_propagate(b, a, num_cascades, e, mode, ctx->stream, g));
     }
     if (emits) {
         ctx->lpv_pack_generation = SAH_GENERATION_TRACKED;
@@ -453,6 +498,66 @@ int sah_lpv_propagate(sah_ctx* ctx, const sah_volume a_rgb[3], const sah_volume 
     for (int i = 0; i < 3 && same; i++) same = same_volume(prev_src[i], last[i]);
     if (same && ctx->cache_epoch == epoch_in + 1) ctx->cache_epoch = epoch_in;  // (nothing but the drop above has moved it: no reallocation, no other layout)
     else if (!same && emits && prev_gen == 0) ctx->cache_epoch++;               // a copy came into being
+    return SAH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sah_lpv_propagate(sah_ctx* ctx, const sah_volume a_rgb[3], const sah_volume b_rgb[3], uint32_t num_cascades, uint32_t steps) {
+    SAH_RANGE();
+    return lpv_propagate(ctx, a_rgb, b_rgb, nullptr, num_cascades, steps);
+}
+
+int sah_lpv_propagate_gv(sah_ctx* ctx, const sah_volume a_rgb[3], const sah_volume b_rgb[3], const sah_volume* geometry, uint32_t num_cascades,
+                         uint32_t steps) {
+    SAH_RANGE();
+    return lpv_propagate(ctx, a_rgb, b_rgb, geometry, num_cascades, steps);
+}
+
+// The two GV injections (lpv_gv.hip).  Neither reads or writes the colour volumes: the Lighting pass's gather copy and the cache epoch stay.
+int sah_lpv_inject_rsm_gv(sah_ctx* ctx, const sah_rsm_targets* rsm, const sah_lpv_cascade_matrices* cascades, uint32_t first_cascade,
+                          uint32_t cascade_count, uint32_t num_cascades, const sah_volume* geometry) {
+    SAH_RANGE();
+    if (!ctx || !rsm || !cascades || !geometry || num_cascades == 0 || num_cascades > 4) return SAH_ERR_INVALID_ARGUMENT;
+    if (first_cascade >= num_cascades || cascade_count > num_cascades - first_cascade)
+        return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "cascades [first, first + count) must lie in [0, num_cascades)");
+    if (!gv_volume_ok(geometry, num_cascades))
+        return fail(ctx, SAH_ERR_UNSUPPORTED_FORMAT, "the geometry volume must be RGBA16F, at least (32*cascades)x32x32, 8-byte aligned");
+    const sah_volume& n = rsm->normals;
+    const sah_volume& d = rsm->depth;
+    const uint32_t layers = first_cascade + cascade_count;
+    if (!n.ptr || !d.ptr || n.format != SAH_FORMAT_R8G8B8A8_UNORM || d.format != SAH_FORMAT_D16_UNORM || !d.width || !d.height ||
+        n.width != d.width || n.height != d.height || n.depth < layers || d.depth < layers || (uint64_t)d.width * d.height >= (1ull << 31) ||
+        (uint64_t)n.row_pitch_bytes < (uint64_t)n.width * 4 || (uint64_t)n.slice_pitch_bytes < (uint64_t)n.row_pitch_bytes * n.height ||
+        (uint64_t)d.row_pitch_bytes < (uint64_t)d.width * 2 || (uint64_t)d.slice_pitch_bytes < (uint64_t)d.row_pitch_bytes * d.height ||
+        ((uintptr_t)n.ptr % 4) != 0 || (n.row_pitch_bytes % 4) != 0 || (n.slice_pitch_bytes % 4) != 0 || ((uintptr_t)d.ptr % 2) != 0 ||
+        (d.row_pitch_bytes % 2) != 0 || (d.slice_pitch_bytes % 2) != 0)
+        return fail(ctx, SAH_ERR_UNSUPPORTED_FORMAT, "RSM: normals R8G8B8A8_UNORM and depth D16_UNORM arrays of equal extents with the cascades' layers");
+    if (cascade_count == 0) return SAH_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t need = (size_t)16 * geometry->width * geometry->height * geometry->depth;
+    HIP_TRY(ctx, grow_scratch(ctx, (void**)&ctx->gv_keys, &ctx->gv_keys_bytes, need));
+    HIP_TRY(ctx, sah::launch_gv_inject_rsm(varg(n), varg(d), cascades, first_cascade, cascade_count, num_cascades, varg(*geometry), ctx->gv_keys,
+                                           ctx->stream));
+    return SAH_OK;
+}
+
+int sah_lpv_inject_scene_gv(sah_ctx* ctx, const sah_plane* depth, const sah_plane* normals, const sah_view_data* view,
+                            const sah_lpv_cascade_matrices* cascades, uint32_t num_cascades, const sah_volume* geometry) {
+    SAH_RANGE();
+    if (!ctx || !depth || !normals || !view || !cascades || !geometry || num_cascades == 0 || num_cascades > 4) return SAH_ERR_INVALID_ARGUMENT;
+    if (!gv_volume_ok(geometry, num_cascades))
+        return fail(ctx, SAH_ERR_UNSUPPORTED_FORMAT, "the geometry volume must be RGBA16F, at least (32*cascades)x32x32, 8-byte aligned");
+    if (!depth->ptr || depth->format != SAH_FORMAT_D32_SFLOAT || !depth->width || !depth->height || (uint64_t)depth->row_pitch_bytes < (uint64_t)depth->width * 4 ||
+        ((uintptr_t)depth->ptr % 4) != 0 || (depth->row_pitch_bytes % 4) != 0 || !rgba16f_ok(normals) || normals->width != depth->width ||
+        normals->height != depth->height || (uint64_t)depth->width * depth->height >= (1ull << 32))
+        return fail(ctx, SAH_ERR_UNSUPPORTED_FORMAT, "scene GV: depth D32_SFLOAT and normals R16G16B16A16_SFLOAT planes of equal extents");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t need = (size_t)16 * geometry->width * geometry->height * geometry->depth;
+    HIP_TRY(ctx, grow_scratch(ctx, (void**)&ctx->gv_keys, &ctx->gv_keys_bytes, need));
+    HIP_TRY(ctx, sah::launch_gv_inject_scene(parg(depth), parg(normals), depth->width, depth->height, *view, cascades, num_cascades, varg(*geometry),
+                                             ctx->gv_keys, ctx->stream));
     return SAH_OK;
 }
 

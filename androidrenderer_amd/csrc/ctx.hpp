@@ -48,6 +48,10 @@ struct sah_ctx {
     size_t irr32_bytes = 0;
     uint32_t irr32_generation = 0;     // sah_gi::probe_generation the copy was built for (0: not reusable)
     sah::VolumeArg irr32_source = {};
+    uint32_t* gv_keys = nullptr;       // device: 4 order-preserving keys per geometry-volume texel, the GV injections' MAX scratch (lpv_gv.hip)
+    size_t gv_keys_bytes = 0;
+    void* gv_factors = nullptr;        // device: the 30 occlusion factors per cell of sah_lpv_propagate_gv (lpv.hip: k_gv_factors)
+    size_t gv_factors_bytes = 0;
     uint8_t* lpv_packed = nullptr;     // device: per-frame interleaved, zero-bordered copy of the three LPV volumes (lighting.hip)
     size_t lpv_packed_bytes = 0;
     uint32_t lpv_pack_generation = 0;  // sah_gi::lpv_generation the gather copy was built for (0: not reusable)

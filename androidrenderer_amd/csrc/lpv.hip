@@ -1,7 +1,8 @@
 // LPV maintenance kernels for gfx950:
 //   clear      RenderCore/shaders/gi/lpv/clear_lpv.comp:22-29        (host light_propagation_volume.cpp:839-926)
 //   propagate  RenderCore/shaders/gi/lpv/lpv_propagate.comp.slang:76-156 (host :970-1063), fp16 arithmetic,
-//              use_gv hard-wired to false by the host (:975) => geo_volume_factor == 1.
+//              use_gv hard-wired to false by the host (:975) => geo_volume_factor == 1 (sah_lpv_propagate);
+//              use_gv = 1 with a geometry volume: sah_lpv_propagate_gv (include/sah_lpv_gv.h).
 // One thread per cell; the three colour volumes are 1 MiB each and stay in the per-XCD L2 between steps.
 #include <hip/hip_runtime.h>
 
@@ -83,6 +84,10 @@ struct PropArgs {
     uint32_t pk_row_pitch, pk_slice_pitch;
     FrameState* state;
     uint32_t hot;  // the tables have the structure propagate_from_hot relies on: waves with finite coefficients take it
+    // use_gv = 1 (sah_lpv_propagate_gv): the geometry volume (GV 2: every step samples it) or its precomputed factors (GV 1: k_gv_factors)
+    VolumeArg gv;
+    const uint4* gv_factors;
+    uint32_t gv_cells;
 };
 
 // tables of the 30 direction pairs: built once per context into device memory (k_build_prop_tables) and read by the propagate kernels
@@ -108,23 +113,111 @@ __global__ void k_build_prop_tables(PropTables* out) { build_prop_tables(*out); 
 __constant__ PropTables c_prop_tables;
 
 // the 30 direction pairs of one cell from its six neighbours' coefficients: lpv_propagate.comp.slang:96-152
-SAH_DEV H4 propagate_from(const PropTables& T, const H4 (&coef)[6]) {
+// GV: use_gv = 1 (sah_lpv_propagate_gv), fac[5 n + s] = geo_volume_factor of side s of neighbour n, fac[5 n + 4] of its direct face
+template <bool GV = false>
+SAH_DEV H4 propagate_from(const PropTables& T, const H4 (&coef)[6], const Hn* fac = nullptr) {
     const Hn direct_sa = Hn(tof(Hn::lit(0.4006696846f)) / 3.1415927f);
     const Hn side_sa = Hn(tof(Hn::lit(0.4234413544f)) / 3.1415927f);
-    // (Hn::lit: compile-time constants.  geo_volume_factor == 1: x * 1.0h is x for every x, the compiler folds it.)
-    const Hn zero = Hn::lit(0.f), geo_volume_factor = Hn::lit(1.f);
+    // (Hn::lit: compile-time constants.  use_gv = 0: geo_volume_factor == 1, x * 1.0h is x for every x, the compiler folds it.)
+    const Hn zero = Hn::lit(0.f), one = Hn::lit(1.f);
     H4 acc = {zero, zero, zero, zero};
 #pragma unroll
     for (int n = 0; n < 6; n++) {
 #pragma unroll
         for (int s = 0; s < 4; s++) {
             const Hn m = nmax(zero, dot4h(coef[n], from_q(T.eval_sh[n][s])));
-            acc = acc + (side_sa * m) * from_q(T.reproj_lobe[n][s]) * geo_volume_factor;
+            acc = acc + (side_sa * m) * from_q(T.reproj_lobe[n][s]) * (GV ? fac[5 * n + s] : one);
         }
         const Hn m = nmax(zero, dot4h(coef[n], from_q(T.cur_sh[n])));
-        acc = acc + (direct_sa * m) * from_q(T.cur_lobe[n]) * geo_volume_factor;
+        acc = acc + (direct_sa * m) * from_q(T.cur_lobe[n]) * (GV ? fac[5 * n + 4] : one);
     }
     return acc;
+}
+
+// ---- the geometry volume's occlusion (use_gv = 1): lpv_propagate.comp.slang:104-114, 135, 146 ------------------------------------------------
+// gv_sh = geo_volume.SampleLevel(((n / 32 + 0.5 / 32) + cascade) / 4, n.yz / 32 + 0.5 / 32) through the LPV's sampler (LINEAR, CLAMP_TO_BORDER,
+// transparent black): the weighted sum of DESIGN.md §3 in fp32 (fma chain from +0 over the eight taps), rounded to half4.  The literal 4 is the
+// shader's: with four cascades the point is a texel centre, with fewer it is not.
+SAH_DEV H4 gv_sample(const VolumeArg& gv, int nx, int ny, int nz, uint32_t cascade) {
+    float c[3] = {(float)nx / 32.f + 0.5f / 32.f, (float)ny / 32.f + 0.5f / 32.f, (float)nz / 32.f + 0.5f / 32.f};
+    c[0] = (c[0] + (float)cascade) / 4.f;
+    const float ext[3] = {(float)gv.width, (float)gv.height, (float)gv.depth};
+    int i0[3];
+    float w0[3], w1[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float p = c[k] * ext[k] - 0.5f;
+        const float f0 = __builtin_floorf(p);
+        w1[k] = p - f0;
+        w0[k] = 1.0f - w1[k];
+        i0[k] = (int)f0;  // (|p| < 2^16: the coordinates are in [-1/128, 1.02])
+    }
+    const float wxy[4] = {w0[0] * w0[1], w1[0] * w0[1], w0[0] * w1[1], w1[0] * w1[1]};
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const float wt = wxy[k & 3] * ((k >> 2) ? w1[2] : w0[2]);
+        const H4 t = load_h4(gv, i0[0] + (k & 1), i0[1] + ((k >> 1) & 1), i0[2] + (k >> 2));
+        acc[0] = __builtin_fmaf(wt, tof(t.x), acc[0]);
+        acc[1] = __builtin_fmaf(wt, tof(t.y), acc[1]);
+        acc[2] = __builtin_fmaf(wt, tof(t.z), acc[2]);
+        acc[3] = __builtin_fmaf(wt, tof(t.w), acc[3]);
+    }
+    return {Hn(acc[0]), Hn(acc[1]), Hn(acc[2]), Hn(acc[3])};
+}
+// 1 - clamp(gv.x * sh.x + abs(dot(gv.yzw, sh.yzw)), 0, 1) in half, the dot product left to right.  clamp is min(max(x, 0), 1) with IEEE
+// maxNum / minNum: a NaN gives 0, so a NaN in the sample leaves the flux unattenuated (factor 1).  The factor is always in [0, 1].
+SAH_DEV Hn gv_face_factor(H4 g, const Q4& q) {
+    const H4 s = from_q(q);
+    const Hn d = (g.y * s.y + g.z * s.z) + g.w * s.w;
+    const Hn t = g.x * s.x + nabs(d);
+    return Hn::lit(1.f) - nmin(nmax(t, Hn::lit(0.f)), Hn::lit(1.f));
+}
+// the 30 factors of cell idx (one per direction pair, in propagate_from's order); a neighbour the shader skips contributes +-0 whatever its
+// factor (any finite factor does): 1
+SAH_DEV void gv_cell_factors(const PropTables& T, const VolumeArg& gv, uint32_t idx, Hn (&fac)[30]) {
+    const int cx = idx & 31, cy = (idx >> 5) & 31, cz = (idx >> 10) & 31;
+    const uint32_t cascade = idx >> 15;
+#pragma unroll
+    for (int n = 0; n < 6; n++) {
+        const int nx = cx - kDir[n][0], ny = cy - kDir[n][1], nz = cz - kDir[n][2];
+        const bool skipped = nx > 31 || ny > 31 || nz > 31;  // (>= -1 always: c in [0, 32), |dir| <= 1)
+        const H4 g = skipped ? H4{Hn::lit(0.f), Hn::lit(0.f), Hn::lit(0.f), Hn::lit(0.f)} : gv_sample(gv, nx, ny, nz, cascade);
+#pragma unroll
+        for (int s = 0; s < 4; s++) fac[5 * n + s] = gv_face_factor(g, T.eval_sh[n][s]);
+        fac[5 * n + 4] = gv_face_factor(g, T.cur_sh[n]);
+    }
+}
+// Precomputed factors: 4 planes of one uint4 per cell (factor j in plane j / 8, half j % 8; halves 30 and 31 unused), 64 bytes per cell
+constexpr uint32_t kGvFactorPlanes = 4;
+SAH_DEV void gv_load_factors(const uint4* f, uint32_t cells, uint32_t idx, Hn (&fac)[30]) {
+#pragma unroll
+    for (uint32_t p = 0; p < kGvFactorPlanes; p++) {
+        const uint4 q = f[p * cells + idx];
+        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int j = (int)p * 8 + k;
+            if (j < 30) fac[j] = Hn::raw(__builtin_bit_cast(_Float16, (uint16_t)(w[k >> 1] >> (16 * (k & 1)))));
+        }
+    }
+}
+__global__ void __launch_bounds__(256) k_gv_factors(VolumeArg gv, uint4* out, uint32_t cells) {
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= cells) return;
+    Hn fac[30];
+    gv_cell_factors(c_prop_tables, gv, idx, fac);
+#pragma unroll
+    for (uint32_t p = 0; p < kGvFactorPlanes; p++) {
+        uint32_t w[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int j0 = (int)p * 8 + 2 * k, j1 = j0 + 1;
+            const uint32_t lo = j0 < 30 ? __builtin_bit_cast(uint16_t, fac[j0].v) : 0u, hi = j1 < 30 ? __builtin_bit_cast(uint16_t, fac[j1].v) : 0u;
+            w[k] = lo | (hi << 16);
+        }
+        out[p * cells + idx] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
 }
 
 // ---- the same 30 direction pairs for FINITE coefficients, at half the arithmetic (round 6) ------------------------------------------------
@@ -168,7 +261,7 @@ template <int K> SAH_DEV void h4_add(H4& a, Hn t) {
 }
 SAH_DEV Hn hneg(Hn a) { return Hn::raw(-a.v); }
 
-template <int N> SAH_DEV void propagate_from_neighbour_hot(const PropTables& T, const H4& c, H4& acc) {
+template <int N, bool GV = false> SAH_DEV void propagate_from_neighbour_hot(const PropTables& T, const H4& c, H4& acc, const Hn* fac = nullptr) {
     constexpr int CU = sh_comp_of_col(N, 0), CV = sh_comp_of_col(N, 1), CW = sh_comp_of_col(N, 2);
     const Hn direct_sa = Hn(tof(Hn::lit(0.4006696846f)) / 3.1415927f);
     const Hn side_sa = Hn(tof(Hn::lit(0.4234413544f)) / 3.1415927f);
@@ -191,8 +284,14 @@ template <int N> SAH_DEV void propagate_from_neighbour_hot(const PropTables& T, 
         }
         const Hn t = side_sa * nmax(zero, dot);
         const H4 lobe = from_q(T.reproj_lobe[N][S]);
-        acc.x = acc.x + t * lobe.x;
-        h4_add<CS>(acc, t * h4_get<CS>(lobe));
+        if constexpr (GV) {  // ((sa * m) * lobe) * factor; the dropped lobe entries stay +-0 (the factor is finite: [0, 1])
+            const Hn f = fac[5 * N + S];
+            acc.x = acc.x + (t * lobe.x) * f;
+            h4_add<CS>(acc, (t * h4_get<CS>(lobe)) * f);
+        } else {
+            acc.x = acc.x + t * lobe.x;
+            h4_add<CS>(acc, t * h4_get<CS>(lobe));
+        }
     };
     side(std::integral_constant<int, 0>{});
     side(std::integral_constant<int, 1>{});
@@ -200,18 +299,25 @@ template <int N> SAH_DEV void propagate_from_neighbour_hot(const PropTables& T, 
     side(std::integral_constant<int, 3>{});
     const Hn t = direct_sa * nmax(zero, p0 + pd);
     const H4 lobe = from_q(T.cur_lobe[N]);
-    acc.x = acc.x + t * lobe.x;
-    h4_add<CW>(acc, t * h4_get<CW>(lobe));
+    if constexpr (GV) {
+        const Hn f = fac[5 * N + 4];
+        acc.x = acc.x + (t * lobe.x) * f;
+        h4_add<CW>(acc, (t * h4_get<CW>(lobe)) * f);
+    } else {
+        acc.x = acc.x + t * lobe.x;
+        h4_add<CW>(acc, t * h4_get<CW>(lobe));
+    }
 }
-SAH_DEV H4 propagate_from_hot(const PropTables& T, const H4 (&coef)[6]) {
+template <bool GV = false>
+SAH_DEV H4 propagate_from_hot(const PropTables& T, const H4 (&coef)[6], const Hn* fac = nullptr) {
     const Hn zero = Hn::lit(0.f);
     H4 acc = {zero, zero, zero, zero};
-    propagate_from_neighbour_hot<0>(T, coef[0], acc);
-    propagate_from_neighbour_hot<1>(T, coef[1], acc);
-    propagate_from_neighbour_hot<2>(T, coef[2], acc);
-    propagate_from_neighbour_hot<3>(T, coef[3], acc);
-    propagate_from_neighbour_hot<4>(T, coef[4], acc);
-    propagate_from_neighbour_hot<5>(T, coef[5], acc);
+    propagate_from_neighbour_hot<0, GV>(T, coef[0], acc, fac);
+    propagate_from_neighbour_hot<1, GV>(T, coef[1], acc, fac);
+    propagate_from_neighbour_hot<2, GV>(T, coef[2], acc, fac);
+    propagate_from_neighbour_hot<3, GV>(T, coef[3], acc, fac);
+    propagate_from_neighbour_hot<4, GV>(T, coef[4], acc, fac);
+    propagate_from_neighbour_hot<5, GV>(T, coef[5], acc, fac);
     return acc;
 }
 
@@ -271,7 +377,7 @@ SAH_DEV uint32_t nonfinite_halves(uint32_t w) { return (w & 0x7c007c00u) + 0x040
 // __constant__ data (rounds 1-5) every neighbour's address waited for a load of its direction, and the waits (vmcnt counts in order) also
 // waited for the neighbour texels requested before: six round trips in series, most of a step's 9.3 us.
 constexpr int8_t kDirC[6][3] = {{0, 0, 1}, {0, 0, -1}, {1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}};
-template <int NC, bool EMIT>
+template <int NC, bool EMIT, int GV = 0>
 SAH_DEV void propagate_cell_hot(const PropTables& T, const PropArgs& a, uint32_t idx, uint32_t c0) {
     const uint32_t cx = idx & 31u, cy = (idx >> 5) & 31u, cz = (idx >> 10) & 31u, x = cx + (idx >> 15) * 32u;
     uint2 q[NC][6];
@@ -303,13 +409,16 @@ SAH_DEV void propagate_cell_hot(const PropTables& T, const PropArgs& a, uint32_t
 #pragma unroll
         for (int n = 0; n < 6; n++) bad |= nonfinite_halves(q[c][n].x) | nonfinite_halves(q[c][n].y);
     const bool general = !a.hot || wave_any((bad & 0x80008000u) != 0u);
+    Hn fac[30];
+    if constexpr (GV == 1) gv_load_factors(a.gv_factors, a.gv_cells, idx, fac);
+    else if constexpr (GV == 2) gv_cell_factors(T, a.gv, idx, fac);
     uint32_t bad_out = 0;
 #pragma unroll
     for (int c = 0; c < NC; c++) {
         H4 coef[6];
 #pragma unroll
         for (int n = 0; n < 6; n++) coef[n] = h4_of(q[c][n]);
-        const H4 out = general ? propagate_from(T, coef) : propagate_from_hot(T, coef);
+        const H4 out = general ? propagate_from<GV != 0>(T, coef, fac) : propagate_from_hot<GV != 0>(T, coef, fac);
         uint2 o;
         o.x = (uint32_t)__builtin_bit_cast(uint16_t, out.x.v) | ((uint32_t)__builtin_bit_cast(uint16_t, out.y.v) << 16);
         o.y = (uint32_t)__builtin_bit_cast(uint16_t, out.z.v) | ((uint32_t)__builtin_bit_cast(uint16_t, out.w.v) << 16);
@@ -326,7 +435,8 @@ SAH_DEV void propagate_cell_hot(const PropTables& T, const PropArgs& a, uint32_t
     }
 }
 
-SAH_DEV H4 propagate_cell(const PropTables& T, const VolumeArg& src, const VolumeArg& dst, uint32_t idx) {
+template <int GV = 0>
+SAH_DEV H4 propagate_cell(const PropTables& T, const VolumeArg& src, const VolumeArg& dst, uint32_t idx, const PropArgs& a) {
     const int cx = idx & 31, cy = (idx >> 5) & 31, cz = (idx >> 10) & 31, cascade = idx >> 15;
     const int xoff = cascade * 32;
     // All 18 neighbour texels are fetched before any arithmetic (one latency phase instead of six: with two waves per SIMD the
@@ -340,18 +450,21 @@ SAH_DEV H4 propagate_cell(const PropTables& T, const VolumeArg& src, const Volum
         const bool skipped = nx < -1 || ny < -1 || nz < -1 || nx > 31 || ny > 31 || nz > 31;
         coef[n] = load_h4(src, skipped ? -1 : nx + xoff, ny, nz);
     }
-    const H4 out = propagate_from(T, coef);
+    Hn fac[30];
+    if constexpr (GV == 1) gv_load_factors(a.gv_factors, a.gv_cells, idx, fac);
+    else if constexpr (GV == 2) gv_cell_factors(T, a.gv, idx, fac);
+    const H4 out = propagate_from<GV != 0>(T, coef, fac);
     store_h4(dst, cx + xoff, cy, cz, out);
     return out;
 }
 
-template <bool EMIT>
+template <bool EMIT, int GV = 0>
 __global__ void __launch_bounds__(256) k_lpv_propagate(PropArgs a) {
     const PropTables& T = c_prop_tables;
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= a.num_cascades * 32768u) return;
     const uint32_t c = blockIdx.y;  // colour volume
-    const H4 out = propagate_cell(T, a.src[c], a.dst[c], idx);
+    const H4 out = propagate_cell<GV>(T, a.src[c], a.dst[c], idx, a);
     if constexpr (EMIT) {
         const uint32_t x = (idx & 31u) + (idx >> 15) * 32u, y = (idx >> 5) & 31u, z = (idx >> 10) & 31u;
         uint2 q;
@@ -381,11 +494,11 @@ __global__ void __launch_bounds__(256) k_lpv_clear(ClearArgs a) {
     }
 }
 
-template <int NC, bool EMIT>
+template <int NC, bool EMIT, int GV = 0>
 __global__ void __launch_bounds__(256) k_lpv_propagate_hot(PropArgs a) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= a.num_cascades * 32768u) return;
-    propagate_cell_hot<NC, EMIT>(c_prop_tables, a, idx, NC == 1 ? blockIdx.y : 0u);
+    propagate_cell_hot<NC, EMIT, GV>(c_prop_tables, a, idx, NC == 1 ? blockIdx.y : 0u);
 }
 
 hipError_t launch_lpv_clear(const VolumeArg* vols, int n, uint32_t num_cascades, hipStream_t st) {
@@ -413,7 +526,26 @@ hipError_t launch_lpv_build_tables(hipStream_t st, bool* hot_structure) {
 
 // `emit` (or null): where the step also writes the Lighting pass's gather copy of `dst` (PropArgs)
 // `mode`: 0 the general form only (rounds 1-5's kernel), 1 hot form, one colour volume per thread, 3 hot form, the three colours of a cell in one thread
-hipError_t launch_lpv_propagate(const VolumeArg src[3], const VolumeArg dst[3], uint32_t num_cascades, const LpvPackEmit* emit, int mode, hipStream_t st) {
+// `gv` (or null): use_gv = 1 with this step's occlusion factors (LpvGvStep::mode 1: precomputed by launch_lpv_gv_factors, 2: sampled by the step)
+template <int GV>
+static void launch_propagate_kernel(const PropArgs& a, uint32_t num_cascades, bool emit, int mode, hipStream_t st) {
+    if (mode != 0) {
+        const dim3 grid(num_cascades * 128, mode == 3 ? 1 : 3);
+        if (mode == 3) {
+            if (emit) hipLaunchKernelGGL((k_lpv_propagate_hot<3, true, GV>), grid, dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((k_lpv_propagate_hot<3, false, GV>), grid, dim3(256), 0, st, a);
+        } else {
+            if (emit) hipLaunchKernelGGL((k_lpv_propagate_hot<1, true, GV>), grid, dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((k_lpv_propagate_hot<1, false, GV>), grid, dim3(256), 0, st, a);
+        }
+        return;
+    }
+    if (emit) hipLaunchKernelGGL((k_lpv_propagate<true, GV>), dim3(num_cascades * 128, 3), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_lpv_propagate<false, GV>), dim3(num_cascades * 128, 3), dim3(256), 0, st, a);
+}
+
+hipError_t launch_lpv_propagate(const VolumeArg src[3], const VolumeArg dst[3], uint32_t num_cascades, const LpvPackEmit* emit, int mode, hipStream_t st,
+                                const LpvGvStep* gv) {
     PropArgs a = {};
     for (int i = 0; i < 3; i++) { a.src[i] = src[i]; a.dst[i] = dst[i]; }
     a.num_cascades = num_cascades;
@@ -423,33 +555,26 @@ hipError_t launch_lpv_propagate(const VolumeArg src[3], const VolumeArg dst[3], 
         a.pk_row_pitch = emit->row_pitch;
         a.pk_slice_pitch = emit->slice_pitch;
         a.state = emit->state;
-    }
-    if (mode != 0) {
-        if (emit) {
-            const hipError_t me = hipMemsetAsync(&emit->state->nonfinite, 0, sizeof(uint32_t), st);  // the copy's verdict starts at "finite"
-            if (me != hipSuccess) return me;
-        }
-        const dim3 grid(num_cascades * 128, mode == 3 ? 1 : 3);
-        if (mode == 3) {
-            if (emit) hipLaunchKernelGGL((k_lpv_propagate_hot<3, true>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((k_lpv_propagate_hot<3, false>), grid, dim3(256), 0, st, a);
-        } else {
-            if (emit) hipLaunchKernelGGL((k_lpv_propagate_hot<1, true>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((k_lpv_propagate_hot<1, false>), grid, dim3(256), 0, st, a);
-        }
-        return hipGetLastError();
-    }
-    if (emit) {
-        a.packed = emit->packed;
-        a.pk_row_pitch = emit->row_pitch;
-        a.pk_slice_pitch = emit->slice_pitch;
-        a.state = emit->state;
         const hipError_t me = hipMemsetAsync(&emit->state->nonfinite, 0, sizeof(uint32_t), st);  // the copy's verdict starts at "finite"
         if (me != hipSuccess) return me;
-        hipLaunchKernelGGL(k_lpv_propagate<true>, dim3(num_cascades * 128, 3), dim3(256), 0, st, a);
-    } else {
-        hipLaunchKernelGGL(k_lpv_propagate<false>, dim3(num_cascades * 128, 3), dim3(256), 0, st, a);
     }
+    const int gv_mode = gv ? gv->mode : 0;
+    if (gv) {
+        a.gv = gv->gv;
+        a.gv_factors = (const uint4*)gv->factors;
+        a.gv_cells = num_cascades * 32768u;
+    }
+    if (gv_mode == 1) launch_propagate_kernel<1>(a, num_cascades, emit != nullptr, mode, st);
+    else if (gv_mode == 2) launch_propagate_kernel<2>(a, num_cascades, emit != nullptr, mode, st);
+    else launch_propagate_kernel<0>(a, num_cascades, emit != nullptr, mode, st);
+    return hipGetLastError();
+}
+
+// the 30 occlusion factors of every propagated cell, once per sah_lpv_propagate_gv call (the GV does not change during its steps):
+// factors = kGvFactorPlanes * 16 * num_cascades * 32768 bytes
+hipError_t launch_lpv_gv_factors(const VolumeArg& gv, void* factors, uint32_t num_cascades, hipStream_t st) {
+    const uint32_t cells = num_cascades * 32768u;
+    hipLaunchKernelGGL(k_gv_factors, dim3(cells / 256u), dim3(256), 0, st, gv, (uint4*)factors, cells);
     return hipGetLastError();
 }
 

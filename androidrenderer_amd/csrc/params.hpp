@@ -128,6 +128,12 @@ struct FastArgs {
 };
 // (an fp32 copy — 48-byte texels, plain v_fma_f32 taps — was measured and loses 67 %: profiles/r3_lpv_pack32_experiment.txt)
 constexpr uint32_t kLpvPackTexel = 24, kLpvPackBorder = 2;
+struct LpvGvStep {  // use_gv = 1 in a propagation step (lpv.hip): the geometry volume, and its factors when precomputed (mode 1; mode 2: sampled per step)
+    VolumeArg gv;
+    void* factors;
+    int mode;
+};
+
 struct LpvPackEmit {  // the gather copy as the emitting propagation step writes it (lpv.hip)
     uint8_t* packed;
     uint32_t row_pitch, slice_pitch;

@@ -27,6 +27,9 @@ EXPORTS = ["sah_abi_version", "sah_status_string", "sah_last_error", "sah_create
            "sah_ipc_open", "sah_ipc_connect", "sah_ipc_export", "sah_ipc_register", "sah_ipc_unregister", "sah_ipc_reset",
            "sah_chain_create", "sah_chain_submit", "sah_chain_flush", "sah_chain_counts", "sah_chain_destroy"]
 
+# the LPV geometry volume's entries: exported, declared in include/sah_lpv_gv.h (not sah_hip.h)
+GV_EXPORTS = ["sah_lpv_inject_rsm_gv", "sah_lpv_inject_scene_gv", "sah_lpv_propagate_gv"]
+
 
 def load():
     """Loads the library (building is a separate, explicit step: python -m androidrenderer_amd.build)."""
@@ -107,6 +110,11 @@ def load():
     lib.sah_debug_chain_graphs.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.sah_chain_destroy.restype = None
     lib.sah_debug_set.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.sah_lpv_inject_rsm_gv.argtypes = [C.c_void_p, C.POINTER(_abi.RsmTargets), C.POINTER(_abi.LpvCascadeMatrices), C.c_uint32, C.c_uint32, C.c_uint32,
+                                          C.POINTER(_abi.Volume)]
+    lib.sah_lpv_inject_scene_gv.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.POINTER(_abi.ViewData),
+                                            C.POINTER(_abi.LpvCascadeMatrices), C.c_uint32, C.POINTER(_abi.Volume)]
+    lib.sah_lpv_propagate_gv.argtypes = [C.c_void_p, C.POINTER(_abi.Volume), C.POINTER(_abi.Volume), C.POINTER(_abi.Volume), C.c_uint32, C.c_uint32]
     _lib = lib
     return lib
 
@@ -194,6 +202,20 @@ class Context:
         a = (_abi.Volume * 3)(*a_rgb)
         b = (_abi.Volume * 3)(*b_rgb)
         self._check(self.lib.sah_lpv_propagate(self.handle, a, b, num_cascades, steps))
+
+    def lpv_inject_rsm_gv(self, rsm, cascades, first_cascade, cascade_count, num_cascades, geometry):
+        """sah_lpv_inject_rsm_gv: rsm an _abi.RsmTargets, cascades an (_abi.LpvCascadeMatrices * n) array"""
+        self._check(self.lib.sah_lpv_inject_rsm_gv(self.handle, C.byref(rsm), cascades, first_cascade, cascade_count, num_cascades, C.byref(geometry)))
+
+    def lpv_inject_scene_gv(self, depth, normals, view, cascades, num_cascades, geometry):
+        self._check(self.lib.sah_lpv_inject_scene_gv(self.handle, C.byref(depth), C.byref(normals), C.byref(view), cascades, num_cascades, C.byref(geometry)))
+
+    def lpv_propagate_gv(self, a_rgb, b_rgb, geometry, num_cascades, steps):
+        """sah_lpv_propagate_gv; geometry None = sah_lpv_propagate"""
+        a = (_abi.Volume * 3)(*a_rgb)
+        b = (_abi.Volume * 3)(*b_rgb)
+        g = C.byref(geometry) if geometry is not None else C.POINTER(_abi.Volume)()
+        self._check(self.lib.sah_lpv_propagate_gv(self.handle, a, b, g, num_cascades, steps))
 
     def sky_update_luts(self, transmittance, multiscattering, sky_view, light_vector):
         lv = (C.c_float * 3)(*[float(v) for v in light_vector])

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "sah_hip.h"
+#include "sah_lpv_gv.h"
 
 namespace sah {
 
@@ -728,6 +729,11 @@ public:
     LightPropagationVolume(const LightPropagationVolume&) = delete;  // owns the VPL buffers
     LightPropagationVolume& operator=(const LightPropagationVolume&) = delete;
     // light_propagation_volume.cpp:548-697: render the RSM of every cascade, extract the VPLs, add them to the A volumes
+    // r.GI.LPV.GvBuildMode (light_propagation_volume.cpp:49-53).  The reference's default frame is DepthBuffers with use_gv off (the
+    // propagation never reads the GV it builds, :975); here both default to off, so the default frame records the passes it always did.
+    enum class GvBuildMode { Disable, DepthBuffers };
+    GvBuildMode gv_build_mode = GvBuildMode::Disable;
+    bool use_gv = false;  // propagate with use_gv = 1 (sah_lpv_propagate_gv, include/sah_lpv_gv.h)
     void inject_indirect_sun_light(RenderGraph& graph, const RenderScene& scene) {
         graph.add_pass(hip_pass("Render RSM", [this, &scene](sah_ctx* ctx) {
                             const sah_rsm_targets rsm = {rsm_flux->desc, rsm_normals->desc, rsm_depth->desc};
@@ -741,6 +747,11 @@ public:
                                 if (int rc = sah_lpv_extract_vpls(ctx, &rsm, cascades.data(), c, 0.25f, list, vpl_counts + c); rc != SAH_OK) return rc;
                                 const sah_volume a[3] = {vol[0]->desc, vol[1]->desc, vol[2]->desc};
                                 return sah_lpv_inject_vpls(ctx, list, vpl_counts + c, num_vpls, cascades.data(), c, num_cascades, a);
+                            }));
+        if (gv_build_mode == GvBuildMode::DepthBuffers)  // :689-693, one pass per cascade there; MAX is order-independent: one launch here
+            graph.add_pass(hip_pass("Inject RSM depth into GV", [this](sah_ctx* ctx) {
+                                const sah_rsm_targets rsm = {rsm_flux->desc, rsm_normals->desc, rsm_depth->desc};
+                                return sah_lpv_inject_rsm_gv(ctx, &rsm, cascades.data(), 0, num_cascades, num_cascades, &vol[6]->desc);
                             }));
     }
     void update_cascade_transforms(const SceneView& view, const DirectionalLight& light) {
@@ -773,9 +784,15 @@ public:
                             return sah_lpv_clear(ctx, &vol[0]->desc, &vol[1]->desc, &vol[2]->desc, &vol[6]->desc, num_cascades);
                         }));
     }
-    void post_render(RenderGraph& graph, const SceneView&, const RenderScene&, const GBuffer&, TextureHandle) override {
+    void post_render(RenderGraph& graph, const SceneView& view, const RenderScene&, const GBuffer& gbuffer, TextureHandle) override {
+        if (gv_build_mode == GvBuildMode::DepthBuffers)  // :238-247, 932-968
+            graph.add_pass(hip_pass("Inject scene depth into GV", [this, &view, &gbuffer](sah_ctx* ctx) {
+                                const sah_plane depth = gbuffer.depth->plane(), normals = gbuffer.normals->plane();
+                                return sah_lpv_inject_scene_gv(ctx, &depth, &normals, &view.get_gpu_data(), cascades.data(), num_cascades, &vol[6]->desc);
+                            }));
         graph.add_pass(hip_pass("LPV Propagation", [this](sah_ctx* ctx) {
                             const sah_volume a[3] = {vol[0]->desc, vol[1]->desc, vol[2]->desc}, b[3] = {vol[3]->desc, vol[4]->desc, vol[5]->desc};
+                            if (use_gv) return sah_lpv_propagate_gv(ctx, a, b, &vol[6]->desc, num_cascades, num_steps);
                             return sah_lpv_propagate(ctx, a, b, num_cascades, num_steps);
                         }));
     }
@@ -804,6 +821,7 @@ public:
     void draw_debug_overlays(RenderGraph&, const SceneView&, const GBuffer&, TextureHandle) override {}  // GV / VPL visualisers: debug views, not on the path
     const sah_lpv_cascade_matrices* get_cascade_matrices() const { return cascades.data(); }
     TextureHandle get_volume(int channel, bool b = false) const { return vol[channel + (b ? 3 : 0)]; }
+    TextureHandle get_geometry_volume() const { return vol[6]; }
 
 private:
     uint32_t num_cascades, num_steps;

@@ -1,0 +1,190 @@
+"""The LPV geometry volume (include/sah_lpv_gv.h) without a GPU: the library exports the three entries, they answer made-up arguments with
+a status code, and the numpy restatement (tools/gen_golden_gv.py) reduces to gen_golden.lpv_propagate without a GV and gives hand-computed
+answers for one GV sample, one face factor and one point through each injection."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from androidrenderer_amd import _abi, lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import gen_golden as gg  # noqa: E402
+import gen_golden_gv as ggv  # noqa: E402
+
+hf = np.float16
+
+
+def test_library_exports_the_gv_entries_its_header_declares():
+    L = lib.load()
+    assert all(hasattr(L, s) for s in lib.GV_EXPORTS)
+    header = open(os.path.join(ROOT, "include", "sah_lpv_gv.h")).read()
+    assert sorted(re.findall(r"^int (sah_\w+)\(", header, re.M)) == sorted(lib.GV_EXPORTS)
+    assert not set(lib.GV_EXPORTS) & set(lib.EXPORTS)
+
+
+@pytest.mark.parametrize("seed", [21, 22])
+def test_no_argument_combination_crashes_a_gv_entry(seed):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "gv_fuzz_child.py"), str(seed), "2000"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       text=True, timeout=600)
+    tail = "\n".join(r.stdout.splitlines()[-10:])
+    if "SKIP:" in r.stdout:
+        pytest.skip(r.stdout.strip().splitlines()[-1])
+    assert r.returncode == 0, f"the fuzz child ended with code {r.returncode}:\n{tail}"
+    assert "OK: 2000 iterations" in r.stdout, tail
+
+
+def test_gv_entries_check_their_arguments():
+    L = lib.load()
+    L.sah_debug_create_detached.argtypes = [C.POINTER(C.c_void_p)]
+    h = C.c_void_p()
+    if L.sah_debug_create_detached(C.byref(h)) == _abi.SAH_ERR_UNSUPPORTED:
+        pytest.skip("a HIP device is present")
+    rgba16 = _abi.FORMAT_R16G16B16A16_SFLOAT
+    vol = lambda w=128, fmt=rgba16, bpp=8: _abi.Volume(0x7F0000000000, w, 32, 32, w * bpp, w * bpp * 32, fmt)
+    casc = (_abi.LpvCascadeMatrices * 4)()
+    res = 128
+    rsm = _abi.RsmTargets(_abi.Volume(0x7F0000000000, res, res, 4, res * 4, res * res * 4, _abi.FORMAT_R8G8B8A8_SRGB),
+                          _abi.Volume(0x7F0000000000, res, res, 4, res * 4, res * res * 4, _abi.FORMAT_R8G8B8A8_UNORM),
+                          _abi.Volume(0x7F0000000000, res, res, 4, res * 2, res * res * 2, _abi.FORMAT_D16_UNORM))
+    gv = vol()
+    inv, fmt, hip = _abi.SAH_ERR_INVALID_ARGUMENT, _abi.SAH_ERR_UNSUPPORTED_FORMAT, _abi.SAH_ERR_HIP
+    R = lambda *a: L.sah_lpv_inject_rsm_gv(h, *a)
+    assert R(None, casc, 0, 4, 4, C.byref(gv)) == inv and R(C.byref(rsm), None, 0, 4, 4, C.byref(gv)) == inv and R(C.byref(rsm), casc, 0, 4, 4, None) == inv
+    for nc in (0, 5, 2 ** 31):
+        assert R(C.byref(rsm), casc, 0, 1, nc, C.byref(gv)) == inv
+    assert R(C.byref(rsm), casc, 4, 1, 4, C.byref(gv)) == inv and R(C.byref(rsm), casc, 2, 3, 4, C.byref(gv)) == inv   # cascades outside [0, 4)
+    assert R(C.byref(rsm), casc, 1, 2 ** 32 - 1, 4, C.byref(gv)) == inv
+    assert R(C.byref(rsm), casc, 0, 4, 4, C.byref(vol(96))) == fmt                                                       # short GV
+    assert R(C.byref(rsm), casc, 0, 4, 4, C.byref(vol(fmt=_abi.FORMAT_R32_SFLOAT, bpp=4))) == fmt                       # wrong GV format
+    bad = _abi.RsmTargets(rsm.flux, rsm.flux, rsm.depth)
+    assert R(C.byref(bad), casc, 0, 4, 4, C.byref(gv)) == fmt                                                           # sRGB normals
+    few = _abi.RsmTargets(rsm.flux, rsm.normals, _abi.Volume(0x7F0000000000, res, res, 2, res * 2, res * res * 2, _abi.FORMAT_D16_UNORM))
+    assert R(C.byref(few), casc, 0, 4, 4, C.byref(gv)) == fmt and R(C.byref(few), casc, 0, 2, 4, C.byref(gv)) == hip    # layers < cascades
+    assert R(C.byref(rsm), casc, 0, 4, 4, C.byref(gv)) == hip  # valid: refused only for want of a device
+    S = lambda *a: L.sah_lpv_inject_scene_gv(h, *a)
+    depth = _abi.Plane(0x7F0000000000, 64, 36, 256, _abi.FORMAT_D32_SFLOAT)
+    normals = _abi.Plane(0x7F0000000000, 64, 36, 512, rgba16)
+    view = _abi.ViewData()
+    assert S(None, C.byref(normals), C.byref(view), casc, 4, C.byref(gv)) == inv and S(C.byref(depth), C.byref(normals), None, casc, 4, C.byref(gv)) == inv
+    assert S(C.byref(depth), C.byref(normals), C.byref(view), casc, 0, C.byref(gv)) == inv and S(C.byref(depth), C.byref(normals), C.byref(view), casc, 5, C.byref(gv)) == inv
+    assert S(C.byref(normals), C.byref(normals), C.byref(view), casc, 4, C.byref(gv)) == fmt                             # depth not D32F
+    short = _abi.Plane(0x7F0000000000, 64, 35, 512, rgba16)
+    assert S(C.byref(depth), C.byref(short), C.byref(view), casc, 4, C.byref(gv)) == fmt                                 # extents differ
+    assert S(C.byref(depth), C.byref(normals), C.byref(view), casc, 4, C.byref(vol(127))) == fmt
+    assert S(C.byref(depth), C.byref(normals), C.byref(view), casc, 4, C.byref(gv)) == hip
+    P = lambda a, b, g, nc, steps: L.sah_lpv_propagate_gv(h, a, b, g, nc, steps)
+    a3, b3 = (_abi.Volume * 3)(vol(), vol(), vol()), (_abi.Volume * 3)(vol(), vol(), vol())
+    assert P(None, b3, C.byref(gv), 4, 32) == inv and P(a3, b3, C.byref(gv), 0, 32) == inv and P(a3, b3, C.byref(gv), 5, 32) == inv
+    assert P(a3, b3, C.byref(vol(fmt=_abi.FORMAT_R32_SFLOAT, bpp=4)), 4, 32) == fmt
+    assert P((_abi.Volume * 3)(vol(96), vol(), vol()), b3, C.byref(gv), 4, 32) == inv                                     # short colour volume
+    assert P(a3, b3, C.byref(gv), 4, 32) == hip and P(a3, b3, None, 4, 32) == hip
+    L.sah_destroy(h)
+
+
+def test_numpy_restatement_without_gv_is_gen_golden_lpv_propagate():
+    rng = np.random.default_rng(5)
+    vols = [rng.uniform(-2, 2, (32, 32, 32, 4)).astype(hf) for _ in range(3)]
+    want = gg.lpv_propagate(vols, 2, 1)
+    for gv in (None, np.zeros((32, 32, 32, 4), np.uint16)):
+        got = ggv.lpv_propagate_gv(vols, gv, 2, 1)
+        for w, g in zip(want, got):
+            assert np.array_equal(w.view(np.uint16), g.view(np.uint16))
+
+
+def test_numpy_restatement_matches_its_fixture():
+    g = np.load(os.path.join(ROOT, "tests", "golden", "lpv_gv_propagate_2c_3steps.npz"))
+    got = ggv.lpv_propagate_gv([a.view(hf) for a in g["a"]], g["gv"], 3, 2)
+    for c in range(3):
+        assert np.array_equal(got[c].view(np.uint16), g["b"][c]), c
+    assert any((g["b"][c] != 0).any() for c in range(3))
+
+
+def test_known_answers_gv_sample_and_face_factor():
+    # one texel: with four cascades the sample point of neighbour (5, 6, 7) of cascade 2 is the centre of texel (69, 6, 7) — the texel itself
+    gv = np.zeros((32, 32, 128, 4), np.uint16)
+    texel = np.array([0.886, -0.5, 0.25, 1.0], hf)
+    gv[7, 6, 69] = texel.view(np.uint16)
+    got = ggv.gv_sample(gv, np.array([5]), np.array([6]), np.array([7]), np.array([2]))
+    assert np.array_equal(got[0], texel)
+    # with three cascades the literal 4 moves the point: x = ((5 / 32 + 1 / 64) + 2) / 4 * 96 - 0.5 = 51.625, between texels 51 and 52
+    gv3 = np.zeros((32, 32, 96, 4), np.uint16)
+    gv3[7, 6, 52] = texel.view(np.uint16)
+    got3 = ggv.gv_sample(gv3, np.array([5]), np.array([6]), np.array([7]), np.array([2]))
+    assert np.array_equal(got3[0], (texel.astype(np.float32) * np.float32(0.625)).astype(hf))
+    # one face factor: direct face of neighbour 0 (direction +z): sh = (0.2821, -0, 0.4886, -0): 1 - clamp(0.886 * 0.2821 + |0.25 * 0.4886|, 0, 1)
+    sh = ggv._sh([hf(0), hf(0), hf(1)])
+    f = ggv.face_factor(texel[None], sh)[0]
+    t = hf(hf(texel[0] * sh[0]) + abs(hf(hf(hf(texel[1] * sh[1]) + hf(texel[2] * sh[2])) + hf(texel[3] * sh[3]))))
+    assert f == hf(1 - t) and abs(float(f) - (1 - (0.886 * 0.2820948 + 0.25 * 0.4886025))) < 2e-3
+    assert ggv.face_factor(np.array([[4.0, 0, 0, 0]], hf), sh)[0] == 0            # saturates: no flux passes
+    assert ggv.face_factor(np.array([[np.nan, 0, 0, 0]], hf), sh)[0] == 1         # NaN: clamp gives 0
+    assert ggv.face_factor(np.array([[-4.0, 0, 0, 0]], hf), sh)[0] == 1           # negative: clamped to 0
+
+
+def _identity_cascade(bias=False):
+    m = (_abi.LpvCascadeMatrices * 1)()
+    eye = np.eye(4, dtype=np.float32)
+    w2c = eye.copy()
+    if bias:  # cascade = world * 0.5 + 0.5 (columns)
+        w2c = np.array([[0.5, 0, 0, 0], [0, 0.5, 0, 0], [0, 0, 0.5, 0], [0.5, 0.5, 0.5, 1]], np.float32)
+    for k in range(16):
+        m[0].inverse_rsm_vp[k] = eye.reshape(16)[k]
+        m[0].world_to_cascade[k] = w2c.reshape(16)[k]
+    return m
+
+
+def test_known_answer_one_rsm_point():
+    res = 8
+    normals = np.zeros((1, res, res, 4), np.uint8)
+    depth = np.full((1, res, res), 65535, np.uint16)  # depth 1: layer int((1 + 1 / 64) * 32) = 32, outside the volume
+    # (6, 5): even column.  NDC (6 / 8 * 2 - 1, 5 / 8 * 2 - 1, 32768 / 65535) = (0.5, 0.25, 0.500008) is the cascade position; + 1 / 64 ->
+    # gl_Position (0.515625 * 2 - 1, 0.265625 * 2 - 1) = (0.03125, -0.46875) -> x_f = 16.5, y_f = 8.5; layer int(0.515633 * 32) = 16
+    normals[0, 5, 6] = (255, 0, 128, 0)
+    depth[0, 5, 6] = 32768
+    # (5, 5): odd column, never injected; (6, 1): NDC y = -0.75 < 0, outside the cascade
+    normals[0, 5, 5] = normals[0, 1, 6] = (255, 255, 255, 0)
+    depth[0, 5, 5] = depth[0, 1, 6] = 32768
+    gv = np.zeros((32, 32, 32, 4), np.uint16)
+    ggv.inject_rsm_gv(normals, depth, _identity_cascade(), 0, 1, 1, gv)
+    nz = np.argwhere(gv.reshape(-1, 4).any(axis=1)).ravel()
+    assert list(nz) == [16 + 32 * (8 + 32 * 16)]
+    n = np.array([1.0, 0.0, 128 / 255], np.float32)  # the UNORM normal as read, no * 2 - 1
+    want = np.array([0.886226925, -1.02332671 * n[1], 1.02332671 * n[2], -1.02332671 * n[0]], np.float32).astype(hf)
+    # onto +0: MAX keeps +0 where the lobe is -0 (y) or negative (x)
+    assert np.array_equal(gv[16, 8, 16], [want.view(np.uint16)[0], 0x0000, want.view(np.uint16)[2], 0x0000])
+    neg = np.full((32, 32, 32, 4), np.array([-2.0], hf).view(np.uint16)[0], np.uint16)
+    ggv.inject_rsm_gv(normals, depth, _identity_cascade(), 0, 1, 1, neg)
+    assert np.array_equal(neg[16, 8, 16], want.view(np.uint16)) and (neg.reshape(-1, 4)[np.arange(32 ** 3) != 16656] == 0xC000).all()
+
+
+def test_known_answer_one_scene_point_and_the_max_blend():
+    W, H = 8, 8
+    depth = np.full((H, W), 5.0, np.float32)  # cascade z = 3: outside
+    normals = np.zeros((H, W, 4), np.uint16)
+    view = _abi.ViewData()
+    for k in range(16):
+        view.inverse_projection[k] = view.inverse_view[k] = float(np.eye(4, dtype=np.float32).reshape(16)[k])
+    # (5, 1): screenspace (5.5 / 8, 1.5 / 8) -> world (0.375, -0.625, 0.5) -> cascade (0.6875, 0.1875, 0.75): gl_Position (0.6875, 0.1875) — no
+    # * 2 - 1 — -> x_f = 27, y_f = 19, layer 24.  The normal (0, 2, 0) is not normalised.
+    depth[1, 5] = 0.5
+    normals[1, 5, :3] = np.array([0.0, 2.0, 0.0], hf).view(np.uint16)
+    depth[3, 5] = 0.5  # row 3 >= H / 4: no vertex reads it
+    normals[3, 5, :3] = np.array([1.0, 0.0, 0.0], hf).view(np.uint16)
+    gv = np.zeros((32, 32, 32, 4), np.uint16)
+    gv[24, 19, 27] = np.array([1.0, -4.0, -0.0, 0.0], hf).view(np.uint16)   # what was there before: MAX per channel
+    gv[0, 0, 0] = np.array([-0.0, 0, 0, 0], hf).view(np.uint16)
+    ggv.inject_scene_gv(depth, normals, view, _identity_cascade(bias=True), 1, gv)
+    nz = np.argwhere(gv.reshape(-1, 4).any(axis=1)).ravel()
+    assert sorted(nz) == [0, 27 + 32 * (19 + 32 * 24)]
+    assert np.array_equal(gv[24, 19, 27].view(hf).view(np.uint16),
+                          np.array([1.0, np.float32(-1.02332671) * 2, 0.0, 0.0], hf).view(np.uint16))  # max(-0, +0) = +0; max(+0, -0) = +0
+    assert gv[24, 19, 27, 3] == 0x0000 and gv[24, 19, 27, 2] == 0x0000
+    # the key order: -0 < +0, NaN sources dropped
+    keys = ggv.gv_key(np.array([0xFC00, 0x8000, 0x0000, 0x7C00, 0x7E00], np.uint16))
+    assert (np.diff(keys.astype(np.int64)) > 0).all() and np.array_equal(ggv.gv_unkey(keys), [0xFC00, 0x8000, 0x0000, 0x7C00, 0x7E00])

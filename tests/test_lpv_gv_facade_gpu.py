@@ -1,0 +1,62 @@
+"""GPU: the C++ host façade's LightPropagationVolume with gv_build_mode = DepthBuffers and use_gv on (tests/cpp/host_lpv_gv.cpp, compiled
+here): post_render injects the scene depth into the GV and propagates through it — both bit for bit against tools/gen_golden_gv.py."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from androidrenderer_amd import _abi, images, mesh, scene
+from tests import util
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import gen_golden_gv as ggv  # noqa: E402
+
+
+def test_lpv_frame_with_gv_through_cpp_facade(tmp_path, hip_ctx):
+    import torch
+    exe = str(tmp_path / "host_lpv_gv")
+    libdir = os.path.join(ROOT, "androidrenderer_amd")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "host_lpv_gv.cpp"),
+                           "-o", exe, "-L", libdir, "-lsah_hip", f"-Wl,-rpath,{libdir}"], timeout=600)
+    W, H, steps = 192, 108, 2
+    view = scene.SceneView.default(W, H)
+    keep = []
+    g = mesh.geometry(mesh.to_device(mesh.atrium(2).arrays()), keep)
+    shapes = {"color": ((H, W, 4), torch.uint8), "normals": ((H, W, 4), torch.int16), "data": ((H, W, 4), torch.uint8),
+              "emission": ((H, W, 4), torch.uint8), "depth": ((H, W), torch.float32)}
+    gb = {k: torch.zeros(s, dtype=t, device="cuda") for k, (s, t) in shapes.items()}
+    hip_ctx.gbuffer_render(g, view.gpu_data, images.gbuffer(gb))
+    torch.cuda.synchronize()
+    depth, normals = util.from_torch(gb["depth"], np.float32).reshape(H, W), util.from_torch(gb["normals"], np.uint16).reshape(H, W, 4)
+    rng = np.random.default_rng(12)
+    vols = [rng.uniform(-1, 1, (32, 32, 128, 4)).astype(np.float16) for _ in range(3)]
+    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
+    with open(inp, "wb") as f:
+        f.write(np.array([W, H, steps], np.uint32).tobytes())
+        f.write(normals.tobytes())
+        f.write(depth.tobytes())
+        for v in vols:
+            f.write(v.tobytes())
+    subprocess.check_call([exe, str(inp), str(outp)], timeout=300)
+    blob = open(outp, "rb").read()
+    off = 0
+
+    def take(n):
+        nonlocal off
+        off += n
+        return blob[off - n:off]
+    vd = _abi.ViewData.from_buffer_copy(take(C.sizeof(_abi.ViewData)))
+    mats = (_abi.LpvCascadeMatrices * 4).from_buffer_copy(take(4 * C.sizeof(_abi.LpvCascadeMatrices)))
+    n = 128 * 32 * 32 * 8
+    gv = np.frombuffer(take(n), np.uint16).reshape(32, 32, 128, 4)
+    got = [np.frombuffer(take(n), np.uint16).reshape(32, 32, 128, 4) for _ in range(3)]
+    want_gv = ggv.inject_scene_gv(depth, normals, vd, mats, 4, np.zeros((32, 32, 128, 4), np.uint16))
+    assert (want_gv != 0).any() and np.array_equal(gv, want_gv)
+    want = ggv.lpv_propagate_gv(vols, want_gv, steps, 4)
+    for c in range(3):
+        assert np.array_equal(got[c], want[c].view(np.uint16)), c

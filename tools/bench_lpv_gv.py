@@ -1,0 +1,84 @@
+"""Timings of the LPV geometry volume (include/sah_lpv_gv.h) on cuda:0, from HIP events around N back-to-back calls (after a warm-up):
+
+    python tools/bench_lpv_gv.py [--calls 200] [--gv-mode 1|2]
+
+  propagate_32       sah_lpv_propagate, 32 steps, 4 cascades (the reference's frame)
+  propagate_gv_32    sah_lpv_propagate_gv with a GV, 32 steps, 4 cascades
+  scene_gv_4k        sah_lpv_inject_scene_gv of a 3840 x 2160 G-buffer of the atrium, 4 cascades
+  rsm_gv_4c          sah_lpv_inject_rsm_gv, the 128^2 RSM of the atrium, 4 cascades in one call
+
+--gv-mode selects how the propagation uses the GV (the experiment switch SAH_LPV_GV_MODE: 1 factors precomputed once per call, the
+default; 2 the GV sampled in every step).  Prints one JSON line, milliseconds per call."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--gv-mode", type=int, default=1)
+    args = ap.parse_args()
+    os.environ["SAH_LPV_GV_MODE"] = str(args.gv_mode)  # (read by the library on its first propagation)
+    import numpy as np
+    import torch
+
+    from androidrenderer_amd import _abi, images, lib, mesh
+    from tests.test_lpv_inject import _hip_rsm, _rsm_desc, _setup
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import gen_golden_gv as ggv
+
+    torch.cuda.set_device(0)
+    ctx = lib.Context(0)
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    rgba16 = _abi.FORMAT_R16G16B16A16_SFLOAT
+    vol = lambda t: images.volume(t, rgba16)
+    rng = np.random.default_rng(1)
+    nc = 4
+    a_t = [torch.from_numpy(rng.uniform(-1, 1, (32, 32, 128, 4)).astype(np.float16).view(np.int16)).cuda() for _ in range(3)]
+    b_t = [torch.zeros_like(t) for t in a_t]
+    gv_t = torch.from_numpy(ggv.random_gv(rng, nc).view(np.int16)).cuda()
+    A, B, G = [vol(t) for t in a_t], [vol(t) for t in b_t], vol(gv_t)
+
+    W, H = 3840, 2160
+    view, sun, lpv = _setup(W, H)
+    keep = []
+    g = mesh.geometry(mesh.to_device(mesh.atrium(2).arrays()), keep)
+    shapes = {"color": ((H, W, 4), torch.uint8), "normals": ((H, W, 4), torch.int16), "data": ((H, W, 4), torch.uint8),
+              "emission": ((H, W, 4), torch.uint8), "depth": ((H, W), torch.float32)}
+    gb = {k: torch.zeros(s, dtype=t, device="cuda") for k, (s, t) in shapes.items()}
+    ctx.gbuffer_render(g, view.gpu_data, images.gbuffer(gb))
+    rsm = _hip_rsm(ctx, mesh.atrium().arrays(), sun, lpv)
+    dp, npl, rd = images.plane(gb["depth"], _abi.FORMAT_D32_SFLOAT), images.plane(gb["normals"], rgba16), _rsm_desc(rsm)
+    gv2 = torch.zeros((32, 32, 128, 4), dtype=torch.int16, device="cuda")
+    G2 = vol(gv2)
+
+    cases = {
+        "propagate_32": lambda: ctx.lpv_propagate(A, B, nc, 32),
+        "propagate_gv_32": lambda: ctx.lpv_propagate_gv(A, B, G, nc, 32),
+        "scene_gv_4k": lambda: ctx.lpv_inject_scene_gv(dp, npl, view.gpu_data, lpv.matrices, nc, G2),
+        "rsm_gv_4c": lambda: ctx.lpv_inject_rsm_gv(rd, lpv.matrices, 0, 4, nc, G2),
+    }
+    out = {"gv_mode": args.gv_mode, "calls": args.calls, "unit": "ms per call"}
+    for name, fn in cases.items():
+        for _ in range(10):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.calls):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out[name] = round(e0.elapsed_time(e1) / args.calls, 5)
+    out["gv_over_plain"] = round(out["propagate_gv_32"] / out["propagate_32"], 3)
+    ctx.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
