@@ -243,6 +243,7 @@ void sah_destroy(sah_ctx* ctx) {
     if (ctx->lpv_packed) (void)hipFree(ctx->lpv_packed);
     if (ctx->gv_keys) (void)hipFree(ctx->gv_keys);
     if (ctx->gv_factors) (void)hipFree(ctx->gv_factors);
+    if (ctx->ml_scratch) (void)hipFree(ctx->ml_scratch);
     if (ctx->irr32) (void)hipFree(ctx->irr32);
     if (ctx->colx_table) (void)hipFree(ctx->colx_table);
     if (ctx->tm_thresholds) (void)hipFree(ctx->tm_thresholds);

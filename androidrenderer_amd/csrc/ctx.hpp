@@ -52,6 +52,8 @@ struct sah_ctx {
     size_t gv_keys_bytes = 0;
     void* gv_factors = nullptr;        // device: the 30 occlusion factors per cell of sah_lpv_propagate_gv (lpv.hip: k_gv_factors)
     size_t gv_factors_bytes = 0;
+    void* ml_scratch = nullptr;        // device: sah_lpv_inject_emissive's keys, sequence indices, VPL pointers and blend sources (lpv_mesh_lights.hip)
+    size_t ml_scratch_bytes = 0;
     uint8_t* lpv_packed = nullptr;     // device: per-frame interleaved, zero-bordered copy of the three LPV volumes (lighting.hip)
     size_t lpv_packed_bytes = 0;
     uint32_t lpv_pack_generation = 0;  // sah_gi::lpv_generation the gather copy was built for (0: not reusable)

@@ -30,6 +30,44 @@ EXPORTS = ["sah_abi_version", "sah_status_string", "sah_last_error", "sah_create
 # the LPV geometry volume's entries: exported, declared in include/sah_lpv_gv.h (not sah_hip.h)
 GV_EXPORTS = ["sah_lpv_inject_rsm_gv", "sah_lpv_inject_scene_gv", "sah_lpv_propagate_gv"]
 
+# the LPV mesh lights' entries: exported, declared in include/sah_lpv_mesh_lights.h (not sah_hip.h)
+ML_EXPORTS = ["sah_mesh_point_cloud", "sah_lpv_emissive_vpls", "sah_lpv_inject_emissive"]
+POINT_CLOUD_ON_SURFACE = 1    # SAH_POINT_CLOUD_ON_SURFACE
+EMISSIVE_MATERIAL_ZERO = 1    # SAH_EMISSIVE_MATERIAL_ZERO
+LPV_EMISSIVE_MAX_ENTRIES = 1 << 24
+
+
+class EmissiveCloud(C.Structure):  # sah_emissive_cloud
+    _fields_ = [("vpls", C.c_void_p), ("count", C.c_uint32), ("primitive", C.c_uint32), ("bounds_min", C.c_float * 3), ("bounds_max", C.c_float * 3)]
+
+
+class LpvCascadeBounds(C.Structure):  # sah_lpv_cascade_bounds
+    _fields_ = [("min_bounds", C.c_float * 3), ("max_bounds", C.c_float * 3)]
+
+
+def mesh_point_cloud(positions, vertex_data, indices, first_index, index_count, vertex_offset, seed, flags=0):
+    """sah_mesh_point_cloud on host arrays (positions (N, 3) float32, vertex_data of mesh.VERTEX_DATA, indices uint32): returns
+    (positions (n, 3) float32, points of mesh.VERTEX_DATA, bounds_min, bounds_max)."""
+    import numpy as np
+    from . import mesh
+    lib = load()
+    pos = np.ascontiguousarray(positions, np.float32)
+    vd = np.ascontiguousarray(vertex_data)
+    idx = np.ascontiguousarray(indices, np.uint32)
+    count, lo, hi = C.c_uint32(0), (C.c_float * 3)(), (C.c_float * 3)()
+    args = (pos.ctypes.data if pos.size else None, vd.ctypes.data if vd.size else None, pos.shape[0], idx.ctypes.data if idx.size else None, idx.shape[0],
+            first_index, index_count, vertex_offset, seed, flags)
+    rc = lib.sah_mesh_point_cloud(*args, None, None, 0, C.byref(count), lo, hi)
+    if rc != _abi.SAH_OK:
+        raise SahError(rc, f"sah_mesh_point_cloud: {lib.sah_status_string(rc).decode()}")
+    out_pos = np.zeros((count.value, 3), np.float32)
+    out_vd = np.zeros(count.value, mesh.VERTEX_DATA)
+    if count.value:
+        rc = lib.sah_mesh_point_cloud(*args, out_pos.ctypes.data, out_vd.ctypes.data, count.value, C.byref(count), lo, hi)
+        if rc != _abi.SAH_OK:
+            raise SahError(rc, f"sah_mesh_point_cloud: {lib.sah_status_string(rc).decode()}")
+    return out_pos, out_vd, np.array(lo[:], np.float32), np.array(hi[:], np.float32)
+
 
 def load():
     """Loads the library (building is a separate, explicit step: python -m androidrenderer_amd.build)."""
@@ -114,6 +152,13 @@ def load():
                                           C.POINTER(_abi.Volume)]
     lib.sah_lpv_inject_scene_gv.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.POINTER(_abi.ViewData),
                                             C.POINTER(_abi.LpvCascadeMatrices), C.c_uint32, C.POINTER(_abi.Volume)]
+    lib.sah_mesh_point_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint64,
+                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
+                                         C.POINTER(C.c_float)]
+    lib.sah_lpv_emissive_vpls.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                          C.c_void_p]
+    lib.sah_lpv_inject_emissive.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.POINTER(EmissiveCloud), C.c_uint32,
+                                            C.POINTER(_abi.LpvCascadeMatrices), C.POINTER(LpvCascadeBounds), C.c_uint32, C.POINTER(_abi.Volume)]
     lib.sah_lpv_propagate_gv.argtypes = [C.c_void_p, C.POINTER(_abi.Volume), C.POINTER(_abi.Volume), C.POINTER(_abi.Volume), C.c_uint32, C.c_uint32]
     _lib = lib
     return lib
@@ -216,6 +261,17 @@ class Context:
         b = (_abi.Volume * 3)(*b_rgb)
         g = C.byref(geometry) if geometry is not None else C.POINTER(_abi.Volume)()
         self._check(self.lib.sah_lpv_propagate_gv(self.handle, a, b, g, num_cascades, steps))
+
+    def lpv_emissive_vpls(self, geometry, primitive_index, positions_ptr, points_ptr, num_points, flags, out_ptr):
+        """sah_lpv_emissive_vpls: geometry an _abi.SceneGeometry over device arrays; the three pointers are device addresses"""
+        self._check(self.lib.sah_lpv_emissive_vpls(self.handle, C.byref(geometry), primitive_index, C.c_void_p(positions_ptr), C.c_void_p(points_ptr),
+                                                   num_points, flags, C.c_void_p(out_ptr)))
+
+    def lpv_inject_emissive(self, geometry, clouds, cascades, bounds, num_cascades, a_rgb):
+        """sah_lpv_inject_emissive: clouds a sequence of EmissiveCloud, bounds an (LpvCascadeBounds * n) array"""
+        table = (EmissiveCloud * max(len(clouds), 1))(*clouds)
+        a = (_abi.Volume * 3)(*a_rgb)
+        self._check(self.lib.sah_lpv_inject_emissive(self.handle, C.byref(geometry), table, len(clouds), cascades, bounds, num_cascades, a))
 
     def sky_update_luts(self, transmittance, multiscattering, sky_view, light_vector):
         lv = (C.c_float * 3)(*[float(v) for v in light_vector])

@@ -208,6 +208,52 @@ def to_device(arrays, device="cuda"):
     return out
 
 
+def emissive_primitives(arrays):
+    """[(primitive index, ordinal of its index range)] of every primitive whose material is emissive — length(emission_factor.rgb) > 0
+    in fp32 or an emission texture (gltf_model.cpp:210-213, 264-276) — in primitive order.  Primitives drawing the same index range
+    (instances) share the ordinal: the reference builds one point cloud per mesh."""
+    f = np.float32
+    out, ranges = [], {}
+    mats, mt = arrays["materials"], arrays.get("material_textures")
+    textured = bool(arrays.get("textures")) and mt is not None
+    for i, p in enumerate(arrays["primitives"]):
+        mi = int(p["material"])
+        if mi >= len(mats):
+            continue
+        e = mats[mi]["emission_factor"].astype(f)
+        length = np.sqrt(f(f(f(e[0] * e[0]) + f(e[1] * e[1])) + f(e[2] * e[2])))
+        if not (length > 0 or (textured and int(mt[mi][3]) != _abi.TEXTURE_NONE)):
+            continue
+        key = (int(p["first_index"]), int(p["index_count"]), int(p["vertex_offset"]))
+        out.append((i, ranges.setdefault(key, len(ranges))))
+    return out
+
+
+def emissive_clouds(ctx, arrays, geometry, seed, flags=0, vpl_flags=0, device="cuda"):
+    """The mesh lights of a host mesh: the point cloud of every emissive primitive's index range (sah_mesh_point_cloud, seed + the
+    range's ordinal) and the primitive's VPL list (sah_lpv_emissive_vpls on `geometry`, the device scene of the same arrays).
+    Returns (records, keep): lib.EmissiveCloud per emissive primitive in ascending primitive index, ready for
+    Context.lpv_inject_emissive, and the device tensors they point to (their VPL lists are keep[i]['vpls'])."""
+    import torch
+    from . import lib
+    ranges, records, keep = {}, [], []
+    for prim, ordinal in emissive_primitives(arrays):
+        p = arrays["primitives"][prim]
+        if ordinal not in ranges:
+            pos, pts, lo, hi = lib.mesh_point_cloud(arrays["positions"], arrays["vertex_data"], arrays["indices"], int(p["first_index"]),
+                                                    int(p["index_count"]), int(p["vertex_offset"]), seed + ordinal, flags)
+            to_dev = lambda a: torch.from_numpy(np.frombuffer(a.tobytes(), np.uint8).copy()).to(device)
+            ranges[ordinal] = (pos, pts, lo, hi, to_dev(pos), to_dev(pts))
+        pos, pts, lo, hi, pos_t, pts_t = ranges[ordinal]
+        n = pos.shape[0]
+        vpls = torch.zeros((max(n, 1), 4), dtype=torch.int32, device=device)
+        if n:
+            ctx.lpv_emissive_vpls(geometry, prim, pos_t.data_ptr(), pts_t.data_ptr(), n, vpl_flags, vpls.data_ptr())
+        records.append(lib.EmissiveCloud(vpls.data_ptr(), n, prim, (C.c_float * 3)(*lo.tolist()), (C.c_float * 3)(*hi.tolist())))
+        keep.append({"vpls": vpls, "positions": pos, "points": pts, "bounds": (lo, hi), "device": (pos_t, pts_t)})
+    return records, keep
+
+
 # materials of synth.atrium_gbuffer: floor, long walls, end walls, gallery slabs, columns, lamps
 _ATRIUM_BASE = [(0.45, 0.40, 0.33), (0.60, 0.52, 0.42), (0.50, 0.30, 0.22), (0.55, 0.55, 0.50), (0.62, 0.58, 0.50), (0.9, 0.8, 0.6)]
 _ATRIUM_ROUGH = [0.65, 0.8, 0.7, 0.5, 0.4, 0.3]

@@ -244,6 +244,8 @@ class LpvCascades:
         self.num_cells, self.base_cell_size, self.num_cascades = num_cells, base_cell_size, num_cascades
         self.behind = behind_camera_percent
         self.matrices = (_abi.LpvCascadeMatrices * num_cascades)()
+        from .lib import LpvCascadeBounds
+        self.bounds = (LpvCascadeBounds * num_cascades)()  # :514-515, snapped offset -+ size / 2 (the mesh lights' selection)
 
     def update_cascade_transforms(self, view, light):
         offset_scale = f32(0.5) - f32(self.behind)
@@ -269,6 +271,8 @@ class LpvCascades:
             rsm_proj = ortho(-half, half, -half, half, 0.0, pull * f32(2))
             rsm_vp = mat_mul(rsm_proj, rsm_view)
             m = self.matrices[ci]
+            self.bounds[ci].min_bounds[:] = [float(x) for x in (snapped - half).astype(f32)]
+            self.bounds[ci].max_bounds[:] = [float(x) for x in (snapped + half).astype(f32)]
             _fill(m.rsm_vp, rsm_vp)
             _fill(m.inverse_rsm_vp, mat_inverse(rsm_vp))
             _fill(m.world_to_cascade, w2c)

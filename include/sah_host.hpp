@@ -28,6 +28,7 @@
 
 #include "sah_hip.h"
 #include "sah_lpv_gv.h"
+#include "sah_lpv_mesh_lights.h"
 
 namespace sah {
 
@@ -678,6 +679,86 @@ struct RenderScene {  // the slice of RenderCore/render/render_scene.hpp the hot
     ProceduralSky sky;
     sah_scene_geometry geometry{};  // device-side mesh pool + primitive buffer (render_scene.hpp: get_meshes(), get_primitive_buffer())
     RaytracingScene raytracing_scene{*this};
+    RenderScene() = default;
+    RenderScene(const RenderScene&) = delete;  // owns the emissive clouds' device buffers
+    RenderScene& operator=(const RenderScene&) = delete;
+    ~RenderScene() {
+        for (auto& c : emissive_clouds) {
+            if (c.positions) (void)hipFree(c.positions);
+            if (c.points) (void)hipFree(c.points);
+            if (c.vpls) (void)hipFree(c.vpls);
+        }
+    }
+    // The host copy of the mesh pool that MeshStorage::add_mesh builds the point clouds from (mesh_storage.cpp:140-166).
+    struct HostMesh {
+        const float* positions;
+        const sah_vertex_data* vertex_data;
+        uint32_t num_vertices;
+        const uint32_t* indices;
+        uint32_t num_indices;
+        const sah_primitive* primitives;
+        uint32_t num_primitives;
+        const sah_material* materials;
+        uint32_t num_materials;
+        const sah_material_textures* material_textures;  // NULL: constant texels only
+        bool has_textures;
+    };
+    struct EmissiveCloud {  // one emissive primitive's cloud and VPL list (MeshPrimitive::emissive_points_buffer)
+        float* positions = nullptr;
+        sah_vertex_data* points = nullptr;
+        sah_packed_vpl* vpls = nullptr;
+        sah_emissive_cloud record{};
+    };
+    std::vector<EmissiveCloud> emissive_clouds;  // ascending primitive index: the order of solid_primitives
+    // RenderScene::generate_emissive_point_clouds (render_scene.cpp:162-174, 255-310): once per NEW emissive primitive — those at or beyond
+    // the ones already looked at — a point cloud per index range (sah_mesh_point_cloud, seed + the range's ordinal among the emissive
+    // ranges; instances share it, as meshes do in the reference) and the primitive's VPL list, recorded as one pass per primitive.
+    // `mesh` describes the same arrays as `geometry`.  Moving a primitive later does not regenerate its cloud, as in the reference.
+    void generate_emissive_point_clouds(RenderGraph& graph, const HostMesh& mesh, uint64_t seed, uint32_t flags = 0) {
+        for (uint32_t p = emissive_seen; p < mesh.num_primitives; p++) {
+            const sah_primitive& prim = mesh.primitives[p];
+            if (prim.material >= mesh.num_materials) continue;
+            const float* e = mesh.materials[prim.material].emission_factor;
+            const bool textured = mesh.has_textures && mesh.material_textures && mesh.material_textures[prim.material].emission != SAH_TEXTURE_NONE;
+            if (!(std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]) > 0.0f) && !textured) continue;
+            const std::array<int64_t, 3> range = {prim.first_index, prim.index_count, prim.vertex_offset};
+            const size_t ordinal = std::find(emissive_ranges.begin(), emissive_ranges.end(), range) - emissive_ranges.begin();
+            if (ordinal == emissive_ranges.size()) emissive_ranges.push_back(range);
+            EmissiveCloud cloud;
+            uint32_t n = 0;
+            auto cloud_of = [&](float* pos, sah_vertex_data* pts, uint32_t cap) {
+                return sah_mesh_point_cloud(mesh.positions, mesh.vertex_data, mesh.num_vertices, mesh.indices, mesh.num_indices, prim.first_index,
+                                            prim.index_count, prim.vertex_offset, seed + ordinal, flags, pos, pts, cap, &n, cloud.record.bounds_min,
+                                            cloud.record.bounds_max);
+            };
+            if (cloud_of(nullptr, nullptr, 0) != SAH_OK) throw std::runtime_error("generate_emissive_point_clouds: bad mesh range");
+            std::vector<float> pos((size_t)n * 3);
+            std::vector<sah_vertex_data> pts(n);
+            if (n && cloud_of(pos.data(), pts.data(), n) != SAH_OK) throw std::runtime_error("generate_emissive_point_clouds: point cloud");
+            if (n && (hipMalloc((void**)&cloud.positions, pos.size() * sizeof(float)) != hipSuccess ||
+                      hipMalloc((void**)&cloud.points, pts.size() * sizeof(sah_vertex_data)) != hipSuccess ||
+                      hipMalloc((void**)&cloud.vpls, (size_t)n * sizeof(sah_packed_vpl)) != hipSuccess ||
+                      hipMemcpy(cloud.positions, pos.data(), pos.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+                      hipMemcpy(cloud.points, pts.data(), pts.size() * sizeof(sah_vertex_data), hipMemcpyHostToDevice) != hipSuccess))
+                throw std::runtime_error("generate_emissive_point_clouds: device buffers");
+            cloud.record.vpls = cloud.vpls;
+            cloud.record.count = n;
+            cloud.record.primitive = p;
+            emissive_clouds.push_back(cloud);
+            const EmissiveCloud& c = emissive_clouds.back();
+            if (n)
+                graph.add_pass(hip_pass("Generate emissive mesh VPLs", [this, c, p, n](sah_ctx* ctx) {
+                                    return sah_lpv_emissive_vpls(ctx, &geometry, p, c.positions, c.points, n, 0, c.vpls);
+                                }));
+        }
+        emissive_seen = std::max(emissive_seen, mesh.num_primitives);
+    }
+
+private:
+    uint32_t emissive_seen = 0;
+    std::vector<std::array<int64_t, 3>> emissive_ranges;
+
+public:
     DirectionalLight& get_sun_light() { return sun; }
     ProceduralSky& get_sky() { return sky; }
     RaytracingScene& get_raytracing_scene() { return raytracing_scene; }
@@ -734,6 +815,19 @@ public:
     enum class GvBuildMode { Disable, DepthBuffers };
     GvBuildMode gv_build_mode = GvBuildMode::Disable;
     bool use_gv = false;  // propagate with use_gv = 1 (sah_lpv_propagate_gv, include/sah_lpv_gv.h)
+    // r.GI.LPV.MeshLight.Enable (light_propagation_volume.cpp:73-75) defaults to 1 in the reference; here it defaults to off, so the default
+    // frame records the passes it always did.  When on, inject_indirect_sun_light ends with inject_emissive_point_clouds (:223-236).
+    bool mesh_lights = false;
+    // light_propagation_volume.cpp:787-834: every cascade's selected emissive clouds, one call (include/sah_lpv_mesh_lights.h)
+    void inject_emissive_point_clouds(RenderGraph& graph, const RenderScene& scene) {
+        graph.add_pass(hip_pass("Emissive mesh injection", [this, &scene](sah_ctx* ctx) {
+                            std::vector<sah_emissive_cloud> clouds;
+                            for (const auto& c : scene.emissive_clouds) clouds.push_back(c.record);
+                            const sah_volume a[3] = {vol[0]->desc, vol[1]->desc, vol[2]->desc};
+                            return sah_lpv_inject_emissive(ctx, &scene.geometry, clouds.data(), (uint32_t)clouds.size(), cascades.data(), bounds.data(),
+                                                           num_cascades, a);
+                        }));
+    }
     void inject_indirect_sun_light(RenderGraph& graph, const RenderScene& scene) {
         graph.add_pass(hip_pass("Render RSM", [this, &scene](sah_ctx* ctx) {
                             const sah_rsm_targets rsm = {rsm_flux->desc, rsm_normals->desc, rsm_depth->desc};
@@ -753,6 +847,7 @@ public:
                                 const sah_rsm_targets rsm = {rsm_flux->desc, rsm_normals->desc, rsm_depth->desc};
                                 return sah_lpv_inject_rsm_gv(ctx, &rsm, cascades.data(), 0, num_cascades, num_cascades, &vol[6]->desc);
                             }));
+        if (mesh_lights) inject_emissive_point_clouds(graph, scene);
     }
     void update_cascade_transforms(const SceneView& view, const DirectionalLight& light) {
         const auto& dir = light.get_constants().direction_and_tan_size;
@@ -773,6 +868,10 @@ public:
             Vec3 centre{};
             for (int i = 0; i < 3; i++) centre[i] = std::round((p[i] + f[i] * (size * (0.5f - 0.1f))) / (cell * 2.f)) * cell * 2.f;
             const float pull = size * 2.f, half = size / 2.f;
+            for (int i = 0; i < 3; i++) {  // :514-515
+                bounds[c].min_bounds[i] = centre[i] - half;
+                bounds[c].max_bounds[i] = centre[i] + half;
+            }
             const Mat4 rsm_view = look_at({centre[0] - light_dir[0] * pull, centre[1] - light_dir[1] * pull, centre[2] - light_dir[2] * pull}, centre, {0.f, 1.f, 0.f});
             const Mat4 rsm_vp = mat_mul(ortho(-half, half, -half, half, 0.f, pull * 2.f), rsm_view);
             std::memcpy(cascades[c].rsm_vp, rsm_vp.data(), 64);
@@ -820,6 +919,7 @@ public:
     }
     void draw_debug_overlays(RenderGraph&, const SceneView&, const GBuffer&, TextureHandle) override {}  // GV / VPL visualisers: debug views, not on the path
     const sah_lpv_cascade_matrices* get_cascade_matrices() const { return cascades.data(); }
+    const sah_lpv_cascade_bounds* get_cascade_bounds() const { return bounds.data(); }
     TextureHandle get_volume(int channel, bool b = false) const { return vol[channel + (b ? 3 : 0)]; }
     TextureHandle get_geometry_volume() const { return vol[6]; }
 
@@ -831,6 +931,7 @@ private:
     sah_packed_vpl* vpl_lists = nullptr;
     uint32_t* vpl_counts = nullptr;
     std::array<sah_lpv_cascade_matrices, 4> cascades{};
+    std::array<sah_lpv_cascade_bounds, 4> bounds{};
 };
 
 // Probe scheduling of the irradiance cache (CPU side) — RenderCore/render/gi/irradiance_cache.hpp:49-105,267-279 and
