@@ -313,6 +313,17 @@ int sah_debug_copy_rebuilds(sah_ctx* ctx, uint32_t out[2]) {
     return SAH_OK;
 }
 
+// Debug / test hook: which kernel and which of its branches the last sah_lighting call of the context chose — recorded host side while the
+// call digests its arguments (no device work, no synchronisation).  All zero before the first call and after a call that failed validation.
+//   [0] kernel family: 0 general, 1 fast (+ fix-up), 2 tiled      [1] pixels per thread (0: tiled)      [2] pos_div_nr
+//   [3] ncasc_pow2 (0 without an LPV gather)      [4] row_magic != 0      [5] sky_ratio      [6] leading sky workgroups
+//   [7] tiled_fast_geom      [8] tiled_fast_lpv      [9] repack (k_lpv_pack runs in front of the kernel)      [10] column / row table rebuilt
+int sah_debug_lighting_dispatch(sah_ctx* ctx, uint32_t out[11]) {
+    if (!ctx || !out) return SAH_ERR_INVALID_ARGUMENT;
+    memcpy(out, ctx->last_dispatch, sizeof(ctx->last_dispatch));
+    return SAH_OK;
+}
+
 int sah_sync(sah_ctx* ctx) {
     if (!ctx) return SAH_ERR_INVALID_ARGUMENT;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -326,6 +337,7 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
     SAH_RANGE();
     using namespace sah;
     if (!ctx || !d) return SAH_ERR_INVALID_ARGUMENT;
+    memset(ctx->last_dispatch, 0, sizeof(ctx->last_dispatch));
     if (!d->gbuffer || !d->lit || !d->view) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "gbuffer, lit and view are required");
     const sah_gbuffer& g = *d->gbuffer;
     const uint32_t W = d->lit->width, H = d->lit->height;
@@ -626,7 +638,9 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
         fast.seg_count = (uint16_t*)((uint8_t*)ctx->list + codes_bytes);
         fast.num_segments = nseg;
         fast.seg_stride = seg_stride;
-        if (gi_kind == SAH_GI_LPV) {
+        // (not for an empty row range — a shard plan may hand a rank no rows: the launcher returns before k_lpv_pack, and a copy recorded as
+        // built here would be gathered from, unbuilt, by the next call with the same generation)
+        if (gi_kind == SAH_GI_LPV && r1 > r0) {
             if (const int rc = prepare_lpv_copy(); rc != SAH_OK) return rc;
         }
         fast.sky_enabled = sky.enabled;
@@ -657,6 +671,7 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
     // per-column numerators of the view-space x and per-row ones of y (IEEE divides per thread / per pixel otherwise; the tiled kernel reads
     // them too): a function of the extent, the render resolution
     // and two entries of the inverse projection — rebuilt when one of them changes
+    uint32_t dispatch[11] = {};  // sah_debug_lighting_dispatch
     if ((use_fast && ppt == 4 && (sun_mode != SAH_SHADOW_MODE_OFF || gi_kind == SAH_GI_LPV)) || tiled_fast_geom) {
         const float key[7] = {a.res[0], fast.p0, fast.p12, a.res[1], fast.p5, fast.p13, (float)H};
         const uint32_t stride = (W + 63u) & ~63u, row_stride = (H + 63u) & ~63u;
@@ -671,15 +686,33 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
             ctx->cache_epoch++;
             ctx->colx_width = 0;
         }
-        if (ctx->colx_width != W || memcmp(key, ctx->colx_key, sizeof(key)) != 0) {
+        const bool table_rebuilt = ctx->colx_width != W || memcmp(key, ctx->colx_key, sizeof(key)) != 0;
+        if (table_rebuilt) {
             HIP_TRY(ctx, launch_colx_table(a, fast, ctx->colx_table, stride, row_stride, ctx->stream));
             ctx->cache_epoch++;
             ctx->colx_width = W;
             memcpy(ctx->colx_key, key, sizeof(key));
         }
+        dispatch[10] = table_rebuilt ? 1u : 0u;
         fast.colx_tab = ctx->colx_table;
         fast.colx_stride = stride;
         fast.rowy_stride = row_stride;
+    }
+    {
+        const bool tiled = a.num_lights != 0 || gi_kind == SAH_GI_CACHE || gi_kind == SAH_GI_RTGI;  // (launch_lighting's own test)
+        const uint64_t blocks = ((uint64_t)(W / (uint32_t)ppt) * (r1 - r0) + 255) / 256;
+        dispatch[0] = tiled ? 2u : (use_fast ? 1u : 0u);
+        dispatch[1] = tiled ? 0u : (uint32_t)ppt;
+        dispatch[2] = (use_fast || tiled_fast_geom) ? fast.pos_div_nr : 0u;
+        dispatch[3] = ((use_fast && gi_kind == SAH_GI_LPV) || tiled_fast_lpv) ? fast.ncasc_pow2 : 0u;
+        dispatch[4] = (use_fast && fast.row_magic != 0u) ? 1u : 0u;
+        dispatch[5] = use_fast ? fast.sky_ratio : 0u;
+        // (lighting.hip's launcher: the sky workgroups lead the grid, one per sky_ratio surface workgroups)
+        dispatch[6] = (use_fast && sky.enabled && fast.sky_first && blocks) ? (uint32_t)((blocks + fast.sky_ratio - 1u) / fast.sky_ratio) : 0u;
+        dispatch[7] = tiled_fast_geom ? 1u : 0u;
+        dispatch[8] = tiled_fast_lpv ? 1u : 0u;
+        dispatch[9] = fast.repack;
+        memcpy(ctx->last_dispatch, dispatch, sizeof(dispatch));
     }
     HIP_TRY(ctx, launch_lighting(a, csm, lpv, cache, rtgi, sky, (use_fast || tiled_fast_geom) ? &fast : nullptr, (int)sun_mode, (int)gi_kind, ppt,
                                  (d->flags & SAH_LIGHTING_BRUTE_FORCE_LIGHTS) != 0, ctx->stream));

@@ -91,6 +91,7 @@ def load():
     lib.sah_sync.argtypes = [C.c_void_p]
     lib.sah_debug_deferred_pixels.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.sah_debug_copy_rebuilds.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.sah_debug_lighting_dispatch.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     lib.sah_lighting.argtypes = [C.c_void_p, C.POINTER(_abi.LightingDesc)]
     lib.sah_copy_scene.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane)]
     lib.sah_copy_scene_rows.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
@@ -203,6 +204,19 @@ class Context:
         out = (C.c_uint32 * 2)()
         self._check(self.lib.sah_debug_copy_rebuilds(self.handle, out))
         return int(out[0]), int(out[1])
+
+    DISPATCH_FIELDS = ("family", "ppt", "pos_div_nr", "ncasc_pow2", "row_magic", "sky_ratio", "sky_workgroups", "tiled_fast_geom", "tiled_fast_lpv",
+                       "repack", "table_rebuilt")
+
+    def lighting_dispatch(self):
+        """Test hook: what the last lighting() call of this context decided, as a dict — family ('general' / 'fast' / 'tiled'), ppt, pos_div_nr,
+        ncasc_pow2, row_magic (1: the multiply-high row split), sky_ratio, sky_workgroups (leading the grid), tiled_fast_geom, tiled_fast_lpv,
+        repack, table_rebuilt.  Recorded on the host: no device work, no synchronisation."""
+        out = (C.c_uint32 * len(self.DISPATCH_FIELDS))()
+        self._check(self.lib.sah_debug_lighting_dispatch(self.handle, out))
+        rep = {k: int(v) for k, v in zip(self.DISPATCH_FIELDS, out)}
+        rep["family"] = ("general", "fast", "tiled")[rep["family"]]
+        return rep
 
     def sync(self):
         self._check(self.lib.sah_sync(self.handle))

@@ -1,0 +1,504 @@
+"""The case list of the Lighting parity matrix and the frame builder behind it — shared by tests/test_lighting_matrix_gpu.py (the HIP library
+against the oracle, every case on the kernel branch it names) and tests/test_lighting_matrix_cpu.py (the oracle alone: every case shades what
+it claims to shade, and the host-side facts the GPU test relies on hold).
+
+A case is a point of the uniform blocks: a camera, a sun, an LPV layout, a memory layout of the planes — the quantities the fast path's proofs
+(api.cpp: detect_fast_path) quantify over, which util.LightingFrame alone holds at one value each."""
+import math
+
+import numpy as np
+
+from androidrenderer_amd import _abi, scene, synth
+from tests import util
+
+SENTINEL = 0xA5  # byte in the padding of a pitched plane / volume, and in rows of `lit` a call must not write
+
+PLANE_FORMATS = {"color": _abi.FORMAT_R8G8B8A8_SRGB, "normals": _abi.FORMAT_R16G16B16A16_SFLOAT, "data": _abi.FORMAT_R8G8B8A8_UNORM,
+                 "emission": _abi.FORMAT_R8G8B8A8_SRGB, "depth": _abi.FORMAT_D32_SFLOAT, "ao": _abi.FORMAT_R32_SFLOAT,
+                 "shadow_mask": _abi.FORMAT_R32_SFLOAT, "lit": _abi.FORMAT_R16G16B16A16_SFLOAT}
+VOLUME_FORMATS = {"lpv_r": _abi.FORMAT_R16G16B16A16_SFLOAT, "lpv_g": _abi.FORMAT_R16G16B16A16_SFLOAT, "lpv_b": _abi.FORMAT_R16G16B16A16_SFLOAT}
+
+
+class Pitched:
+    """A plane (H, W[, C]) or volume (D, H, W[, C]) stored in a backing buffer with a row pitch (and slice pitch) larger than the payload and an
+    optional byte offset of its base; every byte that is not payload holds SENTINEL.  Works on numpy arrays and on torch tensors alike.  The
+    descriptor is built by hand: images.plane() rightly refuses anything that is not tightly packed."""
+
+    def __init__(self, a, fmt, dims, row_pad=0, offset=0, slice_pad=0):
+        self.is_np = isinstance(a, np.ndarray)
+        self.logical, self.fmt, self.dims, self.offset = a, fmt, dims, offset
+        bpp = _abi.FORMAT_BPP[fmt]
+        shape = tuple(a.shape)
+        self.extent = shape[:dims]
+        w = shape[dims - 1]
+        h = shape[dims - 2]
+        d = shape[0] if dims == 3 else 1
+        self.row_bytes = w * bpp
+        self.row_pitch = self.row_bytes + row_pad
+        self.slice_pitch = h * self.row_pitch + slice_pad
+        size = offset + d * self.slice_pitch
+        self._shape, self._strides = (d, h, self.row_bytes), (self.slice_pitch, self.row_pitch, 1)
+        if self.is_np:
+            self.backing = np.full(size, SENTINEL, np.uint8)
+            mask = np.zeros(size, bool)
+            self._payload(mask)[...] = True
+            self.padding = ~mask
+            self._payload(self.backing)[...] = np.ascontiguousarray(a).view(np.uint8).reshape(self._shape)
+        else:
+            import torch
+            self.backing = torch.full((size,), SENTINEL, dtype=torch.uint8, device=a.device)
+            mask = torch.zeros(size, dtype=torch.bool, device=a.device)
+            self._payload(mask)[...] = True
+            self.padding = ~mask
+            self._payload(self.backing)[...] = a.contiguous().view(torch.uint8).reshape(self._shape)
+
+    def _payload(self, buf):
+        if self.is_np:
+            return np.lib.stride_tricks.as_strided(buf[self.offset:], self._shape, tuple(s * buf.itemsize for s in self._strides))
+        import torch
+        return torch.as_strided(buf, self._shape, self._strides, self.offset)
+
+    @property
+    def ptr(self):
+        return (self.backing.ctypes.data if self.is_np else self.backing.data_ptr()) + self.offset
+
+    def plane(self):
+        assert self.dims == 2
+        return _abi.Plane(self.ptr, self.extent[1], self.extent[0], self.row_pitch, self.fmt)
+
+    def volume(self):
+        assert self.dims == 3
+        return _abi.Volume(self.ptr, self.extent[2], self.extent[1], self.extent[0], self.row_pitch, self.slice_pitch, self.fmt)
+
+    def read(self, dtype):
+        """the payload as a tight numpy array of `dtype`, in the logical array's shape"""
+        p = self._payload(self.backing)
+        p = np.ascontiguousarray(p) if self.is_np else p.contiguous().cpu().numpy()
+        return p.view(dtype).reshape(tuple(self.logical.shape))
+
+    def padding_intact(self):
+        return bool((self.backing[self.padding] == SENTINEL).all())
+
+
+# ---- view edits: a raw ViewData edited in place, after the camera's own update_transforms() -------------------------------------------
+
+def _edit_plus_zero(gpu):
+    # np.linalg.inv gives -0.0 in both entries for every camera without jitter (measured; whatever it gives, the case SETS them): the
+    # fast kernel's shared-reciprocal divide requires +0
+    gpu.inverse_projection[12] = 0.0
+    gpu.inverse_projection[13] = 0.0
+
+
+def _edit_ortho(gpu):
+    m = scene.ortho(-8.0, 8.0, -4.5, 4.5, 0.1, 40.0)
+    for i, v in enumerate(scene.mat_inverse(m).reshape(-1)):
+        gpu.inverse_projection[i] = float(v)
+    for i, v in enumerate(m.reshape(-1)):
+        gpu.projection[i] = float(v)
+    _edit_plus_zero(gpu)  # (so that inverse_projection[10] != 0 alone is what switches the shared-reciprocal divide off)
+
+
+def _edit_p4(gpu):
+    gpu.inverse_projection[4] = 1e-3
+
+
+def _edit_v3(gpu):
+    gpu.inverse_view[3] = 1e-3
+
+
+def _edit_far_position(gpu):
+    gpu.view[12] = -float(2 ** 41)  # (the camera position the shaders use is -view[3].xyz)
+
+
+def _edit_p0_tiny(gpu):
+    _edit_plus_zero(gpu)
+    gpu.inverse_projection[0] = float(2.0 ** -17)
+
+
+VIEW_EDITS = {"plus_zero": _edit_plus_zero, "ortho": _edit_ortho, "p4": _edit_p4, "v3": _edit_v3, "far_position": _edit_far_position,
+              "p0_tiny": _edit_p0_tiny}
+
+# ---- cameras ----------------------------------------------------------------------------------------------------------------------------
+# position, yaw / pitch (degrees), fov (degrees), near plane, jitter (pixels), render resolution as a fraction of the extent, view edit,
+# and `atrium_eye`: where the atrium is ray-cast from when the camera itself stands outside it (the G-buffer is the atrium moved with the camera)
+DEFAULT_CAMERA = dict(position=(-7.0, 1.0, 0.0), yaw=90.0, pitch=0.0, fov=75.0, near=0.05, jitter=(0.0, 0.0), res_scale=1.0, edit=None, atrium_eye=None)
+CAMERAS = {
+    "default": {},
+    "plus_zero": dict(edit="plus_zero"),
+    "jitter": dict(jitter=(0.37, -0.21)),
+    "yaw37": dict(position=(3.5, 4.25, -2.0), yaw=37.0, pitch=-20.0, fov=60.0, near=0.1),
+    "down": dict(position=(0.0, 12.0, 0.0), pitch=-80.0, fov=100.0),
+    "up": dict(position=(0.0, 1.0, 0.0), yaw=180.0, pitch=70.0, fov=40.0, near=0.5),
+    "far": dict(position=(10000.5, -300.25, 70000.0), atrium_eye=(-7.0, 1.0, 0.0)),
+    "fov5": dict(fov=5.0, near=1.0),
+    "halfres": dict(res_scale=0.5),
+}
+
+
+def make_view(width, height, position=(-7.0, 1.0, 0.0), yaw=90.0, pitch=0.0, fov=75.0, near=0.05, jitter=(0.0, 0.0), res_scale=1.0, edit=None,
+              atrium_eye=None, res=None):
+    v = scene.SceneView()
+    v.rotate(math.radians(pitch), math.radians(yaw))
+    v.set_position(position)
+    if res is None:
+        res = (width * res_scale, height * res_scale)
+    v.set_render_resolution(res[0], res[1])
+    v.set_perspective_projection(fov, float(width) / float(height), near)
+    v.jitter = np.array(jitter, dtype=np.float32)
+    v.update_transforms()
+    if tuple(jitter) == (0.0, 0.0):
+        # without jitter both entries are zeros whose SIGN decides a kernel branch (pos_div_nr needs +0).  np.linalg.inv happens to give -0.0;
+        # the cases do not depend on that: every camera states the sign — -0.0 here, +0.0 by the plus_zero / ortho / p0_tiny edits
+        assert v.gpu_data.inverse_projection[12] == 0.0 and v.gpu_data.inverse_projection[13] == 0.0
+        v.gpu_data.inverse_projection[12] = -0.0
+        v.gpu_data.inverse_projection[13] = -0.0
+    if edit:
+        VIEW_EDITS[edit](v.gpu_data)
+    return v
+
+
+class MatrixFrame(util.LightingFrame):
+    """util.LightingFrame with the view, the sun, the LPV layout and the memory layout of its planes settable.  After a change of view or sun
+    the shadow cascades and the LPV transforms are refitted, as the renderer does every frame."""
+
+    def __init__(self, width, height, camera=None, sun_dir=None, sun_color=None, lpv=None, pitch=None, seed=1, flavour="random", **kw):
+        self.flavour, self.seed = flavour, seed
+        self.shadowmap_res = kw.get("shadowmap_res", 256)
+        self.pitch = dict(pitch or {})  # key -> dict(row_pad=, offset=, slice_pad=)
+        self.lpv_exposure = None
+        self.camera = dict(DEFAULT_CAMERA)
+        super().__init__(width, height, seed=seed, flavour=flavour, **kw)
+        if sun_dir is not None or sun_color is not None:
+            self.set_sun(sun_dir, sun_color, refit=False)
+        if lpv:
+            self.set_lpv_layout(refit=False, **lpv)
+        # (always through make_view, which states the sign of the zeros in the inverse projection; the default camera is SceneView.default's,
+        # so the G-buffer the base class made stands)
+        self.set_camera(regenerate=bool(camera), **(camera or {}))  # (refits)
+
+    # -- setters
+    def set_camera(self, regenerate=True, **camera):
+        self.camera = dict(DEFAULT_CAMERA, **camera)
+        self.view = make_view(self.width, self.height, **self.camera)
+        if regenerate:
+            if self.flavour == "atrium":
+                cast = self.view
+                if self.camera["atrium_eye"] is not None:
+                    cast = make_view(self.width, self.height, **dict(self.camera, position=self.camera["atrium_eye"], edit=None))
+                g = synth.atrium_gbuffer(self.width, self.height, cast, self.seed)
+            else:
+                g = synth.random_gbuffer(self.width, self.height, self.seed, z_near=self.camera["near"])
+            self.arrays.update(g)
+        self.refit()
+
+    def set_sun(self, direction=None, color=None, refit=True):
+        if direction is not None:
+            self.sun.set_direction(direction)
+        if color is not None:
+            self.sun.set_color(list(color) + [0.0] * (4 - len(color)))
+        if refit:
+            self.refit()
+
+    def set_lpv_layout(self, num_cascades=4, cell=0.25, behind=0.1, exposure=None, refit=True):
+        assert self.gi_kind == _abi.GI_LPV
+        self.lpv = scene.LpvCascades(base_cell_size=cell, num_cascades=num_cascades, behind_camera_percent=behind)
+        if num_cascades != getattr(self, "lpv_num_cascades", 4):
+            self.lpv_num_cascades = num_cascades
+            r, g, b = synth.lpv_volumes(num_cascades, self.seed + 500)  # volumes of matching width: (32 * cascades) x 32 x 32
+            self.arrays["lpv_r"], self.arrays["lpv_g"], self.arrays["lpv_b"] = r, g, b
+        self.lpv_exposure = exposure
+        if refit:
+            self.refit()
+
+    def refit(self):
+        with np.errstate(all="ignore"):  # (a vertical sun: look_at's up vector is parallel to the view axis, NaN matrices — as glm::lookAt gives)
+            if self.sun_mode == _abi.SHADOW_MODE_CSM:
+                self.sun.update_shadow_cascades(self.view, resolution=self.shadowmap_res)
+            if self.lpv is not None:
+                self.lpv.update_cascade_transforms(self.view, self.sun)
+
+    # -- memory layout
+    def _wrap(self, k, a):
+        spec = self.pitch.get(k)
+        if spec is None:
+            return a
+        if k in VOLUME_FORMATS:
+            return Pitched(a, VOLUME_FORMATS[k], 3, **spec)
+        return Pitched(a, PLANE_FORMATS[k], 2, **spec) if k in PLANE_FORMATS else a
+
+    def host_arrays(self):
+        return {k: self._wrap(k, v) for k, v in self.arrays.items()}
+
+    def device_arrays(self, device="cuda"):
+        return {k: self._wrap(k, util.to_torch(v, device)) for k, v in self.arrays.items()}
+
+    def describe(self, arrays, lit):
+        import ctypes as C
+        from androidrenderer_amd import images
+        tight = {k: (v.logical if isinstance(v, Pitched) else v) for k, v in arrays.items()}
+        d32 = tight.pop("shadowmap") if "shadowmap" in tight and str(tight["shadowmap"].dtype).endswith("float32") else None
+        d, keep = super().describe(tight, lit.logical if isinstance(lit, Pitched) else lit)
+        keep += [arrays, lit]
+        if d32 is not None:  # the same depths as a D32_SFLOAT array
+            sm = images.volume(d32, _abi.FORMAT_D32_SFLOAT)
+            d.shadowmap = C.pointer(sm)
+            keep.append(sm)
+        gb = d.gbuffer.contents
+        for k in ("color", "normals", "data", "emission", "depth"):
+            if isinstance(arrays[k], Pitched):
+                setattr(gb, k, arrays[k].plane())
+        if isinstance(lit, Pitched):
+            d.lit.contents = lit.plane()
+        if isinstance(arrays.get("ao"), Pitched):
+            d.ao.contents = arrays["ao"].plane()
+        if isinstance(arrays.get("shadow_mask"), Pitched):
+            d.shadow_mask.contents = arrays["shadow_mask"].plane()
+        if self.gi_kind == _abi.GI_LPV:
+            gi = d.gi.contents
+            for k, field in (("lpv_r", "lpv_red"), ("lpv_g", "lpv_green"), ("lpv_b", "lpv_blue")):
+                if isinstance(arrays[k], Pitched):
+                    setattr(gi, field, arrays[k].volume())
+            if self.lpv_exposure is not None:
+                gi.lpv_exposure = self.lpv_exposure
+        return d, keep
+
+    def _pitched(self, arrays, lit):
+        return [v for v in list(arrays.values()) + [lit] if isinstance(v, Pitched)]
+
+    def run_oracle(self):
+        import ctypes as C
+        arrays = self.host_arrays()
+        lit = self._wrap("lit", np.zeros((self.height, self.width, 4), dtype=np.uint16))
+        d, keep = self.describe(arrays, lit)
+        rc = util.oracle().orc_lighting(C.byref(d))
+        assert rc == 0, rc
+        assert all(p.padding_intact() for p in self._pitched(arrays, lit)), "the oracle wrote into the padding of a pitched plane"
+        return lit.read(np.uint16) if isinstance(lit, Pitched) else lit
+
+    def run_hip(self, ctx, dev=None):
+        import torch
+        dev = dev or self.device_arrays()
+        lit = self._wrap("lit", torch.zeros((self.height, self.width, 4), dtype=torch.int16, device="cuda"))
+        d, keep = self.describe(dev, lit)
+        ctx.lighting(d)
+        torch.cuda.synchronize()
+        assert all(p.padding_intact() for p in self._pitched(dev, lit)), "a Lighting kernel wrote into the padding of a pitched plane or volume"
+        return lit.read(np.uint16) if isinstance(lit, Pitched) else util.from_torch(lit, np.uint16)
+
+    # -- what the frame shades (oracle only)
+    def surface_mask(self):
+        return (self.arrays["depth"] != 0) & (self.arrays["emission"][..., :3].sum(-1) == 0)
+
+    def coverage(self):
+        """(share of the frame that is non-emissive surface, share of those pixels the sun lights, share of them the LPV overlay changes (None
+        without an LPV), share of the frame's pixels whose lit texel is not finite).  'Changes' compares the pass with the overlay against the
+        pass without it: the overlay also replaces the sun blend, so the share says that the overlay's code ran on those pixels, not that the
+        volumes' contents contributed (it is 1.0 even at exposure 0)."""
+        full = self.run_oracle()
+        gi_kind, lpv = self.gi_kind, self.lpv
+        self.gi_kind = _abi.GI_NONE
+        try:
+            no_gi = self.run_oracle()
+        finally:
+            self.gi_kind = gi_kind
+        surf = self.surface_mask()
+        n = max(int(surf.sum()), 1)
+        sunlit = float(((no_gi[..., :3] & 0x7FFF) != 0).any(-1)[surf].sum()) / n
+        changed = float((full != no_gi).any(-1)[surf].sum()) / n if lpv is not None else None
+        nonfinite = float(((full[..., :3] & 0x7C00) == 0x7C00).any(-1).mean())
+        return float(surf.mean()), sunlit, changed, nonfinite
+
+
+# ---- the case list --------------------------------------------------------------------------------------------------------------------
+
+CSM_LPV = dict(sun_mode=_abi.SHADOW_MODE_CSM, gi=_abi.GI_LPV)
+RT_NONE = dict(sun_mode=_abi.SHADOW_MODE_RT, gi=_abi.GI_NONE)
+MODES = {"csm_lpv": CSM_LPV, "rt_none": RT_NONE}
+
+
+class Case:
+    """name; frame arguments; `expect`: the dispatch report of the automatic path (a subset of lib.Context.lighting_dispatch()'s keys);
+    `exempt`: None, or the reason why the coverage conditions and the deferred-pixel cap do not apply to the case (adversarial texels, non-finite
+    images, a frame without a surface pixel — nothing else is exempt); `vec4`: 16-byte planes
+    (4 and 2 pixels per thread can be forced); `nonfinite`: least share of non-finite lit texels the oracle must produce; `post`: an edit of
+    the built frame (name in FRAME_EDITS)."""
+
+    def __init__(self, name, width, height, expect, exempt=None, vec4=True, nonfinite=0.0, post=None, lights=0, **frame):
+        self.name, self.width, self.height, self.expect, self.exempt, self.vec4 = name, width, height, dict(expect), exempt, vec4
+        self.nonfinite, self.post, self.lights, self.frame = nonfinite, post, lights, frame
+
+    def build(self):
+        kw = dict(self.frame)
+        if self.lights:
+            cam = dict(DEFAULT_CAMERA, **(kw.get("camera") or {}))
+            kw["lights"] = synth.point_lights(make_view(self.width, self.height, **cam), self.lights, 6.0, seed=kw.get("seed", 1) + 800)
+        f = MatrixFrame(self.width, self.height, **kw)
+        if self.post:
+            FRAME_EDITS[self.post](f)
+        return f
+
+    def __repr__(self):
+        return self.name
+
+
+def _edit_lpv_rotation(f):
+    f.lpv.matrices[0].world_to_cascade[1] = 1e-3
+
+
+def _edit_d32_shadowmap(f):
+    f.arrays["shadowmap"] = (f.arrays["shadowmap"].astype(np.float64) / 65535.0).astype(np.float32)
+
+
+def _edit_poison(f):
+    g = {k: f.arrays[k] for k in ("color", "normals", "data", "emission", "depth")}
+    util.poison_gbuffer(g, np.random.default_rng(5))
+
+
+def _edit_all_sky(f):
+    for k in ("color", "normals", "data", "emission", "depth"):
+        f.arrays[k] = np.zeros_like(f.arrays[k])
+
+
+def _edit_no_sky(f):
+    d = f.arrays["depth"]
+    d[d == 0] = np.float32(0.01)
+
+
+def _edit_sky_last3(f):
+    _edit_no_sky(f)
+    for k in ("color", "normals", "data", "emission", "depth"):
+        f.arrays[k][-1, -3:] = 0
+
+
+def _edit_sky_trailing_rows(f):
+    _edit_no_sky(f)
+    for k in ("color", "normals", "data", "emission", "depth"):
+        f.arrays[k][-37:] = 0
+
+
+FRAME_EDITS = {"lpv_rotation": _edit_lpv_rotation, "d32_shadowmap": _edit_d32_shadowmap, "poison": _edit_poison, "all_sky": _edit_all_sky,
+               "no_sky": _edit_no_sky, "sky_last3": _edit_sky_last3, "sky_trailing_rows": _edit_sky_trailing_rows}
+
+FAST = dict(family="fast", ppt=1, pos_div_nr=0)
+GENERAL = dict(family="general")
+
+
+def _cases():
+    out = []
+    seed = 100
+    # cameras: CSM + LPV and RT + none, coherent (atrium) and incoherent (random) waves
+    for cam in ("default", "plus_zero", "jitter", "yaw37", "down", "up", "far", "fov5", "halfres"):
+        for mode in ("csm_lpv", "rt_none"):
+            for flavour in ("atrium", "random"):
+                seed += 1
+                exp = dict(FAST, pos_div_nr=1 if cam == "plus_zero" else 0)
+                if mode == "csm_lpv":
+                    exp["ncasc_pow2"] = 1
+                out.append(Case(f"camera-{cam}-{mode}-{flavour}", 256, 144, exp, camera=CAMERAS[cam], flavour=flavour, seed=seed, **MODES[mode]))
+    # the adversarial texels of test_lighting_adversarial_inputs under the +0 camera: with pos_div_nr on they meet the |vw| domain check
+    for mode in ("csm_lpv", "rt_none"):
+        seed += 1
+        out.append(Case(f"poison-plus_zero-{mode}", 192, 96, dict(FAST, pos_div_nr=1), exempt="adversarial texels", camera=CAMERAS["plus_zero"], flavour="random",
+                        seed=seed, post="poison", **MODES[mode]))
+    # uniform blocks the proofs exclude: the general kernel (a light list: the tiled kernel without the borrowed geometry)
+    excluded = [("p4", dict(camera=dict(edit="p4")), None), ("v3", dict(camera=dict(edit="v3")), None),
+                ("far_position", dict(camera=dict(edit="far_position")), None),
+                ("lpv_pitches_differ", dict(pitch={"lpv_r": dict(row_pad=0), "lpv_g": dict(row_pad=16), "lpv_b": dict(row_pad=32)}), None),
+                ("exposure_inf", dict(lpv=dict(exposure=float("inf"))), None), ("lpv_rotation", {}, "lpv_rotation"), ("d32_shadowmap", {}, "d32_shadowmap")]
+    for name, kw, post in excluded:
+        seed += 1
+        exempt = "an infinite exposure: non-finite lit texels on most of the frame" if name == "exposure_inf" else None
+        out.append(Case(f"excluded-{name}", 192, 108, GENERAL, exempt=exempt, flavour="random", seed=seed, post=post, **dict(CSM_LPV, **kw)))
+    for name in ("p4", "v3", "far_position"):
+        seed += 1
+        out.append(Case(f"excluded-{name}-lights", 192, 108, dict(family="tiled", tiled_fast_geom=0, tiled_fast_lpv=0), flavour="random", seed=seed,
+                        lights=24, camera=dict(edit=name), **CSM_LPV))
+    # ... and three the proofs keep on the fast path with the shared-reciprocal divide switched off: an orthographic inverse projection
+    # (separable like a perspective one; [10] != 0, [11] == 0), a render resolution below width / 256, |inverse_projection[0]| < 2^-16
+    seed += 1
+    out.append(Case("kept-ortho", 192, 108, dict(FAST, pos_div_nr=0), flavour="random", seed=seed, camera=dict(edit="ortho"), **CSM_LPV))
+    seed += 1
+    out.append(Case("kept-ortho-lights", 192, 108, dict(family="tiled", tiled_fast_geom=1, tiled_fast_lpv=1, pos_div_nr=0), flavour="random",
+                    seed=seed, lights=24, camera=dict(edit="ortho"), **CSM_LPV))
+    seed += 1
+    out.append(Case("kept-tiny_render_resolution", 256, 144, dict(FAST, pos_div_nr=0), flavour="random", seed=seed,
+                    camera=dict(edit="plus_zero", res_scale=1.0 / 300.0), **CSM_LPV))  # width > 256 * render_resolution
+    seed += 1
+    out.append(Case("kept-p0_tiny", 256, 144, dict(FAST, pos_div_nr=0), flavour="random", seed=seed, camera=dict(edit="p0_tiny"), **CSM_LPV))
+    # suns
+    for name, kw, exempt, nonfin in (("default", {}, None, 0.0), ("grazing", dict(sun_dir=(1.0, -0.02, 0.3)), None, 0.0),
+                                     ("minus_x", dict(sun_dir=(-1.0, 0.0, 0.0)), None, 0.0),
+                                     ("vertical", dict(sun_dir=(0.0, -1.0, 0.0)), "NaN cascade matrices: non-finite lit texels, no sun", 0.01),
+                                     ("zero_channel", dict(sun_color=(80000.0, 0.0, 80000.0)), None, 0.0),
+                                     ("colour_1e30", dict(sun_color=(1e30, 80000.0, 80000.0)), "non-finite lit texels wherever the sun reaches", 0.0)):
+        for flavour in ("atrium", "random"):
+            seed += 1
+            exp = dict(GENERAL) if name == "vertical" else dict(FAST, ncasc_pow2=1)
+            out.append(Case(f"sun-{name}-{flavour}", 256, 144, exp, exempt=exempt, nonfinite=nonfin, flavour=flavour, seed=seed, **dict(CSM_LPV, **kw)))
+    # LPV layouts
+    for n in (1, 2, 3, 4):
+        for flavour in ("atrium", "random"):
+            seed += 1
+            out.append(Case(f"lpv-{n}_cascades-{flavour}", 256, 144, dict(FAST, ncasc_pow2=0 if n == 3 else 1), flavour=flavour, seed=seed,
+                            lpv=dict(num_cascades=n), **CSM_LPV))
+    for name, lpv in (("cell_0.5", dict(cell=0.5)), ("behind_0.4", dict(behind=0.4)), ("exposure_0", dict(exposure=0.0)),
+                              ("exposure_1e4", dict(exposure=1e4))):
+        seed += 1
+        out.append(Case(f"lpv-{name}", 256, 144, dict(FAST, ncasc_pow2=1), flavour="atrium", seed=seed, lpv=lpv, **CSM_LPV))
+    seed += 1
+    vp = dict(row_pad=24, slice_pad=40)
+    out.append(Case("lpv-pitched_volumes", 256, 144, dict(FAST, ncasc_pow2=1, repack=1), flavour="atrium", seed=seed,
+                    pitch={"lpv_r": vp, "lpv_g": vp, "lpv_b": vp}, **CSM_LPV))
+    for n in (1, 3):
+        seed += 1
+        out.append(Case(f"lpv-{n}_cascades-lights", 192, 108, dict(family="tiled", tiled_fast_geom=1, tiled_fast_lpv=1, ncasc_pow2=0 if n == 3 else 1),
+                        flavour="atrium", seed=seed, lights=24, lpv=dict(num_cascades=n), **CSM_LPV))
+    # planes: padded pitches, base offsets
+    keys = {"csm_lpv": ("color", "normals", "data", "emission", "depth", "ao", "lit"), "rt_none": ("color", "normals", "data", "emission", "depth", "shadow_mask", "lit")}
+    for pad in (16, 64, 4):
+        for mode in ("csm_lpv", "rt_none"):
+            seed += 1
+            out.append(Case(f"planes-pad{pad}-{mode}", 256, 144, FAST, vec4=(pad != 4), flavour="atrium", seed=seed,
+                            pitch={k: dict(row_pad=pad) for k in keys[mode]}, **MODES[mode]))
+    for k in ("color", "normals", "data", "emission", "depth", "ao", "lit"):
+        seed += 1
+        out.append(Case(f"planes-offset8-{k}", 256, 144, FAST, vec4=False, flavour="random", seed=seed, pitch={k: dict(row_pad=8, offset=8)}, **CSM_LPV))
+    seed += 1
+    out.append(Case("planes-offset8-shadow_mask", 256, 144, FAST, vec4=False, flavour="random", seed=seed, pitch={"shadow_mask": dict(row_pad=8, offset=8)}, **RT_NONE))
+    # extents
+    for w in (1, 2, 3, 4, 5, 8, 12, 260, 262):
+        seed += 1
+        out.append(Case(f"extent-{w}x45", w, 45, FAST, vec4=(w % 4 == 0), flavour="random", seed=seed, **CSM_LPV))
+    seed += 1
+    out.append(Case("extent-256x1", 256, 1, FAST, flavour="random", seed=seed, **CSM_LPV))
+    # sky extremes: sky enabled, RT sun, without GI and with the LPV
+    for name in ("all_sky", "no_sky", "sky_last3", "sky_trailing_rows"):
+        for gi_name, gi in (("none", _abi.GI_NONE), ("lpv", _abi.GI_LPV)):
+            seed += 1
+            exempt = "no surface pixel" if name == "all_sky" else None
+            out.append(Case(f"sky-{name}-{gi_name}", 256, 144, FAST, exempt=exempt, flavour="random", seed=seed, post=name, sun_mode=_abi.SHADOW_MODE_RT, gi=gi))
+    return out
+
+
+CASES = _cases()
+BY_NAME = {c.name: c for c in CASES}
+assert len(BY_NAME) == len(CASES)
+
+# launch-geometry edges that only large launches reach (tests/test_lighting_matrix_gpu.py: test_launch_geometry_edges)
+BIG_WIDTH, BIG_HEIGHTS, BIG_SHARDS = 3840, (291, 292), ((0, 97), (97, 200), (200, None))
+
+
+def big_frame(height, flavour):
+    return MatrixFrame(BIG_WIDTH, height, flavour=flavour, seed=900 + height + (7 if flavour == "random" else 0), **CSM_LPV)
+
+
+def expected_ppt(width, rows, vec4, forced=0):
+    """The launch rule restated (api.cpp): 4 pixels per thread where the planes allow 16-byte accesses, halved while the launch would be fewer
+    than 1,536 workgroups; a forced 2 / 4 only where the planes and the width allow it, a forced 1 always."""
+    ok = vec4 and width % 4 == 0
+    ppt = 4 if ok else 1
+    while ppt > 1 and (width // ppt) * rows < 1536 * 256:
+        ppt //= 2
+    if forced == 1 or (forced in (2, 4) and ok and width % forced == 0):
+        ppt = forced
+    return ppt

@@ -118,6 +118,30 @@ def report_ulp(name, d):
     return f"{name}: max {int(d.max())} ulp, {nz}/{n} differ ({100.0 * nz / n:.4f} %), >1ulp: {int((d > 1).sum())}"
 
 
+MAX_ULP = 1  # the Lighting pass's bar, BASELINE.json north_star: within 1 ULP per channel of the stored RGBA16F value
+
+
+def poison_gbuffer(g, rng):
+    """Adversarial texels: zero / huge / inf / NaN normals, roughness 0, denormal / inf / NaN / negative depth."""
+    h, w = g["depth"].shape
+    n = g["normals"].view(np.uint16)
+    d = g["depth"].view(np.uint32)
+    for k, (nb, db) in enumerate([((0, 0, 0), None), ((0x7BFF, 0x7BFF, 0x7BFF), None), ((0x7C00, 0x3C00, 0), None),
+                                  ((0x7E00, 0x3C00, 0x3C00), None), (None, 0x00000001), (None, 0x7F800000), (None, 0x7FC00000),
+                                  (None, 0xBF000000), ((0x0001, 0, 0), None), (None, 0x00800000), ((0x8000, 0x8000, 0x3C00), 0x3F7FFFFF)]):
+        ys, xs = rng.integers(0, h, 40), rng.integers(0, w, 40)
+        if nb is not None:
+            for c in range(3):
+                n[ys, xs, c] = nb[c]
+        if db is not None:
+            d[ys, xs] = db
+    ys, xs = rng.integers(0, h, 300), rng.integers(0, w, 300)
+    g["data"][ys, xs, 1] = 0  # roughness 0: the NaN-producing corner of D_GGX
+    ys, xs = rng.integers(0, h, 100), rng.integers(0, w, 100)
+    g["data"][ys, xs, 1] = 0
+    g["normals"][ys, xs, :3] = g["normals"][ys, xs, :3]  # keep
+
+
 # ---- a lighting frame ---------------------------------------------------------------------------------
 
 class LightingFrame(frame.LightingInputs):
