@@ -18,7 +18,8 @@
 
 namespace sah {
 hipError_t launch_lighting(const LightingArgs& a, const CsmArgs& csm, const LpvArgs& lpv, const CacheArgs& cache, const RtgiArgs& rtgi,
-                           const SkyArgs& sky, const FastArgs* fast, int sun_mode, int gi, int ppt, bool brute_force_lights, hipStream_t st);
+                           const SkyArgs& sky, LightingFamily family, const FastArgs* fast, int sun_mode, int gi, int ppt, bool brute_force_lights,
+                           hipStream_t st);
 hipError_t launch_colx_table(const LightingArgs& a, const FastArgs& f, float* out, uint32_t stride, uint32_t row_stride, hipStream_t st);
 hipError_t launch_probe_irr_unpack(const VolumeArg& src, uint8_t* dst, hipStream_t st);
 hipError_t launch_copy_scene(const PlaneArg& src, uint32_t sw, uint32_t sh, const PlaneArg& dst, uint32_t dw, uint32_t dh, uint32_t row_begin,
@@ -130,7 +131,7 @@ bool detect_fast_path(const sah_lighting_desc* d, uint32_t sun_mode, uint32_t gi
 }  // namespace
 
 void SahRange::resolve(push_fn& push, pop_fn& pop) {
-    const char* on = getenv("SAH_ROCTX");
+    const char* on = getenv("SAH_ROCTX");  // (kept: opt-in tracing, changes nothing that is launched)
     if (!on || atoi(on) == 0) return;
     for (const char* lib : {"librocprofiler-sdk-roctx.so", "librocprofiler-sdk-roctx.so.1", "libroctx64.so", "libroctx64.so.4"}) {
         void* h = dlopen(lib, RTLD_NOW | RTLD_GLOBAL);
@@ -202,12 +203,9 @@ int sah_create(sah_ctx** out, int device, int rank, int world, const void* comm_
         sah_destroy(ctx);
         return SAH_ERR_HIP;
     }
-    const char* ppt = getenv("SAH_FORCE_PPT");
-    if (ppt) ctx->force_ppt = atoi(ppt);
+    // (kept: read once per context, selects code that ships — every bin list whole — and is how tests/test_raster.py reaches it)
     const char* mc = getenv("SAH_RASTER_MERGE_CAPACITY");
     if (mc) ctx->raster_merge_cap = (uint32_t)atoi(mc);
-    const char* gen = getenv("SAH_FORCE_GENERAL");
-    if (gen) ctx->force_general = atoi(gen) != 0;
     *out = ctx;
     return SAH_OK;
 }
@@ -502,20 +500,17 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
                        ((uintptr_t)gi.probe_irradiance.ptr % 4) == 0;
         if (cache.hot_ok) {
             const size_t need = 4 * (size_t)bytes(gi.probe_irradiance);
-            if (ctx->irr32_bytes < need) {
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                if (ctx->irr32) (void)hipFree(ctx->irr32);
-                ctx->irr32 = nullptr;
-                ctx->irr32_bytes = 0;
-                if (hipMalloc((void**)&ctx->irr32, need) == hipSuccess) {
-                    ctx->irr32_bytes = need;
-                    ctx->irr32_generation = 0;
-                    ctx->cache_epoch++;
-                } else {  // no room for the widened copy: the general gather needs none
-                    (void)hipGetLastError();
-                    ctx->irr32 = nullptr;
-                    cache.hot_ok = 0;
-                }
+            bool grew = false;
+            const hipError_t ge = sah_grow(ctx, (void**)&ctx->irr32, &ctx->irr32_bytes, need, &grew);
+            if (ge == hipErrorOutOfMemory) {  // no room for the widened copy: the general gather needs none
+                (void)hipGetLastError();
+                cache.hot_ok = 0;
+            } else {
+                HIP_TRY(ctx, ge);
+            }
+            if (grew) {
+                ctx->irr32_generation = 0;
+                ctx->cache_epoch++;
             }
         }
         if (cache.hot_ok) {
@@ -581,14 +576,15 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
     memset(&fast, 0, sizeof(fast));
     const bool fast_kind = (gi_kind == SAH_GI_NONE || gi_kind == SAH_GI_LPV) && a.num_lights == 0;
     const bool use_fast = fast_kind && !ctx->force_general && detect_fast_path(d, sun_mode, gi_kind, csm, &fast);
+    // the kernel family that runs (what launch_lighting launches and sah_debug_lighting_dispatch reports): point lights and the GI overlays
+    // without a fast path take the 16x16-tile kernel (lighting_tiled.hip)
+    const LightingFamily family = !fast_kind ? kLightingTiled : (use_fast ? kLightingFast : kLightingGeneral);
     // the tiled kernel (light list, cache / RTGI overlays) borrows the fast kernel's geometry and CSM sun when the uniform blocks allow
     // (its LPV overlay, if any, stays the general one: the LPV part of the check is skipped)
-    static const bool no_tiled_fast_geom = getenv("SAH_TILED_GENERAL_GEOMETRY") != nullptr;  // A/B switch (tools/ab.sh)
-    const bool tiled_fast_geom = !fast_kind && !ctx->force_general && !no_tiled_fast_geom && detect_fast_path(d, sun_mode, SAH_GI_NONE, csm, &fast);
+    const bool tiled_fast_geom = !fast_kind && !ctx->force_general && detect_fast_path(d, sun_mode, SAH_GI_NONE, csm, &fast);
     // ... and, round 6, the fast kernel's LPV overlay (gather from the packed copy) where the LPV part of the check holds as well: a light list
     // over an LPV frame (configs[4]) no longer pays the general overlay's nine trilinear fetches per pixel
-    static const bool no_tiled_fast_lpv = getenv("SAH_TILED_GENERAL_LPV") != nullptr;  // A/B switch
-    const bool tiled_fast_lpv = tiled_fast_geom && gi_kind == SAH_GI_LPV && !no_tiled_fast_lpv && ctx->state && detect_fast_path(d, sun_mode, SAH_GI_LPV, csm, &fast);
+    const bool tiled_fast_lpv = tiled_fast_geom && gi_kind == SAH_GI_LPV && ctx->state && detect_fast_path(d, sun_mode, SAH_GI_LPV, csm, &fast);
     fast.lpv_fast = tiled_fast_lpv ? 1u : 0u;
     // the gather copy of the LPV volumes for a kernel that reads it: rebuilt by k_lpv_pack (in front of the kernel: lighting.hip) unless the caller's
     // change counter says it stands (SAH_GENERATION_TRACKED: the last step of sah_lpv_propagate has written it — api_post.cpp)
@@ -624,16 +620,10 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
         const uint32_t nseg = (uint32_t)((groups + 63) / 64);
         const uint32_t seg_stride = 64u * (uint32_t)ppt;
         const size_t codes_bytes = ((size_t)nseg * seg_stride + 255) & ~(size_t)255;
-        const size_t need = codes_bytes + 2 * (size_t)nseg * sizeof(uint16_t) + 256;  // two counts per segment: general (front), sky (back)
-        if (ctx->list_bytes < need) {  // grow-only workspace
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->list) (void)hipFree(ctx->list);
-            ctx->list = nullptr;
-            ctx->list_bytes = 0;
-            HIP_TRY(ctx, hipMalloc((void**)&ctx->list, need));
-            ctx->list_bytes = need;
-            ctx->cache_epoch++;
-        }
+        const size_t need = codes_bytes + (size_t)nseg * sizeof(uint16_t) + 256;
+        bool grew = false;
+        HIP_TRY(ctx, sah_grow(ctx, (void**)&ctx->list, &ctx->list_bytes, need, &grew));
+        if (grew) ctx->cache_epoch++;
         fast.seg_list = (uint8_t*)ctx->list;
         fast.seg_count = (uint16_t*)((uint8_t*)ctx->list + codes_bytes);
         fast.num_segments = nseg;
@@ -651,14 +641,10 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
             // workgroup slots, two sky waves on every SIMD of a sky-heavy frame; more only hold slots in front of the surface workgroups to find
             // nothing (4K: 2,025 sky workgroups 0.1649 ms, 506 0.1615), fewer make the walk the critical path of a short launch (1920 x 1080: 127
             // sky workgroups 0.058 ms against 0.0507 with 506).  tools/experiments/r6/README.md §2.
-            static const int env_ratio = getenv("SAH_SKY_RATIO") ? atoi(getenv("SAH_SKY_RATIO")) : 0;  // experiments (tools/experiments/r6)
-            static const int env_interleaved = getenv("SAH_SKY_INTERLEAVED") ? atoi(getenv("SAH_SKY_INTERLEAVED")) : 0;
-            const uint64_t blocks = ((uint64_t)(W / (uint32_t)ppt) * (r1 - r0) + 255) / 256;
+            const uint64_t blocks = (groups + 255) / 256;
             const uint64_t want = (blocks + 511) / 512;
             fast.sky_ratio = (uint32_t)(want < 4 ? 4 : (want > 32 ? 32 : want));
-            if (env_ratio > 0) fast.sky_ratio = (uint32_t)env_ratio;
-            fast.sky_first = env_interleaved ? 0u : 1u;  // (lighting.hip's launcher turns the flag into the number of sky workgroups)
-            if (env_interleaved && env_ratio <= 0) fast.sky_ratio = 4;  // (rounds 2-5: every fifth workgroup)
+            fast.sky_first = sky.enabled ? (uint32_t)((blocks + fast.sky_ratio - 1u) / fast.sky_ratio) : 0u;
         }
         {  // thread index -> (row, group in row) by a multiply-high: exact while gid * groups_per_row < 2^32 (magic = floor(2^32 / d) + 1)
             const uint64_t gpr = W / (uint32_t)ppt, threads = (gpr * (r1 - r0) + 255) / 256 * 256;
@@ -675,14 +661,9 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
     if ((use_fast && ppt == 4 && (sun_mode != SAH_SHADOW_MODE_OFF || gi_kind == SAH_GI_LPV)) || tiled_fast_geom) {
         const float key[7] = {a.res[0], fast.p0, fast.p12, a.res[1], fast.p5, fast.p13, (float)H};
         const uint32_t stride = (W + 63u) & ~63u, row_stride = (H + 63u) & ~63u;
-        const uint32_t need = 2 * stride + 2 * row_stride;
-        if (ctx->colx_capacity < need) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->colx_table) (void)hipFree(ctx->colx_table);
-            ctx->colx_table = nullptr;
-            ctx->colx_capacity = 0;
-            HIP_TRY(ctx, hipMalloc((void**)&ctx->colx_table, (size_t)need * sizeof(float)));
-            ctx->colx_capacity = need;
+        bool grew = false;
+        HIP_TRY(ctx, sah_grow(ctx, (void**)&ctx->colx_table, &ctx->colx_bytes, ((size_t)2 * stride + 2 * row_stride) * sizeof(float), &grew));
+        if (grew) {
             ctx->cache_epoch++;
             ctx->colx_width = 0;
         }
@@ -699,22 +680,19 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
         fast.rowy_stride = row_stride;
     }
     {
-        const bool tiled = a.num_lights != 0 || gi_kind == SAH_GI_CACHE || gi_kind == SAH_GI_RTGI;  // (launch_lighting's own test)
-        const uint64_t blocks = ((uint64_t)(W / (uint32_t)ppt) * (r1 - r0) + 255) / 256;
-        dispatch[0] = tiled ? 2u : (use_fast ? 1u : 0u);
-        dispatch[1] = tiled ? 0u : (uint32_t)ppt;
+        dispatch[0] = family;
+        dispatch[1] = family == kLightingTiled ? 0u : (uint32_t)ppt;
         dispatch[2] = (use_fast || tiled_fast_geom) ? fast.pos_div_nr : 0u;
         dispatch[3] = ((use_fast && gi_kind == SAH_GI_LPV) || tiled_fast_lpv) ? fast.ncasc_pow2 : 0u;
         dispatch[4] = (use_fast && fast.row_magic != 0u) ? 1u : 0u;
         dispatch[5] = use_fast ? fast.sky_ratio : 0u;
-        // (lighting.hip's launcher: the sky workgroups lead the grid, one per sky_ratio surface workgroups)
-        dispatch[6] = (use_fast && sky.enabled && fast.sky_first && blocks) ? (uint32_t)((blocks + fast.sky_ratio - 1u) / fast.sky_ratio) : 0u;
+        dispatch[6] = use_fast ? fast.sky_first : 0u;
         dispatch[7] = tiled_fast_geom ? 1u : 0u;
         dispatch[8] = tiled_fast_lpv ? 1u : 0u;
         dispatch[9] = fast.repack;
         memcpy(ctx->last_dispatch, dispatch, sizeof(dispatch));
     }
-    HIP_TRY(ctx, launch_lighting(a, csm, lpv, cache, rtgi, sky, (use_fast || tiled_fast_geom) ? &fast : nullptr, (int)sun_mode, (int)gi_kind, ppt,
+    HIP_TRY(ctx, launch_lighting(a, csm, lpv, cache, rtgi, sky, family, (use_fast || tiled_fast_geom) ? &fast : nullptr, (int)sun_mode, (int)gi_kind, ppt,
                                  (d->flags & SAH_LIGHTING_BRUTE_FORCE_LIGHTS) != 0, ctx->stream));
     if (use_fast) {
         ctx->last_seg_count = fast.seg_count;

@@ -25,7 +25,7 @@ hipError_t launch_tonemap(const TonemapArgs& t, hipStream_t st);
 hipError_t launch_tonemap_tol(const TonemapArgs& t, hipStream_t st);
 hipError_t launch_tonemap_axis_tables(const TonemapArgs& t, TmAxis* out, hipStream_t st);
 hipError_t launch_lpv_clear(const VolumeArg* vols, int n, uint32_t num_cascades, hipStream_t st);
-hipError_t launch_lpv_propagate(const VolumeArg src[3], const VolumeArg dst[3], uint32_t num_cascades, const LpvPackEmit* emit, int mode, hipStream_t st,
+hipError_t launch_lpv_propagate(const VolumeArg src[3], const VolumeArg dst[3], uint32_t num_cascades, const LpvPackEmit* emit, bool hot, hipStream_t st,
                                 const LpvGvStep* gv = nullptr);
 hipError_t launch_lpv_gv_factors(const VolumeArg& gv, void* factors, uint32_t num_cascades, hipStream_t st);
 hipError_t launch_gv_inject_rsm(const VolumeArg& normals, const VolumeArg& depth, const sah_lpv_cascade_matrices* cascades, uint32_t first_cascade,
@@ -354,15 +354,9 @@ int sah_tonemap_ex(sah_ctx* ctx, const sah_plane* scene, const sah_mipchain* blo
         key[18] = bloom->num_mips;
         t.axis_stride = (std::max(out->width, out->height) + 63u) & ~63u;
         const size_t need = (size_t)6 * 2 * 4 * t.axis_stride * sizeof(sah::TmAxis);
-        const bool rebuild = !ctx->tm_axis || ctx->tm_axis_bytes < need || memcmp(key, ctx->tm_axis_key, sizeof(key)) != 0;
-        if (!ctx->tm_axis || ctx->tm_axis_bytes < need) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->tm_axis) (void)hipFree(ctx->tm_axis);
-            ctx->tm_axis = nullptr;
-            ctx->tm_axis_bytes = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->tm_axis, need));
-            ctx->tm_axis_bytes = need;
-        }
+        bool grew = false;
+        HIP_TRY(ctx, sah_grow(ctx, &ctx->tm_axis, &ctx->tm_axis_bytes, need, &grew));
+        const bool rebuild = grew || memcmp(key, ctx->tm_axis_key, sizeof(key)) != 0;
         t.axis_tables = (const sah::TmAxis*)ctx->tm_axis;
         if (rebuild) {
             HIP_TRY(ctx, sah::launch_tonemap_axis_tables(t, (sah::TmAxis*)ctx->tm_axis, ctx->stream));
@@ -398,20 +392,6 @@ int sah_lpv_clear(sah_ctx* ctx, const sah_volume* red, const sah_volume* green, 
 }  // extern "C"
 
 namespace {
-// a device buffer of the context that only grows (the GV scratch): synchronises only when it has to free a smaller one
-hipError_t grow_scratch(sah_ctx* ctx, void** ptr, size_t* bytes, size_t need) {
-    if (*bytes >= need) return hipSuccess;
-    if (*ptr) {
-        const hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return e;
-        (void)hipFree(*ptr);
-    }
-    *ptr = nullptr;
-    *bytes = 0;
-    const hipError_t e = hipMalloc(ptr, need);
-    if (e == hipSuccess) *bytes = need;
-    return e;
-}
 bool gv_volume_ok(const sah_volume* v, uint32_t num_cascades) {
     return lpv_vol_ok(v) && v->width >= 32 * num_cascades && v->height >= 32 && v->depth >= 32 && (uint64_t)v->width * v->height * v->depth <= (1ull << 26) &&
            (uint64_t)v->slice_pitch_bytes * v->depth < (1ull << 32);
@@ -444,13 +424,12 @@ int lpv_propagate(sah_ctx* ctx, const sah_volume a_rgb[3], const sah_volume b_rg
         HIP_TRY(ctx, sah::launch_lpv_build_tables(ctx->stream, &ctx->lpv_hot_structure));
         ctx->lpv_tables_built = true;
     }
-    // lpv.hip: the hot form of the 30 direction pairs (finite coefficients; the three colours of a cell in one thread) when the tables the device
-    // built have the structure it relies on; the general form for a context under sah_debug_set(force_general) — the tests' cross-check
-    static const int env_mode = getenv("SAH_LPV_MODE") ? atoi(getenv("SAH_LPV_MODE")) : -1;  // experiments: 0 general, 1 hot, 3 hot + three colours per thread
+    // lpv.hip: the hot form of the 30 direction pairs (finite coefficients) when the tables the device built have the structure it relies on;
+    // the general form for a context under sah_debug_set(force_general) — the tests' cross-check
     bool offsets32 = true;  // (the hot kernels address a volume by 32-bit byte offsets)
     for (int i = 0; i < 3; i++)
         offsets32 = offsets32 && (uint64_t)a[i].slice_pitch * a[i].depth < (1ull << 32) && (uint64_t)b[i].slice_pitch * b[i].depth < (1ull << 32);
-    const int mode = (!ctx->lpv_hot_structure || ctx->force_general || !offsets32) ? 0 : ((env_mode == 0 || env_mode == 1 || env_mode == 3) ? env_mode : 1);
+    const bool hot = ctx->lpv_hot_structure && !ctx->force_general && offsets32;
     // light_propagation_volume.cpp:1016-1034: `steps` dispatches ping-ponging A -> B -> A ...  (Two steps per launch — 8^3 bricks with
     // their halo in LDS, bit-identical — were measured: 28 us per pair against 2 x 9.3 us, 1.5x the arithmetic in longer dependency
     // chains; not kept.)
@@ -470,23 +449,19 @@ int lpv_propagate(sah_ctx* ctx, const sah_volume a_rgb[3], const sah_volume b_rg
         emit = {ctx->lpv_packed, pk.row_pitch, pk.slice_pitch, ctx->state};
     }
     // use_gv = 1: the GV does not change during the steps, so its 30 factors per cell are computed once, ahead of them, and every step
-    // reads them (64 bytes per cell); SAH_LPV_GV_MODE=2 samples the GV in every step instead (the other variant: DESIGN.md §5i, §7)
+    // reads them (64 bytes per cell; sampling the GV in every step instead was measured and lost: DESIGN.md §5i, §7)
     sah::LpvGvStep gv = {};
     if (geometry && steps > 0) {
-        static const int env_gv = getenv("SAH_LPV_GV_MODE") ? atoi(getenv("SAH_LPV_GV_MODE")) : 1;  // experiments: 1 precomputed, 2 sampled per step
         gv.gv = varg(*geometry);
-        gv.mode = env_gv == 2 ? 2 : 1;
-        if (gv.mode == 1) {
-            HIP_TRY(ctx, grow_scratch(ctx, &ctx->gv_factors, &ctx->gv_factors_bytes, (size_t)4 * 16 * 32768 * 4));
-            gv.factors = ctx->gv_factors;
-            HIP_TRY(ctx, sah::launch_lpv_gv_factors(gv.gv, gv.factors, num_cascades, ctx->stream));
-        }
+        HIP_TRY(ctx, sah_grow(ctx, &ctx->gv_factors, &ctx->gv_factors_bytes, (size_t)4 * 16 * 32768 * 4));
+        gv.factors = ctx->gv_factors;
+        HIP_TRY(ctx, sah::launch_lpv_gv_factors(gv.gv, gv.factors, num_cascades, ctx->stream));
     }
     const sah::LpvGvStep* g = geometry ? &gv : nullptr;
     for (uint32_t s = 0; s < steps; s++) {
         const sah::LpvPackEmit* e = (emits && s + 1 == steps) ? &emit : nullptr;
-        if ((s & 1) == 0) HIP_TRY(ctx, sah::launch_lpv_propagate(a, b, num_cascades, e, mode, ctx->stream, g));
-        else HIP_TRY(ctx, sah::launch_lpv_propagate(b, a, num_cascades, e, mode, ctx->stream, g));
+        if ((s & 1) == 0) HIP_TRY(ctx, sah::launch_lpv_propagate(a, b, num_cascades, e, hot, ctx->stream, g));
+        else HIP_TRY(ctx, sah::launch_lpv_propagate(b, a, num_cascades, e, hot, ctx->stream, g));
     }
     if (emits) {
         ctx->lpv_pack_generation = SAH_GENERATION_TRACKED;
@@ -537,7 +512,7 @@ int sah_lpv_inject_rsm_gv(sah_ctx* ctx, const sah_rsm_targets* rsm, const sah_lp
     if (cascade_count == 0) return SAH_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t need = (size_t)16 * geometry->width * geometry->height * geometry->depth;
-    HIP_TRY(ctx, grow_scratch(ctx, (void**)&ctx->gv_keys, &ctx->gv_keys_bytes, need));
+    HIP_TRY(ctx, sah_grow(ctx, (void**)&ctx->gv_keys, &ctx->gv_keys_bytes, need));
     HIP_TRY(ctx, sah::launch_gv_inject_rsm(varg(n), varg(d), cascades, first_cascade, cascade_count, num_cascades, varg(*geometry), ctx->gv_keys,
                                            ctx->stream));
     return SAH_OK;
@@ -555,7 +530,7 @@ int sah_lpv_inject_scene_gv(sah_ctx* ctx, const sah_plane* depth, const sah_plan
         return fail(ctx, SAH_ERR_UNSUPPORTED_FORMAT, "scene GV: depth D32_SFLOAT and normals R16G16B16A16_SFLOAT planes of equal extents");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t need = (size_t)16 * geometry->width * geometry->height * geometry->depth;
-    HIP_TRY(ctx, grow_scratch(ctx, (void**)&ctx->gv_keys, &ctx->gv_keys_bytes, need));
+    HIP_TRY(ctx, sah_grow(ctx, (void**)&ctx->gv_keys, &ctx->gv_keys_bytes, need));
     HIP_TRY(ctx, sah::launch_gv_inject_scene(parg(depth), parg(normals), depth->width, depth->height, *view, cascades, num_cascades, varg(*geometry),
                                              ctx->gv_keys, ctx->stream));
     return SAH_OK;
@@ -717,6 +692,8 @@ int sah_comm_init(sah_ctx* ctx, const void* comm_id) {
     // is a collective over the parent and must not overlap its other operations).  If the installed RCCL cannot split, the reversed
     // exchange falls back to grouped point-to-point transfers on the parent communicator.
     ctx->comm_reversed = nullptr;
+    // (kept: read once per communicator, selects code that ships — the send/recv fall-back for an RCCL without ncclCommSplit — and is how
+    // tests/test_shard_chain.py and tests/test_comm_gpu.py reach it)
     const char* no_split = getenv("SAH_COMM_NO_SPLIT");
     auto split = RCCL_SYM(ctx->rccl, ncclCommSplit);
     ncclComm_t rev = nullptr;

@@ -64,7 +64,8 @@ struct sah_ctx {
     uint32_t lpv_pack_extent[3] = {0, 0, 0};
     bool lpv_pack_all_zero = false;
     float* colx_table = nullptr;       // device: per-column view-space x numerators of the fast kernel, two flavours (lighting.hip: k_colx_table)
-    uint32_t colx_capacity = 0, colx_width = 0;
+    size_t colx_bytes = 0;
+    uint32_t colx_width = 0;
     float colx_key[7] = {};            // render_resolution, p0, p12, p5, p13, height the tables were built for
     // Raised whenever something changes that a launch of sah_lighting / sah_tonemap_ex DEPENDS on beyond its arguments: a context buffer is
     // reallocated, a table is rebuilt for other extents, a gather copy that calls were re-using is dropped or has to be rebuilt.  While it
@@ -185,6 +186,26 @@ inline hipError_t sah_guard_leave(sah_ctx* ctx, SahCacheGuard& g, bool drained) 
         hipError_t e_ = (expr);                                                                     \
         if (e_ != hipSuccess) return fail(ctx, SAH_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+// A device buffer of the context that only grows.  Nothing happens while it holds `need` bytes; else a smaller one is freed — behind a
+// synchronisation of ctx->stream, whose work may still use it — and a new one allocated.  `grew` (optional): a new buffer was made; what the
+// caller keeps about the old one's contents (a key, a generation, the cache epoch) is the caller's to reset.  After a failure there is no buffer.
+inline hipError_t sah_grow(sah_ctx* ctx, void** ptr, size_t* bytes, size_t need, bool* grew = nullptr) {
+    if (grew) *grew = false;
+    if (*bytes >= need) return hipSuccess;
+    if (*ptr) {
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return e;
+        (void)hipFree(*ptr);
+    }
+    *ptr = nullptr;
+    *bytes = 0;
+    const hipError_t e = hipMalloc(ptr, need);
+    if (e != hipSuccess) return e;
+    *bytes = need;
+    if (grew) *grew = true;
+    return hipSuccess;
+}
 
 inline void sah_drop_lpv_copy(sah_ctx* ctx) {  // the volumes change: the Lighting pass's gather copy of them is stale
     if (ctx->lpv_pack_generation != 0) ctx->cache_epoch++;

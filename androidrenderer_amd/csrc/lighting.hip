@@ -28,8 +28,7 @@ namespace sah {
 template <int SUN, int GI, int PPT>
 __global__ void __launch_bounds__(256) k_lighting_general(const LightingArgs a, const CsmArgs csm, const LpvArgs lpv, const SkyArgs sky) {
     __shared__ float s_lut[512];
-    s_lut[threadIdx.x] = a.luts[threadIdx.x];
-    s_lut[threadIdx.x + 256] = a.luts[threadIdx.x + 256];
+    stage_format_tables(s_lut, a.luts);
     __syncthreads();
 
     const uint32_t groups_per_row = a.width / PPT;
@@ -81,10 +80,7 @@ __global__ void __launch_bounds__(256) k_lighting_general(const LightingArgs a, 
 constexpr uint32_t kFixupSegs = 16;
 // (at most this many workgroups, striding over the groups of segments: 512 leave an empty list 0.7 us sooner than 2,048, but take
 //  3.7 % longer over a frame that lists 29 K pixels — tools/experiments/r5/ab_fixup_grid.sh)
-#ifndef SAH_FIXUP_MAX_WGS
-#define SAH_FIXUP_MAX_WGS 2048
-#endif
-constexpr uint32_t kFixupMaxWorkgroups = SAH_FIXUP_MAX_WGS;
+constexpr uint32_t kFixupMaxWorkgroups = 2048;
 template <int SUN, int GI, int PPT>
 __global__ void __launch_bounds__(256) k_lighting_fixup(const LightingArgs a, const CsmArgs csm, const LpvArgs lpv, const SkyArgs sky,
                                                         const FastArgs f) {
@@ -92,8 +88,7 @@ __global__ void __launch_bounds__(256) k_lighting_fixup(const LightingArgs a, co
     if (__hip_atomic_load(&f.state->deferred_hint[f.hint_slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;
     __shared__ uint32_t s_pref[kFixupSegs + 1];
     __shared__ float s_lut[512];
-    s_lut[threadIdx.x] = a.luts[threadIdx.x];
-    s_lut[threadIdx.x + 256] = a.luts[threadIdx.x + 256];
+    stage_format_tables(s_lut, a.luts);
     const uint32_t ngroups = (f.num_segments + kFixupSegs - 1u) / kFixupSegs;
     for (uint32_t grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
     __syncthreads();  // (s_pref of the previous group is read no more; the LUT is in place)
@@ -141,7 +136,6 @@ __global__ void __launch_bounds__(256) k_lighting_fixup(const LightingArgs a, co
     }
 }
 
-// ---- sky kernel: the deferred depth == 0 pixels (back half of the segments) ---------------------------------------------------------
 // ---- LPV gather copy + finiteness scan -----------------------------------------------------------------------------------
 // Once per Lighting pass (3 MiB in, 4 MiB out, L2 resident): interleaves the three RGBA16F volumes into 24-byte texels
 // {R[4], G[4], B[4]} surrounded by a two-texel border of zeros, and flags inf / NaN texels (feeds the "specular quirk is inert"
@@ -178,27 +172,8 @@ __global__ void __launch_bounds__(256) k_lpv_pack(const VolumeArg r, const Volum
     if (wave_any(bad != 0) && (threadIdx.x & 63) == 0) atomicMax(&state->nonfinite, 1u);
 }
 
-// per-column numerator of the view-space x (inverse_projection separable: vs.x = p0 * ndc.x + p12), with the two texcoord conventions:
-// GLSL ((x + 0.5) + 0.5) / W (gl_FragCoord already carries the half), Slang (x + 0.5) / W
-SAH_DEV float colx_glsl_of(const LightingArgs& a, const FastArgs& f, uint32_t x) {
-    const Fn tx = (Fn((float)x + 0.5f) + Fn(0.5f)) / Fn(a.res[0]);
-    return (Fn(f.p0) * (tx * Fn(2.0f) - Fn(1.0f)) + Fn(f.p12)).v;
-}
-SAH_DEV float colx_slang_of(const LightingArgs& a, const FastArgs& f, uint32_t x) {
-    const Fn tx = (Fn((float)x) + Fn(0.5f)) / Fn(a.res[0]);
-    return (Fn(f.p0) * (tx * Fn(2.0f) - Fn(1.0f)) + Fn(f.p12)).v;
-}
-// the same values for every column, once per (width, render resolution, p0, p12): the kernel then loads PPT of them instead of dividing
-// ... and the per-row numerators of the view-space y (vs.y = p5 * ndc.y + p13), rows [0, height): at out + 2 * stride (GLSL) and
-// out + 2 * stride + row_stride (Slang) — two IEEE divides per THREAD otherwise, which at four pixels per thread is 8 instructions per pixel
-SAH_DEV float rowy_glsl_of(const LightingArgs& a, const FastArgs& f, uint32_t y) {
-    const Fn ty = (Fn((float)y + 0.5f) + Fn(0.5f)) / Fn(a.res[1]);
-    return (Fn(f.p5) * (ty * Fn(2.0f) - Fn(1.0f)) + Fn(f.p13)).v;
-}
-SAH_DEV float rowy_slang_of(const LightingArgs& a, const FastArgs& f, uint32_t y) {
-    const Fn ty = (Fn((float)y) + Fn(0.5f)) / Fn(a.res[1]);
-    return (Fn(f.p5) * (ty * Fn(2.0f) - Fn(1.0f)) + Fn(f.p13)).v;
-}
+// the numerators of lighting_fast.hpp (colx_*_of / rowy_*_of) for every column and row, once per (extent, render resolution, p0, p12, p5, p13):
+// columns [0, width) at out (GLSL) and out + stride (Slang), rows [0, height) at out + 2 * stride (GLSL) and out + 2 * stride + row_stride (Slang)
 __global__ void __launch_bounds__(256) k_colx_table(const LightingArgs a, const FastArgs f, float* out, uint32_t stride, uint32_t row_stride) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i < a.width) {
@@ -227,18 +202,19 @@ template <int SUN, int GI, int PPT, bool SKY>
 __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const LightingArgs a, const CsmArgs csm, const LpvArgs lpv, const SkyArgs sky,
                                                                                  const FastArgs f) {
     // Sky.  ProceduralSky::render_sky overwrites lit_scene where depth == 0 (sky_unified.slang:185-206): those pixels need their
-    // coordinates and two fp64 transcendentals each, nothing of the surface code.  With a sky bound, one workgroup in sky_ratio + 1
-    // is a sky workgroup: it reads the depth of the pixels of the sky_ratio surface workgroups before it and shades the sky among them;
-    // surface workgroups leave those pixels alone.  Interleaved like this the sky's arithmetic fills issue slots the surface waves leave
-    // idle (as a kernel of its own behind this one it cost 20 us on the 4 % of sky in the atrium frame: one busy wave per SIMD, in series).
+    // coordinates and two fp64 transcendentals each, nothing of the surface code.  With a sky bound the first f.sky_first workgroups of the
+    // grid are sky workgroups: workgroup i reads the depth of the pixels of surface workgroups [i * sky_ratio, (i + 1) * sky_ratio) and shades
+    // the sky among them; surface workgroups leave those pixels alone.  In the same launch the sky's arithmetic fills issue slots the surface
+    // waves leave idle (as a kernel of its own behind this one it cost 20 us on the 4 % of sky in the atrium frame: one busy wave per SIMD, in
+    // series); leading the grid, the walk is not the launch's tail (api.cpp, where sky_ratio and sky_first are chosen).
     uint32_t block_id = blockIdx.x;
     if (SKY) {
-        const uint32_t ratio = f.sky_ratio, period = ratio + 1u, turn = f.sky_first ? blockIdx.x : blockIdx.x / period;
-        if (f.sky_first ? blockIdx.x < f.sky_first : blockIdx.x - turn * period == ratio) {
+        if (blockIdx.x < f.sky_first) {
+            const uint32_t ratio = f.sky_ratio;
             const uint32_t groups_per_row = a.width / PPT, total = groups_per_row * (a.row_end - a.row_begin);
 #pragma unroll 1
             for (uint32_t k = 0; k < ratio; k++) {
-                const uint32_t gid = (turn * ratio + k) * 256u + threadIdx.x;
+                const uint32_t gid = (blockIdx.x * ratio + k) * 256u + threadIdx.x;
                 if (gid >= total) break;
                 const uint32_t ry = gid / groups_per_row, y = a.row_begin + ry, x0 = (gid - ry * groups_per_row) * PPT;
                 uint32_t wz[PPT];
@@ -253,7 +229,7 @@ __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const Lighti
             }
             return;
         }
-        block_id = f.sky_first ? blockIdx.x - f.sky_first : blockIdx.x - turn;
+        block_id = blockIdx.x - f.sky_first;
     }
     // the thread's plane loads are requested first: the LUT staging and its barrier below then overlap their latency
     const uint32_t groups_per_row = a.width / PPT;
@@ -290,20 +266,7 @@ __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const Lighti
         }
     }
     __shared__ __attribute__((aligned(16))) float s_lut[TAB_SIZE];
-    s_lut[threadIdx.x] = a.luts[threadIdx.x];
-    s_lut[threadIdx.x + 256] = a.luts[threadIdx.x + 256];
-    if (SUN == SAH_SHADOW_MODE_CSM && threadIdx.x < 48) {  // [cascade][row x,y,z][col 0..3] of biasMat * cascade_matrices
-        const uint32_t c = threadIdx.x / 12u, j = threadIdx.x % 12u;
-        s_lut[TAB_CSM + threadIdx.x] = csm.biased[c][(j & 3u) * 4u + (j >> 2)];
-    }
-    if (GI == SAH_GI_LPV && threadIdx.x >= 64 && threadIdx.x < 96) {  // [cascade][sx sy sz - tx ty tz -]
-        const uint32_t t = threadIdx.x - 64u, c = t >> 3, j = t & 7u;
-        s_lut[TAB_LPV + t] = (j & 3u) == 3u ? 0.f : (j < 4u ? f.lpv_s[c][j] : f.lpv_t[c][j - 4u]);
-    }
-    if (threadIdx.x >= 128 && threadIdx.x < 140) {  // rows x,y,z of the (affine) inverse view matrix: (m[i], m[4+i], m[8+i], m[12+i])
-        const uint32_t t = threadIdx.x - 128u;
-        s_lut[TAB_VIEW + t] = a.inv_view[(t & 3u) * 4u + (t >> 2)];
-    }
+    stage_fast_tables<SUN == SAH_SHADOW_MODE_CSM, GI == SAH_GI_LPV>(s_lut, a, csm, f);
     __syncthreads();
 
     // per-row / per-column terms of the view-space position (two texcoord conventions, see lighting_common.hpp): from the table where
@@ -426,11 +389,8 @@ static hipError_t launch_fast_ppt(const LightingArgs& a, const CsmArgs& csm, con
     const dim3 block(256);
     auto launch = [&](auto ppt_c) {
         constexpr int P = decltype(ppt_c)::value;
-        if (sky.enabled && f.sky_first) {
-            FastArgs g = f;
-            g.sky_first = (blocks + f.sky_ratio - 1u) / f.sky_ratio;
-            hipLaunchKernelGGL((k_lighting_fast<SUN, GI, P, true>), dim3(g.sky_first + blocks), block, 0, st, a, csm, lpv, sky, g);
-        } else if (sky.enabled) hipLaunchKernelGGL((k_lighting_fast<SUN, GI, P, true>), dim3((f.sky_ratio + 1u) * ((blocks + f.sky_ratio - 1u) / f.sky_ratio)), block, 0, st, a, csm, lpv, sky, f);
+        // (f.sky_first sky workgroups lead the grid: api.cpp)
+        if (sky.enabled) hipLaunchKernelGGL((k_lighting_fast<SUN, GI, P, true>), dim3(f.sky_first + blocks), block, 0, st, a, csm, lpv, sky, f);
         else hipLaunchKernelGGL((k_lighting_fast<SUN, GI, P, false>), dim3(blocks), block, 0, st, a, csm, lpv, sky, f);
     };
     if (ppt == 4) launch(std::integral_constant<int, 4>{});
@@ -466,9 +426,10 @@ hipError_t launch_lighting_tiled(const LightingArgs& a, const CsmArgs& csm, cons
                                  const SkyArgs& sky, int sun_mode, int gi, bool brute_force_lights, const FastArgs* fast, hipStream_t st);
 
 hipError_t launch_lighting(const LightingArgs& a, const CsmArgs& csm, const LpvArgs& lpv, const CacheArgs& cache, const RtgiArgs& rtgi,
-                           const SkyArgs& sky, const FastArgs* fast, int sun_mode, int gi, int ppt, bool brute_force_lights, hipStream_t st) {
-    // point lights and the GI overlays without a fast path run in the 16x16-tile kernel (lighting_tiled.hip)
-    if (a.num_lights || gi == SAH_GI_CACHE || gi == SAH_GI_RTGI) {
+                           const SkyArgs& sky, LightingFamily family, const FastArgs* fast, int sun_mode, int gi, int ppt, bool brute_force_lights,
+                           hipStream_t st) {
+    // `fast`: what the host established about the uniform blocks (the fast kernel's arguments; for the tiled kernel, when not null, its fast geometry)
+    if (family == kLightingTiled) {
         if (gi == SAH_GI_LPV && fast && fast->lpv_fast && fast->repack && a.row_end > a.row_begin) {
             const hipError_t pe = launch_lpv_pack(lpv, *fast, st);
             if (pe != hipSuccess) return pe;

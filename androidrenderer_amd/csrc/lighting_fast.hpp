@@ -16,6 +16,52 @@ SAH_DEV bool finite_f(float x) { return __builtin_fabsf(x) < __builtin_inff(); }
 // LDS table of the fast kernel: [0,512) format LUTs, then the per-cascade rows that are indexed per lane
 enum : uint32_t { TAB_CSM = 512, TAB_LPV = 512 + 48, TAB_VIEW = 512 + 48 + 32, TAB_SIZE = 512 + 48 + 32 + 12 };
 
+// The LDS staging of a 256-thread workgroup, called ahead of the kernel's barrier: the 512 format-table entries (api.cpp: sRGB8 -> linear,
+// UNORM8 -> float) ...
+SAH_DEV void stage_format_tables(float* s_lut, const float* luts) {
+    s_lut[threadIdx.x] = luts[threadIdx.x];
+    s_lut[threadIdx.x + 256] = luts[threadIdx.x + 256];
+}
+// ... and behind them the rows that are indexed per lane (TAB_*): the CSM rows with a CSM sun, the LPV rows with an LPV (lpv_s / lpv_t valid)
+template <bool CSM, bool LPV>
+SAH_DEV void stage_fast_tables(float* s_lut, const LightingArgs& a, const CsmArgs& csm, const FastArgs& f) {
+    stage_format_tables(s_lut, a.luts);
+    if (CSM && threadIdx.x < 48) {  // [cascade][row x,y,z][col 0..3] of biasMat * cascade_matrices
+        const uint32_t c = threadIdx.x / 12u, j = threadIdx.x % 12u;
+        s_lut[TAB_CSM + threadIdx.x] = csm.biased[c][(j & 3u) * 4u + (j >> 2)];
+    }
+    if (LPV && threadIdx.x >= 64 && threadIdx.x < 96) {  // [cascade][sx sy sz - tx ty tz -]
+        const uint32_t t = threadIdx.x - 64u, c = t >> 3, j = t & 7u;
+        s_lut[TAB_LPV + t] = (j & 3u) == 3u ? 0.f : (j < 4u ? f.lpv_s[c][j] : f.lpv_t[c][j - 4u]);
+    }
+    if (threadIdx.x >= 128 && threadIdx.x < 140) {  // rows x,y,z of the (affine) inverse view matrix: (m[i], m[4+i], m[8+i], m[12+i])
+        const uint32_t t = threadIdx.x - 128u;
+        s_lut[TAB_VIEW + t] = a.inv_view[(t & 3u) * 4u + (t >> 2)];
+    }
+}
+
+// per-column numerator of the view-space x (inverse_projection separable: vs.x = p0 * ndc.x + p12), with the two texcoord conventions:
+// GLSL ((x + 0.5) + 0.5) / W (gl_FragCoord already carries the half), Slang (x + 0.5) / W
+SAH_DEV float colx_glsl_of(const LightingArgs& a, const FastArgs& f, uint32_t x) {
+    const Fn tx = (Fn((float)x + 0.5f) + Fn(0.5f)) / Fn(a.res[0]);
+    return (Fn(f.p0) * (tx * Fn(2.0f) - Fn(1.0f)) + Fn(f.p12)).v;
+}
+SAH_DEV float colx_slang_of(const LightingArgs& a, const FastArgs& f, uint32_t x) {
+    const Fn tx = (Fn((float)x) + Fn(0.5f)) / Fn(a.res[0]);
+    return (Fn(f.p0) * (tx * Fn(2.0f) - Fn(1.0f)) + Fn(f.p12)).v;
+}
+// the same values for every column, once per (width, render resolution, p0, p12): the kernel then loads PPT of them instead of dividing
+// ... and the per-row numerators of the view-space y (vs.y = p5 * ndc.y + p13), rows [0, height): at out + 2 * stride (GLSL) and
+// out + 2 * stride + row_stride (Slang) — two IEEE divides per THREAD otherwise, which at four pixels per thread is 8 instructions per pixel
+SAH_DEV float rowy_glsl_of(const LightingArgs& a, const FastArgs& f, uint32_t y) {
+    const Fn ty = (Fn((float)y + 0.5f) + Fn(0.5f)) / Fn(a.res[1]);
+    return (Fn(f.p5) * (ty * Fn(2.0f) - Fn(1.0f)) + Fn(f.p13)).v;
+}
+SAH_DEV float rowy_slang_of(const LightingArgs& a, const FastArgs& f, uint32_t y) {
+    const Fn ty = (Fn((float)y) + Fn(0.5f)) / Fn(a.res[1]);
+    return (Fn(f.p5) * (ty * Fn(2.0f) - Fn(1.0f)) + Fn(f.p13)).v;
+}
+
 struct FastPixelOut {
     uint2 lit;
     bool deferred;
@@ -290,23 +336,6 @@ SAH_DEV FastPixelOut shade_pixel_fast_sl(const LightingArgs& a, const CsmArgs& c
         lpv_v = cpy.v;
         lpv_w = cpz.v;
     }
-#ifdef SAH_EXP_LPV_TOUCH
-    // experiment (tools/experiments/r6): one dword of each of the four (y, z) rows of the LPV footprint requested BEFORE the sun's arithmetic, consumed
-    // behind it: the twelve 16-byte loads of lpv_fetch_packed() then find their lines in the vector cache
-    uint32_t lpv_touch[4] = {0u, 0u, 0u, 0u};
-    if constexpr (GI == SAH_GI_LPV && SUN == SAH_SHADOW_MODE_CSM) {
-        const int W = (int)lpv.red.width, H = (int)lpv.red.height, Dd = (int)lpv.red.depth;
-        const float px = lpv_u * (float)W - 0.5f, py = lpv_v * (float)H - 0.5f, pz = lpv_w * (float)Dd - 0.5f;
-        const int b = (int)kLpvPackBorder;
-        const uint32_t x0 = (uint32_t)(min(max(clamp_to_int(__builtin_floorf(px)), -b), W) + b), y0 = (uint32_t)(min(max(clamp_to_int(__builtin_floorf(py)), -b), H) + b),
-                       z0 = (uint32_t)(min(max(clamp_to_int(__builtin_floorf(pz)), -b), Dd) + b);
-        const uint32_t base = z0 * f.pk_slice_pitch + y0 * f.pk_row_pitch + x0 * kLpvPackTexel;
-        lpv_touch[0] = *reinterpret_cast<const uint32_t*>(f.lpv_packed + base);
-        lpv_touch[1] = *reinterpret_cast<const uint32_t*>(f.lpv_packed + base + f.pk_row_pitch);
-        lpv_touch[2] = *reinterpret_cast<const uint32_t*>(f.lpv_packed + base + f.pk_slice_pitch);
-        lpv_touch[3] = *reinterpret_cast<const uint32_t*>(f.lpv_packed + base + f.pk_slice_pitch + f.pk_row_pitch);
-    }
-#endif
 
     // ---------------- a1: sun, CSM mode ----------------
     // direct = ((ndotl * brdf) * colour) * shadow is exactly 0 (or NaN, which the shader's guard turns into 0) whenever
@@ -327,9 +356,6 @@ SAH_DEV FastPixelOut shade_pixel_fast_sl(const LightingArgs& a, const CsmArgs& c
 
     // ---------------- a3: LPV overlay ----------------
     if constexpr (GI == SAH_GI_LPV) {
-#ifdef SAH_EXP_LPV_TOUCH
-        asm volatile("" ::"v"(lpv_touch[0]), "v"(lpv_touch[1]), "v"(lpv_touch[2]), "v"(lpv_touch[3]));
-#endif
         Fn indirect[3];
         lpv_fetch_packed(lpv, f.lpv_packed, f.pk_row_pitch, f.pk_slice_pitch, lpv_u, lpv_v, lpv_w, nc, indirect);
         // Fd(surface, N, N) == diffuse_color * (1/pi) exactly when N is a finite normalised vector, and the specular term

@@ -34,17 +34,16 @@ SAH_DEV float wave_max(float v) {
     return v;
 }
 
-#ifndef SAH_EXP_CACHE_WAVES
-#define SAH_EXP_CACHE_WAVES 1  // experiments (tools/experiments/r6): waves per SIMD the cache-GI body without a light list is held to (1: the allocator's own 4)
-#endif
 template <int SUN, int GI, bool LIGHTS>
-__global__ void __launch_bounds__(256, ((GI == SAH_GI_CACHE && !LIGHTS) ? SAH_EXP_CACHE_WAVES : 1)) k_lighting_tiled(const LightingArgs a, const CsmArgs csm, const LpvArgs lpv, const CacheArgs cache,
+__global__ void __launch_bounds__(256) k_lighting_tiled(const LightingArgs a, const CsmArgs csm, const LpvArgs lpv, const CacheArgs cache,
                                                         const RtgiArgs rtgi, const SkyArgs sky, const uint32_t brute_force, const FastArgs f,
                                                         const uint32_t fast_geom) {
     // `fast_geom`: the uniform blocks have the structure the fast kernel's geometry and CSM sun rely on (api.cpp: detect_fast_path);
     // then the fp32 geometry (normal, position, view vector) and the CSM sun come from lighting_fast.hpp — the same bits at a third of
     // the instructions — and only pixels outside their domains take the general restatement.
     __shared__ __attribute__((aligned(16))) float s_lut[TAB_SIZE];
+    // (staged here in this kernel's own order, not through stage_fast_tables() of lighting_fast.hpp: with the helper the registers stay what
+    // they are but the kernel's instructions are scheduled differently, and the light workloads measure 0.3 % slower)
     if (SUN == SAH_SHADOW_MODE_CSM && threadIdx.x < 48) {  // [cascade][row x,y,z][col 0..3] of biasMat * cascade_matrices
         const uint32_t c = threadIdx.x / 12u, j = threadIdx.x % 12u;
         s_lut[TAB_CSM + threadIdx.x] = csm.biased[c][(j & 3u) * 4u + (j >> 2)];
@@ -61,8 +60,7 @@ __global__ void __launch_bounds__(256, ((GI == SAH_GI_CACHE && !LIGHTS) ? SAH_EX
     __shared__ uint32_t s_wave_count[4];
     __shared__ uint16_t s_list[kMaxTileLights];
     __shared__ float2 s_lconst[LIGHTS ? kMaxTileLights : 1u];  // per kept light: far2, refined 1 / radius (see the shading loop)
-    s_lut[threadIdx.x] = a.luts[threadIdx.x];
-    s_lut[threadIdx.x + 256] = a.luts[threadIdx.x + 256];
+    stage_format_tables(s_lut, a.luts);
     __syncthreads();
 
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -114,6 +112,8 @@ __global__ void __launch_bounds__(256, ((GI == SAH_GI_CACHE && !LIGHTS) ? SAH_EX
                 colx_glsl = f.colx_tab[xt];
                 rowy_glsl = f.colx_tab[2u * f.colx_stride + yt];
             } else {
+                // (colx_glsl_of / rowy_glsl_of of lighting_fast.hpp written out, here and for the Slang pair below: called as functions the same
+                //  operators are scheduled differently through the whole kernel — same registers, the light workloads 0.3 % slower)
                 const Fn tx = (Fn((float)x + 0.5f) + Fn(0.5f)) / Fn(a.res[0]), ty = (Fn((float)y + 0.5f) + Fn(0.5f)) / Fn(a.res[1]);
                 colx_glsl = (Fn(f.p0) * (tx * Fn(2.0f) - Fn(1.0f)) + Fn(f.p12)).v;
                 rowy_glsl = (Fn(f.p5) * (ty * Fn(2.0f) - Fn(1.0f)) + Fn(f.p13)).v;

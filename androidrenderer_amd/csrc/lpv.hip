@@ -84,8 +84,7 @@ struct PropArgs {
     uint32_t pk_row_pitch, pk_slice_pitch;
     FrameState* state;
     uint32_t hot;  // the tables have the structure propagate_from_hot relies on: waves with finite coefficients take it
-    // use_gv = 1 (sah_lpv_propagate_gv): the geometry volume (GV 2: every step samples it) or its precomputed factors (GV 1: k_gv_factors)
-    VolumeArg gv;
+    // use_gv = 1 (sah_lpv_propagate_gv): the geometry volume's precomputed factors (k_gv_factors)
     const uint4* gv_factors;
     uint32_t gv_cells;
 };
@@ -367,8 +366,7 @@ SAH_DEV H4 h4_of(uint2 q) {
 // bit 15 / bit 31 set <=> the low / high half of w has an all-ones exponent (inf or NaN): 0x7c00 + 0x0400 carries into the sign position
 SAH_DEV uint32_t nonfinite_halves(uint32_t w) { return (w & 0x7c007c00u) + 0x04000400u; }
 
-// NC colour volumes per thread (1: blockIdx.y picks the colour; 3: all of them — the neighbour tests, addresses and the scalar table reads are
-// shared, a third as many waves each three times as long).
+// One colour volume per thread (c0: blockIdx.y).
 // The neighbour of direction n is the cell at c - kDir[n]; which of them exist is one compare each, because c is in [0, 32)^3 and the host has
 // checked the extents ((32 * cascades) x 32 x 32 at least, api_post.cpp):  c - 1 is outside the volume only below 0 — for x that is x == 0 of
 // cascade 0: a cell of column 0 of a later cascade reads the last column of the cascade before it, the shader's own quirk —, and c + 1 is the
@@ -377,8 +375,11 @@ SAH_DEV uint32_t nonfinite_halves(uint32_t w) { return (w & 0x7c007c00u) + 0x040
 // __constant__ data (rounds 1-5) every neighbour's address waited for a load of its direction, and the waits (vmcnt counts in order) also
 // waited for the neighbour texels requested before: six round trips in series, most of a step's 9.3 us.
 constexpr int8_t kDirC[6][3] = {{0, 0, 1}, {0, 0, -1}, {1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}};
-template <int NC, bool EMIT, int GV = 0>
+template <bool EMIT, bool GV = false>
 SAH_DEV void propagate_cell_hot(const PropTables& T, const PropArgs& a, uint32_t idx, uint32_t c0) {
+    // (The loops over the thread's colour volumes are one-trip since the three-colours-per-thread variant went.  They stay as written: folded
+    // by hand the same arithmetic is allocated and scheduled differently, 59 -> 33 VGPRs for the plain step, and nobody has timed that kernel.)
+    constexpr int NC = 1;
     const uint32_t cx = idx & 31u, cy = (idx >> 5) & 31u, cz = (idx >> 10) & 31u, x = cx + (idx >> 15) * 32u;
     uint2 q[NC][6];
     uint32_t off_c[NC];
@@ -410,15 +411,14 @@ SAH_DEV void propagate_cell_hot(const PropTables& T, const PropArgs& a, uint32_t
         for (int n = 0; n < 6; n++) bad |= nonfinite_halves(q[c][n].x) | nonfinite_halves(q[c][n].y);
     const bool general = !a.hot || wave_any((bad & 0x80008000u) != 0u);
     Hn fac[30];
-    if constexpr (GV == 1) gv_load_factors(a.gv_factors, a.gv_cells, idx, fac);
-    else if constexpr (GV == 2) gv_cell_factors(T, a.gv, idx, fac);
+    if constexpr (GV) gv_load_factors(a.gv_factors, a.gv_cells, idx, fac);
     uint32_t bad_out = 0;
 #pragma unroll
     for (int c = 0; c < NC; c++) {
         H4 coef[6];
 #pragma unroll
         for (int n = 0; n < 6; n++) coef[n] = h4_of(q[c][n]);
-        const H4 out = general ? propagate_from<GV != 0>(T, coef, fac) : propagate_from_hot<GV != 0>(T, coef, fac);
+        const H4 out = general ? propagate_from<GV>(T, coef, fac) : propagate_from_hot<GV>(T, coef, fac);
         uint2 o;
         o.x = (uint32_t)__builtin_bit_cast(uint16_t, out.x.v) | ((uint32_t)__builtin_bit_cast(uint16_t, out.y.v) << 16);
         o.y = (uint32_t)__builtin_bit_cast(uint16_t, out.z.v) | ((uint32_t)__builtin_bit_cast(uint16_t, out.w.v) << 16);
@@ -435,7 +435,7 @@ SAH_DEV void propagate_cell_hot(const PropTables& T, const PropArgs& a, uint32_t
     }
 }
 
-template <int GV = 0>
+template <bool GV = false>
 SAH_DEV H4 propagate_cell(const PropTables& T, const VolumeArg& src, const VolumeArg& dst, uint32_t idx, const PropArgs& a) {
     const int cx = idx & 31, cy = (idx >> 5) & 31, cz = (idx >> 10) & 31, cascade = idx >> 15;
     const int xoff = cascade * 32;
@@ -451,14 +451,13 @@ SAH_DEV H4 propagate_cell(const PropTables& T, const VolumeArg& src, const Volum
         coef[n] = load_h4(src, skipped ? -1 : nx + xoff, ny, nz);
     }
     Hn fac[30];
-    if constexpr (GV == 1) gv_load_factors(a.gv_factors, a.gv_cells, idx, fac);
-    else if constexpr (GV == 2) gv_cell_factors(T, a.gv, idx, fac);
-    const H4 out = propagate_from<GV != 0>(T, coef, fac);
+    if constexpr (GV) gv_load_factors(a.gv_factors, a.gv_cells, idx, fac);
+    const H4 out = propagate_from<GV>(T, coef, fac);
     store_h4(dst, cx + xoff, cy, cz, out);
     return out;
 }
 
-template <bool EMIT, int GV = 0>
+template <bool EMIT, bool GV = false>
 __global__ void __launch_bounds__(256) k_lpv_propagate(PropArgs a) {
     const PropTables& T = c_prop_tables;
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
@@ -494,11 +493,11 @@ __global__ void __launch_bounds__(256) k_lpv_clear(ClearArgs a) {
     }
 }
 
-template <int NC, bool EMIT, int GV = 0>
+template <bool EMIT, bool GV = false>
 __global__ void __launch_bounds__(256) k_lpv_propagate_hot(PropArgs a) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= a.num_cascades * 32768u) return;
-    propagate_cell_hot<NC, EMIT, GV>(c_prop_tables, a, idx, NC == 1 ? blockIdx.y : 0u);
+    propagate_cell_hot<EMIT, GV>(c_prop_tables, a, idx, blockIdx.y);
 }
 
 hipError_t launch_lpv_clear(const VolumeArg* vols, int n, uint32_t num_cascades, hipStream_t st) {
@@ -525,31 +524,26 @@ hipError_t launch_lpv_build_tables(hipStream_t st, bool* hot_structure) {
 }
 
 // `emit` (or null): where the step also writes the Lighting pass's gather copy of `dst` (PropArgs)
-// `mode`: 0 the general form only (rounds 1-5's kernel), 1 hot form, one colour volume per thread, 3 hot form, the three colours of a cell in one thread
-// `gv` (or null): use_gv = 1 with this step's occlusion factors (LpvGvStep::mode 1: precomputed by launch_lpv_gv_factors, 2: sampled by the step)
-template <int GV>
-static void launch_propagate_kernel(const PropArgs& a, uint32_t num_cascades, bool emit, int mode, hipStream_t st) {
-    if (mode != 0) {
-        const dim3 grid(num_cascades * 128, mode == 3 ? 1 : 3);
-        if (mode == 3) {
-            if (emit) hipLaunchKernelGGL((k_lpv_propagate_hot<3, true, GV>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((k_lpv_propagate_hot<3, false, GV>), grid, dim3(256), 0, st, a);
-        } else {
-            if (emit) hipLaunchKernelGGL((k_lpv_propagate_hot<1, true, GV>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((k_lpv_propagate_hot<1, false, GV>), grid, dim3(256), 0, st, a);
-        }
-        return;
+// `hot`: the hot form (waves with finite coefficients take it); else the general form only (rounds 1-5's kernel)
+// `gv` (or null): use_gv = 1 with this step's occlusion factors, precomputed by launch_lpv_gv_factors
+template <bool GV>
+static void launch_propagate_kernel(const PropArgs& a, uint32_t num_cascades, bool emit, bool hot, hipStream_t st) {
+    const dim3 grid(num_cascades * 128, 3);  // (y: the colour volume)
+    if (hot) {
+        if (emit) hipLaunchKernelGGL((k_lpv_propagate_hot<true, GV>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_lpv_propagate_hot<false, GV>), grid, dim3(256), 0, st, a);
+    } else {
+        if (emit) hipLaunchKernelGGL((k_lpv_propagate<true, GV>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_lpv_propagate<false, GV>), grid, dim3(256), 0, st, a);
     }
-    if (emit) hipLaunchKernelGGL((k_lpv_propagate<true, GV>), dim3(num_cascades * 128, 3), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_lpv_propagate<false, GV>), dim3(num_cascades * 128, 3), dim3(256), 0, st, a);
 }
 
-hipError_t launch_lpv_propagate(const VolumeArg src[3], const VolumeArg dst[3], uint32_t num_cascades, const LpvPackEmit* emit, int mode, hipStream_t st,
+hipError_t launch_lpv_propagate(const VolumeArg src[3], const VolumeArg dst[3], uint32_t num_cascades, const LpvPackEmit* emit, bool hot, hipStream_t st,
                                 const LpvGvStep* gv) {
     PropArgs a = {};
     for (int i = 0; i < 3; i++) { a.src[i] = src[i]; a.dst[i] = dst[i]; }
     a.num_cascades = num_cascades;
-    a.hot = mode != 0 ? 1u : 0u;
+    a.hot = hot ? 1u : 0u;
     if (emit) {
         a.packed = emit->packed;
         a.pk_row_pitch = emit->row_pitch;
@@ -558,15 +552,12 @@ hipError_t launch_lpv_propagate(const VolumeArg src[3], const VolumeArg dst[3], 
         const hipError_t me = hipMemsetAsync(&emit->state->nonfinite, 0, sizeof(uint32_t), st);  // the copy's verdict starts at "finite"
         if (me != hipSuccess) return me;
     }
-    const int gv_mode = gv ? gv->mode : 0;
     if (gv) {
-        a.gv = gv->gv;
         a.gv_factors = (const uint4*)gv->factors;
         a.gv_cells = num_cascades * 32768u;
     }
-    if (gv_mode == 1) launch_propagate_kernel<1>(a, num_cascades, emit != nullptr, mode, st);
-    else if (gv_mode == 2) launch_propagate_kernel<2>(a, num_cascades, emit != nullptr, mode, st);
-    else launch_propagate_kernel<0>(a, num_cascades, emit != nullptr, mode, st);
+    if (gv) launch_propagate_kernel<true>(a, num_cascades, emit != nullptr, hot, st);
+    else launch_propagate_kernel<false>(a, num_cascades, emit != nullptr, hot, st);
     return hipGetLastError();
 }
 

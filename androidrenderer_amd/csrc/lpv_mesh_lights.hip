@@ -597,16 +597,7 @@ int sah_lpv_inject_emissive(sah_ctx* ctx, const sah_scene_geometry* scene, const
     for (int c = 0; c < 3; c++) m.rgb[c] = varg(a_rgb[c]);
     // scratch grows only; freeing a smaller one waits for the work that may still use it
     const size_t need = sah::ml_scratch_bytes((uint32_t)std::max<uint64_t>(T, 4096));
-    if (ctx->ml_scratch_bytes < need) {
-        if (ctx->ml_scratch) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(ctx->ml_scratch);
-        }
-        ctx->ml_scratch = nullptr;
-        ctx->ml_scratch_bytes = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->ml_scratch, need));
-        ctx->ml_scratch_bytes = need;
-    }
+    HIP_TRY(ctx, sah_grow(ctx, &ctx->ml_scratch, &ctx->ml_scratch_bytes, need));
     HIP_TRY(ctx, sah::launch_inject_emissive(m, recs, ctx->ml_scratch, ctx->stream));
     return SAH_OK;
 }

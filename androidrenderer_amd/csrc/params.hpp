@@ -86,7 +86,6 @@ struct FrameState {
     // so no memset, no atomic and no "last workgroup" ticket is needed (2,025 tickets on one address cost 0.1 ms).  A captured launch that
     // is replayed by itself keeps its slot: its word is then never cleared, which costs the early exit, not correctness.
     uint32_t deferred_hint[2];
-    uint32_t unused;
     // 1 when the gather copy of the LPV volumes holds an inf / NaN texel: cleared (a 4-byte memset in front of the kernel) and raised by whatever
     // writes the copy — k_lpv_pack, or the emitting step of the propagation — and read by the Lighting kernels; a copy that is kept over several
     // Lighting calls keeps its verdict.  (Rounds 2-4 compared a tag with the copy's serial number, a KERNEL ARGUMENT: a captured launch replays
@@ -105,7 +104,7 @@ struct FastArgs {
     uint32_t pos_div_nr;  // view-space position quotients may use the shared-reciprocal divide (lighting_fast.hpp)
     uint32_t sky_enabled;
     uint32_t sky_ratio;  // surface workgroups per sky workgroup of k_lighting_fast's grid (lighting.hip); >= 1
-    uint32_t sky_first;  // 0: every (sky_ratio + 1)-th workgroup of the grid is a sky workgroup; else the number of sky workgroups, which lead the grid
+    uint32_t sky_first;  // the number of sky workgroups, which lead the grid: ceil(surface workgroups / sky_ratio) with a sky bound, else 0
     uint32_t row_magic;  // floor(2^32 / groups per row) + 1 when mulhi(gid, row_magic) == gid / groups_per_row for every thread of the call, else 0
     uint32_t repack;       // 1: this call rebuilds the gather copy first
     const float* colx_tab; // per-column view-space x numerators (k_colx_table): [0, width) the GLSL flavour, [colx_stride, ..) the Slang one; or null
@@ -113,9 +112,9 @@ struct FastArgs {
     uint32_t rowy_stride;  // per-row numerators of the view-space y behind the two column tables: [2 * colx_stride, ..) GLSL, [2 * colx_stride + rowy_stride, ..) Slang
     FrameState* state;
     // Deferred pixels, without atomics: the wave that shades thread groups [64 s, 64 s + 64) owns segment s — kSegSize(PPT) byte codes
-    // (lane * PPT + pixel) at seg_list + s * seg_stride — general pixels from the front, sky pixels (depth == 0) from the back — and
-    // their numbers in seg_count[s] / seg_count[num_segments + s], which it always writes (0 included), so nothing has to be cleared
-    // between calls.  The fix-up and sky kernels walk 16 segments per workgroup.
+    // (lane * PPT + pixel) at seg_list + s * seg_stride — and their number in seg_count[s], which it always writes (0 included), so nothing
+    // has to be cleared between calls.  Sky pixels (depth == 0 with a sky bound) are not listed: the sky workgroups find them by their depth.
+    // The fix-up kernel walks 16 segments per workgroup.
     uint8_t* seg_list;
     uint16_t* seg_count;
     uint32_t num_segments, seg_stride;
@@ -128,10 +127,9 @@ struct FastArgs {
 };
 // (an fp32 copy — 48-byte texels, plain v_fma_f32 taps — was measured and loses 67 %: profiles/r3_lpv_pack32_experiment.txt)
 constexpr uint32_t kLpvPackTexel = 24, kLpvPackBorder = 2;
-struct LpvGvStep {  // use_gv = 1 in a propagation step (lpv.hip): the geometry volume, and its factors when precomputed (mode 1; mode 2: sampled per step)
+struct LpvGvStep {  // use_gv = 1 in a propagation step (lpv.hip): the geometry volume and its precomputed factors (k_gv_factors)
     VolumeArg gv;
     void* factors;
-    int mode;
 };
 
 struct LpvPackEmit {  // the gather copy as the emitting propagation step writes it (lpv.hip)
@@ -139,6 +137,9 @@ struct LpvPackEmit {  // the gather copy as the emitting propagation step writes
     uint32_t row_pitch, slice_pitch;
     FrameState* state;
 };
+
+// which kernel family a Lighting call runs (api.cpp decides, launch_lighting launches, sah_debug_lighting_dispatch reports it as word 0)
+enum LightingFamily : uint32_t { kLightingGeneral = 0, kLightingFast = 1, kLightingTiled = 2 };
 
 struct LightingArgs {
     PlaneArg color, normals, data, emission, depth, ao, shadow_mask, lit;

@@ -29,8 +29,6 @@
 // LDS per workgroup: G 32.3 KB + texels 10.8 KB + tables 9 KB = 52.3 KB, 3 workgroups per CU.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "post_common.hpp"
 
 namespace sah {
@@ -40,19 +38,15 @@ constexpr int kTile = 32;     // tile width in pixels
 constexpr int kPitch = 32;    // cells per staged row (a rectangle is at most 25 texel columns wide)
 constexpr int kMaxCols = 25;
 constexpr int kStageMips = 3;
-// Tile height and how the mips are grouped into stages.  32 rows: {0}, {1, 2}, {3, 4, 5} — 21 staged rows hold each stage of a
+// Tile height and how the mips are grouped into stages: 32 rows, {0}, {1, 2}, {3, 4, 5} — 21 staged rows hold each stage of a
 // half-resolution chain (mip 0 needs 20, mips 1 + 2 12 + 8, mips 3..5 6 + 6 + 6); 52.3 KB of LDS, three workgroups per CU (22 rows: 54.4 KB,
-// which did NOT fit three times into a CU's 160 KB — two per CU, 1.47 x the time).  16 rows, for row bands whose 32-row tiles would not
-// fill the chip twice (a rank's rows of a sharded frame): {0}, {1, 2}, {3, 4}, {5} in 14 rows, 34 KB, four workgroups per CU.
-template <int TH> struct TmShape;
-template <> struct TmShape<32> {
-    static constexpr int kMaxRows = 21, kWaves = 3;
-    static SAH_DEV uint32_t first(uint32_t s) { return s == 0 ? 0u : (s == 1 ? 1u : (s == 2 ? 3u : 6u)); }
-};
-template <> struct TmShape<16> {
-    static constexpr int kMaxRows = 14, kWaves = 4;
-    static SAH_DEV uint32_t first(uint32_t s) { return s == 0 ? 0u : (s == 1 ? 1u : (s == 2 ? 3u : (s == 3 ? 5u : 6u))); }
-};
+// which did NOT fit three times into a CU's 160 KB — two per CU, 1.47 x the time).
+// (Measured and lost, tools/experiments/r6/README.md §9: 16-row tiles — {0}, {1, 2}, {3, 4}, {5} in 14 rows, 34 KB, four workgroups per CU — for
+// row bands whose 32-row tiles do not fill the chip twice.  Level by itself at 270 rows, 43.6 against 45.6 us, but a third more staged rows per
+// pixel row: whole frame 0.238 against 0.179 ms, one rank of eight 0.1058 against 0.0930 ms per frame.)
+constexpr int kTileH = 32, kMaxRows = 21, kWaves = 3;
+constexpr int kThreads = 256;  // a thread owns two adjacent columns of kTileH / 16 rows
+SAH_DEV uint32_t stage_first_of(uint32_t s) { return s == 0 ? 0u : (s == 1 ? 1u : (s == 2 ? 3u : 6u)); }
 
 struct AxisS {  // one axis set-up in LDS: offset of the first of the two texels / rows (x: float4 cells, y: floats into a G plane) and the
     int o;      // fraction f (x) or f / 16 (y); the two weights are 1 - f, f (resp. 1/16 - f/16, f/16: the same bits as (1 - f) / 16)
@@ -124,20 +118,15 @@ __global__ void __launch_bounds__(256) k_tonemap_axis_tables(TonemapArgs t, TmAx
     out[(size_t)blockIdx.y * t.axis_stride + i] = e;
 }
 
-// kThreads: 256 (the product: a thread owns two adjacent columns of kTileH / 16 rows) or 512 — round 6's experiment (SAH_TM_THREADS=512; VERDICT r5 item 3:
-// "512- or 1,024-thread workgroups, so a SIMD has another wave to run while one waits at a barrier"): the same tile, rectangles, stages and LDS with twice
-// the waves, each thread one row of the 32-row tile; 114 VGPRs, so TWO such workgroups per CU = four waves per SIMD where three 256-thread workgroups are
-// three.  Same codes (tests, tools/stress_post.py) and SLOWER: 0.2073 ms against 0.1794 for the 4K frame (two tiles in flight per CU instead of three
-// outweigh the second wave per SIMD); held to six waves per SIMD (80 VGPRs, 144 B of scratch) 0.352.  tools/experiments/r6/README.md §8.
-template <int kTileH, int kThreads>
-__global__ void __launch_bounds__(kThreads, (kThreads == 512 ? 4 : TmShape<kTileH>::kWaves)) k_tonemap_tol(TonemapArgs t) {
-    using Shape = TmShape<kTileH>;
+// (Measured and lost, tools/experiments/r6/README.md §8: 512-thread workgroups, a thread one row of the same tile — 114 VGPRs, two workgroups per CU:
+// 0.2073 ms against 0.1794 for the 4K frame; held to six waves per SIMD, 80 VGPRs and 144 B of scratch, 0.352.)
+__global__ void __launch_bounds__(kThreads, kWaves) k_tonemap_tol(TonemapArgs t) {
     constexpr int kRowStep = kThreads / 16;  // pixel rows (and pass-1 items) a sweep of the workgroup covers
     constexpr int kStageRowStep = kThreads / 32;  // staged rows a sweep of the staging loads covers
-    constexpr int kMaxRows = Shape::kMaxRows, kPlane = kMaxRows * kTile * 3, kStageIters = (kMaxRows + kStageRowStep - 1) / kStageRowStep;
+    constexpr int kPlane = kMaxRows * kTile * 3, kStageIters = (kMaxRows + kStageRowStep - 1) / kStageRowStep;
     constexpr int kA = kTileH / kRowStep;  // pixel rows per thread: tile rows tr + kRowStep a
     static_assert(kA >= 1 && kTileH % kRowStep == 0, "tile height / threads");
-    const uint32_t tid8 = threadIdx.x & 255u;  // the 256 table entries of a mip are fetched and stored by every 256-thread half alike (same values)
+    const uint32_t tid8 = threadIdx.x;  // the thread's one of the 256 table entries of a mip
     // (s_src and s_xt are read by pass 1 only, which every thread has left before anybody commits the next stage: single buffers; s_yt is
     // read by pass 2, which overlaps the next commit: double buffer)
     __shared__ __attribute__((aligned(16))) float4 s_src[kMaxRows * kPitch];  // staged texels, fp32 rgb (w unused), edge replication applied
@@ -162,10 +151,9 @@ __global__ void __launch_bounds__(kThreads, (kThreads == 512 ? 4 : TmShape<kTile
     __syncthreads();
     // stages: mips [first, first + count) filtered between one pair of barriers.  A mip whose rows do not fit beside the others of its stage
     // (chains that are not half-resolution pyramids) is marked bad for this tile and evaluated strictly
-    auto stage_first_of = [](uint32_t s) __attribute__((always_inline)) { return Shape::first(s); };
     uint32_t nstages = 0;
-    while (Shape::first(nstages) < nmips) nstages++;
-    auto stage_count = [&](uint32_t s) __attribute__((always_inline)) { return min(Shape::first(s + 1u), nmips) - Shape::first(s); };
+    while (stage_first_of(nstages) < nmips) nstages++;
+    auto stage_count = [&](uint32_t s) __attribute__((always_inline)) { return min(stage_first_of(s + 1u), nmips) - stage_first_of(s); };
 
     // the thread's table entry of a mip: (axis, variant, column / row) = (tid / 128, tid / 32 % 4, tid % 32)
     const uint32_t entry_off = (((tid8 >> 7) * 4u + ((tid8 >> 5) & 3u)) * t.axis_stride) +
@@ -452,19 +440,7 @@ hipError_t launch_tonemap_tol(const TonemapArgs& t, hipStream_t st) {
     const uint32_t rows = t.row_end - t.row_begin;
     if (rows == 0) return hipSuccess;
     const uint32_t cols = (t.out_w + kTile - 1) / kTile;
-    // 32-row tiles for every launch (round 6).  Rounds 4-5 gave row bands that would not fill the chip's 768 workgroup slots twice (a rank's rows of a
-    // sharded frame) 16-row tiles, four per CU, for the band's latency BY ITSELF — where the two shapes are level at 270 rows (43.6 against 45.6 us) and the
-    // 32-row one ahead below (72 / 144 rows: 16.0 / 18.5 against 19.0 / 27.3).  But a band never runs by itself: in the rank's three-stream frame loop the
-    // chip is shared with the lighting and reduction of the next frame, what counts is the composite's WORK, and the 16-row shape stages a third more rows
-    // per pixel row (whole frame 0.238 against 0.179 ms): one rank of eight 0.1058 -> 0.0930 ms per frame with 32-row tiles on its band
-    // (tools/experiments/r6/README.md §9).  SAH_TM_BAND16=1 brings the old rule back (A/B).
-    static const int env_threads = getenv("SAH_TM_THREADS") ? atoi(getenv("SAH_TM_THREADS")) : 0;  // experiments (tools/experiments/r6): 256 / 512
-    static const int env_band16 = getenv("SAH_TM_BAND16") ? atoi(getenv("SAH_TM_BAND16")) : 0;
-    const bool big = (uint64_t)cols * ((rows + 31) / 32) >= 2 * 768;
-    if (big || !env_band16) {
-        if (env_threads == 512) hipLaunchKernelGGL((k_tonemap_tol<32, 512>), dim3(cols, (rows + 31) / 32), dim3(512), 0, st, t);
-        else hipLaunchKernelGGL((k_tonemap_tol<32, 256>), dim3(cols, (rows + 31) / 32), dim3(256), 0, st, t);
-    } else hipLaunchKernelGGL((k_tonemap_tol<16, 256>), dim3(cols, (rows + 15) / 16), dim3(256), 0, st, t);
+    hipLaunchKernelGGL(k_tonemap_tol, dim3(cols, (rows + kTileH - 1) / kTileH), dim3(kThreads), 0, st, t);  // (32-row tiles for every launch, row bands too)
     return hipGetLastError();
 }
 

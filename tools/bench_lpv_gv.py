@@ -1,14 +1,13 @@
 """Timings of the LPV geometry volume (include/sah_lpv_gv.h) on cuda:0, from HIP events around N back-to-back calls (after a warm-up):
 
-    python tools/bench_lpv_gv.py [--calls 200] [--gv-mode 1|2]
+    python tools/bench_lpv_gv.py [--calls 200]
 
   propagate_32       sah_lpv_propagate, 32 steps, 4 cascades (the reference's frame)
   propagate_gv_32    sah_lpv_propagate_gv with a GV, 32 steps, 4 cascades
   scene_gv_4k        sah_lpv_inject_scene_gv of a 3840 x 2160 G-buffer of the atrium, 4 cascades
   rsm_gv_4c          sah_lpv_inject_rsm_gv, the 128^2 RSM of the atrium, 4 cascades in one call
 
---gv-mode selects how the propagation uses the GV (the experiment switch SAH_LPV_GV_MODE: 1 factors precomputed once per call, the
-default; 2 the GV sampled in every step).  Prints one JSON line, milliseconds per call."""
+Prints one JSON line, milliseconds per call."""
 import argparse
 import json
 import os
@@ -21,9 +20,7 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=200)
-    ap.add_argument("--gv-mode", type=int, default=1)
     args = ap.parse_args()
-    os.environ["SAH_LPV_GV_MODE"] = str(args.gv_mode)  # (read by the library on its first propagation)
     import numpy as np
     import torch
 
@@ -63,7 +60,7 @@ def main():
         "scene_gv_4k": lambda: ctx.lpv_inject_scene_gv(dp, npl, view.gpu_data, lpv.matrices, nc, G2),
         "rsm_gv_4c": lambda: ctx.lpv_inject_rsm_gv(rd, lpv.matrices, 0, 4, nc, G2),
     }
-    out = {"gv_mode": args.gv_mode, "calls": args.calls, "unit": "ms per call"}
+    out = {"calls": args.calls, "unit": "ms per call"}
     for name, fn in cases.items():
         for _ in range(10):
             fn()

@@ -1,12 +1,18 @@
-"""Print per-kernel register/LDS/occupancy usage for a HIP source (hipcc -Rpass-analysis=kernel-resource-usage)."""
+"""Print per-kernel register/LDS/occupancy usage for a HIP source (hipcc -Rpass-analysis=kernel-resource-usage), compiled with the
+library's options (androidrenderer_amd/build.py: FLAGS and the per-source SOURCE_FLAGS of the file's name).
+
+    python tools/kernel_resources.py androidrenderer_amd/csrc/lighting.hip"""
+import os
 import re
 import subprocess
 import sys
 
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from androidrenderer_amd import build as hip_build  # noqa: E402
+
 src = sys.argv[1]
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
-       "-fhip-fp32-correctly-rounded-divide-sqrt", "-x", "hip", "-c", src,
-       "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
+cmd = (["/opt/rocm/bin/hipcc"] + hip_build.FLAGS + hip_build.SOURCE_FLAGS.get(os.path.basename(src), []) +
+       ["-c", src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"])
 out = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True).stderr
 rows, cur = [], {}
 for line in out.splitlines():
