@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/sah_hip.h"
+#include "../../include/sah_motion_vectors.h"
 #include "ctx.hpp"
 #include "raster_args.hpp"
 
@@ -21,7 +22,7 @@ hipError_t launch_inject_vpls(const sah_packed_vpl* list, const uint32_t* count,
 namespace {
 constexpr uint32_t kTile = sah::kRasterTile;
 constexpr uint32_t kMaxExtent = 8192;  // keeps every snapped coordinate inside the guard band below 2^24.1
-enum Scratch { S_COUNTERS, S_TRI_BASE, S_RECORDS, S_ATTRS, S_TILES, S_PAIRS, S_SEQ, S_CLIPQ, S_VPL_CELLS, S_VPL_CANDIDATES, S_HEAVY, S_EXTRA, S_TICKETS, S_MERGE };
+enum Scratch { S_COUNTERS, S_TRI_BASE, S_RECORDS, S_ATTRS, S_TILES, S_PAIRS, S_SEQ, S_CLIPQ, S_VPL_CELLS, S_VPL_CANDIDATES, S_HEAVY, S_EXTRA, S_TICKETS, S_MERGE, S_MOTION };
 
 int ensure(sah_ctx* ctx, int slot, size_t bytes) {
     auto& r = ctx->raster;
@@ -90,8 +91,10 @@ int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, bool 
         if (int rc = ensure(ctx, S_RECORDS, want_records * sizeof(sah::RasterRecord)); rc != SAH_OK) return rc;
         // shadow pass: the alpha test of CUTOUT primitives needs their vertex colours and materials (lean records, raster_args.hpp)
         const bool shadow_attrs = !gbuffer && scene->vertex_data && scene->materials && scene->num_materials;
-        if (gbuffer)
+        if (gbuffer && !a.motion)
             if (int rc = ensure(ctx, S_ATTRS, want_records * sizeof(sah::RasterAttr)); rc != SAH_OK) return rc;
+        if (a.motion)  // the motion-vectors pass carries its varying in records of its own; the G-buffer's attributes stay as they are
+            if (int rc = ensure(ctx, S_MOTION, want_records * sizeof(sah::MotionAttr)); rc != SAH_OK) return rc;
         if (shadow_attrs)
             if (int rc = ensure(ctx, S_ATTRS, want_records * sizeof(sah::ShadowAttr)); rc != SAH_OK) return rc;
         if (int rc = ensure(ctx, S_PAIRS, want_pairs * sizeof(uint32_t)); rc != SAH_OK) return rc;
@@ -105,7 +108,9 @@ int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, bool 
         a.attrs = (sah::RasterAttr*)r.ptr[S_ATTRS];
         a.shadow_attrs = shadow_attrs ? (sah::ShadowAttr*)r.ptr[S_ATTRS] : nullptr;
         a.record_capacity = (uint32_t)std::min<size_t>(r.bytes[S_RECORDS] / sizeof(sah::RasterRecord), 0xffffffffu);
-        if (gbuffer) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.bytes[S_ATTRS] / sizeof(sah::RasterAttr));
+        if (gbuffer && !a.motion) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.bytes[S_ATTRS] / sizeof(sah::RasterAttr));
+        if (a.motion) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.bytes[S_MOTION] / sizeof(sah::MotionAttr));
+        a.motion_attrs = a.motion ? (sah::MotionAttr*)r.ptr[S_MOTION] : nullptr;
         if (shadow_attrs) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.bytes[S_ATTRS] / sizeof(sah::ShadowAttr));
         a.tile_count = (uint32_t*)r.ptr[S_TILES];
         a.tile_cursor = a.tile_count + ntiles;
@@ -118,7 +123,7 @@ int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, bool 
         // number of those is capped: tiles beyond it are processed whole)
         a.extra_capacity = a.pairs_capacity / sah::kRasterSplit + 1u;
         a.merge_capacity = std::min<uint32_t>(a.extra_capacity, ctx->raster_merge_cap);
-        const size_t tile_bytes = (size_t)kTile * kTile * (gbuffer ? 8 : 4);
+        const size_t tile_bytes = (size_t)kTile * kTile * (gbuffer && !a.motion ? 8 : 4);
         if (int rc = ensure(ctx, S_HEAVY, (size_t)ntiles * sizeof(uint32_t)); rc != SAH_OK) return rc;
         if (int rc = ensure(ctx, S_EXTRA, (size_t)a.extra_capacity * sizeof(uint2)); rc != SAH_OK) return rc;
         if (int rc = ensure(ctx, S_TICKETS, (size_t)a.merge_capacity * sizeof(uint32_t)); rc != SAH_OK) return rc;
@@ -128,6 +133,7 @@ int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, bool 
         a.tickets = (uint32_t*)r.ptr[S_TICKETS];
         a.merge_depth = (uint32_t*)r.ptr[S_MERGE];
         a.merge_keys = (unsigned long long*)r.ptr[S_MERGE];
+        a.merge_seq = (uint32_t*)r.ptr[S_MERGE];
         HIP_TRY(ctx, sah::launch_raster_setup(a, gbuffer, ctx->stream));
         HIP_TRY(ctx, sah::launch_raster_tiles(a, gbuffer, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(r.host_counters, a.counters, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -273,6 +279,48 @@ int sah_rsm_render(sah_ctx* ctx, const sah_scene_geometry* scene, const sah_sun_
     a.rsm_flux = varg(rsm->flux);
     a.rsm_normals = varg(rsm->normals);
     a.rsm_depth = varg(rsm->depth);
+    return run(ctx, a, scene, true, stats);
+}
+
+int sah_motion_vectors_render(sah_ctx* ctx, const sah_scene_geometry* scene, const sah_view_data* view, const sah_plane* depth,
+                              const sah_plane* motion_vectors, uint32_t* stats) {
+    SAH_RANGE();
+    if (!ctx) return SAH_ERR_INVALID_ARGUMENT;
+    if (!geometry_ok(scene, false) || !view || !depth || !motion_vectors)
+        return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_vectors_render: bad scene, view or planes");
+    const uint32_t W = depth->width, H = depth->height;
+    if (W == 0 || H == 0 || W > kMaxExtent || H > kMaxExtent) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_vectors_render: extent must be 1..%u", kMaxExtent);
+    if (!plane_ok(depth, SAH_FORMAT_D32_SFLOAT, SAH_FORMAT_D32_SFLOAT, W, H) || ((uintptr_t)depth->ptr % 4) || (depth->row_pitch_bytes % 4))
+        return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_vectors_render: 'depth' must be a D32_SFLOAT plane, 4-byte aligned, its pitch at least a row");
+    // (r.MotionVectors.FullRes, a target of another extent than the depth buffer, is not supported: DESIGN.md §8)
+    if (!plane_ok(motion_vectors, SAH_FORMAT_R16G16_SFLOAT, SAH_FORMAT_R16G16_SFLOAT, W, H) || ((uintptr_t)motion_vectors->ptr % 4) ||
+        (motion_vectors->row_pitch_bytes % 4))
+        return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_vectors_render: 'motion_vectors' must be an R16G16_SFLOAT plane of the depth plane's extent, 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, sah_guard_touch(ctx, ctx->guard_raster));
+    sah::RasterArgs a{};
+    fill_scene(ctx, a, scene);
+    a.vertex_data = nullptr;  // positions, indices and primitives are all this pass reads
+    a.materials = nullptr;
+    a.textures = nullptr;
+    a.material_textures = nullptr;
+    a.num_textures = 0;
+    a.motion = 1;
+    a.num_views = 1;
+    std::memcpy(a.view_matrix, view->view, 64);
+    std::memcpy(a.clip_matrix[0], view->projection, 64);
+    std::memcpy(a.prev_view_matrix, view->last_frame_view, 64);
+    std::memcpy(a.prev_clip_matrix, view->last_frame_projection, 64);
+    a.render_resolution[0] = view->render_resolution[0];
+    a.render_resolution[1] = view->render_resolution[1];
+    a.width = W;
+    a.height = H;
+    a.half_w = (float)W * 0.5f;
+    a.half_h = (float)H * 0.5f;
+    a.tiles_x = (W + kTile - 1) / kTile;
+    a.tiles_y = (H + kTile - 1) / kTile;
+    a.mv_depth = parg(depth);
+    a.out_motion = parg(motion_vectors);
     return run(ctx, a, scene, true, stats);
 }
 

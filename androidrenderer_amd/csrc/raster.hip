@@ -221,8 +221,8 @@ struct SetupStats {
     uint32_t in = 0, culled = 0, dropped = 0, raster = 0;
 };
 
-// One window-space triangle of the fan: facing, bounding box, record.
-template <bool GBUFFER>
+// One window-space triangle of the fan: facing, bounding box, record.  MV: the motion-vectors pass (SOLID primitives only; its own varyings).
+template <bool GBUFFER, bool MV = false>
 SAH_DEV void emit_triangle(const RasterArgs& a, SetupStats& st, uint32_t view, uint32_t p, const sah_primitive& prim, uint32_t tri, uint32_t seq,
                            const WindowVertex& v0, WindowVertex v1, WindowVertex v2, uint32_t slot) {
     if (!v0.finite || !v1.finite || !v2.finite) { st.dropped++; return; }
@@ -271,7 +271,22 @@ SAH_DEV void emit_triangle(const RasterArgs& a, SetupStats& st, uint32_t view, u
             atomicAdd(&a.counters[C_CUTOUT_NO_ATTR], 1u);  // the host turns this into SAH_ERR_INVALID_ARGUMENT (api_raster.cpp)
         }
     }
-    if (GBUFFER) {
+    if (MV) {  // motion_vectors.vert.slang:27-31: the same model matrix serves both frames
+        MotionAttr ma;
+        ma.inv_w[0] = v0.inv_w; ma.inv_w[1] = v1.inv_w; ma.inv_w[2] = v2.inv_w;
+        for (int k = 0; k < 3; k++) { ma.bary[0][k] = v0.bary[k]; ma.bary[1][k] = v1.bary[k]; ma.bary[2][k] = v2.bary[k]; }
+        for (int k = 0; k < 3; k++) {
+            const float* pos = a.positions + 3 * ((int64_t)prim.vertex_offset + a.indices[prim.first_index + 3 * tri + k]);
+            const float local[4] = {pos[0], pos[1], pos[2], 1.0f};
+            float world[4], vs[4], prev[4];
+            mat_vec(prim.model, local, world);
+            mat_vec(a.prev_view_matrix, world, vs);
+            mat_vec(a.prev_clip_matrix, vs, prev);
+            ma.prev[k][0] = prev[0]; ma.prev[k][1] = prev[1]; ma.prev[k][2] = prev[3];
+        }
+        a.motion_attrs[r] = ma;
+    }
+    if (GBUFFER && !MV) {
         RasterAttr at;
         at.inv_w[0] = v0.inv_w; at.inv_w[1] = v1.inv_w; at.inv_w[2] = v2.inv_w;
         for (int k = 0; k < 3; k++) { at.bary[0][k] = v0.bary[k]; at.bary[1][k] = v1.bary[k]; at.bary[2][k] = v2.bary[k]; }
@@ -312,7 +327,7 @@ SAH_DEV ClipVertex clip_vertex(const RasterArgs& a, const sah_primitive& prim, u
 
 // Rare path: the triangle crosses a clipping plane.  k_setup queues it and this kernel, launched right after, clips and fans it, so
 // that the polygon arrays (scratch memory) and their registers burden only the triangles that need them.
-template <bool GBUFFER>
+template <bool GBUFFER, bool MV = false>
 __global__ __launch_bounds__(64) void k_setup_clipped(const RasterArgs a) {
     // the polygons live in LDS, 12 vertices per lane and buffer: dynamically indexed private arrays would sit in scratch memory,
     // and the clipping loop is one long chain of dependent accesses to them
@@ -332,7 +347,7 @@ __global__ __launch_bounds__(64) void k_setup_clipped(const RasterArgs a) {
         WindowVertex prev = to_window(poly[1], a.half_w, a.half_h);
         for (int i = 1; i + 1 < n; i++) {
             const WindowVertex next = to_window(poly[i + 1], a.half_w, a.half_h);
-            emit_triangle<GBUFFER>(a, st, view, p, prim, tri, t * 8u + (uint32_t)(i - 1), v0, prev, next, kAppend);
+            emit_triangle<GBUFFER, MV>(a, st, view, p, prim, tri, t * 8u + (uint32_t)(i - 1), v0, prev, next, kAppend);
             prev = next;
         }
     }
@@ -341,7 +356,7 @@ __global__ __launch_bounds__(64) void k_setup_clipped(const RasterArgs a) {
     block_flush<4>(&a.counters[C_STATS], local, s_acc);
 }
 
-template <bool GBUFFER>
+template <bool GBUFFER, bool MV = false>
 __global__ __launch_bounds__(256) void k_setup(const RasterArgs a) {
     const uint32_t total = a.counters[C_TRIS];
     const uint64_t work = (uint64_t)total * a.num_views;
@@ -353,9 +368,10 @@ __global__ __launch_bounds__(256) void k_setup(const RasterArgs a) {
         const uint32_t tri = t - a.tri_base[p];
         st.in++;
         if (w < a.record_capacity) mark_empty(a.records[w]);  // overwritten below if the triangle survives unclipped
+        if (MV && prim.type != SAH_PRIMITIVE_TYPE_SOLID) { st.culled++; continue; }  // scene.draw_opaque: nothing else is drawn
         // a draw that points outside the index / vertex / material arrays is dropped, never dereferenced
         bool in_range = (uint64_t)prim.first_index + 3ull * tri + 3ull <= a.num_indices &&
-                        (!(GBUFFER || (a.shadow_attrs && prim.type == SAH_PRIMITIVE_TYPE_CUTOUT)) || prim.material < a.num_materials);
+                        (MV || !(GBUFFER || (a.shadow_attrs && prim.type == SAH_PRIMITIVE_TYPE_CUTOUT)) || prim.material < a.num_materials);
         for (int k = 0; k < 3 && in_range; k++) {
             const int64_t v = (int64_t)prim.vertex_offset + a.indices[prim.first_index + 3 * tri + k];
             in_range = v >= 0 && v < (int64_t)a.num_vertices;
@@ -369,7 +385,7 @@ __global__ __launch_bounds__(256) void k_setup(const RasterArgs a) {
             inside = inside && plane_distance(c0, plane) >= 0.0f && plane_distance(c1, plane) >= 0.0f && plane_distance(c2, plane) >= 0.0f;
         if (!finite) { st.dropped++; continue; }
         if (inside) {
-            emit_triangle<GBUFFER>(a, st, view, p, prim, tri, t * 8u, to_window(c0, a.half_w, a.half_h), to_window(c1, a.half_w, a.half_h),
+            emit_triangle<GBUFFER, MV>(a, st, view, p, prim, tri, t * 8u, to_window(c0, a.half_w, a.half_h), to_window(c1, a.half_w, a.half_h),
                                    to_window(c2, a.half_w, a.half_h), w < a.record_capacity ? (uint32_t)w : a.record_capacity);
         } else {
             const uint32_t q = wave_alloc(&a.counters[C_CLIPPED], true);
@@ -633,12 +649,17 @@ __global__ __launch_bounds__(256) void k_check_textures(const RasterArgs a) {
     if (bad) atomicAdd(&a.counters[C_BAD_TEXTURE], 1u);
 }
 
-// depth test of a covered pixel; v = its edge functions (read by cutout fragments only)
-template <bool GBUFFER, bool TEX>
+// depth test of a covered pixel; v = its edge functions (read by cutout fragments only).  MV (k_motion_tiles): s_depth holds the tile's
+// depth texels and s_key, 32 bits per pixel, the latest sequence number + 1 whose fragment depth is bit-equal to the texel.
+template <bool GBUFFER, bool TEX, bool MV = false, class Key = unsigned long long>
 SAH_DEV void emit_fragment(const RasterArgs& a, const EdgeSetup& e, uint32_t rec_index, int32_t px, int32_t py, const double v[3], int32_t tile_x, int32_t tile_y,
-                           uint32_t* s_depth, unsigned long long* s_key) {
+                           uint32_t* s_depth, Key* s_key) {
     const float z = fragment_depth(e, px, py);
     const uint32_t slot = (uint32_t)(py - tile_y) * kTile + (uint32_t)(px - tile_x);
+    if constexpr (MV) {  // compare EQUAL, no depth write; every passing fragment overwrites the target: the last in draw order stays
+        if (__float_as_uint(z) == s_depth[slot]) atomicMax(&s_key[slot], e.seq + 1u);
+        return;
+    }
     if (!GBUFFER) {
         if (e.cutout) {  // shadow_masked fragment stage: discard when tinted_base_color.a <= opacity_threshold
             const ShadowAttr& sa = a.shadow_attrs[rec_index];
@@ -684,19 +705,19 @@ SAH_DEV void emit_fragment(const RasterArgs& a, const EdgeSetup& e, uint32_t rec
         atomicMax(&s_key[slot], ((unsigned long long)depth_key << 32) | (unsigned long long)(a.rsm ? ~order : order));
     }
 }
-template <bool GBUFFER, bool TEX>
+template <bool GBUFFER, bool TEX, bool MV = false, class Key = unsigned long long>
 SAH_DEV void test_pixel(const RasterArgs& a, const EdgeSetup& e, uint32_t rec_index, int32_t px, int32_t py, int32_t tile_x, int32_t tile_y, uint32_t* s_depth,
-                        unsigned long long* s_key) {
+                        Key* s_key) {
     double v[3];
-    if (cover(e, px, py, v)) emit_fragment<GBUFFER, TEX>(a, e, rec_index, px, py, v, tile_x, tile_y, s_depth, s_key);
+    if (cover(e, px, py, v)) emit_fragment<GBUFFER, TEX, MV>(a, e, rec_index, px, py, v, tile_x, tile_y, s_depth, s_key);
 }
 
 // One wave sweeps rows first_row, first_row + row_step, ... of 8x8 pixel blocks over the clipped bounding box, lanes as the pixels of
 // a block.  Per block the edge functions advance by one fp64 add each (exact: integers below 2^52); a block whose most favourable
 // corner is outside an edge is skipped, one whose least favourable corner is inside all three needs no per-pixel coverage test.
-template <bool GBUFFER, bool TEX>
+template <bool GBUFFER, bool TEX, bool MV = false, class Key = unsigned long long>
 SAH_DEV void sweep(const RasterArgs& a, const EdgeSetup& e, uint32_t rec_index, int32_t sx0, int32_t sx1, int32_t bx1, int32_t by1, int32_t first_row,
-                   int32_t row_step, uint32_t lane, int32_t tile_x, int32_t tile_y, uint32_t* s_depth, unsigned long long* s_key) {
+                   int32_t row_step, uint32_t lane, int32_t tile_x, int32_t tile_y, uint32_t* s_depth, Key* s_key) {
     // blocks start at x = sx0, sx0 + 8, ... <= sx1; pixels beyond (bx1, by1) are outside the record's clipped bounding box
     const int32_t bx0 = sx0;
     const int32_t lx = (int32_t)(lane & 7u), ly = (int32_t)(lane >> 3);
@@ -727,7 +748,7 @@ SAH_DEV void sweep(const RasterArgs& a, const EdgeSetup& e, uint32_t rec_index, 
                         covered = covered & ((v[i] > 0.0) | ((v[i] == 0.0) & (((e.tl >> i) & 1u) != 0u)));
                     }
                 }
-                if (covered) emit_fragment<GBUFFER, TEX>(a, e, rec_index, px, py, v, tile_x, tile_y, s_depth, s_key);
+                if (covered) emit_fragment<GBUFFER, TEX, MV>(a, e, rec_index, px, py, v, tile_x, tile_y, s_depth, s_key);
             }
             for (int i = 0; i < 3; i++) base[i] += step_x[i];
         }
@@ -1015,9 +1036,149 @@ __global__ __launch_bounds__(kTileThreads, (GBUFFER && !TEX) ? 3 : 1) void k_ras
     }
 }
 
+// ---- motion vectors (sah_motion_vectors.h): MotionVectorsPhase::render, motion_vectors_phase.cpp:55-103 ----------------------------
+// fragment stage of the winning triangle (motion_vectors_opaque.frag.slang:18-24); SV_Position.xy is the pixel centre
+SAH_DEV uint32_t motion_vector_of(const RasterArgs& a, const EdgeSetup& e, const MotionAttr& ma, int32_t px, int32_t py) {
+    float lambda[3], v[3];
+    lambda_at(e, ma.inv_w, ma.bary, px, py, lambda);
+    for (int c = 0; c < 3; c++) v[c] = (lambda[0] * ma.prev[0][c] + lambda[1] * ma.prev[1][c]) + lambda[2] * ma.prev[2][c];
+    const float centre[2] = {(float)px + 0.5f, (float)py + 0.5f};
+    uint32_t bits = 0;
+    for (int c = 0; c < 2; c++) {
+        const float ndc = v[c] / v[2];
+        const float uv = ndc * 0.5f + 0.5f;
+        const float mv = uv * a.render_resolution[c] - centre[c];
+        bits |= (uint32_t)f2h(mv) << (16 * c);
+    }
+    return bits;
+}
+
+// One workgroup per tile (or per part of a split list), the G-buffer kernel's walk over the bin list with another test: the tile's
+// depth texels are loaded once into LDS, a covered pixel whose fragment depth is bit-equal to its texel takes ds_max_u32 of the
+// record's sequence number + 1 (the last in draw order stays, whatever the order of the list), and the winner alone is interpolated
+// and divided.  No textures, no materials, one 4-byte store per pixel.
+__global__ __launch_bounds__(kTileThreads) void k_motion_tiles(const RasterArgs a) {
+    __shared__ uint32_t s_depth[kTile * kTile];
+    __shared__ uint32_t s_win[kTile * kTile];
+    const uint32_t ntiles = a.tiles_x * a.tiles_y;
+    uint32_t tile = blockIdx.x, part = 0;
+    if (blockIdx.x >= ntiles) {
+        const uint32_t k = blockIdx.x - ntiles;
+        if (k >= min(a.counters[C_EXTRA], a.extra_capacity)) return;
+        tile = a.extra_parts[k].x;
+        part = a.extra_parts[k].y;
+        if (tile >= ntiles) return;
+    }
+    const int32_t tile_x = (int32_t)(tile % a.tiles_x) * kTile, tile_y = (int32_t)(tile / a.tiles_x) * kTile;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    for (uint32_t i = tid; i < kTile * kTile; i += kTileThreads) {
+        const uint32_t px = (uint32_t)tile_x + i % kTile, py = (uint32_t)tile_y + i / kTile;
+        // (outside the image: a pattern no clamped depth has)
+        s_depth[i] = px < a.width && py < a.height ? *(const uint32_t*)(a.mv_depth.ptr + (size_t)py * a.mv_depth.pitch + (size_t)px * 4) : 0xffffffffu;
+        s_win[i] = 0u;
+    }
+    __syncthreads();
+    __shared__ BigRecord s_big[kBigSlots];
+    __shared__ uint32_t s_nbig;
+    const uint32_t whole = (uint64_t)a.tile_offset[tile] + a.tile_count[tile] <= a.pairs_capacity ? a.tile_count[tile] : 0u;
+    const uint32_t slot_of_tile = a.heavy_slot[tile] < a.merge_capacity ? a.heavy_slot[tile] : ~0u;
+    const uint32_t parts = slot_of_tile != ~0u ? (whole + kSplit - 1) / kSplit : 1u;
+    if (part >= parts) return;
+    const uint32_t first = slot_of_tile != ~0u ? part * kSplit : 0u;
+    const uint32_t begin = a.tile_offset[tile] + first, count = slot_of_tile != ~0u ? min(kSplit, whole - min(whole, first)) : whole;
+    for (uint32_t base = 0; base < count; base += kTileThreads) {
+        if (tid == 0) s_nbig = 0;
+        __syncthreads();
+        const uint32_t li = base + lane * (kTileThreads / 64u) + wave;
+        uint32_t rec_index = 0, area = 0;
+        int32_t x0 = 1, x1 = 0, y0 = 1, y1 = 0;
+        EdgeSetup mine{};
+        bool medium_rec = false;
+        if (li < count) {
+            rec_index = a.pairs[begin + li];
+            const RasterRecord rec = a.records[rec_index];
+            x0 = max((int32_t)rec.x0, tile_x); x1 = min((int32_t)rec.x1, tile_x + kTile - 1);
+            y0 = max((int32_t)rec.y0, tile_y); y1 = min((int32_t)rec.y1, tile_y + kTile - 1);
+            area = (uint32_t)((x1 - x0 + 1) * (y1 - y0 + 1));
+            mine = edge_setup(rec);
+            medium_rec = area > kSmallArea && area <= kMediumArea;
+            if (area <= kSmallArea) {
+                for (int32_t py = y0; py <= y1; py++)
+                    for (int32_t px = x0; px <= x1; px++) test_pixel<true, false, true>(a, mine, rec_index, px, py, tile_x, tile_y, s_depth, s_win);
+            } else if (area > kMediumArea) {
+                const uint32_t slot = atomicAdd(&s_nbig, 1u);
+                if (slot < kBigSlots) {
+                    s_big[slot].e = mine;
+                    s_big[slot].rec_index = rec_index;
+                    s_big[slot].x0 = x0; s_big[slot].x1 = x1; s_big[slot].y0 = y0; s_big[slot].y1 = y1;
+                } else {
+                    medium_rec = true;
+                }
+            }
+        }
+        uint64_t medium = __ballot(medium_rec);
+        while (medium) {
+            const int src = __builtin_ctzll(medium);
+            medium &= medium - 1;
+            const uint32_t ri = readlane(rec_index, src);
+            const int32_t bx0 = (int32_t)readlane((uint32_t)x0, src), bx1 = (int32_t)readlane((uint32_t)x1, src);
+            const int32_t by0 = (int32_t)readlane((uint32_t)y0, src), by1 = (int32_t)readlane((uint32_t)y1, src);
+            const EdgeSetup e = broadcast(mine, src);
+            sweep<true, false, true>(a, e, ri, bx0, bx1, bx1, by1, by0, 8, lane, tile_x, tile_y, s_depth, s_win);
+        }
+        __syncthreads();
+        const uint32_t nbig = min(s_nbig, kBigSlots);
+        for (uint32_t k = 0; k < nbig; k++) {
+            const EdgeSetup e = s_big[k].e;
+            sweep<true, false, true>(a, e, s_big[k].rec_index, s_big[k].x0, s_big[k].x1, s_big[k].x1, s_big[k].y1, s_big[k].y0 + 8 * (int32_t)wave,
+                                     8 * (int32_t)(kTileThreads / 64u), lane, tile_x, tile_y, s_depth, s_win);
+        }
+        __syncthreads();
+    }
+    if (parts > 1) {  // the latest sequence number that matched, over the parts: max is associative; the part that arrives last writes
+        __shared__ uint32_t s_last;
+        const size_t base_index = (size_t)slot_of_tile * (kTile * kTile);
+        for (uint32_t i = tid; i < kTile * kTile; i += kTileThreads)
+            if (s_win[i] != 0u) atomicMax(&a.merge_seq[base_index + i], s_win[i]);
+        __threadfence();
+        __syncthreads();
+        if (tid == 0) s_last = atomicAdd(&a.tickets[slot_of_tile], 1u) == parts - 1u;
+        __syncthreads();
+        if (!s_last) return;
+        __threadfence();
+        for (uint32_t i = tid; i < kTile * kTile; i += kTileThreads)
+            s_win[i] = __hip_atomic_load(&a.merge_seq[base_index + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+    }
+    uint32_t cached = ~0u;
+    EdgeSetup e_c{};
+    MotionAttr ma_c{};
+    for (uint32_t i = tid; i < kTile * kTile; i += kTileThreads) {
+        const int32_t px = tile_x + (int32_t)(i % kTile), py = tile_y + (int32_t)(i / kTile);
+        if ((uint32_t)px >= a.width || (uint32_t)py >= a.height) continue;
+        uint32_t bits = 0u;  // clear value, motion_vectors_phase.cpp:90-92
+        if (s_win[i] != 0u) {
+            // as the G-buffer resolve: an unclipped triangle sits in the slot of its work item, fans are found through the table
+            const uint32_t seq = s_win[i] - 1u;
+            uint64_t r = seq >> 3;
+            if ((seq & 7u) != 0u || r >= a.record_capacity || is_empty(a.records[r])) {
+                r = seq < a.seq_capacity ? a.seq_to_record[seq] : 0u;
+                if (r >= a.record_capacity) r = 0;  // only when a scratch buffer was too small: the pass is repeated
+            }
+            if ((uint32_t)r != cached) {
+                cached = (uint32_t)r;
+                e_c = edge_setup(a.records[r]);
+                ma_c = a.motion_attrs[r];
+            }
+            bits = motion_vector_of(a, e_c, ma_c, px, py);
+        }
+        *(uint32_t*)(a.out_motion.ptr + (size_t)py * a.out_motion.pitch + (size_t)px * 4) = bits;
+    }
+}
+
 // Cuts long bin lists into parts: a tile with more than kSplit entries gets a merge buffer (initialised here to the identity of its
 // depth test), a ticket, and one extra workgroup per further part.  Tiles beyond the scratch capacity stay unsplit (slower, not wrong).
-template <bool GBUFFER>
+template <bool GBUFFER, bool MV = false>
 __global__ __launch_bounds__(256) void k_split(const RasterArgs a) {
     const uint32_t ntiles = a.tiles_x * a.tiles_y * a.num_views;
     const uint32_t tile = blockIdx.x;  // one workgroup per tile: the merge buffer of a heavy tile is initialised by all 256 threads
@@ -1045,7 +1206,9 @@ __global__ __launch_bounds__(256) void k_split(const RasterArgs a) {
     if (s_slot == ~0u) return;
     const size_t base_index = (size_t)s_slot * (kTile * kTile);
     for (uint32_t i = threadIdx.x; i < kTile * kTile; i += 256) {
-        if (GBUFFER) a.merge_keys[base_index + i] = 0ull; else a.merge_depth[base_index + i] = 0xffffu;
+        if (MV) a.merge_seq[base_index + i] = 0u;
+        else if (GBUFFER) a.merge_keys[base_index + i] = 0ull;
+        else a.merge_depth[base_index + i] = 0xffffu;
     }
 }
 
@@ -1071,7 +1234,10 @@ hipError_t launch_raster_setup(const RasterArgs& a, bool gbuffer, hipStream_t st
     if (a.num_primitives == 0) return hipSuccess;
     if (a.textures) hipLaunchKernelGGL(k_check_textures, dim3((a.num_textures + a.num_materials + 255u) / 256u), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, st, a.primitives, (const uint32_t*)nullptr, a.num_primitives, a.tri_base, &a.counters[C_TRIS]);
-    if (gbuffer) {
+    if (a.motion) {
+        hipLaunchKernelGGL((k_setup<true, true>), dim3(1024), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((k_setup_clipped<true, true>), dim3(256), dim3(64), 0, st, a);
+    } else if (gbuffer) {
         hipLaunchKernelGGL(k_setup<true>, dim3(1024), dim3(256), 0, st, a);
         hipLaunchKernelGGL(k_setup_clipped<true>, dim3(256), dim3(64), 0, st, a);
     } else {
@@ -1091,11 +1257,13 @@ hipError_t launch_raster_tiles(const RasterArgs& a, bool gbuffer, hipStream_t st
         if (gbuffer) hipLaunchKernelGGL(k_seq_table, dim3(64), dim3(256), 0, st, a);
     }
     // every tile gets its heavy_slot (~0 when its list stays whole), also for an empty scene
-    if (gbuffer) hipLaunchKernelGGL(k_split<true>, dim3(ntiles), dim3(256), 0, st, a);
+    if (a.motion) hipLaunchKernelGGL((k_split<true, true>), dim3(ntiles), dim3(256), 0, st, a);
+    else if (gbuffer) hipLaunchKernelGGL(k_split<true>, dim3(ntiles), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_split<false>, dim3(ntiles), dim3(256), 0, st, a);
     // (the texture-sampling fragment stages are their own instantiations: 30-45 more VGPRs, which would cost the plain ones a wave per SIMD)
     const dim3 grid(ntiles + a.extra_capacity);
-    if (gbuffer && a.textures) hipLaunchKernelGGL((k_raster_tiles<true, true>), grid, dim3(kTileThreads), 0, st, a);
+    if (a.motion) hipLaunchKernelGGL(k_motion_tiles, grid, dim3(kTileThreads), 0, st, a);
+    else if (gbuffer && a.textures) hipLaunchKernelGGL((k_raster_tiles<true, true>), grid, dim3(kTileThreads), 0, st, a);
     else if (gbuffer) hipLaunchKernelGGL((k_raster_tiles<true, false>), grid, dim3(kTileThreads), 0, st, a);
     else if (a.textures && a.shadow_attrs) hipLaunchKernelGGL((k_raster_tiles<false, true>), grid, dim3(kTileThreads), 0, st, a);
     else hipLaunchKernelGGL((k_raster_tiles<false, false>), grid, dim3(kTileThreads), 0, st, a);

@@ -56,6 +56,14 @@ struct ShadowAttr {
 };
 static_assert(sizeof(ShadowAttr) == 96, "ShadowAttr layout");
 
+// Motion-vectors pass only (sah_motion_vectors.h): what its fragment stage needs to interpolate previous_clipspace_location.
+struct MotionAttr {
+    float inv_w[3];
+    float bary[3][3];  // as RasterAttr::bary
+    float prev[3][3];  // (x, y, w) of last_frame_projection * (last_frame_view * (model * p)) at the input triangle's vertices
+};
+static_assert(sizeof(MotionAttr) == 84, "MotionAttr layout");
+
 struct RasterArgs {
     // scene
     const float* positions;
@@ -108,6 +116,13 @@ struct RasterArgs {
     // outputs
     VolumeArg shadowmap;
     PlaneArg out_color, out_normals, out_data, out_emission, out_depth;
+    // motion-vectors variant of the G-buffer path (sah_motion_vectors_render): SOLID primitives only, compare EQUAL against mv_depth
+    uint32_t motion;
+    float prev_view_matrix[16], prev_clip_matrix[16];  // last_frame_view, last_frame_projection
+    float render_resolution[2];
+    MotionAttr* motion_attrs;  // one per record
+    uint32_t* merge_seq;       // per slot: kRasterTile^2 winners (seq + 1, 0 = none) of a split list
+    PlaneArg mv_depth, out_motion;
 };
 
 }  // namespace sah

@@ -177,3 +177,14 @@ class LightingInputs:
         ctx.lighting(d)
         torch.cuda.synchronize()
         return from_torch(lit, np.uint16)
+
+
+def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, stats_ptr=None):
+    """The rasterised part of a frame: sah_gbuffer_render into `gbuffer` (dict of device arrays: color, normals, data, emission, depth)
+    and — only when a `motion_vectors` target (H, W, 2) int16 device array is given — sah_motion_vectors_render against the depth the
+    G-buffer pass has just written, as the reference runs its motion-vectors phase after its depth pass (scene_renderer.cpp:308-316).
+    Without the target the frame is what it always was."""
+    ctx.gbuffer_render(geometry, view_data, images.gbuffer(gbuffer), stats_ptr)
+    if motion_vectors is not None:
+        ctx.motion_vectors_render(geometry, view_data, images.plane(gbuffer["depth"], _abi.FORMAT_D32_SFLOAT),
+                                  images.plane(motion_vectors, _abi.FORMAT_R16G16_SFLOAT))

@@ -30,6 +30,9 @@ EXPORTS = ["sah_abi_version", "sah_status_string", "sah_last_error", "sah_create
 # the LPV geometry volume's entries: exported, declared in include/sah_lpv_gv.h (not sah_hip.h)
 GV_EXPORTS = ["sah_lpv_inject_rsm_gv", "sah_lpv_inject_scene_gv", "sah_lpv_propagate_gv"]
 
+# the motion-vectors pass: exported, declared in include/sah_motion_vectors.h (not sah_hip.h)
+MV_EXPORTS = ["sah_motion_vectors_render"]
+
 # the LPV mesh lights' entries: exported, declared in include/sah_lpv_mesh_lights.h (not sah_hip.h)
 ML_EXPORTS = ["sah_mesh_point_cloud", "sah_lpv_emissive_vpls", "sah_lpv_inject_emissive"]
 POINT_CLOUD_ON_SURFACE = 1    # SAH_POINT_CLOUD_ON_SURFACE
@@ -119,6 +122,8 @@ def load():
     lib.sah_shadow_render.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.POINTER(_abi.SunLightConstants), C.c_uint32,
                                       C.POINTER(_abi.Volume), C.c_void_p]
     lib.sah_gbuffer_render.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.POINTER(_abi.ViewData), C.POINTER(_abi.GBuffer), C.c_void_p]
+    lib.sah_motion_vectors_render.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.POINTER(_abi.ViewData), C.POINTER(_abi.Plane), C.POINTER(_abi.Plane),
+                                              C.c_void_p]
     lib.sah_rsm_render.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.POINTER(_abi.SunLightConstants), C.POINTER(_abi.LpvCascadeMatrices),
                                    C.c_uint32, C.POINTER(_abi.RsmTargets), C.c_void_p]
     lib.sah_lpv_extract_vpls.argtypes = [C.c_void_p, C.POINTER(_abi.RsmTargets), C.POINTER(_abi.LpvCascadeMatrices), C.c_uint32, C.c_float, C.c_void_p,
@@ -313,6 +318,11 @@ class Context:
 
     def gbuffer_render(self, scene, view, gbuffer, stats_ptr=None):
         self._check(self.lib.sah_gbuffer_render(self.handle, C.byref(scene), C.byref(view), C.byref(gbuffer), C.c_void_p(stats_ptr)))
+
+    def motion_vectors_render(self, scene, view, depth, out, stats=None):
+        """sah_motion_vectors_render (include/sah_motion_vectors.h): depth, out: _abi.Plane of device memory (D32_SFLOAT read only,
+        R16G16_SFLOAT of the same extent); stats: device pointer to SAH_RASTER_STATS_WORDS words, or None."""
+        self._check(self.lib.sah_motion_vectors_render(self.handle, C.byref(scene), C.byref(view), C.byref(depth), C.byref(out), C.c_void_p(stats)))
 
     def rsm_render(self, scene, sun, cascades, num_cascades, rsm, stats_ptr=None):
         """cascades: (LpvCascadeMatrices * n) host array; rsm: _abi.RsmTargets of device volumes."""

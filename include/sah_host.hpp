@@ -29,6 +29,7 @@
 #include "sah_hip.h"
 #include "sah_lpv_gv.h"
 #include "sah_lpv_mesh_lights.h"
+#include "sah_motion_vectors.h"
 
 namespace sah {
 
@@ -1255,6 +1256,37 @@ public:
                             return sah_gbuffer_render(ctx, &scene.geometry, &player_view.get_gpu_data(), &g, nullptr);
                         }));
     }
+};
+
+// RenderCore/render/phase/motion_vectors_phase.hpp:13-33, .cpp:27-107; SceneRenderer runs it after the depth pre-pass when
+// `needs_motion_vectors` is set (scene_renderer.cpp:308-316: an anti-aliasing mode or an upscaler asked for it) — here after
+// GbufferPhase::render, which is where this library's depth comes from.  Off by default: AA = None needs no motion vectors and the
+// default frame stays as it is.  r.MotionVectors.FullRes (a target of the output resolution) is not supported: the target always has
+// the render resolution, and the output resolution is only taken for the signature's sake.
+class MotionVectorsPhase {
+public:
+    bool needs_motion_vectors = false;
+    explicit MotionVectorsPhase(ResourceAllocator& allocator_in) : allocator(allocator_in) {}
+    static bool render_full_res() { return false; }
+    void set_render_resolution(const uint32_t resolution[2], const uint32_t /*output_resolution*/[2]) {
+        if (motion_vectors && motion_vectors->desc.width == resolution[0] && motion_vectors->desc.height == resolution[1]) return;
+        motion_vectors = allocator.create_texture("motion_vectors", SAH_FORMAT_R16G16_SFLOAT, resolution[0], resolution[1]);
+    }
+    // the indirect draw buffers of the reference have no counterpart (GbufferPhase): every SOLID primitive of the scene is drawn
+    void render(RenderGraph& graph, const RenderScene& scene, const SceneView& player_view, TextureHandle depth_buffer) {
+        if (!needs_motion_vectors) return;
+        TextureHandle target = motion_vectors;
+        graph.add_pass(hip_pass("motion_vectors", [&scene, &player_view, depth_buffer, target](sah_ctx* ctx) {
+                            if (!target) return (int)SAH_ERR_INVALID_ARGUMENT;  // set_render_resolution has not been called
+                            const sah_plane d = depth_buffer->plane(), m = target->plane();
+                            return sah_motion_vectors_render(ctx, &scene.geometry, &player_view.get_gpu_data(), &d, &m, nullptr);
+                        }));
+    }
+    TextureHandle get_motion_vectors() const { return motion_vectors; }
+
+private:
+    ResourceAllocator& allocator;
+    TextureHandle motion_vectors = nullptr;
 };
 
 class LightingPhase {
