@@ -89,9 +89,15 @@ bool detect_fast_path(const sah_lighting_desc* d, uint32_t sun_mode, uint32_t gi
         // when p10 == 0, which holds for every perspective projection's inverse.
         auto in = [](float v, float lo, float hi) { return std::fabs(v) >= lo && std::fabs(v) <= hi; };
         const float r0 = d->view->render_resolution[0], r1 = d->view->render_resolution[1];
-        f->pos_div_nr = P[10] == 0.0f && P[12] == 0.0f && !std::signbit(P[12]) && P[13] == 0.0f && !std::signbit(P[13]) &&
-                        in(P[0], 0x1p-16f, 0x1p+30f) && in(P[5], 0x1p-16f, 0x1p+30f) && in(P[14], 0x1p-40f, 0x1p+40f) && r0 > 0.f && r1 > 0.f &&
-                        (float)d->lit->width <= 256.0f * r0 && (float)d->lit->height <= 256.0f * r1;
+        const bool bounded = P[10] == 0.0f && P[12] == 0.0f && P[13] == 0.0f && in(P[0], 0x1p-16f, 0x1p+30f) && in(P[5], 0x1p-16f, 0x1p+30f) &&
+                             in(P[14], 0x1p-40f, 0x1p+40f) && r0 > 0.f && r1 > 0.f && (float)d->lit->width <= 256.0f * r0 &&
+                             (float)d->lit->height <= 256.0f * r1;
+        f->pos_div_nr = bounded && !std::signbit(P[12]) && !std::signbit(P[13]);
+        // With a -0 in [12] or [13] (what a numerically inverted projection carries) a numerator is -0 exactly where the product is -0 as well:
+        // every other entry is the product itself (x + -0 == x), inside the same bounds.  The numerators then have to come from the context's
+        // table, whose build records whether it holds a -0 (FrameState::colx_neg_zero): sah_lighting keeps the flag only where the kernel reads
+        // the table, and the kernel shares the reciprocal only when the table is clean.  Z is p14 whatever the sign of p10's zero.
+        f->pos_div_shared = bounded && !f->pos_div_nr;
     }
     if (sun_mode == SAH_SHADOW_MODE_CSM) {
         if (!csm.shadowmap.ptr || (uint64_t)csm.shadowmap.slice_pitch * csm.shadowmap.depth >= (1ull << 32)) return false;
@@ -316,9 +322,19 @@ int sah_debug_copy_rebuilds(sah_ctx* ctx, uint32_t out[2]) {
 //   [0] kernel family: 0 general, 1 fast (+ fix-up), 2 tiled      [1] pixels per thread (0: tiled)      [2] pos_div_nr
 //   [3] ncasc_pow2 (0 without an LPV gather)      [4] row_magic != 0      [5] sky_ratio      [6] leading sky workgroups
 //   [7] tiled_fast_geom      [8] tiled_fast_lpv      [9] repack (k_lpv_pack runs in front of the kernel)      [10] column / row table rebuilt
-int sah_debug_lighting_dispatch(sah_ctx* ctx, uint32_t out[11]) {
+//   [11] pos_div_shared: the call shared one reciprocal among the position divides through the condition for zeros of either sign (0 where
+//   pos_div_nr is 1).  The kernel decides this from FrameState::colx_neg_zero, so this word alone reads device memory: where the host's half
+//   of the condition held, the stream is synchronised and the table's word fetched.
+int sah_debug_lighting_dispatch(sah_ctx* ctx, uint32_t out[12]) {
     if (!ctx || !out) return SAH_ERR_INVALID_ARGUMENT;
     memcpy(out, ctx->last_dispatch, sizeof(ctx->last_dispatch));
+    if (out[11] && ctx->state) {
+        uint32_t neg_zero = 0;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(&neg_zero, &ctx->state->colx_neg_zero, sizeof(neg_zero), hipMemcpyDeviceToHost));
+        out[11] = neg_zero == 0u ? 1u : 0u;
+    }
     return SAH_OK;
 }
 
@@ -657,8 +673,11 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
     // per-column numerators of the view-space x and per-row ones of y (IEEE divides per thread / per pixel otherwise; the tiled kernel reads
     // them too): a function of the extent, the render resolution
     // and two entries of the inverse projection — rebuilt when one of them changes
-    uint32_t dispatch[11] = {};  // sah_debug_lighting_dispatch
-    if ((use_fast && ppt == 4 && (sun_mode != SAH_SHADOW_MODE_OFF || gi_kind == SAH_GI_LPV)) || tiled_fast_geom) {
+    uint32_t dispatch[12] = {};  // sah_debug_lighting_dispatch
+    // ... and, where the zeros of the inverse projection are not all +0 (pos_div_shared), at every pixel count: the table's build is what tells
+    // whether a numerator is -0, which decides whether the three position divides may share one reciprocal
+    const bool geom_fast = use_fast && (sun_mode == SAH_SHADOW_MODE_CSM || gi_kind == SAH_GI_LPV);  // the fast kernel calls fast_geometry()
+    if ((use_fast && ppt == 4 && (sun_mode != SAH_SHADOW_MODE_OFF || gi_kind == SAH_GI_LPV)) || (geom_fast && fast.pos_div_shared) || tiled_fast_geom) {
         const float key[7] = {a.res[0], fast.p0, fast.p12, a.res[1], fast.p5, fast.p13, (float)H};
         const uint32_t stride = (W + 63u) & ~63u, row_stride = (H + 63u) & ~63u;
         bool grew = false;
@@ -668,6 +687,7 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
             ctx->colx_width = 0;
         }
         const bool table_rebuilt = ctx->colx_width != W || memcmp(key, ctx->colx_key, sizeof(key)) != 0;
+        fast.state = ctx->state;  // (k_colx_table raises colx_neg_zero there; the kernels read it under pos_div_shared)
         if (table_rebuilt) {
             HIP_TRY(ctx, launch_colx_table(a, fast, ctx->colx_table, stride, row_stride, ctx->stream));
             ctx->cache_epoch++;
@@ -679,6 +699,8 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
         fast.colx_stride = stride;
         fast.rowy_stride = row_stride;
     }
+    // no table, no verdict on its zeros (an RT sun alone takes no shared divide either: its quotients are the Slang flavour's IEEE ones)
+    if (!fast.colx_tab || !ctx->state || !(geom_fast || tiled_fast_geom)) fast.pos_div_shared = 0u;
     {
         dispatch[0] = family;
         dispatch[1] = family == kLightingTiled ? 0u : (uint32_t)ppt;
@@ -690,6 +712,7 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
         dispatch[7] = tiled_fast_geom ? 1u : 0u;
         dispatch[8] = tiled_fast_lpv ? 1u : 0u;
         dispatch[9] = fast.repack;
+        dispatch[11] = fast.pos_div_shared;  // (the host's half: sah_debug_lighting_dispatch adds the table's)
         memcpy(ctx->last_dispatch, dispatch, sizeof(dispatch));
     }
     HIP_TRY(ctx, launch_lighting(a, csm, lpv, cache, rtgi, sky, family, (use_fast || tiled_fast_geom) ? &fast : nullptr, (int)sun_mode, (int)gi_kind, ppt,

@@ -75,7 +75,7 @@ struct sah_ctx {
     uint32_t dbg_lpv_packs = 0, dbg_irr_unpacks = 0;  // full rebuilds of the two gather copies by sah_lighting (debug hook sah_debug_copy_rebuilds)
     const uint16_t* last_seg_count = nullptr;  // debug hook (sah_debug_deferred_pixels)
     uint32_t last_num_segments = 0;
-    uint32_t last_dispatch[11] = {};   // debug hook (sah_debug_lighting_dispatch): what the last sah_lighting call decided, host side
+    uint32_t last_dispatch[12] = {};   // debug hook (sah_debug_lighting_dispatch): what the last sah_lighting call decided, host side
     float* tm_thresholds = nullptr;    // device: 256 tonemap code thresholds + the first-level bucket table (api_post.cpp)
     float* tm_code_table = nullptr;    // device: the same search as one float4 per bucket (TonemapArgs::code_table)
     uint32_t tm_bucket_base = 0, tm_bucket_count = 0;

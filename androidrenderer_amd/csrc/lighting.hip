@@ -174,16 +174,24 @@ __global__ void __launch_bounds__(256) k_lpv_pack(const VolumeArg r, const Volum
 
 // the numerators of lighting_fast.hpp (colx_*_of / rowy_*_of) for every column and row, once per (extent, render resolution, p0, p12, p5, p13):
 // columns [0, width) at out (GLSL) and out + stride (Slang), rows [0, height) at out + 2 * stride (GLSL) and out + 2 * stride + row_stride (Slang)
+// An entry whose bits are 0x80000000 (-0: a -0 product plus a -0 addend) raises FrameState::colx_neg_zero, which the launcher has cleared: the
+// shared-reciprocal divide under FastArgs::pos_div_shared is proven for +0 numerators only.
 __global__ void __launch_bounds__(256) k_colx_table(const LightingArgs a, const FastArgs f, float* out, uint32_t stride, uint32_t row_stride) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    bool neg_zero = false;
+    auto put = [&](uint32_t at, float v) {
+        out[at] = v;
+        neg_zero = neg_zero || __float_as_uint(v) == 0x80000000u;
+    };
     if (i < a.width) {
-        out[i] = colx_glsl_of(a, f, i);
-        out[stride + i] = colx_slang_of(a, f, i);
+        put(i, colx_glsl_of(a, f, i));
+        put(stride + i, colx_slang_of(a, f, i));
     }
     if (i < a.height) {
-        out[2u * stride + i] = rowy_glsl_of(a, f, i);
-        out[2u * stride + row_stride + i] = rowy_slang_of(a, f, i);
+        put(2u * stride + i, rowy_glsl_of(a, f, i));
+        put(2u * stride + row_stride + i, rowy_slang_of(a, f, i));
     }
+    if (wave_any(neg_zero) && (threadIdx.x & 63u) == 0u) atomicOr(&f.state->colx_neg_zero, 1u);
 }
 
 // surface workgroups per sky workgroup: FastArgs::sky_ratio, chosen by the host with the launch (api.cpp: a whole 4K frame 4 — 1, 2, 8, 16 measured
@@ -240,6 +248,7 @@ __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const Lighti
     const uint32_t y = a.row_begin + ry;
     const uint32_t x0 = active ? (gid - ry * groups_per_row) * PPT : 0u;
     const bool lpv_bad = (GI == SAH_GI_LPV) ? (f.state->nonfinite != 0u) : false;
+    const bool div_shared = (SUN == SAH_SHADOW_MODE_CSM || GI == SAH_GI_LPV) ? pos_div_shared_of(f) : false;
 
     uint32_t wc[PPT], wd[PPT], we[PPT], wz[PPT], wn[2 * PPT], wao[PPT], wm[PPT];
     float colx_g[PPT], colx_s[PPT];
@@ -310,7 +319,7 @@ __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const Lighti
             if (SUN == SAH_SHADOW_MODE_CSM || GI == SAH_GI_LPV) colx_glsl = colx_glsl_of(a, f, x);
             if (SUN == SAH_SHADOW_MODE_RT) colx_slang = colx_slang_of(a, f, x);
         }
-        const FastPixelOut r = shade_pixel_fast_sl<SUN, GI>(a, csm, lpv, f, colx_glsl, rowy_glsl, colx_slang, rowy_slang, p, s_lut, lpv_bad, emissive_wave);
+        const FastPixelOut r = shade_pixel_fast_sl<SUN, GI>(a, csm, lpv, f, colx_glsl, rowy_glsl, colx_slang, rowy_slang, p, s_lut, lpv_bad, emissive_wave, div_shared);
         out[2 * i] = r.lit.x;
         out[2 * i + 1] = r.lit.y;
         if (r.deferred) deferred_mask |= 1u << i;
@@ -418,6 +427,8 @@ static hipError_t launch_gi(const LightingArgs& a, const CsmArgs& csm, const Lpv
 }
 
 hipError_t launch_colx_table(const LightingArgs& a, const FastArgs& f, float* out, uint32_t stride, uint32_t row_stride, hipStream_t st) {
+    const hipError_t me = hipMemsetAsync(&f.state->colx_neg_zero, 0, sizeof(uint32_t), st);  // the new table's verdict starts at "no -0"
+    if (me != hipSuccess) return me;
     hipLaunchKernelGGL(k_colx_table, dim3((max(a.width, a.height) + 255u) / 256u), dim3(256), 0, st, a, f, out, stride, row_stride);
     return hipGetLastError();
 }

@@ -62,6 +62,10 @@ SAH_DEV float rowy_slang_of(const LightingArgs& a, const FastArgs& f, uint32_t y
     return (Fn(f.p5) * (ty * Fn(2.0f) - Fn(1.0f)) + Fn(f.p13)).v;
 }
 
+// Whether the view-space position quotients of this launch share one reciprocal (fast_geometry): pos_div_nr, or pos_div_shared with a table
+// that holds no -0 (FrameState::colx_neg_zero, a wave-uniform read like `nonfinite`; f.state is valid wherever pos_div_shared is set)
+SAH_DEV bool pos_div_shared_of(const FastArgs& f) { return f.pos_div_nr != 0u || (f.pos_div_shared != 0u && f.state->colx_neg_zero == 0u); }
+
 struct FastPixelOut {
     uint2 lit;
     bool deferred;
@@ -74,8 +78,9 @@ struct FastGeom {
     F3 N, ws, V;
     Fn vsz;
 };
+// `div_shared` (uniform): pos_div_shared_of() above.
 SAH_DEV FastGeom fast_geometry(const LightingArgs& a, const FastArgs& f, float colx_glsl, float rowy_glsl, float D, const SurfIn& si, float dn,
-                               const float* tab, bool& ok) {
+                               const float* tab, bool div_shared, bool& ok) {
     FastGeom g;
     // dn is a sum of squares of fp16 values: 2^-48 <= dn < 2^35 whenever it is positive and finite (checked above), so the
     // restricted-range sqrt / reciprocal apply (numerics.hpp)
@@ -85,10 +90,11 @@ SAH_DEV FastGeom fast_geometry(const LightingArgs& a, const FastArgs& f, float c
     const Fn vw = Fn(f.p11) * Fn(D) + Fn(f.p15);
     const Fn vzn = Fn(f.p10) * Fn(D) + Fn(f.p14);
     Fn vx, vy;
-    if (f.pos_div_nr) {
+    if (div_shared) {
         // The three quotients share one refined reciprocal (div_nr with the y1 steps hoisted): 8 + 4 + 3 * 10 cycles instead of
         // 3 * 34.  Domain: |vw| in [2^-40, 2^40] (checked here), numerators +0 or in [2^-40, 2^40] in magnitude (host:
-        // detect_fast_path bounds p0, p5, p14 and requires p10 == p12 == p13 == +0, so x / y numerators are products of a
+        // detect_fast_path bounds p0, p5, p14 and requires p10 == 0, and either p12 == p13 == +0 — pos_div_nr — or zeros of any sign
+        // there with numerators from a table that holds no -0 — pos_div_shared —, so x / y numerators are products of a
         // bounded coefficient with a multiple of 2^-24 and the z numerator is the constant p14).
         const float aw = __builtin_fabsf(vw.v);
         ok = ok && aw >= kDivLo && aw <= kDivHi;
@@ -257,7 +263,7 @@ SAH_DEV void fast_lpv_overlay(const LpvArgs& lpv, const FastArgs& f, const float
 template <int SUN, int GI>
 SAH_DEV FastPixelOut shade_pixel_fast_sl(const LightingArgs& a, const CsmArgs& csm, const LpvArgs& lpv, const FastArgs& f, float colx_glsl,
                                          float rowy_glsl, float colx_slang, float rowy_slang, const Px& p, const float* tab,
-                                         bool lpv_has_nonfinite, bool emissive_wave) {
+                                         bool lpv_has_nonfinite, bool emissive_wave, bool div_shared) {
     const float* lut = tab;
     const float D = p.depth;
     const bool sky_px = D == 0.f;
@@ -273,7 +279,7 @@ SAH_DEV FastPixelOut shade_pixel_fast_sl(const LightingArgs& a, const CsmArgs& c
     F3 N, ws, V;
     Fn vsz;
     if (SUN == SAH_SHADOW_MODE_CSM || GI == SAH_GI_LPV) {
-        const FastGeom g = fast_geometry(a, f, colx_glsl, rowy_glsl, D, si, dn, tab, ok);
+        const FastGeom g = fast_geometry(a, f, colx_glsl, rowy_glsl, D, si, dn, tab, div_shared, ok);
         N = g.N;
         ws = g.ws;
         V = g.V;

@@ -56,6 +56,7 @@ __global__ void __launch_bounds__(256) k_lighting_tiled(const LightingArgs a, co
         const uint32_t t = threadIdx.x - 64u, c = t >> 3, j = t & 7u;
         s_lut[TAB_LPV + t] = (j & 3u) == 3u ? 0.f : (j < 4u ? f.lpv_s[c][j] : f.lpv_t[c][j - 4u]);
     }
+    const bool div_shared = fast_geom != 0u && pos_div_shared_of(f);  // (uniform) one reciprocal for the three position quotients
     __shared__ float s_box[4][6];
     __shared__ uint32_t s_wave_count[4];
     __shared__ uint16_t s_list[kMaxTileLights];
@@ -118,7 +119,7 @@ __global__ void __launch_bounds__(256) k_lighting_tiled(const LightingArgs a, co
                 colx_glsl = (Fn(f.p0) * (tx * Fn(2.0f) - Fn(1.0f)) + Fn(f.p12)).v;
                 rowy_glsl = (Fn(f.p5) * (ty * Fn(2.0f) - Fn(1.0f)) + Fn(f.p13)).v;
             }
-            g = fast_geometry(a, f, colx_glsl, rowy_glsl, p.depth, si, dn, s_lut, geom_ok);
+            g = fast_geometry(a, f, colx_glsl, rowy_glsl, p.depth, si, dn, s_lut, div_shared, geom_ok);
         }
         s.base_color = {Fn(si.color[0]), Fn(si.color[1]), Fn(si.color[2])};
         s.normal = g.N;
@@ -308,7 +309,7 @@ __global__ void __launch_bounds__(256) k_lighting_tiled(const LightingArgs a, co
         // the bits of worldspace_location_slang() / normalize() inside the domains its `ok` reports (depth and distance from the camera
         // within 2^+-40), the general form for the pixels outside them
         bool hot = false;
-        if (fast_geom && f.pos_div_nr) {
+        if (div_shared) {
             const uint32_t xt = min(x, a.width - 1u), yt = min(y, a.height - 1u);
             float colx, rowy;
             if (f.colx_tab) {
@@ -320,7 +321,7 @@ __global__ void __launch_bounds__(256) k_lighting_tiled(const LightingArgs a, co
                 rowy = (Fn(f.p5) * (ty * Fn(2.0f) - Fn(1.0f)) + Fn(f.p13)).v;
             }
             hot = surface && finite_f(p.depth);
-            const FastGeom fg = fast_geometry(a, f, colx, rowy, p.depth, si, 1.0f, s_lut, hot);  // (its fp32 normal is not used: dn = 1)
+            const FastGeom fg = fast_geometry(a, f, colx, rowy, p.depth, si, 1.0f, s_lut, div_shared, hot);  // (its fp32 normal is not used: dn = 1)
             sg.s.base_color = {Hn(si.color[0]), Hn(si.color[1]), Hn(si.color[2])};
             sg.s.normal = normalize(H3{Hn(si.normal[0]), Hn(si.normal[1]), Hn(si.normal[2])});
             sg.s.roughness = Hn(si.rough);

@@ -91,6 +91,10 @@ struct FrameState {
     // Lighting calls keeps its verdict.  (Rounds 2-4 compared a tag with the copy's serial number, a KERNEL ARGUMENT: a captured launch replays
     // its arguments, so the verdict now lives in memory only.)
     uint32_t nonfinite;
+    // 1 when the column / row table of view-space numerators (k_colx_table) holds an entry whose bits are 0x80000000 (-0): cleared (a 4-byte
+    // memset) and raised where the table is rebuilt, read by the Lighting kernels that may share one reciprocal among the position divides
+    // (FastArgs::pos_div_shared); a table that is kept over several Lighting calls keeps its verdict.
+    uint32_t colx_neg_zero;
 };
 
 // What the fast kernel may assume, established by the host (api.cpp: detect_fast_path):
@@ -119,6 +123,9 @@ struct FastArgs {
     uint16_t* seg_count;
     uint32_t num_segments, seg_stride;
     uint32_t hint_slot;  // which word of FrameState::deferred_hint this call uses (0 / 1, alternating per Lighting call of the context)
+    // the shared-reciprocal divide with zeros of EITHER sign in inverse_projection[10], [12], [13]: holds where pos_div_nr's bounds do, the numerators
+    // come from the table (colx_tab, state valid) and FrameState::colx_neg_zero is clear (DESIGN.md "Fast path proofs")
+    uint32_t pos_div_shared;
     // LPV gather copy (k_lpv_pack): texel (x,y,z) of the three volumes interleaved as 24 bytes {R[4], G[4], B[4]} (fp16) at
     // ((z+2) * pk_slice_pitch + (y+2) * pk_row_pitch + (x+2) * 24), inside a two-texel border of zeros (= CLAMP_TO_BORDER)
     const uint8_t* lpv_packed;

@@ -211,12 +211,14 @@ class Context:
         return int(out[0]), int(out[1])
 
     DISPATCH_FIELDS = ("family", "ppt", "pos_div_nr", "ncasc_pow2", "row_magic", "sky_ratio", "sky_workgroups", "tiled_fast_geom", "tiled_fast_lpv",
-                       "repack", "table_rebuilt")
+                       "repack", "table_rebuilt", "pos_div_shared")
 
     def lighting_dispatch(self):
         """Test hook: what the last lighting() call of this context decided, as a dict — family ('general' / 'fast' / 'tiled'), ppt, pos_div_nr,
         ncasc_pow2, row_magic (1: the multiply-high row split), sky_ratio, sky_workgroups (leading the grid), tiled_fast_geom, tiled_fast_lpv,
-        repack, table_rebuilt.  Recorded on the host: no device work, no synchronisation."""
+        repack, table_rebuilt, pos_div_shared (1: the position divides shared one reciprocal through the condition for zeros of either sign in the
+        inverse projection; 0 where pos_div_nr is 1).  Recorded on the host: no device work, no synchronisation — except for pos_div_shared where
+        the host's half of its condition held: the kernel decides from a word the table's build leaves on the device, which is then fetched."""
         out = (C.c_uint32 * len(self.DISPATCH_FIELDS))()
         self._check(self.lib.sah_debug_lighting_dispatch(self.handle, out))
         rep = {k: int(v) for k, v in zip(self.DISPATCH_FIELDS, out)}

@@ -4,7 +4,9 @@
 //         tools/microbench/exact_math_check.hip -o tools/microbench/exact_math_check && tools/microbench/exact_math_check
 // sqrt_nr / sqrt_nr0 / rcp_nr: EVERY fp32 bit pattern whose magnitude lies in [2^-100, 2^100] (and +0 for sqrt_nr0).
 // div_nr: 2^36 pseudo-random operand pairs with |a|, |b| in [2^-40, 2^40], a quarter of them with mantissas within a few ulps of
-// all-zeros / all-ones (the hard cases of Newton division), plus a = +0.
+// all-zeros / all-ones (the hard cases of Newton division), plus a = +0.  Both operands carry pseudo-random signs; a second sweep
+// ("div_nr a<0") takes the same 2^36 pairs with every non-zero numerator made negative — the view-space position's numerators under a
+// camera whose inverse projection has negative entries (DESIGN.md "Fast path proofs": every step of div_nr is odd in a).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -67,7 +69,7 @@ __device__ inline float make_operand(uint32_t r, uint32_t r2, bool hard) {
     const uint32_t sign = (r2 >> 31) << 31;
     return __uint_as_float(sign | (exp << 23) | mant);
 }
-__global__ void __launch_bounds__(256) k_div(Report* rep, uint32_t pairs_per_thread, uint64_t seed) {
+__global__ void __launch_bounds__(256) k_div(Report* rep, uint32_t pairs_per_thread, uint64_t seed, int negative_a) {
     const uint64_t tid = blockIdx.x * 256ull + threadIdx.x;
     unsigned long long tested = 0;
     for (uint32_t j = 0; j < pairs_per_thread; j++) {
@@ -75,6 +77,7 @@ __global__ void __launch_bounds__(256) k_div(Report* rep, uint32_t pairs_per_thr
         const bool hard_a = ((h2 >> 40) & 3u) == 0u, hard_b = ((h2 >> 42) & 1u) == 0u && (((h2 >> 43) & 1u) == 0u);
         float a = make_operand((uint32_t)h, (uint32_t)(h2 >> 8), hard_a);
         const float b = make_operand((uint32_t)(h >> 32), (uint32_t)h2, hard_b);
+        if (negative_a) a = -__builtin_fabsf(a);
         if (((h2 >> 50) & 1023u) == 0u) a = 0.0f;  // +0 numerator
         if (!same(div_nr(a, b), a / b)) fail(rep, __float_as_uint(a), __float_as_uint(b));
         tested++;
@@ -104,10 +107,12 @@ int main() {
     bad |= report("sqrt_nr0", d_rep);
     hipLaunchKernelGGL(k_unary, dim3(256 * 32), dim3(256), 0, 0, d_rep, 2);
     bad |= report("rcp_nr", d_rep);
-    for (int pass = 0; pass < 16; pass++) {  // 16 x 2^32 pairs
-        hipLaunchKernelGGL(k_div, dim3(1 << 16), dim3(256), 0, 0, d_rep, 256u, 0x1234567ull + (uint64_t)pass * (1ull << 40));
+    for (int negative_a = 0; negative_a < 2; negative_a++) {
+        for (int pass = 0; pass < 16; pass++) {  // 16 x 2^32 pairs
+            hipLaunchKernelGGL(k_div, dim3(1 << 16), dim3(256), 0, 0, d_rep, 256u, 0x1234567ull + (uint64_t)pass * (1ull << 40), negative_a);
+        }
+        bad |= report(negative_a ? "div_nr a<0" : "div_nr", d_rep);
     }
-    bad |= report("div_nr", d_rep);
     (void)hipFree(d_rep);
     return bad;
 }
