@@ -5,18 +5,7 @@
 
 #include "../../include/sah_hip.h"
 #include "ctx.hpp"
-
-namespace sah {
-struct IpcPeers {
-    uint32_t* slot[SAH_IPC_MAX_WORLD];
-};
-struct IpcCopies {
-    uint8_t* dst[SAH_IPC_MAX_WORLD];
-};
-hipError_t launch_ipc_signal(const IpcPeers& peers, uint32_t value, const uint32_t* abort, hipStream_t st);
-hipError_t launch_ipc_wait(const IpcPeers& own, uint32_t value, uint32_t* abort, uint32_t* timed_out, const IpcPeers& notes, hipStream_t st);
-hipError_t launch_ipc_copy(const IpcCopies& c, int world, const uint8_t* src, uint64_t bytes, const uint32_t* abort, const uint32_t* gave_up, hipStream_t st);
-}  // namespace sah
+#include "launch.hpp"
 
 namespace {
 constexpr uint32_t kMagic = 0x53414849u;  // "SAHI"

@@ -10,36 +10,7 @@
 #include "../../include/sah_hip.h"
 #include "../../include/sah_lpv_gv.h"
 #include "ctx.hpp"
-#include "post_args.hpp"
-
-namespace sah {
-hipError_t launch_copy_scene(const PlaneArg& src, uint32_t sw, uint32_t sh, const PlaneArg& dst, uint32_t dw, uint32_t dh, uint32_t row_begin,
-                             uint32_t row_end, hipStream_t st);
-hipError_t launch_bloom_downsample(const PlaneArg& src, uint32_t sw, uint32_t sh, const PlaneArg& dst, uint32_t dw, uint32_t dh, uint32_t row_begin,
-                                   uint32_t row_end, hipStream_t st);
-bool launch_copy_bloom_mip0(const PlaneArg& lit, uint32_t lw, uint32_t lh, const PlaneArg& aa, uint32_t aw, uint32_t ah, const PlaneArg& mip0, uint32_t mw, uint32_t mh,
-                            uint32_t mip_row_begin, uint32_t mip_row_end, uint32_t aa_row_begin, uint32_t aa_row_end, hipStream_t st, hipError_t* err);
-bool launch_bloom_pair(const PlaneArg& s, uint32_t sw, uint32_t sh, const PlaneArg& a, uint32_t aw, uint32_t ah, const PlaneArg& b, uint32_t bw, uint32_t bh,
-                       hipStream_t st, hipError_t* err);
-hipError_t launch_tonemap(const TonemapArgs& t, hipStream_t st);
-hipError_t launch_tonemap_tol(const TonemapArgs& t, hipStream_t st);
-hipError_t launch_tonemap_axis_tables(const TonemapArgs& t, TmAxis* out, hipStream_t st);
-hipError_t launch_lpv_clear(const VolumeArg* vols, int n, uint32_t num_cascades, hipStream_t st);
-hipError_t launch_lpv_propagate(const VolumeArg src[3], const VolumeArg dst[3], uint32_t num_cascades, const LpvPackEmit* emit, bool hot, hipStream_t st,
-                                const LpvGvStep* gv = nullptr);
-hipError_t launch_lpv_gv_factors(const VolumeArg& gv, void* factors, uint32_t num_cascades, hipStream_t st);
-hipError_t launch_gv_inject_rsm(const VolumeArg& normals, const VolumeArg& depth, const sah_lpv_cascade_matrices* cascades, uint32_t first_cascade,
-                                uint32_t cascade_count, uint32_t num_cascades, const VolumeArg& gv, uint32_t* keys, hipStream_t st);
-hipError_t launch_gv_inject_scene(const PlaneArg& depth, const PlaneArg& normals, uint32_t width, uint32_t height, const sah_view_data& view,
-                                  const sah_lpv_cascade_matrices* cascades, uint32_t num_cascades, const VolumeArg& gv, uint32_t* keys, hipStream_t st);
-hipError_t launch_lpv_build_tables(hipStream_t st, bool* hot_structure);
-hipError_t launch_sky_luts(const PlaneArg& transmittance, const PlaneArg& multiscattering, const PlaneArg& sky_view, const float light_vector[3], hipStream_t st);
-hipError_t launch_fill_r32f(const PlaneArg& dst, uint32_t w, uint32_t h, float value, hipStream_t st);
-hipError_t launch_probe_copy(const ProbeAtlasArgs& src, const ProbeAtlasArgs& dst, const float movement[4][3], hipStream_t st);
-hipError_t launch_probe_irr_unpack_probes(const VolumeArg& src, uint8_t* dst, const uint32_t* probes, uint32_t num_probes, hipStream_t st);  // lighting_tiled.hip
-hipError_t launch_probe_update(const ProbeAtlasArgs& atl, const VolumeArg& trace, const uint32_t* probes, uint32_t num_probes, uint32_t* slots,
-                               hipStream_t st);
-}  // namespace sah
+#include "launch.hpp"
 
 namespace {
 bool rgba16f_ok(const sah_plane* p) {
@@ -108,11 +79,6 @@ bool lpv_vol_ok(const sah_volume* v) {
            (v->row_pitch_bytes % 8) == 0 && (v->slice_pitch_bytes % 8) == 0;
 }
 }  // namespace
-
-int sah_ipc_find(const sah_ctx* ctx, const void* ptr, uint64_t bytes);
-int sah_ipc_gather(sah_ctx* ctx, uint32_t id, uint8_t* buffer, uint64_t bytes_per_rank, bool reversed, hipStream_t st);
-
-bool sah_ipc_timed_out(const sah_ctx* ctx);  // api_ipc.cpp
 
 extern "C" {
 

@@ -8,16 +8,7 @@
 #include "../../include/sah_hip.h"
 #include "../../include/sah_motion_vectors.h"
 #include "ctx.hpp"
-#include "raster_args.hpp"
-
-namespace sah {
-hipError_t launch_raster_setup(const RasterArgs& a, bool gbuffer, hipStream_t st);
-hipError_t launch_raster_tiles(const RasterArgs& a, bool gbuffer, hipStream_t st);
-hipError_t launch_extract_vpls(const VolumeArg& flux, const VolumeArg& normals, const VolumeArg& depth, const sah_lpv_cascade_matrices& c, uint32_t cascade,
-                               float grid_cell_size, const float* luts, sah_packed_vpl* list, uint32_t* count, void* scratch, hipStream_t st);
-hipError_t launch_inject_vpls(const sah_packed_vpl* list, const uint32_t* count, uint32_t capacity, const sah_lpv_cascade_matrices& c, uint32_t cascade,
-                              uint32_t num_cascades, const VolumeArg rgb[3], uint32_t* cells_scratch, hipStream_t st);
-}  // namespace sah
+#include "launch.hpp"
 
 namespace {
 constexpr uint32_t kTile = sah::kRasterTile;

@@ -7,15 +7,9 @@
 #include <stdint.h>
 
 #include "../../include/sah_hip.h"
+#include "launch.hpp"
 
 namespace sah {
-
-struct IpcPeers {
-    uint32_t* slot[SAH_IPC_MAX_WORLD];  // where to store (signal) / what to poll (wait); null: skipped
-};
-struct IpcCopies {
-    uint8_t* dst[SAH_IPC_MAX_WORLD];  // the own slot inside every peer's buffer; null: skipped
-};
 
 // `abort`: a device word of this context that a wait which gave up has raised.  From then on the gather it belongs to — and every later
 // one — neither signals nor copies: a peer that did not arrive may still be reading or writing its buffer.

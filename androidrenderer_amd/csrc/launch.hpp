@@ -1,0 +1,93 @@
+// Every kernel launcher (sah::launch_*) and host helper that one translation unit of the library defines and another calls, declared once.
+// Included by the callers (api*.cpp) AND by the defining files, so that the compiler checks each definition against the one declaration.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/sah_hip.h"
+#include "params.hpp"
+#include "post_args.hpp"
+#include "raster_args.hpp"
+#include "rt_args.hpp"
+
+struct sah_ctx;  // ctx.hpp
+
+namespace sah {
+
+// --- lighting.hip, lighting_tiled.hip
+hipError_t launch_lighting(const LightingArgs& a, const CsmArgs& csm, const LpvArgs& lpv, const CacheArgs& cache, const RtgiArgs& rtgi,
+                           const SkyArgs& sky, LightingFamily family, const FastArgs* fast, int sun_mode, int gi, int ppt, bool brute_force_lights,
+                           hipStream_t st);
+hipError_t launch_lighting_tiled(const LightingArgs& a, const CsmArgs& csm, const LpvArgs& lpv, const CacheArgs& cache, const RtgiArgs& rtgi,
+                                 const SkyArgs& sky, int sun_mode, int gi, bool brute_force_lights, const FastArgs* fast, hipStream_t st);
+hipError_t launch_colx_table(const LightingArgs& a, const FastArgs& f, float* out, uint32_t stride, uint32_t row_stride, hipStream_t st);
+hipError_t launch_probe_irr_unpack(const VolumeArg& src, uint8_t* dst, hipStream_t st);
+hipError_t launch_probe_irr_unpack_probes(const VolumeArg& src, uint8_t* dst, const uint32_t* probes, uint32_t num_probes, hipStream_t st);
+
+// --- post.hip, tonemap.hip, tonemap_tol.hip, sky_luts.hip
+hipError_t launch_copy_scene(const PlaneArg& src, uint32_t sw, uint32_t sh, const PlaneArg& dst, uint32_t dw, uint32_t dh, uint32_t row_begin,
+                             uint32_t row_end, hipStream_t st);
+hipError_t launch_bloom_downsample(const PlaneArg& src, uint32_t sw, uint32_t sh, const PlaneArg& dst, uint32_t dw, uint32_t dh, uint32_t row_begin,
+                                   uint32_t row_end, hipStream_t st);
+bool launch_copy_bloom_mip0(const PlaneArg& lit, uint32_t lw, uint32_t lh, const PlaneArg& aa, uint32_t aw, uint32_t ah, const PlaneArg& mip0, uint32_t mw, uint32_t mh,
+                            uint32_t mip_row_begin, uint32_t mip_row_end, uint32_t aa_row_begin, uint32_t aa_row_end, hipStream_t st, hipError_t* err);
+bool launch_bloom_pair(const PlaneArg& s, uint32_t sw, uint32_t sh, const PlaneArg& a, uint32_t aw, uint32_t ah, const PlaneArg& b, uint32_t bw, uint32_t bh,
+                       hipStream_t st, hipError_t* err);
+hipError_t launch_fill_r32f(const PlaneArg& dst, uint32_t w, uint32_t h, float value, hipStream_t st);
+hipError_t launch_tonemap(const TonemapArgs& t, hipStream_t st);
+hipError_t launch_tonemap_tol(const TonemapArgs& t, hipStream_t st);
+hipError_t launch_tonemap_axis_tables(const TonemapArgs& t, TmAxis* out, hipStream_t st);
+hipError_t launch_sky_luts(const PlaneArg& transmittance, const PlaneArg& multiscattering, const PlaneArg& sky_view, const float light_vector[3], hipStream_t st);
+
+// --- lpv.hip, lpv_gv.hip, vpl.hip
+hipError_t launch_lpv_clear(const VolumeArg* vols, int n, uint32_t num_cascades, hipStream_t st);
+hipError_t launch_lpv_build_tables(hipStream_t st, bool* hot_structure);
+hipError_t launch_lpv_propagate(const VolumeArg src[3], const VolumeArg dst[3], uint32_t num_cascades, const LpvPackEmit* emit, bool hot, hipStream_t st,
+                                const LpvGvStep* gv = nullptr);
+hipError_t launch_lpv_gv_factors(const VolumeArg& gv, void* factors, uint32_t num_cascades, hipStream_t st);
+hipError_t launch_gv_inject_rsm(const VolumeArg& normals, const VolumeArg& depth, const sah_lpv_cascade_matrices* cascades, uint32_t first_cascade,
+                                uint32_t cascade_count, uint32_t num_cascades, const VolumeArg& gv, uint32_t* keys, hipStream_t st);
+hipError_t launch_gv_inject_scene(const PlaneArg& depth, const PlaneArg& normals, uint32_t width, uint32_t height, const sah_view_data& view,
+                                  const sah_lpv_cascade_matrices* cascades, uint32_t num_cascades, const VolumeArg& gv, uint32_t* keys, hipStream_t st);
+hipError_t launch_extract_vpls(const VolumeArg& flux, const VolumeArg& normals, const VolumeArg& depth, const sah_lpv_cascade_matrices& c, uint32_t cascade,
+                               float grid_cell_size, const float* luts, sah_packed_vpl* list, uint32_t* count, void* scratch, hipStream_t st);
+hipError_t launch_inject_vpls(const sah_packed_vpl* list, const uint32_t* count, uint32_t capacity, const sah_lpv_cascade_matrices& c, uint32_t cascade,
+                              uint32_t num_cascades, const VolumeArg rgb[3], uint32_t* cells_scratch, hipStream_t st);
+
+// --- probes.hip
+hipError_t launch_probe_copy(const ProbeAtlasArgs& src, const ProbeAtlasArgs& dst, const float movement[4][3], hipStream_t st);
+hipError_t launch_probe_update(const ProbeAtlasArgs& atl, const VolumeArg& trace, const uint32_t* probes, uint32_t num_probes, uint32_t* slots,
+                               hipStream_t st);
+
+// --- raster.hip
+hipError_t launch_raster_setup(const RasterArgs& a, bool gbuffer, hipStream_t st);
+hipError_t launch_raster_tiles(const RasterArgs& a, bool gbuffer, hipStream_t st);
+
+// --- rt.hip
+hipError_t launch_rt_scan(const sah_primitive* prims, uint32_t n, uint32_t* tri_base, RtBuildState* st, hipStream_t s);
+hipError_t launch_rt_world(const RtScene& sc, const uint32_t* tri_base, uint32_t total, RtTriangle* out, RtBuildState* st, hipStream_t s);
+hipError_t launch_rt_sort(const RtTriangle* tris, const RtBuildState* st, unsigned long long* keys, uint32_t padded, hipStream_t s);
+hipError_t launch_rt_nodes(const RtTriangle* unsorted, const unsigned long long* keys, RtTriangle* sorted, RtNodeGroup* nodes, const RtBvh& bvh, hipStream_t s);
+hipError_t launch_rtao(const RtaoArgs& a, const RtBvh& bvh, const RtScene& sc, hipStream_t s);
+hipError_t launch_sun_shadow_mask(const ShadowMaskArgs& a, const RtBvh& bvh, const RtScene& sc, hipStream_t s);
+hipError_t launch_noise_dirs(const PlaneArg& noise, const float* luts, float* out, hipStream_t s);
+hipError_t launch_probe_trace(const ProbeTraceArgs& a, const RtBvh& bvh, const RtScene& sc, hipStream_t s);
+hipError_t launch_rtgi_trace(const RtgiTraceArgs& a, const RtBvh& bvh, const RtScene& sc, hipStream_t s);
+
+// --- ipc.hip (direct exchange)
+struct IpcPeers {
+    uint32_t* slot[SAH_IPC_MAX_WORLD];  // where to store (signal) / what to poll (wait); null: skipped
+};
+struct IpcCopies {
+    uint8_t* dst[SAH_IPC_MAX_WORLD];  // the own slot inside every peer's buffer; null: skipped
+};
+hipError_t launch_ipc_signal(const IpcPeers& peers, uint32_t value, const uint32_t* abort, hipStream_t st);
+hipError_t launch_ipc_wait(const IpcPeers& own, uint32_t value, uint32_t* abort, uint32_t* timed_out, const IpcPeers& notes, hipStream_t st);
+hipError_t launch_ipc_copy(const IpcCopies& c, int world, const uint8_t* src, uint64_t bytes, const uint32_t* abort, const uint32_t* gave_up, hipStream_t st);
+
+}  // namespace sah
+
+// --- api_ipc.cpp: the direct exchange as the other entry points use it
+int sah_ipc_find(const sah_ctx* ctx, const void* ptr, uint64_t bytes);
+int sah_ipc_gather(sah_ctx* ctx, uint32_t id, uint8_t* buffer, uint64_t bytes_per_rank, bool reversed, hipStream_t st);
+bool sah_ipc_timed_out(const sah_ctx* ctx);

@@ -19,6 +19,7 @@
 #include "../../include/sah_hip.h"
 #include "lighting_common.hpp"
 #include "lighting_fast.hpp"
+#include "launch.hpp"
 #include "numerics.hpp"
 #include "params.hpp"
 
@@ -432,9 +433,6 @@ hipError_t launch_colx_table(const LightingArgs& a, const FastArgs& f, float* ou
     hipLaunchKernelGGL(k_colx_table, dim3((max(a.width, a.height) + 255u) / 256u), dim3(256), 0, st, a, f, out, stride, row_stride);
     return hipGetLastError();
 }
-
-hipError_t launch_lighting_tiled(const LightingArgs& a, const CsmArgs& csm, const LpvArgs& lpv, const CacheArgs& cache, const RtgiArgs& rtgi,
-                                 const SkyArgs& sky, int sun_mode, int gi, bool brute_force_lights, const FastArgs* fast, hipStream_t st);
 
 hipError_t launch_lighting(const LightingArgs& a, const CsmArgs& csm, const LpvArgs& lpv, const CacheArgs& cache, const RtgiArgs& rtgi,
                            const SkyArgs& sky, LightingFamily family, const FastArgs* fast, int sun_mode, int gi, int ppt, bool brute_force_lights,

@@ -16,6 +16,7 @@
 #include "lighting_common.hpp"
 #include "lighting_fast.hpp"
 #include "lighting_gi_ext.hpp"
+#include "launch.hpp"
 #include "numerics.hpp"
 #include "params.hpp"
 

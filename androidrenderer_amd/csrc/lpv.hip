@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "../../include/sah_hip.h"
+#include "launch.hpp"
 #include "numerics.hpp"
 #include "params.hpp"
 

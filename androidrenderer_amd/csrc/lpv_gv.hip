@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/sah_hip.h"
+#include "launch.hpp"
 #include "numerics.hpp"
 #include "params.hpp"
 

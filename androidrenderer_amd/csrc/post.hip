@@ -6,6 +6,7 @@
 
 #include <algorithm>
 
+#include "launch.hpp"
 #include "post_common.hpp"
 
 namespace sah {

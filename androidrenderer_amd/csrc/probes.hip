@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sah_hip.h"
+#include "launch.hpp"
 #include "octahedral.hpp"
 #include "numerics.hpp"
 #include "params.hpp"

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch.hpp"
 #include "numerics.hpp"
 #include "raster_args.hpp"
 #include "texture_sample.hpp"

@@ -14,6 +14,7 @@
 
 #include "lighting_common.hpp"
 #include "lighting_gi_ext.hpp"
+#include "launch.hpp"
 #include "numerics.hpp"
 #include "octahedral.hpp"
 #include "rt_args.hpp"

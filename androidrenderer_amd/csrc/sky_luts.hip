@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sah_hip.h"
+#include "launch.hpp"
 #include "lighting_common.hpp"
 
 namespace sah {

@@ -3,6 +3,7 @@
 
 #include <type_traits>
 
+#include "launch.hpp"
 #include "post_common.hpp"
 
 // (both overridable from the command line for A/B builds: SAH_EXTRA_HIPCC_FLAGS, androidrenderer_amd/build.py)

@@ -29,6 +29,7 @@
 // LDS per workgroup: G 32.3 KB + texels 10.8 KB + tables 9 KB = 52.3 KB, 3 workgroups per CU.
 #include <hip/hip_runtime.h>
 
+#include "launch.hpp"
 #include "post_common.hpp"
 
 namespace sah {

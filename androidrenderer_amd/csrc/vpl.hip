@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch.hpp"
 #include "numerics.hpp"
 #include "params.hpp"
 #include "../../include/sah_hip.h"
