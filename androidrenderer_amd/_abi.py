@@ -20,8 +20,9 @@ FORMAT_R32_SFLOAT = 100
 FORMAT_B10G11R11_UFLOAT_PACK32 = 122
 FORMAT_D16_UNORM = 124
 FORMAT_D32_SFLOAT = 126
+FORMAT_R8_UINT = 13  # include/sah_vrsaa.h: accepted by the VRSAA entries only
 
-FORMAT_BPP = {9: 1, 37: 4, 43: 4, 76: 2, 83: 4, 97: 8, 100: 4, 122: 4, 124: 2, 126: 4}
+FORMAT_BPP = {9: 1, 13: 1, 37: 4, 43: 4, 76: 2, 83: 4, 97: 8, 100: 4, 122: 4, 124: 2, 126: 4}
 
 SHADOW_MODE_OFF, SHADOW_MODE_CSM, SHADOW_MODE_RT = 0, 1, 2
 GI_NONE, GI_LPV, GI_CACHE, GI_RTGI = 0, 1, 2, 3
@@ -41,6 +42,11 @@ class Plane(C.Structure):
 class Volume(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("depth", C.c_uint32),
                 ("row_pitch_bytes", C.c_uint32), ("slice_pitch_bytes", C.c_uint32), ("format", C.c_uint32)]
+
+
+class ShadingRateParams(C.Structure):  # sah_shading_rate_params (include/sah_vrsaa.h): 92 bytes
+    _fields_ = [("contrast_image_resolution", C.c_uint32 * 2), ("shading_rate_image_resolution", C.c_uint32 * 2), ("max_rate", C.c_uint32 * 2),
+                ("num_shading_rates", C.c_uint32), ("rates", (C.c_uint32 * 2) * 8)]
 
 
 class ProbeAtlases(C.Structure):  # sah_probe_atlases

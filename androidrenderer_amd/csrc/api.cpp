@@ -727,6 +727,13 @@ int sah_debug_copy_rebuilds(sah_ctx* ctx, uint32_t out[2]) {
     return SAH_OK;
 }
 
+// Debug / test hook: the context's cache epoch (ctx.hpp) — how a test shows that a call left it alone.
+int sah_debug_cache_epoch(sah_ctx* ctx, uint64_t* out) {
+    if (!ctx || !out) return SAH_ERR_INVALID_ARGUMENT;
+    *out = ctx->cache_epoch;
+    return SAH_OK;
+}
+
 // Debug / test hook: which kernel and which of its branches the last sah_lighting call of the context chose — recorded host side while the
 // call digests its arguments (no device work, no synchronisation).  All zero before the first call and after a call that failed validation.
 //   [0] kernel family: 0 general, 1 fast (+ fix-up), 2 tiled      [1] pixels per thread (0: tiled)      [2] pos_div_nr

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/sah_hip.h"
+#include "../../include/sah_vrsaa.h"
 #include "params.hpp"
 #include "post_args.hpp"
 #include "raster_args.hpp"
@@ -38,6 +39,12 @@ hipError_t launch_tonemap(const TonemapArgs& t, hipStream_t st);
 hipError_t launch_tonemap_tol(const TonemapArgs& t, hipStream_t st);
 hipError_t launch_tonemap_axis_tables(const TonemapArgs& t, TmAxis* out, hipStream_t st);
 hipError_t launch_sky_luts(const PlaneArg& transmittance, const PlaneArg& multiscattering, const PlaneArg& sky_view, const float light_vector[3], hipStream_t st);
+
+// --- vrsaa.hip
+hipError_t launch_vrsaa_contrast(const PlaneArg& color, const PlaneArg& depth, const PlaneArg& out, uint32_t w, uint32_t h, uint32_t row_begin,
+                                 uint32_t row_end, const float* luts, hipStream_t st);
+hipError_t launch_vrsaa_shading_rate(const PlaneArg& contrast, uint32_t cw, uint32_t ch, const PlaneArg& out, uint32_t sw, uint32_t sh, uint32_t d,
+                                     const sah_shading_rate_params& params, hipStream_t st);
 
 // --- lpv.hip, lpv_gv.hip, vpl.hip
 hipError_t launch_lpv_clear(const VolumeArg* vols, int n, uint32_t num_cascades, hipStream_t st);

@@ -179,12 +179,35 @@ class LightingInputs:
         return from_torch(lit, np.uint16)
 
 
-def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, stats_ptr=None):
+def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, stats_ptr=None, vrsaa=None):
     """The rasterised part of a frame: sah_gbuffer_render into `gbuffer` (dict of device arrays: color, normals, data, emission, depth)
     and — only when a `motion_vectors` target (H, W, 2) int16 device array is given — sah_motion_vectors_render against the depth the
     G-buffer pass has just written, as the reference runs its motion-vectors phase after its depth pass (scene_renderer.cpp:308-316).
-    Without the target the frame is what it always was."""
+    Without the target the frame is what it always was.
+
+    `vrsaa` (off by default): a dict with "rates" [(x, y), ...] and "texel_size" (x, y), and optionally the device arrays "contrast"
+    (H, W, 2) int16 — the LAST frame's contrast image — and "shading_rate_image" (uint8, the extent of
+    scene.shading_rate_image_extent); missing arrays are created, zeroed.  In the reference's order (scene_renderer.cpp:357-361, 476-481):
+    the shading-rate image is made from the previous contrast image before the G-buffer pass, and this frame's contrast is measured into the
+    same array at the end, from the G-buffer's colour and depth.  Returns (contrast, shading_rate_image) then, None otherwise."""
+    sri = contrast = None
+    if vrsaa is not None:
+        import torch
+        h, w = gbuffer["depth"].shape[0], gbuffer["depth"].shape[1]
+        sw, sh = scene.shading_rate_image_extent((w, h), vrsaa["texel_size"])
+        contrast = vrsaa.get("contrast")
+        if contrast is None:
+            contrast = torch.zeros((h, w, 2), dtype=torch.int16, device=gbuffer["depth"].device)
+        sri = vrsaa.get("shading_rate_image")
+        if sri is None:
+            sri = torch.zeros((sh, sw), dtype=torch.uint8, device=gbuffer["depth"].device)
+        contrast_p = images.plane(contrast, _abi.FORMAT_R16G16_SFLOAT)
+        ctx.vrsaa_shading_rate_image(contrast_p, images.plane(sri, _abi.FORMAT_R8_UINT), scene.shading_rate_params((w, h), (sw, sh), vrsaa["rates"]))
     ctx.gbuffer_render(geometry, view_data, images.gbuffer(gbuffer), stats_ptr)
     if motion_vectors is not None:
         ctx.motion_vectors_render(geometry, view_data, images.plane(gbuffer["depth"], _abi.FORMAT_D32_SFLOAT),
                                   images.plane(motion_vectors, _abi.FORMAT_R16G16_SFLOAT))
+    if vrsaa is not None:
+        ctx.vrsaa_measure_aliasing(images.plane(gbuffer["color"], _abi.FORMAT_R8G8B8A8_SRGB), images.plane(gbuffer["depth"], _abi.FORMAT_D32_SFLOAT), contrast_p)
+        return contrast, sri
+    return None

@@ -33,6 +33,9 @@ GV_EXPORTS = ["sah_lpv_inject_rsm_gv", "sah_lpv_inject_scene_gv", "sah_lpv_propa
 # the motion-vectors pass: exported, declared in include/sah_motion_vectors.h (not sah_hip.h)
 MV_EXPORTS = ["sah_motion_vectors_render"]
 
+# the VRSAA passes: exported, declared in include/sah_vrsaa.h (not sah_hip.h)
+VRSAA_EXPORTS = ["sah_vrsaa_measure_aliasing", "sah_vrsaa_shading_rate_image"]
+
 # the LPV mesh lights' entries: exported, declared in include/sah_lpv_mesh_lights.h (not sah_hip.h)
 ML_EXPORTS = ["sah_mesh_point_cloud", "sah_lpv_emissive_vpls", "sah_lpv_inject_emissive"]
 POINT_CLOUD_ON_SURFACE = 1    # SAH_POINT_CLOUD_ON_SURFACE
@@ -166,6 +169,8 @@ def load():
     lib.sah_lpv_inject_emissive.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.POINTER(EmissiveCloud), C.c_uint32,
                                             C.POINTER(_abi.LpvCascadeMatrices), C.POINTER(LpvCascadeBounds), C.c_uint32, C.POINTER(_abi.Volume)]
     lib.sah_lpv_propagate_gv.argtypes = [C.c_void_p, C.POINTER(_abi.Volume), C.POINTER(_abi.Volume), C.POINTER(_abi.Volume), C.c_uint32, C.c_uint32]
+    lib.sah_vrsaa_measure_aliasing.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
+    lib.sah_vrsaa_shading_rate_image.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.POINTER(_abi.ShadingRateParams)]
     _lib = lib
     return lib
 
@@ -325,6 +330,16 @@ class Context:
         """sah_motion_vectors_render (include/sah_motion_vectors.h): depth, out: _abi.Plane of device memory (D32_SFLOAT read only,
         R16G16_SFLOAT of the same extent); stats: device pointer to SAH_RASTER_STATS_WORDS words, or None."""
         self._check(self.lib.sah_motion_vectors_render(self.handle, C.byref(scene), C.byref(view), C.byref(depth), C.byref(out), C.c_void_p(stats)))
+
+    def vrsaa_measure_aliasing(self, color, depth, contrast, rows=(0, 0)):
+        """sah_vrsaa_measure_aliasing (include/sah_vrsaa.h): color R8G8B8A8_SRGB, depth D32_SFLOAT, contrast R16G16_SFLOAT, _abi.Plane of device
+        memory of one extent; rows of `contrast` to write, (0, 0) = all."""
+        self._check(self.lib.sah_vrsaa_measure_aliasing(self.handle, C.byref(color), C.byref(depth), C.byref(contrast), rows[0], rows[1]))
+
+    def vrsaa_shading_rate_image(self, contrast, sri, params):
+        """sah_vrsaa_shading_rate_image: contrast R16G16_SFLOAT, sri R8_UINT (_abi.Plane of device memory), params an _abi.ShadingRateParams
+        (scene.shading_rate_params)."""
+        self._check(self.lib.sah_vrsaa_shading_rate_image(self.handle, C.byref(contrast), C.byref(sri), C.byref(params)))
 
     def rsm_render(self, scene, sun, cascades, num_cascades, rsm, stats_ptr=None):
         """cascades: (LpvCascadeMatrices * n) host array; rsm: _abi.RsmTargets of device volumes."""

@@ -102,6 +102,29 @@ def _fill(dst, arr):
         dst[i] = float(v)
 
 
+def shading_rate_params(contrast_extent, sri_extent, rates):
+    """VRSAA::create_params_buffer (sampling_rate_calculator.cpp:134-175): the uniform block of sah_vrsaa_shading_rate_image for a contrast
+    image and a shading-rate image of (width, height) extents and the device's shading rates [(x, y), ...] (at most 8): max_rate is the
+    per-component maximum, the list is padded with (0, 0) to eight."""
+    rates = [(int(x), int(y)) for x, y in rates]
+    if len(rates) > 8:
+        raise ValueError("at most 8 shading rates")
+    p = _abi.ShadingRateParams()
+    p.contrast_image_resolution[:] = [int(v) for v in contrast_extent]
+    p.shading_rate_image_resolution[:] = [int(v) for v in sri_extent]
+    p.max_rate[0] = max([r[0] for r in rates], default=0)
+    p.max_rate[1] = max([r[1] for r in rates], default=0)
+    p.num_shading_rates = len(rates)
+    for i, (x, y) in enumerate(rates):
+        p.rates[i][0], p.rates[i][1] = x, y
+    return p
+
+
+def shading_rate_image_extent(resolution, texel_size):
+    """VRSAA::create_shading_rate_image (sampling_rate_calculator.cpp:107-123): ceil(resolution / texel size) per axis."""
+    return tuple(-(-int(r) // int(t)) for r, t in zip(resolution, texel_size))
+
+
 class SceneView:
     """scene_view.hpp:17-125 — camera → ViewDataGPU."""
 

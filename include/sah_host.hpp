@@ -30,6 +30,7 @@
 #include "sah_lpv_gv.h"
 #include "sah_lpv_mesh_lights.h"
 #include "sah_motion_vectors.h"
+#include "sah_vrsaa.h"
 
 namespace sah {
 
@@ -65,7 +66,7 @@ using BufferUsageList = std::vector<BufferUsageToken>;
 
 inline uint32_t format_bytes(uint32_t f) {
     switch (f) {
-        case SAH_FORMAT_R8_UNORM: return 1;
+        case SAH_FORMAT_R8_UNORM: case SAH_FORMAT_R8_UINT: return 1;
         case SAH_FORMAT_R16_SFLOAT: case SAH_FORMAT_D16_UNORM: return 2;
         case SAH_FORMAT_R16G16B16A16_SFLOAT: return 8;
         default: return 4;
@@ -1287,6 +1288,61 @@ public:
 private:
     ResourceAllocator& allocator;
     TextureHandle motion_vectors = nullptr;
+};
+
+// RenderCore/render/phase/sampling_rate_calculator.hpp / .cpp:11-175.  SceneRenderer makes one when AntiAliasingType::VRSAA is selected
+// (scene_renderer.cpp:142-154), calls generate_shading_rate_image before the G-buffer pass (:357-361: it reads the LAST frame's contrast
+// image) and measure_aliasing after lighting (:476-481).  Not instantiated by the default frame (AA = None).  The two backend queries of the
+// reference — get_max_shading_rate_texel_size() and get_shading_rates() — have setters here; set them before init().  Nothing in this
+// library consumes the shading-rate image (hardware VRS; LightingPhase::render ignores it as the reference's TODO does).
+class VRSAA {
+public:
+    explicit VRSAA(ResourceAllocator& allocator_in) : allocator(allocator_in) {}
+    void set_max_shading_rate_texel_size(uint32_t x, uint32_t y) { texel_size = {x, y}; }
+    void set_shading_rates(const std::vector<std::array<uint32_t, 2>>& rates) {
+        if (rates.size() > 8) throw std::runtime_error("VRSAA: at most 8 shading rates");
+        shading_rates = rates;
+    }
+    // sampling_rate_calculator.cpp:26-30
+    void init(const uint32_t resolution[2]) {
+        if (texel_size[0] == 0 || texel_size[1] == 0) throw std::runtime_error("Max shading rate texel size is 0!");  // (:108-111 logs and returns)
+        contrast_image = allocator.create_texture("Contrast", SAH_FORMAT_R16G16_SFLOAT, resolution[0], resolution[1]);
+        shading_rate_image = allocator.create_texture("Shading rate", SAH_FORMAT_R8_UINT, (resolution[0] + texel_size[0] - 1) / texel_size[0],
+                                                      (resolution[1] + texel_size[1] - 1) / texel_size[1]);  // ceil(resolution / texel size), :113-119
+        // create_params_buffer, :134-175
+        params = sah_shading_rate_params{};
+        params.contrast_image_resolution[0] = resolution[0], params.contrast_image_resolution[1] = resolution[1];
+        params.shading_rate_image_resolution[0] = shading_rate_image->desc.width, params.shading_rate_image_resolution[1] = shading_rate_image->desc.height;
+        params.num_shading_rates = (uint32_t)shading_rates.size();
+        for (size_t i = 0; i < shading_rates.size(); i++) {
+            params.max_rate[0] = std::max(params.max_rate[0], shading_rates[i][0]);
+            params.max_rate[1] = std::max(params.max_rate[1], shading_rates[i][1]);
+            params.rates[i][0] = shading_rates[i][0], params.rates[i][1] = shading_rates[i][1];
+        }
+    }
+    void generate_shading_rate_image(RenderGraph& graph) const {
+        graph.add_pass(hip_pass("Calculate shading rate", [this](sah_ctx* ctx) {
+                            if (!contrast_image || !shading_rate_image) return (int)SAH_ERR_INVALID_ARGUMENT;  // init has not been called
+                            const sah_plane c = contrast_image->plane(), s = shading_rate_image->plane();
+                            return sah_vrsaa_shading_rate_image(ctx, &c, &s, &params);
+                        }));
+    }
+    void measure_aliasing(RenderGraph& graph, TextureHandle scene_color, TextureHandle gbuffer_depth) const {
+        graph.add_pass(hip_pass("Contrast", [this, scene_color, gbuffer_depth](sah_ctx* ctx) {
+                            if (!contrast_image) return (int)SAH_ERR_INVALID_ARGUMENT;
+                            const sah_plane c = scene_color->plane(), d = gbuffer_depth->plane(), o = contrast_image->plane();
+                            return sah_vrsaa_measure_aliasing(ctx, &c, &d, &o, 0, 0);
+                        }));
+    }
+    TextureHandle get_shading_rate_image() const { return shading_rate_image; }
+    TextureHandle get_contrast_image() const { return contrast_image; }
+
+private:
+    ResourceAllocator& allocator;
+    std::array<uint32_t, 2> texel_size = {0, 0};
+    std::vector<std::array<uint32_t, 2>> shading_rates;
+    TextureHandle contrast_image = nullptr, shading_rate_image = nullptr;
+    sah_shading_rate_params params = {};
 };
 
 class LightingPhase {

@@ -1,0 +1,100 @@
+"""GPU: the C++ host façade's VRSAA class (tests/cpp/host_vrsaa.cpp, built by build(); compiled here when that program is missing) and
+frame.rasterised_frame(vrsaa=...).  Both produce the images the direct calls produce; with the option off — the default — the frame adds no
+pass and its planes are the ones it writes without the feature."""
+import faulthandler
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from androidrenderer_amd import _abi, frame, images, mesh, scene
+from tests import util
+from tests import vrsaa_ref as ref
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(autouse=True)
+def _time_limit():
+    faulthandler.dump_traceback_later(300, exit=True)  # an overrun ends the process
+    yield
+    faulthandler.cancel_dump_traceback_later()
+
+
+def _host_program(tmp_path):
+    built = os.path.join(ROOT, "tests", "cpp", "host_vrsaa")
+    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_vrsaa.h")]
+    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
+        return built
+    exe, libdir = str(tmp_path / "host_vrsaa"), os.path.join(ROOT, "androidrenderer_amd")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
+                           f"-Wl,-rpath,{libdir}"], timeout=600)
+    return exe
+
+
+def test_vrsaa_through_cpp_facade(tmp_path, hip_ctx):
+    import torch
+    fx = np.load(os.path.join(ROOT, "tests", "golden", "vrsaa_97x61.npz"))
+    W, H, texel = 97, 61, (8, 8)
+    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
+    with open(inp, "wb") as f:
+        f.write(np.array([W, H, texel[0], texel[1], len(ref.RATES)], np.uint32).tobytes())
+        f.write(np.array(ref.RATES, np.uint32).tobytes())
+        f.write(fx["color"].tobytes())
+        f.write(fx["depth"].tobytes())
+    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    blob = open(outp, "rb").read()
+    sw, sh = (int(v) for v in np.frombuffer(blob[:8], np.uint32))
+    assert (sw, sh) == scene.shading_rate_image_extent((W, H), texel) == (13, 8)
+    sri1 = np.frombuffer(blob[8:8 + sw * sh], np.uint8).reshape(sh, sw)
+    sri2 = np.frombuffer(blob[8 + sw * sh:8 + 2 * sw * sh], np.uint8).reshape(sh, sw)
+    contrast = np.frombuffer(blob[8 + 2 * sw * sh:], np.uint16).reshape(H, W, 2)
+    # the direct calls
+    color_t, depth_t = torch.from_numpy(fx["color"]).cuda(), torch.from_numpy(fx["depth"]).cuda()
+    contrast_t = torch.zeros((H, W, 2), dtype=torch.int16, device="cuda")
+    sri_t = torch.zeros((sh, sw), dtype=torch.uint8, device="cuda")
+    cp = images.plane(contrast_t, _abi.FORMAT_R16G16_SFLOAT)
+    hip_ctx.vrsaa_measure_aliasing(images.plane(color_t, _abi.FORMAT_R8G8B8A8_SRGB), images.plane(depth_t, _abi.FORMAT_D32_SFLOAT), cp)
+    hip_ctx.vrsaa_shading_rate_image(cp, images.plane(sri_t, _abi.FORMAT_R8_UINT), scene.shading_rate_params((W, H), (sw, sh), ref.RATES))
+    torch.cuda.synchronize()
+    assert np.array_equal(contrast, util.from_torch(contrast_t, np.uint16)) and np.array_equal(contrast, fx["contrast"])
+    assert np.array_equal(sri2, sri_t.cpu().numpy()) and np.array_equal(sri2, fx["shading_rate_image"])
+    assert (sri1 == ref.rate_code(4, 4)).all()  # the first frame reads a contrast image of zeros: the coarsest rate everywhere
+
+
+def test_rasterised_frame_with_and_without_vrsaa(hip_ctx):
+    import torch
+    W, H, texel = 200, 112, (16, 16)
+    arrays = mesh.random_soup(43, triangles=400, extent=8.0).arrays()
+    view = scene.SceneView.default(W, H)
+    keep = []
+    geo = mesh.geometry(mesh.to_device(arrays), keep)
+
+    def targets():
+        return {"color": torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda"), "normals": torch.zeros((H, W, 4), dtype=torch.int16, device="cuda"),
+                "data": torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda"), "emission": torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda"),
+                "depth": torch.zeros((H, W), dtype=torch.float32, device="cuda")}
+    plain, with_aa = targets(), targets()
+    assert frame.rasterised_frame(hip_ctx, geo, view.gpu_data, plain) is None
+    opts = {"rates": ref.RATES, "texel_size": texel}
+    contrast, sri = frame.rasterised_frame(hip_ctx, geo, view.gpu_data, with_aa, vrsaa=opts)
+    torch.cuda.synchronize()
+    for k in plain:  # the frame's own planes do not depend on the option
+        assert torch.equal(plain[k], with_aa[k]), k
+    color, depth = with_aa["color"].cpu().numpy(), with_aa["depth"].cpu().numpy()
+    assert (depth > 0).any()
+    want = ref.contrast(color, depth)
+    got = util.from_torch(contrast, np.uint16)
+    assert np.array_equal(got, want) and (got != 0).any()
+    sw, sh = scene.shading_rate_image_extent((W, H), texel)
+    assert tuple(sri.shape) == (sh, sw) == (7, 13)
+    assert (sri.cpu().numpy() == ref.rate_code(4, 4)).all()  # made BEFORE the frame, from the (zero) contrast image of the frame before
+    # the next frame makes its shading-rate image from this frame's contrast
+    contrast2, sri2 = frame.rasterised_frame(hip_ctx, geo, view.gpu_data, with_aa, vrsaa=dict(opts, contrast=contrast, shading_rate_image=sri))
+    torch.cuda.synchronize()
+    assert contrast2 is contrast and sri2 is sri
+    want_sri = ref.shading_rate_image(want, (sw, sh), ref.RATES)
+    assert np.array_equal(sri.cpu().numpy(), want_sri)
+    assert np.array_equal(util.from_torch(contrast, np.uint16), want)
