@@ -203,30 +203,21 @@ int lighting_gi_lpv(sah_ctx* ctx, const sah_lighting_desc* d, const LightingCall
 int lighting_irr32_copy(sah_ctx* ctx, const sah_gi& gi, CacheArgs& cache) {
     if (cache.hot_ok) {
         const size_t need = 4 * (size_t)((uint64_t)gi.probe_irradiance.slice_pitch_bytes * gi.probe_irradiance.depth);
-        bool grew = false;
-        const hipError_t ge = sah_grow(ctx, (void**)&ctx->irr32, &ctx->irr32_bytes, need, &grew);
+        const hipError_t ge = ctx->irr32_copy.reserve(ctx->stream, ctx->cache_epoch, need);
         if (ge == hipErrorOutOfMemory) {  // no room for the widened copy: the general gather needs none
             (void)hipGetLastError();
             cache.hot_ok = 0;
         } else {
             HIP_TRY(ctx, ge);
         }
-        if (grew) {
-            ctx->irr32_generation = 0;
-            ctx->cache_epoch++;
-        }
     }
     if (cache.hot_ok) {
-        const bool reuse = gi.probe_generation != 0 && gi.probe_generation == ctx->irr32_generation &&
-                           same_volume(cache.irradiance, ctx->irr32_source);
-        if (!reuse) {
-            if (gi.probe_generation != 0) ctx->cache_epoch++;  // (with 0 every call rebuilds: the same launches every time)
-            HIP_TRY(ctx, launch_probe_irr_unpack(cache.irradiance, ctx->irr32, ctx->stream));
+        if (!ctx->irr32_copy.reusable_for(gi.probe_generation, cache.irradiance)) {
+            HIP_TRY(ctx, launch_probe_irr_unpack(cache.irradiance, ctx->irr32_copy.data(), ctx->stream));
             ctx->dbg_irr_unpacks++;
-            ctx->irr32_generation = gi.probe_generation;
-            ctx->irr32_source = cache.irradiance;
+            ctx->irr32_copy.rebuilt(ctx->cache_epoch, gi.probe_generation, cache.irradiance);
         }
-        cache.irr32 = ctx->irr32;
+        cache.irr32 = ctx->irr32_copy.data();
     }
     return SAH_OK;
 }
@@ -426,26 +417,23 @@ FastPath detect_fast_path(const sah_ctx* ctx, const sah_lighting_desc* d, const 
 }
 
 // the gather copy of the LPV volumes for a kernel that reads it: rebuilt by k_lpv_pack (in front of the kernel: lighting.hip) unless the caller's
-// change counter says it stands (SAH_GENERATION_TRACKED: the last step of sah_lpv_propagate has written it — api_post.cpp)
+// change counter says it stands (SAH_GENERATION_TRACKED: the last step of sah_lpv_propagate has written it — api_lpv.cpp)
 int prepare_lpv_copy(sah_ctx* ctx, const sah_lighting_desc* d, const LpvArgs& lpv, FastArgs& fast) {
-    const SahLpvPackLayout pk = sah_lpv_pack_layout(lpv.red.width, lpv.red.height, lpv.red.depth);
+    SahLpvCopy& copy = ctx->lpv_copy;
+    const SahLpvPackLayout pk = SahLpvCopy::layout(lpv.red.width, lpv.red.height, lpv.red.depth);
     if (pk.total >= (1ull << 32)) return fail(ctx, SAH_ERR_UNSUPPORTED, "LPV volumes too large for the packed gather copy");
-    HIP_TRY(ctx, sah_lpv_pack_reserve(ctx, pk.total));
-    fast.lpv_packed = ctx->lpv_packed;
+    HIP_TRY(ctx, copy.reserve(ctx->stream, ctx->cache_epoch, pk.total));
+    fast.lpv_packed = copy.data();
     fast.pk_row_pitch = pk.row_pitch;
     fast.pk_slice_pitch = pk.slice_pitch;
     // the copy of the previous call is kept when the caller's change counter says the volumes are the ones it was made from
     const VolumeArg src[3] = {lpv.red, lpv.green, lpv.blue};
     const uint32_t gen = d->gi->lpv_generation;
-    const bool reuse = gen != 0 && gen == ctx->lpv_pack_generation && same_volume(src[0], ctx->lpv_pack_source[0]) &&
-                       same_volume(src[1], ctx->lpv_pack_source[1]) && same_volume(src[2], ctx->lpv_pack_source[2]);
+    const bool reuse = copy.reusable_for(gen, src);
     fast.repack = reuse ? 0u : 1u;
     if (!reuse) {
-        if (gen != 0) ctx->cache_epoch++;  // (with 0 every call rebuilds: the same launches every time)
         ctx->dbg_lpv_packs++;
-        ctx->lpv_pack_generation = gen;
-        for (int i = 0; i < 3; i++) ctx->lpv_pack_source[i] = src[i];
-        sah_lpv_pack_written_by_pack(ctx, lpv.red.width, lpv.red.height, lpv.red.depth);
+        copy.rebuilt_by_pack(ctx->cache_epoch, gen, src, lpv.red.width, lpv.red.height, lpv.red.depth);
     }
     return SAH_OK;
 }
@@ -459,11 +447,9 @@ int lighting_fast_layout(sah_ctx* ctx, const sah_lighting_desc* d, const Lightin
     const uint32_t seg_stride = 64u * (uint32_t)ppt;
     const size_t codes_bytes = ((size_t)nseg * seg_stride + 255) & ~(size_t)255;
     const size_t need = codes_bytes + (size_t)nseg * sizeof(uint16_t) + 256;
-    bool grew = false;
-    HIP_TRY(ctx, sah_grow(ctx, (void**)&ctx->list, &ctx->list_bytes, need, &grew));
-    if (grew) ctx->cache_epoch++;
-    fast.seg_list = (uint8_t*)ctx->list;
-    fast.seg_count = (uint16_t*)((uint8_t*)ctx->list + codes_bytes);
+    HIP_TRY(ctx, ctx->list.grow_in_epoch(ctx->stream, ctx->cache_epoch, need));
+    fast.seg_list = (uint8_t*)ctx->list.ptr;
+    fast.seg_count = (uint16_t*)((uint8_t*)ctx->list.ptr + codes_bytes);
     fast.num_segments = nseg;
     fast.seg_stride = seg_stride;
     // (not for an empty row range — a shard plan may hand a rank no rows: the launcher returns before k_lpv_pack, and a copy recorded as
@@ -504,23 +490,18 @@ int lighting_colx_table(sah_ctx* ctx, const LightingCall& call, const LightingAr
     const bool geom_fast = path.use_fast && (call.sun_mode == SAH_SHADOW_MODE_CSM || call.gi_kind == SAH_GI_LPV);  // the fast kernel calls fast_geometry()
     *table_rebuilt = false;
     if ((path.use_fast && ppt == 4 && lit_px) || (geom_fast && fast.pos_div_shared) || path.tiled_fast_geom) {
-        const float key[7] = {a.res[0], fast.p0, fast.p12, a.res[1], fast.p5, fast.p13, (float)H};
+        const struct {
+            float f[7];
+            uint32_t width;
+        } key = {{a.res[0], fast.p0, fast.p12, a.res[1], fast.p5, fast.p13, (float)H}, W};
         const uint32_t stride = (W + 63u) & ~63u, row_stride = (H + 63u) & ~63u;
-        bool grew = false;
-        HIP_TRY(ctx, sah_grow(ctx, (void**)&ctx->colx_table, &ctx->colx_bytes, ((size_t)2 * stride + 2 * row_stride) * sizeof(float), &grew));
-        if (grew) {
-            ctx->cache_epoch++;
-            ctx->colx_width = 0;
-        }
-        *table_rebuilt = ctx->colx_width != W || memcmp(key, ctx->colx_key, sizeof(key)) != 0;
+        HIP_TRY(ctx, ctx->colx.prepare(ctx->stream, ctx->cache_epoch, ((size_t)2 * stride + 2 * row_stride) * sizeof(float), &key, sizeof(key), true, table_rebuilt));
         fast.state = ctx->state;  // (k_colx_table raises colx_neg_zero there; the kernels read it under pos_div_shared)
         if (*table_rebuilt) {
-            HIP_TRY(ctx, launch_colx_table(a, fast, ctx->colx_table, stride, row_stride, ctx->stream));
-            ctx->cache_epoch++;
-            ctx->colx_width = W;
-            memcpy(ctx->colx_key, key, sizeof(key));
+            HIP_TRY(ctx, launch_colx_table(a, fast, (float*)ctx->colx.buf.ptr, stride, row_stride, ctx->stream));
+            ctx->colx.built(ctx->cache_epoch, &key, sizeof(key));
         }
-        fast.colx_tab = ctx->colx_table;
+        fast.colx_tab = (const float*)ctx->colx.buf.ptr;
         fast.colx_stride = stride;
         fast.rowy_stride = row_stride;
     }
@@ -653,22 +634,13 @@ void sah_destroy(sah_ctx* ctx) {
     if (ctx->probe_slots) (void)hipFree(ctx->probe_slots);
     if (ctx->probe_done) (void)hipEventDestroy(ctx->probe_done);
     if (ctx->state) (void)hipFree(ctx->state);
-    if (ctx->list) (void)hipFree(ctx->list);
-    if (ctx->lpv_packed) (void)hipFree(ctx->lpv_packed);
-    if (ctx->gv_keys) (void)hipFree(ctx->gv_keys);
-    if (ctx->gv_factors) (void)hipFree(ctx->gv_factors);
-    if (ctx->ml_scratch) (void)hipFree(ctx->ml_scratch);
-    if (ctx->irr32) (void)hipFree(ctx->irr32);
-    if (ctx->colx_table) (void)hipFree(ctx->colx_table);
-    if (ctx->tm_thresholds) (void)hipFree(ctx->tm_thresholds);
-    if (ctx->tm_code_table) (void)hipFree(ctx->tm_code_table);
-    if (ctx->tm_axis) (void)hipFree(ctx->tm_axis);
+    std::vector<SahBuffer*> buffers = {&ctx->list, &ctx->lpv_copy.buf, &ctx->gv_keys, &ctx->gv_factors, &ctx->ml_scratch, &ctx->irr32_copy.buf, &ctx->colx.buf, &ctx->tm_axis.buf};
+    for (SahBuffer& b : ctx->raster.buf) buffers.push_back(&b);
+    for (SahBuffer& b : ctx->rt.buf) buffers.push_back(&b);
+    for (SahBuffer* b : buffers) b->release();
+    ctx->tm_codes.release();
     for (SahCacheGuard* g : {&ctx->guard_lighting, &ctx->guard_tonemap, &ctx->guard_raster, &ctx->guard_rt})
         if (g->done) (void)hipEventDestroy(g->done);
-    for (void* p : ctx->raster.ptr)
-        if (p) (void)hipFree(p);
-    for (void* p : ctx->rt.ptr)
-        if (p) (void)hipFree(p);
     if (ctx->raster.half_to_srgb8) (void)hipFree(ctx->raster.half_to_srgb8);
     if (ctx->raster.host_counters) (void)hipHostFree(ctx->raster.host_counters);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);

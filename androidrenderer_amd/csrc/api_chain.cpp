@@ -166,7 +166,7 @@ template <class Body> static int run_half(sah_chain* c, HalfGraph& g, hipStream_
     return SAH_OK;
 }
 
-// the stream the exchanges are enqueued on (allgather_bytes_impl, api_post.cpp): the side stream if there is one
+// the stream the exchanges are enqueued on (allgather_bytes_impl, api_comm.cpp): the side stream if there is one
 static hipStream_t exchange_stream(const sah_ctx* ctx) { return (ctx->comm_stream && ctx->comm_stream != ctx->stream) ? ctx->comm_stream : ctx->stream; }
 
 // A frame in three parts, each on its stream (streams may coincide):

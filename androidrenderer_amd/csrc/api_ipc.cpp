@@ -101,10 +101,10 @@ extern "C" void sah_ipc_destroy(sah_ctx* ctx) {
     for (auto& b : s.buffers) b = {};
 }
 
-// a wait of an earlier gather gave up: every exchange entry point fails from then on (api.cpp: sah_sync, api_post.cpp: sah_comm_wait)
+// a wait of an earlier gather gave up: every exchange entry point fails from then on (api.cpp: sah_sync, api_comm.cpp: sah_comm_wait)
 bool sah_ipc_timed_out(const sah_ctx* ctx) { return ctx->ipc.timed_out && *ctx->ipc.timed_out != 0; }
 
-// the gather itself: called by allgather_bytes_impl (api_post.cpp) when `buffer` lies inside a registered buffer
+// the gather itself: called by allgather_bytes_impl (api_comm.cpp) when `buffer` lies inside a registered buffer
 int sah_ipc_gather(sah_ctx* ctx, uint32_t id, uint8_t* buffer, uint64_t bytes_per_rank, bool reversed, hipStream_t st) {
     using namespace sah;
     auto& s = ctx->ipc;

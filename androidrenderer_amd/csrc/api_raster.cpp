@@ -16,14 +16,12 @@ constexpr uint32_t kMaxExtent = 8192;  // keeps every snapped coordinate inside 
 enum Scratch { S_COUNTERS, S_TRI_BASE, S_RECORDS, S_ATTRS, S_TILES, S_PAIRS, S_SEQ, S_CLIPQ, S_VPL_CELLS, S_VPL_CANDIDATES, S_HEAVY, S_EXTRA, S_TICKETS, S_MERGE, S_MOTION };
 
 int ensure(sah_ctx* ctx, int slot, size_t bytes) {
-    auto& r = ctx->raster;
-    if (r.bytes[slot] >= bytes && r.ptr[slot]) return SAH_OK;
-    if (r.ptr[slot]) (void)hipFree(r.ptr[slot]);
-    r.ptr[slot] = nullptr;
-    r.bytes[slot] = 0;
+    SahBuffer& b = ctx->raster.buf[slot];
+    if (b.bytes >= bytes && b.ptr) return SAH_OK;
+    b.release();
     const size_t want = bytes + bytes / 4 + 256;
-    HIP_TRY(ctx, hipMalloc(&r.ptr[slot], want));
-    r.bytes[slot] = want;
+    HIP_TRY(ctx, hipMalloc(&b.ptr, want));
+    b.bytes = want;
     return SAH_OK;
 }
 
@@ -75,8 +73,8 @@ int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, bool 
     // read once, at the end: if any buffer turned out too small (the kernels never write past a buffer, they only count), it is grown
     // and the pass repeated.  From the second frame of a scene on this is one iteration with no idle gap on the GPU.
     size_t want_records = (size_t)(scene->num_indices / 3) * a.num_views + 1024, want_clipped = want_records / 8 + 1024;
-    size_t want_pairs = std::max<size_t>(r.bytes[S_PAIRS] / sizeof(uint32_t), 2 * want_records + 4 * (size_t)ntiles);
-    size_t want_seq = gbuffer ? std::max<size_t>(r.bytes[S_SEQ] / sizeof(uint32_t), (size_t)(scene->num_indices / 3) * 8 * a.num_views + 64) : 0;
+    size_t want_pairs = std::max<size_t>(r.buf[S_PAIRS].bytes / sizeof(uint32_t), 2 * want_records + 4 * (size_t)ntiles);
+    size_t want_seq = gbuffer ? std::max<size_t>(r.buf[S_SEQ].bytes / sizeof(uint32_t), (size_t)(scene->num_indices / 3) * 8 * a.num_views + 64) : 0;
     for (int attempt = 0; attempt < 4; attempt++) {
         if (int rc = ensure(ctx, S_CLIPQ, want_clipped * sizeof(uint2)); rc != SAH_OK) return rc;
         if (int rc = ensure(ctx, S_RECORDS, want_records * sizeof(sah::RasterRecord)); rc != SAH_OK) return rc;
@@ -91,25 +89,25 @@ int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, bool 
         if (int rc = ensure(ctx, S_PAIRS, want_pairs * sizeof(uint32_t)); rc != SAH_OK) return rc;
         if (gbuffer)
             if (int rc = ensure(ctx, S_SEQ, want_seq * sizeof(uint32_t)); rc != SAH_OK) return rc;
-        a.clip_queue = (uint2*)r.ptr[S_CLIPQ];
-        a.clip_capacity = (uint32_t)std::min<size_t>(r.bytes[S_CLIPQ] / sizeof(uint2), 0xffffffffu);
-        a.counters = (uint32_t*)r.ptr[S_COUNTERS];
-        a.tri_base = (uint32_t*)r.ptr[S_TRI_BASE];
-        a.records = (sah::RasterRecord*)r.ptr[S_RECORDS];
-        a.attrs = (sah::RasterAttr*)r.ptr[S_ATTRS];
-        a.shadow_attrs = shadow_attrs ? (sah::ShadowAttr*)r.ptr[S_ATTRS] : nullptr;
-        a.record_capacity = (uint32_t)std::min<size_t>(r.bytes[S_RECORDS] / sizeof(sah::RasterRecord), 0xffffffffu);
-        if (gbuffer && !a.motion) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.bytes[S_ATTRS] / sizeof(sah::RasterAttr));
-        if (a.motion) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.bytes[S_MOTION] / sizeof(sah::MotionAttr));
-        a.motion_attrs = a.motion ? (sah::MotionAttr*)r.ptr[S_MOTION] : nullptr;
-        if (shadow_attrs) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.bytes[S_ATTRS] / sizeof(sah::ShadowAttr));
-        a.tile_count = (uint32_t*)r.ptr[S_TILES];
+        a.clip_queue = (uint2*)r.buf[S_CLIPQ].ptr;
+        a.clip_capacity = (uint32_t)std::min<size_t>(r.buf[S_CLIPQ].bytes / sizeof(uint2), 0xffffffffu);
+        a.counters = (uint32_t*)r.buf[S_COUNTERS].ptr;
+        a.tri_base = (uint32_t*)r.buf[S_TRI_BASE].ptr;
+        a.records = (sah::RasterRecord*)r.buf[S_RECORDS].ptr;
+        a.attrs = (sah::RasterAttr*)r.buf[S_ATTRS].ptr;
+        a.shadow_attrs = shadow_attrs ? (sah::ShadowAttr*)r.buf[S_ATTRS].ptr : nullptr;
+        a.record_capacity = (uint32_t)std::min<size_t>(r.buf[S_RECORDS].bytes / sizeof(sah::RasterRecord), 0xffffffffu);
+        if (gbuffer && !a.motion) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.buf[S_ATTRS].bytes / sizeof(sah::RasterAttr));
+        if (a.motion) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.buf[S_MOTION].bytes / sizeof(sah::MotionAttr));
+        a.motion_attrs = a.motion ? (sah::MotionAttr*)r.buf[S_MOTION].ptr : nullptr;
+        if (shadow_attrs) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.buf[S_ATTRS].bytes / sizeof(sah::ShadowAttr));
+        a.tile_count = (uint32_t*)r.buf[S_TILES].ptr;
         a.tile_cursor = a.tile_count + ntiles;
         a.tile_offset = a.tile_count + 2 * (size_t)ntiles;
-        a.pairs = (uint32_t*)r.ptr[S_PAIRS];
-        a.pairs_capacity = (uint32_t)std::min<size_t>(r.bytes[S_PAIRS] / sizeof(uint32_t), 0xffffffffu);
-        a.seq_to_record = (uint32_t*)r.ptr[S_SEQ];
-        a.seq_capacity = gbuffer ? r.bytes[S_SEQ] / sizeof(uint32_t) : 0;
+        a.pairs = (uint32_t*)r.buf[S_PAIRS].ptr;
+        a.pairs_capacity = (uint32_t)std::min<size_t>(r.buf[S_PAIRS].bytes / sizeof(uint32_t), 0xffffffffu);
+        a.seq_to_record = (uint32_t*)r.buf[S_SEQ].ptr;
+        a.seq_capacity = gbuffer ? r.buf[S_SEQ].bytes / sizeof(uint32_t) : 0;
         // long bin lists are cut into parts of kRasterSplit entries: at most pairs / kRasterSplit further parts, and a merge buffer per split tile (the
         // number of those is capped: tiles beyond it are processed whole)
         a.extra_capacity = a.pairs_capacity / sah::kRasterSplit + 1u;
@@ -119,12 +117,12 @@ int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, bool 
         if (int rc = ensure(ctx, S_EXTRA, (size_t)a.extra_capacity * sizeof(uint2)); rc != SAH_OK) return rc;
         if (int rc = ensure(ctx, S_TICKETS, (size_t)a.merge_capacity * sizeof(uint32_t)); rc != SAH_OK) return rc;
         if (int rc = ensure(ctx, S_MERGE, (size_t)a.merge_capacity * tile_bytes); rc != SAH_OK) return rc;
-        a.heavy_slot = (uint32_t*)r.ptr[S_HEAVY];
-        a.extra_parts = (uint2*)r.ptr[S_EXTRA];
-        a.tickets = (uint32_t*)r.ptr[S_TICKETS];
-        a.merge_depth = (uint32_t*)r.ptr[S_MERGE];
-        a.merge_keys = (unsigned long long*)r.ptr[S_MERGE];
-        a.merge_seq = (uint32_t*)r.ptr[S_MERGE];
+        a.heavy_slot = (uint32_t*)r.buf[S_HEAVY].ptr;
+        a.extra_parts = (uint2*)r.buf[S_EXTRA].ptr;
+        a.tickets = (uint32_t*)r.buf[S_TICKETS].ptr;
+        a.merge_depth = (uint32_t*)r.buf[S_MERGE].ptr;
+        a.merge_keys = (unsigned long long*)r.buf[S_MERGE].ptr;
+        a.merge_seq = (uint32_t*)r.buf[S_MERGE].ptr;
         HIP_TRY(ctx, sah::launch_raster_setup(a, gbuffer, ctx->stream));
         HIP_TRY(ctx, sah::launch_raster_tiles(a, gbuffer, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(r.host_counters, a.counters, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -332,14 +330,14 @@ int sah_lpv_extract_vpls(sah_ctx* ctx, const sah_rsm_targets* rsm, const sah_lpv
     const size_t invocations = (size_t)(res / 2) * (res / 2);
     if (int rc = ensure(ctx, S_VPL_CANDIDATES, invocations * (sizeof(sah_packed_vpl) + sizeof(uint32_t))); rc != SAH_OK) return rc;
     HIP_TRY(ctx, sah::launch_extract_vpls(varg(rsm->flux), varg(rsm->normals), varg(rsm->depth), cascades[cascade_index], cascade_index, grid_cell_size, ctx->luts,
-                                          vpl_list, vpl_count, ctx->raster.ptr[S_VPL_CANDIDATES], ctx->stream));
+                                          vpl_list, vpl_count, ctx->raster.buf[S_VPL_CANDIDATES].ptr, ctx->stream));
     return SAH_OK;
 }
 
 int sah_lpv_inject_vpls(sah_ctx* ctx, const sah_packed_vpl* vpl_list, const uint32_t* vpl_count, uint32_t capacity, const sah_lpv_cascade_matrices* cascades,
                         uint32_t cascade_index, uint32_t num_cascades, const sah_volume rgb[3]) {
     SAH_RANGE();
-    if (ctx) sah_drop_lpv_copy(ctx);
+    if (ctx) ctx->lpv_copy.drop(ctx->cache_epoch);
     if (!ctx) return SAH_ERR_INVALID_ARGUMENT;
     if (!vpl_list || !vpl_count || !cascades || !rgb || num_cascades == 0 || num_cascades > 4 || cascade_index >= num_cascades)
         return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "lpv_inject_vpls: null argument or cascade index");
@@ -357,7 +355,7 @@ int sah_lpv_inject_vpls(sah_ctx* ctx, const sah_packed_vpl* vpl_list, const uint
     // cell index per light, then (16-byte aligned) the 12 blend sources of up to 4096 sorted lights (vpl.hip: k_inject_sorted)
     if (int rc = ensure(ctx, S_VPL_CELLS, ((size_t)capacity + 8) * sizeof(uint32_t) + (size_t)4096 * 12 * sizeof(float)); rc != SAH_OK) return rc;
     HIP_TRY(ctx, sah::launch_inject_vpls(vpl_list, vpl_count, capacity, cascades[cascade_index], cascade_index, num_cascades, v,
-                                         (uint32_t*)ctx->raster.ptr[S_VPL_CELLS], ctx->stream));
+                                         (uint32_t*)ctx->raster.buf[S_VPL_CELLS].ptr, ctx->stream));
     return SAH_OK;
 }
 

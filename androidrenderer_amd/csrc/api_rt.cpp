@@ -12,14 +12,12 @@ namespace {
 enum Slot { R_TRI_BASE, R_STATE, R_UNSORTED, R_SORTED, R_KEYS, R_NODES, R_NOISE_DIRS };
 
 int ensure(sah_ctx* ctx, int slot, size_t bytes) {
-    auto& r = ctx->rt;
-    if (r.bytes[slot] >= bytes && r.ptr[slot]) return SAH_OK;
-    if (r.ptr[slot]) (void)hipFree(r.ptr[slot]);
-    r.ptr[slot] = nullptr;
-    r.bytes[slot] = 0;
+    SahBuffer& b = ctx->rt.buf[slot];
+    if (b.bytes >= bytes && b.ptr) return SAH_OK;
+    b.release();
     const size_t want = bytes + bytes / 8 + 256;
-    HIP_TRY(ctx, hipMalloc(&r.ptr[slot], want));
-    r.bytes[slot] = want;
+    HIP_TRY(ctx, hipMalloc(&b.ptr, want));
+    b.bytes = want;
     return SAH_OK;
 }
 
@@ -87,8 +85,8 @@ int sah_rt_build(sah_ctx* ctx, const sah_scene_geometry* scene, uint32_t* stats)
     if (scene->num_primitives) {
         if (int rc = ensure(ctx, R_TRI_BASE, (size_t)(scene->num_primitives + 1) * sizeof(uint32_t)); rc != SAH_OK) return rc;
         if (int rc = ensure(ctx, R_STATE, sizeof(RtBuildState)); rc != SAH_OK) return rc;
-        auto* st = (RtBuildState*)rt.ptr[R_STATE];
-        HIP_TRY(ctx, launch_rt_scan(scene->primitives, scene->num_primitives, (uint32_t*)rt.ptr[R_TRI_BASE], st, ctx->stream));
+        auto* st = (RtBuildState*)rt.buf[R_STATE].ptr;
+        HIP_TRY(ctx, launch_rt_scan(scene->primitives, scene->num_primitives, (uint32_t*)rt.buf[R_TRI_BASE].ptr, st, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         const uint32_t total = host.total;
@@ -100,8 +98,8 @@ int sah_rt_build(sah_ctx* ctx, const sah_scene_geometry* scene, uint32_t* stats)
             // (+ kRtFanout spare entries behind the triangles and the nodes: the walk loads groups of four without a predicate)
             if (int rc = ensure(ctx, R_SORTED, (size_t)(total + kRtFanout) * sizeof(RtTriangle)); rc != SAH_OK) return rc;
             if (int rc = ensure(ctx, R_KEYS, (size_t)padded * sizeof(unsigned long long)); rc != SAH_OK) return rc;
-            HIP_TRY(ctx, launch_rt_world(sc, (const uint32_t*)rt.ptr[R_TRI_BASE], total, (RtTriangle*)rt.ptr[R_UNSORTED], st, ctx->stream));
-            HIP_TRY(ctx, launch_rt_sort((const RtTriangle*)rt.ptr[R_UNSORTED], st, (unsigned long long*)rt.ptr[R_KEYS], padded, ctx->stream));
+            HIP_TRY(ctx, launch_rt_world(sc, (const uint32_t*)rt.buf[R_TRI_BASE].ptr, total, (RtTriangle*)rt.buf[R_UNSORTED].ptr, st, ctx->stream));
+            HIP_TRY(ctx, launch_rt_sort((const RtTriangle*)rt.buf[R_UNSORTED].ptr, st, (unsigned long long*)rt.buf[R_KEYS].ptr, padded, ctx->stream));
             HIP_TRY(ctx, hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             bvh.num_tris = host.kept;
@@ -120,10 +118,10 @@ int sah_rt_build(sah_ctx* ctx, const sah_scene_geometry* scene, uint32_t* stats)
             bvh.num_levels = levels;
             if (bvh.num_tris) {
                 if (int rc = ensure(ctx, R_NODES, (size_t)offset * sizeof(RtNodeGroup)); rc != SAH_OK) return rc;
-                bvh.tris = (const RtTriangle*)rt.ptr[R_SORTED];
-                bvh.nodes = (const RtNodeGroup*)rt.ptr[R_NODES];
-                HIP_TRY(ctx, launch_rt_nodes((const RtTriangle*)rt.ptr[R_UNSORTED], (const unsigned long long*)rt.ptr[R_KEYS], (RtTriangle*)rt.ptr[R_SORTED],
-                                             (RtNodeGroup*)rt.ptr[R_NODES], bvh, ctx->stream));
+                bvh.tris = (const RtTriangle*)rt.buf[R_SORTED].ptr;
+                bvh.nodes = (const RtNodeGroup*)rt.buf[R_NODES].ptr;
+                HIP_TRY(ctx, launch_rt_nodes((const RtTriangle*)rt.buf[R_UNSORTED].ptr, (const unsigned long long*)rt.buf[R_KEYS].ptr, (RtTriangle*)rt.buf[R_SORTED].ptr,
+                                             (RtNodeGroup*)rt.buf[R_NODES].ptr, bvh, ctx->stream));
             }
         }
     }
@@ -229,8 +227,8 @@ int sah_sun_shadow_mask(sah_ctx* ctx, const sah_view_data* view, const sah_sun_l
     rt_rows(ctx, H, &a.row_begin, &a.row_end);
     // every sample of every pixel reads one of 16 384 noise directions: normalised once per call instead of once per ray
     if (int rc = ensure(ctx, R_NOISE_DIRS, 128u * 128u * 16u); rc != SAH_OK) return rc;
-    a.noise_dirs = static_cast<const float*>(ctx->rt.ptr[R_NOISE_DIRS]);
-    HIP_TRY(ctx, launch_noise_dirs(a.noise, ctx->rt.scene.luts, static_cast<float*>(ctx->rt.ptr[R_NOISE_DIRS]), ctx->stream));
+    a.noise_dirs = static_cast<const float*>(ctx->rt.buf[R_NOISE_DIRS].ptr);
+    HIP_TRY(ctx, launch_noise_dirs(a.noise, ctx->rt.scene.luts, static_cast<float*>(ctx->rt.buf[R_NOISE_DIRS].ptr), ctx->stream));
     HIP_TRY(ctx, launch_sun_shadow_mask(a, ctx->rt.bvh, ctx->rt.scene, ctx->stream));
     return SAH_OK;
 }

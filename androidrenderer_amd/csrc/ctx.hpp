@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/sah_hip.h"
+#include "ctx_cache.hpp"
 #include "params.hpp"
 #include "rt_args.hpp"
 
@@ -42,31 +43,17 @@ struct sah_ctx {
     int force_ppt = 0;      // tuning/testing hook: 0 = auto
     bool force_general = false;  // testing hook: always run the general kernel
     sah::FrameState* state = nullptr;  // device
-    uint32_t* list = nullptr;          // device: deferred-pixel list
-    size_t list_bytes = 0;
-    uint8_t* irr32 = nullptr;          // device: fp32 copy of the probe irradiance atlas (lighting_tiled.hip: k_probe_irr_unpack)
-    size_t irr32_bytes = 0;
-    uint32_t irr32_generation = 0;     // sah_gi::probe_generation the copy was built for (0: not reusable)
-    sah::VolumeArg irr32_source = {};
-    uint32_t* gv_keys = nullptr;       // device: 4 order-preserving keys per geometry-volume texel, the GV injections' MAX scratch (lpv_gv.hip)
-    size_t gv_keys_bytes = 0;
-    void* gv_factors = nullptr;        // device: the 30 occlusion factors per cell of sah_lpv_propagate_gv (lpv.hip: k_gv_factors)
-    size_t gv_factors_bytes = 0;
-    void* ml_scratch = nullptr;        // device: sah_lpv_inject_emissive's keys, sequence indices, VPL pointers and blend sources (lpv_mesh_lights.hip)
-    size_t ml_scratch_bytes = 0;
-    uint8_t* lpv_packed = nullptr;     // device: per-frame interleaved, zero-bordered copy of the three LPV volumes (lighting.hip)
-    size_t lpv_packed_bytes = 0;
-    uint32_t lpv_pack_generation = 0;  // sah_gi::lpv_generation the gather copy was built for (0: not reusable)
-    sah::VolumeArg lpv_pack_source[3] = {};
-    // the volume extent whose two-texel border of the gather copy holds zeros ({0,0,0} + lpv_pack_all_zero: a new allocation, zero everywhere).
-    // The buffer is grow-only and shared by every extent it is asked for: k_lpv_pack writes the border itself, the emitting propagation step
-    // writes interior texels only and needs the border of ITS extent to be zero already (sah_lpv_pack_borders_for)
-    uint32_t lpv_pack_extent[3] = {0, 0, 0};
-    bool lpv_pack_all_zero = false;
-    float* colx_table = nullptr;       // device: per-column view-space x numerators of the fast kernel, two flavours (lighting.hip: k_colx_table)
-    size_t colx_bytes = 0;
-    uint32_t colx_width = 0;
-    float colx_key[7] = {};            // render_resolution, p0, p12, p5, p13, height the tables were built for
+    // ---- derived device state (ctx_cache.hpp): its operations are the only writers of these members and of cache_epoch
+    SahBuffer list;                    // deferred-pixel list
+    SahBuffer gv_keys;                 // 4 order-preserving keys per geometry-volume texel, the GV injections' MAX scratch (lpv_gv.hip)
+    SahBuffer gv_factors;              // the 30 occlusion factors per cell of sah_lpv_propagate_gv (lpv.hip: k_gv_factors)
+    SahBuffer ml_scratch;              // sah_lpv_inject_emissive's keys, sequence indices, VPL pointers and blend sources (lpv_mesh_lights.hip)
+    SahLpvCopy lpv_copy;               // per-frame interleaved, zero-bordered copy of the three LPV volumes (lighting.hip)
+    SahIrr32Copy irr32_copy;           // fp32 copy of the probe irradiance atlas (lighting_tiled.hip: k_probe_irr_unpack)
+    SahKeyedTable colx;                // per-column view-space x numerators of the fast kernel, two flavours (lighting.hip: k_colx_table); key:
+                                       // render_resolution, p0, p12, p5, p13, height, width the tables were built for
+    SahKeyedTable tm_axis;             // axis set-ups of the tolerance-mode composite (tonemap_tol.hip); key: output extent, mip extents, number of mips
+    SahTonemapCodeTables tm_codes;
     // Raised whenever something changes that a launch of sah_lighting / sah_tonemap_ex DEPENDS on beyond its arguments: a context buffer is
     // reallocated, a table is rebuilt for other extents, a gather copy that calls were re-using is dropped or has to be rebuilt.  While it
     // stands, the same call enqueues the same kernels with the same kernel arguments — what sah_chain's captured graphs rely on (api_chain.cpp).
@@ -76,22 +63,13 @@ struct sah_ctx {
     const uint16_t* last_seg_count = nullptr;  // debug hook (sah_debug_deferred_pixels)
     uint32_t last_num_segments = 0;
     uint32_t last_dispatch[12] = {};   // debug hook (sah_debug_lighting_dispatch): what the last sah_lighting call decided, host side
-    float* tm_thresholds = nullptr;    // device: 256 tonemap code thresholds + the first-level bucket table (api_post.cpp)
-    float* tm_code_table = nullptr;    // device: the same search as one float4 per bucket (TonemapArgs::code_table)
-    uint32_t tm_bucket_base = 0, tm_bucket_count = 0;
-    float tm_thr_lo = 0.f, tm_thr_hi = 0.f;
-    void* tm_axis = nullptr;           // device: axis set-ups of the tolerance-mode composite (tonemap_tol.hip), rebuilt when the extents change
-    size_t tm_axis_bytes = 0;
-    uint32_t tm_axis_key[2 + 2 * 8 + 1] = {};  // output extent, mip extents, number of mips
     struct RasterScratch {             // device buffers of the scene rasteriser, grown on demand (api_raster.cpp)
-        void* ptr[16] = {};
-        size_t bytes[16] = {};
+        SahBuffer buf[16];
         uint8_t* half_to_srgb8 = nullptr;
         uint32_t* host_counters = nullptr;  // pinned, 16 words
     } raster;
     struct RtState {                   // acceleration structure of sah_rt_build (api_rt.cpp); buffers grow on demand
-        void* ptr[7] = {};             // tri_base, build state, unsorted triangles, sorted triangles, keys, nodes, noise directions
-        size_t bytes[7] = {};
+        SahBuffer buf[7];              // tri_base, build state, unsorted triangles, sorted triangles, keys, nodes, noise directions
         sah::RtBvh bvh = {};
         sah::RtScene scene = {};
         bool built = false;
@@ -187,81 +165,6 @@ inline hipError_t sah_guard_leave(sah_ctx* ctx, SahCacheGuard& g, bool drained) 
         if (e_ != hipSuccess) return fail(ctx, SAH_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// A device buffer of the context that only grows.  Nothing happens while it holds `need` bytes; else a smaller one is freed — behind a
-// synchronisation of ctx->stream, whose work may still use it — and a new one allocated.  `grew` (optional): a new buffer was made; what the
-// caller keeps about the old one's contents (a key, a generation, the cache epoch) is the caller's to reset.  After a failure there is no buffer.
-inline hipError_t sah_grow(sah_ctx* ctx, void** ptr, size_t* bytes, size_t need, bool* grew = nullptr) {
-    if (grew) *grew = false;
-    if (*bytes >= need) return hipSuccess;
-    if (*ptr) {
-        const hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return e;
-        (void)hipFree(*ptr);
-    }
-    *ptr = nullptr;
-    *bytes = 0;
-    const hipError_t e = hipMalloc(ptr, need);
-    if (e != hipSuccess) return e;
-    *bytes = need;
-    if (grew) *grew = true;
-    return hipSuccess;
-}
-
-inline void sah_drop_lpv_copy(sah_ctx* ctx) {  // the volumes change: the Lighting pass's gather copy of them is stale
-    if (ctx->lpv_pack_generation != 0) ctx->cache_epoch++;
-    ctx->lpv_pack_generation = 0;
-}
-inline void sah_drop_irr32_copy(sah_ctx* ctx) {  // the same for the fp32 copy of an irradiance atlas
-    if (ctx->irr32_generation != 0) ctx->cache_epoch++;
-    ctx->irr32_generation = 0;
-}
-
-// The gather copy of the LPV volumes (params.hpp: FastArgs::lpv_packed): its geometry for a volume extent, and the context's grow-only buffer.
-// A NEW buffer is zeroed on ctx->stream: k_lpv_pack writes the border texels itself, the emitting propagation step (lpv.hip) relies on them
-// being zero already.
-struct SahLpvPackLayout {
-    uint32_t row_pitch, slice_pitch;
-    uint64_t total;
-};
-inline SahLpvPackLayout sah_lpv_pack_layout(uint32_t w, uint32_t h, uint32_t d) {
-    const uint64_t row = (uint64_t)(w + 2 * sah::kLpvPackBorder) * sah::kLpvPackTexel;
-    const uint64_t slice = row * (h + 2 * sah::kLpvPackBorder);
-    return {(uint32_t)row, (uint32_t)slice, slice * (d + 2 * sah::kLpvPackBorder) + 64};  // + slack: the last x-pair is read as 48 bytes
-}
-inline hipError_t sah_lpv_pack_reserve(sah_ctx* ctx, uint64_t total) {
-    if (ctx->lpv_packed_bytes >= total) return hipSuccess;
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return e;
-    if (ctx->lpv_packed) (void)hipFree(ctx->lpv_packed);
-    ctx->lpv_packed = nullptr;
-    ctx->lpv_packed_bytes = 0;
-    ctx->lpv_pack_generation = 0;
-    ctx->cache_epoch++;
-    e = hipMalloc((void**)&ctx->lpv_packed, total);
-    if (e != hipSuccess) return e;
-    ctx->lpv_packed_bytes = total;
-    ctx->lpv_pack_extent[0] = ctx->lpv_pack_extent[1] = ctx->lpv_pack_extent[2] = 0;
-    ctx->lpv_pack_all_zero = true;
-    return hipMemsetAsync(ctx->lpv_packed, 0, total, ctx->stream);
-}
-// k_lpv_pack has been enqueued for a w x h x d volume: interior and border of that layout are its own
-inline void sah_lpv_pack_written_by_pack(sah_ctx* ctx, uint32_t w, uint32_t h, uint32_t d) {
-    ctx->lpv_pack_extent[0] = w, ctx->lpv_pack_extent[1] = h, ctx->lpv_pack_extent[2] = d;
-    ctx->lpv_pack_all_zero = false;
-}
-// The emitting propagation step is about to store the interior texels of a w x h x d layout: the border texels of THAT layout must hold zeros.
-// They do in a new allocation and after any writer of the same extent; a buffer last laid out for another extent (a context that lit a
-// 128 x 32 x 32 volume and now propagates three cascades: the grow-only buffer is not reallocated) holds old interior texels where the new
-// border lies — cleared here, on ctx->stream, ahead of the steps.
-inline hipError_t sah_lpv_pack_borders_for(sah_ctx* ctx, uint32_t w, uint32_t h, uint32_t d, uint64_t total) {
-    const bool same = ctx->lpv_pack_extent[0] == w && ctx->lpv_pack_extent[1] == h && ctx->lpv_pack_extent[2] == d;
-    hipError_t e = hipSuccess;
-    if (!same && !ctx->lpv_pack_all_zero) e = hipMemsetAsync(ctx->lpv_packed, 0, total, ctx->stream);
-    ctx->lpv_pack_extent[0] = w, ctx->lpv_pack_extent[1] = h, ctx->lpv_pack_extent[2] = d;
-    ctx->lpv_pack_all_zero = false;
-    return e;
-}
-
 // Uniform sub-expressions of sky_unified.slang:80-135 for a sun direction as get_sky_color() receives it (`sun_dir`): the Lighting pass's sky
 // fill passes -normalize(direction) (:199), the GI miss shader the raw direction (:229).  Evaluated here in fp32, operator by operator (this
 // header is compiled with -ffp-contract=off), exactly as the per-pixel code would.  Returns false when the LUTs are not RGBA16F.
@@ -318,10 +221,9 @@ inline bool plane_ok(const sah_plane* p, uint32_t fmt_a, uint32_t fmt_b, uint32_
     return (uint64_t)p->row_pitch_bytes >= (uint64_t)w * format_bpp(p->format);
 }
 
-// (field by field: VolumeArg has four bytes of padding behind its last member, which aggregate initialisation leaves unspecified — two
-// descriptors of the same volume built on different paths need not be memcmp-equal)
-inline bool same_volume(const sah::VolumeArg& a, const sah::VolumeArg& b) {
-    return a.ptr == b.ptr && a.width == b.width && a.height == b.height && a.depth == b.depth && a.row_pitch == b.row_pitch && a.slice_pitch == b.slice_pitch;
+inline bool rgba16f_ok(const sah_plane* p) {
+    return p && p->ptr && p->format == SAH_FORMAT_R16G16B16A16_SFLOAT && p->width && p->height &&
+           (uint64_t)p->row_pitch_bytes >= (uint64_t)p->width * 8 && ((uintptr_t)p->ptr % 8) == 0 && (p->row_pitch_bytes % 8) == 0;
 }
 
 inline sah::PlaneArg parg(const sah_plane* p) { return sah::PlaneArg{p ? (const uint8_t*)p->ptr : nullptr, p ? p->row_pitch_bytes : 0}; }

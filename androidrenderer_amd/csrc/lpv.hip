@@ -369,7 +369,7 @@ SAH_DEV uint32_t nonfinite_halves(uint32_t w) { return (w & 0x7c007c00u) + 0x040
 
 // One colour volume per thread (c0: blockIdx.y).
 // The neighbour of direction n is the cell at c - kDir[n]; which of them exist is one compare each, because c is in [0, 32)^3 and the host has
-// checked the extents ((32 * cascades) x 32 x 32 at least, api_post.cpp):  c - 1 is outside the volume only below 0 — for x that is x == 0 of
+// checked the extents ((32 * cascades) x 32 x 32 at least, api_lpv.cpp):  c - 1 is outside the volume only below 0 — for x that is x == 0 of
 // cascade 0: a cell of column 0 of a later cascade reads the last column of the cascade before it, the shader's own quirk —, and c + 1 is the
 // shader's skipped neighbour exactly when c == 31 (the asymmetric [-1, 31] test: column 31 never reads the next cascade).  Offsets are 32-bit
 // (host-checked) from the centre cell's: one add per neighbour, no 64-bit multiply-adds; directions are compile-time constants — as

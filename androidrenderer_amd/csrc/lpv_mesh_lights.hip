@@ -577,7 +577,7 @@ int sah_lpv_inject_emissive(sah_ctx* ctx, const sah_scene_geometry* scene, const
                     SAH_LPV_EMISSIVE_MAX_ENTRIES);
     if (T == 0) return SAH_OK;
     if (!scene->primitives || !scene->materials) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "lpv_inject_emissive: the scene needs primitives and materials");
-    sah_drop_lpv_copy(ctx);
+    ctx->lpv_copy.drop(ctx->cache_epoch);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     sah::MlArgs m{};
     m.primitives = scene->primitives;
@@ -597,8 +597,8 @@ int sah_lpv_inject_emissive(sah_ctx* ctx, const sah_scene_geometry* scene, const
     for (int c = 0; c < 3; c++) m.rgb[c] = varg(a_rgb[c]);
     // scratch grows only; freeing a smaller one waits for the work that may still use it
     const size_t need = sah::ml_scratch_bytes((uint32_t)std::max<uint64_t>(T, 4096));
-    HIP_TRY(ctx, sah_grow(ctx, &ctx->ml_scratch, &ctx->ml_scratch_bytes, need));
-    HIP_TRY(ctx, sah::launch_inject_emissive(m, recs, ctx->ml_scratch, ctx->stream));
+    HIP_TRY(ctx, ctx->ml_scratch.grow(ctx->stream, need));
+    HIP_TRY(ctx, sah::launch_inject_emissive(m, recs, ctx->ml_scratch.ptr, ctx->stream));
     return SAH_OK;
 }
 

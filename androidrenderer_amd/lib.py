@@ -97,6 +97,7 @@ def load():
     lib.sah_sync.argtypes = [C.c_void_p]
     lib.sah_debug_deferred_pixels.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.sah_debug_copy_rebuilds.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.sah_debug_cache_epoch.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.sah_debug_lighting_dispatch.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     lib.sah_lighting.argtypes = [C.c_void_p, C.POINTER(_abi.LightingDesc)]
     lib.sah_copy_scene.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane)]
@@ -214,6 +215,13 @@ class Context:
         out = (C.c_uint32 * 2)()
         self._check(self.lib.sah_debug_copy_rebuilds(self.handle, out))
         return int(out[0]), int(out[1])
+
+    def cache_epoch(self):
+        """Test hook: the context's cache epoch — it moves when something changes that a launch depends on beyond its arguments (a context
+        buffer reallocated, a table rebuilt, a gather copy dropped or rebuilt); captured graphs are replayed only while it stands."""
+        e = C.c_uint64()
+        self._check(self.lib.sah_debug_cache_epoch(self.handle, C.byref(e)))
+        return int(e.value)
 
     DISPATCH_FIELDS = ("family", "ppt", "pos_div_nr", "ncasc_pow2", "row_magic", "sky_ratio", "sky_workgroups", "tiled_fast_geom", "tiled_fast_lpv",
                        "repack", "table_rebuilt", "pos_div_shared")

@@ -306,17 +306,12 @@ def test_chain_on_a_side_stream_without_host_sync_and_under_capture(fixture):
 
 
 def test_no_side_effects_on_the_context(hip_ctx, fixture):
-    import ctypes as C
     import torch
     f = util.LightingFrame(64, 36, seed=5, sun_mode=_abi.SHADOW_MODE_CSM, gi=_abi.GI_LPV, flavour="atrium")
     f.run_hip(hip_ctx)
-    L = hip_ctx.lib
-    L.sah_debug_cache_epoch.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
 
     def state():
-        e = C.c_uint64()
-        assert L.sah_debug_cache_epoch(hip_ctx.handle, C.byref(e)) == 0
-        return int(e.value), hip_ctx.lighting_dispatch(), hip_ctx.copy_rebuilds()
+        return hip_ctx.cache_epoch(), hip_ctx.lighting_dispatch(), hip_ctx.copy_rebuilds()
     before = state()
     c, d, o, r = _chain_images(fixture)
     hip_ctx.vrsaa_measure_aliasing(c.plane, d.plane, o.plane)
