@@ -600,6 +600,10 @@ int sah_create(sah_ctx** out, int device, int rank, int world, const void* comm_
         sah_destroy(ctx);
         return SAH_ERR_HIP;
     }
+    if (ctx->mip_chain_counter.create() != hipSuccess) {
+        sah_destroy(ctx);
+        return SAH_ERR_HIP;
+    }
     // (kept: read once per context, selects code that ships — every bin list whole — and is how tests/test_raster.py reaches it)
     const char* mc = getenv("SAH_RASTER_MERGE_CAPACITY");
     if (mc) ctx->raster_merge_cap = (uint32_t)atoi(mc);
@@ -639,7 +643,8 @@ void sah_destroy(sah_ctx* ctx) {
     for (SahBuffer& b : ctx->rt.buf) buffers.push_back(&b);
     for (SahBuffer* b : buffers) b->release();
     ctx->tm_codes.release();
-    for (SahCacheGuard* g : {&ctx->guard_lighting, &ctx->guard_tonemap, &ctx->guard_raster, &ctx->guard_rt})
+    ctx->mip_chain_counter.release();
+    for (SahCacheGuard* g : {&ctx->guard_lighting, &ctx->guard_tonemap, &ctx->guard_raster, &ctx->guard_rt, &ctx->guard_mip_chain})
         if (g->done) (void)hipEventDestroy(g->done);
     if (ctx->raster.half_to_srgb8) (void)hipFree(ctx->raster.half_to_srgb8);
     if (ctx->raster.host_counters) (void)hipHostFree(ctx->raster.host_counters);
@@ -657,7 +662,7 @@ int sah_set_stream(sah_ctx* ctx, void* hip_stream) {
     if ((hipStream_t)hip_stream == ctx->stream && !ctx->own_stream) return SAH_OK;
     const bool drained = ctx->own_stream && ctx->stream;
     if (drained) (void)hipStreamSynchronize(ctx->stream);
-    SahCacheGuard* guards[] = {&ctx->guard_lighting, &ctx->guard_tonemap, &ctx->guard_raster, &ctx->guard_rt};
+    SahCacheGuard* guards[] = {&ctx->guard_lighting, &ctx->guard_tonemap, &ctx->guard_raster, &ctx->guard_rt, &ctx->guard_mip_chain};
     for (SahCacheGuard* g : guards) HIP_TRY(ctx, sah_guard_leave(ctx, *g, drained));
     if (drained) (void)hipStreamDestroy(ctx->stream);
     ctx->stream = (hipStream_t)hip_stream;

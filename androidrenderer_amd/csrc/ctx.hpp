@@ -54,6 +54,7 @@ struct sah_ctx {
                                        // render_resolution, p0, p12, p5, p13, height, width the tables were built for
     SahKeyedTable tm_axis;             // axis set-ups of the tolerance-mode composite (tonemap_tol.hip); key: output extent, mip extents, number of mips
     SahTonemapCodeTables tm_codes;
+    SahTicketCounter mip_chain_counter;  // sah_mip_chain_generate (mip_chain.hip)
     // Raised whenever something changes that a launch of sah_lighting / sah_tonemap_ex DEPENDS on beyond its arguments: a context buffer is
     // reallocated, a table is rebuilt for other extents, a gather copy that calls were re-using is dropped or has to be rebuilt.  While it
     // stands, the same call enqueues the same kernels with the same kernel arguments — what sah_chain's captured graphs rely on (api_chain.cpp).
@@ -96,7 +97,7 @@ struct sah_ctx {
             uint32_t seq = 0;          // gathers made through this index (mailbox counters only ever grow, whoever uses the index)
         } buffers[SAH_IPC_MAX_BUFFERS];
     } ipc;
-    SahCacheGuard guard_lighting, guard_tonemap, guard_raster, guard_rt;  // see SahCacheGuard
+    SahCacheGuard guard_lighting, guard_tonemap, guard_raster, guard_rt, guard_mip_chain;  // see SahCacheGuard
     uint32_t raster_merge_cap = 2048;  // tiles whose bin list may be split (testing hook SAH_RASTER_MERGE_CAPACITY: 0 = every list whole)
     std::string last_error;
 };

@@ -1,8 +1,8 @@
 // The derived device state of a context — what a launch depends on beyond its arguments — and the ONE place where the cache epoch moves.
 //
-// Three kinds: the two gather copies of the Lighting pass (SahLpvCopy, SahIrr32Copy), the keyed tables (SahKeyedTable: the fast kernel's column
-// table, the tolerance composite's axis tables; SahTonemapCodeTables) and grow-only scratch (SahBuffer).  Plain structs of host values and device
-// pointers, members of sah_ctx (ctx.hpp).  An operation that can change what the NEXT identical call would enqueue takes the context's
+// Four kinds: the two gather copies of the Lighting pass (SahLpvCopy, SahIrr32Copy), the keyed tables (SahKeyedTable: the fast kernel's column
+// table, the tolerance composite's axis tables; SahTonemapCodeTables), grow-only scratch (SahBuffer) and the mip-chain generator's ticket counter
+// (SahTicketCounter).  Plain structs of host values and device pointers, members of sah_ctx (ctx.hpp).  An operation that can change what the NEXT identical call would enqueue takes the context's
 // `cache_epoch` and raises it; nothing outside this header writes the epoch, a generation, or the extent / all-zero record of the LPV copy.
 // While the epoch stands, the same call enqueues the same kernels with the same kernel arguments — what sah_chain's captured graphs rely on
 // (api_chain.cpp reads it, never writes it).
@@ -208,6 +208,22 @@ struct SahKeyedTable {
         cache_epoch++;
         memcpy(key, k, k_bytes);
         valid = true;
+    }
+};
+
+// The ticket counter of the mip-chain generator (mip_chain.hip): one word of device memory, made with the context so that the call
+// allocates nothing.  Zero between calls: sah_mip_chain_generate zeroes it on the stream ahead of every launch and the kernel's last
+// workgroup sets it back.  No launch of any other entry depends on it: it never moves the epoch.
+struct SahTicketCounter {
+    uint32_t* word = nullptr;
+
+    hipError_t create() {
+        const hipError_t e = hipMalloc((void**)&word, sizeof(uint32_t));
+        return e != hipSuccess ? e : hipMemset(word, 0, sizeof(uint32_t));
+    }
+    void release() {
+        if (word) (void)hipFree(word);
+        word = nullptr;
     }
 };
 

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/sah_hip.h"
+#include "../../include/sah_mip_chain.h"
 #include "../../include/sah_vrsaa.h"
 #include "params.hpp"
 #include "post_args.hpp"
@@ -45,6 +46,19 @@ hipError_t launch_vrsaa_contrast(const PlaneArg& color, const PlaneArg& depth, c
                                  uint32_t row_end, const float* luts, hipStream_t st);
 hipError_t launch_vrsaa_shading_rate(const PlaneArg& contrast, uint32_t cw, uint32_t ch, const PlaneArg& out, uint32_t sw, uint32_t sh, uint32_t d,
                                      const sah_shading_rate_params& params, hipStream_t st);
+
+// --- mip_chain.hip
+struct MipChainArgs {
+    PlaneArg src;
+    uint32_t src_w, src_h;
+    float inv_w, inv_h;                                   // fl(1 / extent) of the source
+    PlaneArg slot[SAH_MIP_CHAIN_MAX_LEVELS];              // imgDst[12]: level i, or level 1 from num_dst_levels on
+    uint32_t slot_w[SAH_MIP_CHAIN_MAX_LEVELS], slot_h[SAH_MIP_CHAIN_MAX_LEVELS];  // what bounds a store to slot i: the extent level i has or would have
+    uint32_t mips, num_workgroups;
+    uint32_t* counter;
+};
+enum MipChainKind : int { kMipChainR32Min = 0, kMipChainR16 = 1, kMipChainRGBA16 = 2, kMipChainR11G11B10 = 3 };
+hipError_t launch_mip_chain(const MipChainArgs& a, MipChainKind kind, hipStream_t st);
 
 // --- lpv.hip, lpv_gv.hip, vpl.hip
 hipError_t launch_lpv_clear(const VolumeArg* vols, int n, uint32_t num_cascades, hipStream_t st);

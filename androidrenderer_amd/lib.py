@@ -36,6 +36,11 @@ MV_EXPORTS = ["sah_motion_vectors_render"]
 # the VRSAA passes: exported, declared in include/sah_vrsaa.h (not sah_hip.h)
 VRSAA_EXPORTS = ["sah_vrsaa_measure_aliasing", "sah_vrsaa_shading_rate_image"]
 
+# the mip-chain generator: exported, declared in include/sah_mip_chain.h (not sah_hip.h)
+MIP_CHAIN_EXPORTS = ["sah_mip_chain_generate"]
+MIP_CHAIN_MAX_LEVELS = 12     # SAH_MIP_CHAIN_MAX_LEVELS
+MIP_CHAIN_MAX_SOURCE = 4096   # SAH_MIP_CHAIN_MAX_SOURCE
+
 # the LPV mesh lights' entries: exported, declared in include/sah_lpv_mesh_lights.h (not sah_hip.h)
 ML_EXPORTS = ["sah_mesh_point_cloud", "sah_lpv_emissive_vpls", "sah_lpv_inject_emissive"]
 POINT_CLOUD_ON_SURFACE = 1    # SAH_POINT_CLOUD_ON_SURFACE
@@ -172,6 +177,7 @@ def load():
     lib.sah_lpv_propagate_gv.argtypes = [C.c_void_p, C.POINTER(_abi.Volume), C.POINTER(_abi.Volume), C.POINTER(_abi.Volume), C.c_uint32, C.c_uint32]
     lib.sah_vrsaa_measure_aliasing.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
     lib.sah_vrsaa_shading_rate_image.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.POINTER(_abi.ShadingRateParams)]
+    lib.sah_mip_chain_generate.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32]
     _lib = lib
     return lib
 
@@ -348,6 +354,12 @@ class Context:
         """sah_vrsaa_shading_rate_image: contrast R16G16_SFLOAT, sri R8_UINT (_abi.Plane of device memory), params an _abi.ShadingRateParams
         (scene.shading_rate_params)."""
         self._check(self.lib.sah_vrsaa_shading_rate_image(self.handle, C.byref(contrast), C.byref(sri), C.byref(params)))
+
+    def mip_chain_generate(self, src, levels):
+        """sah_mip_chain_generate (include/sah_mip_chain.h): src an _abi.Plane of device memory, levels a sequence of _abi.Plane, the levels
+        of one image from level 0 on."""
+        arr = (_abi.Plane * len(levels))(*levels)
+        self._check(self.lib.sah_mip_chain_generate(self.handle, C.byref(src), arr, len(levels)))
 
     def rsm_render(self, scene, sun, cascades, num_cascades, rsm, stats_ptr=None):
         """cascades: (LpvCascadeMatrices * n) host array; rsm: _abi.RsmTargets of device volumes."""

@@ -29,6 +29,7 @@
 #include "sah_hip.h"
 #include "sah_lpv_gv.h"
 #include "sah_lpv_mesh_lights.h"
+#include "sah_mip_chain.h"
 #include "sah_motion_vectors.h"
 #include "sah_vrsaa.h"
 
@@ -1343,6 +1344,49 @@ private:
     std::vector<std::array<uint32_t, 2>> shading_rates;
     TextureHandle contrast_image = nullptr, shading_rate_image = nullptr;
     sah_shading_rate_params params = {};
+};
+
+// RenderCore/render/mip_chain_generator.hpp / .cpp:12-177: AMD's single-pass downsampler behind one call.  The reference's destination is
+// one image with mip views; here the levels are textures of the allocator, level 0 first (as TextureDescriptorPool::create_texture_srv
+// takes them).  The counter buffer and its "Clear counter" pass live in the library (include/sah_mip_chain.h).
+class MipChainGenerator {
+public:
+    void fill_mip_chain(RenderGraph& graph, TextureHandle src_texture, const std::vector<TextureHandle>& dest_levels) const {
+        graph.add_pass(hip_pass("Downsample", [src_texture, dest_levels](sah_ctx* ctx) {
+                            if (!src_texture || dest_levels.empty() || dest_levels.size() > SAH_MIP_CHAIN_MAX_LEVELS) return (int)SAH_ERR_INVALID_ARGUMENT;
+                            sah_plane levels[SAH_MIP_CHAIN_MAX_LEVELS];
+                            for (size_t i = 0; i < dest_levels.size(); i++) levels[i] = dest_levels[i]->plane();
+                            const sah_plane s = src_texture->plane();
+                            return sah_mip_chain_generate(ctx, &s, levels, (uint32_t)dest_levels.size());
+                        }));
+    }
+};
+
+// RenderCore/render/phase/depth_culling_phase.hpp / .cpp — the Hi-Z pyramid alone: set_render_resolution (:96-107) and the "Build Hi-Z
+// pyramid" step of render() (:162-164).  The depth pre-pass is GbufferPhase's here, and the culling that follows the pyramid in the
+// reference marks every primitive visible (hi_z_culling.comp:147-162): neither it nor the draw lists made from it are part of this library.
+class DepthCullingPhase {
+public:
+    explicit DepthCullingPhase(ResourceAllocator& allocator_in) : allocator(allocator_in) {}
+    void set_render_resolution(const uint32_t resolution[2]) {
+        // :96-98 — hi_z_resolution = resolution / 2u; num_mips = round(log2(float(max(x, y))))
+        const uint32_t hi_z_resolution[2] = {resolution[0] / 2, resolution[1] / 2};
+        const uint32_t major_dimension = std::max(hi_z_resolution[0], hi_z_resolution[1]);
+        if (major_dimension == 0) throw std::runtime_error("DepthCullingPhase: a render resolution below 2 has no Hi-Z buffer");
+        const uint32_t num_mips = (uint32_t)std::round(std::log2((float)major_dimension));
+        if (num_mips > SAH_MIP_CHAIN_MAX_LEVELS) throw std::runtime_error("DepthCullingPhase: more than 12 Hi-Z levels");
+        hi_z_levels.clear();
+        for (uint32_t i = 0; i < num_mips; i++)  // (a 1 x 1 buffer has round(log2(1)) = 0 levels in the reference too)
+            hi_z_levels.push_back(allocator.create_texture("Hi Z Buffer mip " + std::to_string(i), SAH_FORMAT_R32_SFLOAT, std::max(1u, hi_z_resolution[0] >> i),
+                                                           std::max(1u, hi_z_resolution[1] >> i)));
+    }
+    void build_hi_z(RenderGraph& graph, TextureHandle depth_buffer) const { downsampler.fill_mip_chain(graph, depth_buffer, hi_z_levels); }
+    const std::vector<TextureHandle>& get_hi_z_levels() const { return hi_z_levels; }
+
+private:
+    ResourceAllocator& allocator;
+    MipChainGenerator downsampler;
+    std::vector<TextureHandle> hi_z_levels;
 };
 
 class LightingPhase {
