@@ -137,6 +137,44 @@ int sah_rt_build(sah_ctx* ctx, const sah_scene_geometry* scene, uint32_t* stats)
     return SAH_OK;
 }
 
+// Debug / test hook (tests/test_rt_structure_gpu.py): the structure the last sah_rt_build left behind, copied to host memory — the scalars
+// of RtBvh, the triangles in structure order, the node groups of every level.  Host-side copies behind a wait for the context's stream: no
+// launch, no guard, nothing of the context changes.
+int sah_debug_rt_structure(sah_ctx* ctx, uint32_t* header, void* triangles, uint64_t triangles_bytes, void* nodes, uint64_t nodes_bytes) {
+    using namespace sah;
+    static_assert(SAH_RT_STRUCTURE_HEADER_WORDS == 4 + 2 * kRtMaxLevels, "header: four scalars and the two level tables");
+    static_assert(SAH_RT_TRIANGLE_BYTES == sizeof(RtTriangle) && SAH_RT_NODE_GROUP_BYTES == sizeof(RtNodeGroup), "record sizes of sah_hip.h");
+    if (!ctx) return SAH_ERR_INVALID_ARGUMENT;
+    if (!ctx->rt.built) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sah_rt_build has not been called on this context");
+    const RtBvh& bvh = ctx->rt.bvh;
+    uint32_t groups = 0;
+    if (bvh.num_levels) groups = bvh.level_offset[bvh.num_levels - 1] + (bvh.level_count[bvh.num_levels - 1] + kRtFanout - 1) / kRtFanout;
+    const uint64_t tri_bytes = (uint64_t)bvh.num_tris * sizeof(RtTriangle), node_bytes = (uint64_t)groups * sizeof(RtNodeGroup);
+    if (triangles && triangles_bytes < tri_bytes)
+        return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "triangles: %llu bytes given, the structure's %u triangles take %llu", (unsigned long long)triangles_bytes,
+                    bvh.num_tris, (unsigned long long)tri_bytes);
+    if (nodes && nodes_bytes < node_bytes)
+        return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "nodes: %llu bytes given, the structure's %u node groups take %llu", (unsigned long long)nodes_bytes, groups,
+                    (unsigned long long)node_bytes);
+    if ((triangles && tri_bytes) || (nodes && node_bytes)) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (triangles && tri_bytes) HIP_TRY(ctx, hipMemcpy(triangles, bvh.tris, tri_bytes, hipMemcpyDeviceToHost));
+        if (nodes && node_bytes) HIP_TRY(ctx, hipMemcpy(nodes, bvh.nodes, node_bytes, hipMemcpyDeviceToHost));
+    }
+    if (header) {
+        header[0] = bvh.num_tris;
+        header[1] = bvh.num_levels;
+        header[2] = groups;
+        memcpy(&header[3], &bvh.pad, 4);
+        for (uint32_t l = 0; l < kRtMaxLevels; l++) {
+            header[4 + l] = bvh.level_offset[l];
+            header[4 + kRtMaxLevels + l] = bvh.level_count[l];
+        }
+    }
+    return SAH_OK;
+}
+
 static int check_cutout_inputs(sah_ctx* ctx) {
     // the any-hit stage reads vertex colours, texcoords and materials: a structure built without them cannot shade CUTOUT candidates
     const sah::RtScene& sc = ctx->rt.scene;

@@ -5,6 +5,8 @@ entry point raises SahError on a non-zero status."""
 import ctypes as C
 import os
 
+import numpy as np
+
 from . import _abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -23,7 +25,7 @@ _lib = None
 EXPORTS = ["sah_abi_version", "sah_status_string", "sah_last_error", "sah_create", "sah_destroy", "sah_comm_unique_id", "sah_set_stream",
            "sah_sync", "sah_lighting", "sah_copy_scene", "sah_copy_scene_rows", "sah_copy_scene_bloom_mip0_rows", "sah_bloom", "sah_bloom_mip0_rows", "sah_bloom_from_mip0", "sah_bloom_mip_rows", "sah_bloom_from_mip", "sah_bloom_source_rows", "sah_tonemap", "sah_tonemap_ex", "sah_lpv_clear", "sah_lpv_propagate", "sah_probe_notify_updated",
            "sah_sky_update_luts", "sah_ao_clear", "sah_probe_copy", "sah_probe_update", "sah_shadow_render", "sah_gbuffer_render", "sah_rsm_render", "sah_lpv_extract_vpls",
-           "sah_lpv_inject_vpls", "sah_rt_build", "sah_rtao", "sah_sun_shadow_mask", "sah_probe_trace", "sah_rtgi_trace", "sah_rt_set_rows", "sah_rt_set_bounces", "sah_allgather_rows", "sah_allgather_rows_reversed", "sah_allgather_bytes", "sah_comm_set_stream", "sah_comm_wait",
+           "sah_lpv_inject_vpls", "sah_rt_build", "sah_rtao", "sah_sun_shadow_mask", "sah_probe_trace", "sah_rtgi_trace", "sah_rt_set_rows", "sah_rt_set_bounces", "sah_debug_rt_structure", "sah_allgather_rows", "sah_allgather_rows_reversed", "sah_allgather_bytes", "sah_comm_set_stream", "sah_comm_wait",
            "sah_ipc_open", "sah_ipc_connect", "sah_ipc_export", "sah_ipc_register", "sah_ipc_unregister", "sah_ipc_reset",
            "sah_chain_create", "sah_chain_submit", "sah_chain_flush", "sah_chain_counts", "sah_chain_destroy"]
 
@@ -46,6 +48,15 @@ ML_EXPORTS = ["sah_mesh_point_cloud", "sah_lpv_emissive_vpls", "sah_lpv_inject_e
 POINT_CLOUD_ON_SURFACE = 1    # SAH_POINT_CLOUD_ON_SURFACE
 EMISSIVE_MATERIAL_ZERO = 1    # SAH_EMISSIVE_MATERIAL_ZERO
 LPV_EMISSIVE_MAX_ENTRIES = 1 << 24
+
+# sah_debug_rt_structure: header words, levels in its two tables, the 48-byte triangle record (SAH_RT_STRUCTURE_HEADER_WORDS, ...)
+RT_STRUCTURE_HEADER_WORDS = 34
+RT_MAX_LEVELS = 15
+
+
+RT_TRIANGLE = np.dtype([("v0", np.float32, 3), ("primitive", np.uint32), ("v1", np.float32, 3), ("triangle", np.uint32), ("v2", np.float32, 3),
+                        ("flags", np.uint32)])
+assert RT_TRIANGLE.itemsize == 48
 
 
 class EmissiveCloud(C.Structure):  # sah_emissive_cloud
@@ -146,6 +157,7 @@ def load():
                                         C.POINTER(_abi.Plane), C.POINTER(_abi.Plane)]
     lib.sah_rt_set_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
     lib.sah_rt_set_bounces.argtypes = [C.c_void_p, C.c_uint32]
+    lib.sah_debug_rt_structure.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
     lib.sah_probe_trace.argtypes = [C.c_void_p, C.POINTER(_abi.ProbeTraceDesc)]
     lib.sah_rtgi_trace.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData), C.POINTER(_abi.SunLightConstants), C.POINTER(_abi.SkyLuts)] + [C.POINTER(_abi.Plane)] * 5
     lib.sah_ipc_open.argtypes = [C.c_void_p, C.c_void_p]
@@ -396,6 +408,21 @@ class Context:
     def rt_set_bounces(self, num_bounces=0):
         """remaining_bounces of the rays probe_trace / rtgi_trace generate from now on (0..2; 0 = what the reference's generators set)"""
         self._check(self.lib.sah_rt_set_bounces(self.handle, num_bounces))
+
+    def rt_structure(self):
+        """Test hook (sah_debug_rt_structure): the structure the last rt_build left behind, read back to host memory (synchronises) — a dict
+        of num_tris, num_levels, pad_bits (the fp32 pad's bits), level_offset (node groups) and level_count (nodes) of the existing levels,
+        tris (num_tris records of RT_TRIANGLE, structure order) and nodes (node groups x {lo, hi} x axis x lane, float32)."""
+        header = (C.c_uint32 * RT_STRUCTURE_HEADER_WORDS)()
+        self._check(self.lib.sah_debug_rt_structure(self.handle, header, None, 0, None, 0))  # the sizes
+        num_tris, num_levels, groups = int(header[0]), int(header[1]), int(header[2])
+        tris, nodes = np.zeros(num_tris, RT_TRIANGLE), np.zeros((groups, 2, 3, 4), np.float32)
+        self._check(self.lib.sah_debug_rt_structure(self.handle, header, tris.ctypes.data, tris.nbytes, nodes.ctypes.data, nodes.nbytes))
+        assert (int(header[0]), int(header[1]), int(header[2])) == (num_tris, num_levels, groups)
+        return {"num_tris": num_tris, "num_levels": num_levels, "pad_bits": int(header[3]),
+                "level_offset": [int(v) for v in header[4:4 + num_levels]],
+                "level_count": [int(v) for v in header[4 + RT_MAX_LEVELS:4 + RT_MAX_LEVELS + num_levels]],
+                "header": [int(v) for v in header], "tris": tris, "nodes": nodes}
 
     def probe_trace(self, desc):
         """desc: _abi.ProbeTraceDesc (device addresses); 400 GI rays per probe into desc.trace_results."""

@@ -648,6 +648,24 @@ int sah_rt_set_rows(sah_ctx* ctx, uint32_t row_begin, uint32_t row_end);
  * forwards the constant. */
 int sah_rt_set_bounces(sah_ctx* ctx, uint32_t num_bounces);
 
+/* Debug / test hook (no reference counterpart): copies the acceleration structure the last sah_rt_build of the context left behind to HOST
+ * memory, so that a test can check the structure itself and not only what rays see through it.  Waits for the context's stream, launches
+ * nothing and changes nothing.
+ *   header     HOST, SAH_RT_STRUCTURE_HEADER_WORDS words or NULL: [0] triangles in the structure, [1] hierarchy levels, [2] node groups,
+ *              [3] the bits of `pad` (fp32), [4 .. 18] level_offset (in node groups), [19 .. 33] level_count (in nodes); entries of levels
+ *              that do not exist are 0.  Level 0 is one padded box per triangle (same index); node n of level L is lane n % 4 of group
+ *              level_offset[L] + n / 4 and covers nodes 4n .. 4n + 3 of level L - 1; the top level has one node.
+ *   triangles  HOST or NULL: header[0] records of 48 bytes in structure order — {v0.xyz, primitive} {v1.xyz, triangle in the primitive}
+ *              {v2.xyz, flags}, 32-bit words; flags bit 0: CUTOUT primitive.
+ *   nodes      HOST or NULL: header[2] groups of 96 bytes — float lo[3][4], hi[3][4]: axis, then the group's four lanes.
+ * A call with triangles == nodes == NULL answers the sizes.  A non-NULL buffer whose *_bytes is less than its array is refused with
+ * SAH_ERR_INVALID_ARGUMENT before anything is written (the header included).  Without a structure (no sah_rt_build yet) it fails like the
+ * ray generators: SAH_ERR_INVALID_ARGUMENT. */
+#define SAH_RT_STRUCTURE_HEADER_WORDS 34
+#define SAH_RT_TRIANGLE_BYTES 48
+#define SAH_RT_NODE_GROUP_BYTES 96
+int sah_debug_rt_structure(sah_ctx* ctx, uint32_t* header, void* triangles, uint64_t triangles_bytes, void* nodes, uint64_t nodes_bytes);
+
 /* Multi-GPU exchange step (no reference counterpart: the reference drives one device, RenderCore/render/backend/render_backend.cpp:135-153;
  * BASELINE.json north_star: "RCCL all-gather over xGMI to reassemble the final image").
  * In-place all-gather of row blocks of `image` over RCCL on the context's stream: rank r owns rows [rows_per_rank*r, rows_per_rank*(r+1))

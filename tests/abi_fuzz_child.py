@@ -217,6 +217,14 @@ def main():
         d.trace_results = f.volume(rgba16, (20, 20, 1024))
         return L.sah_probe_trace(ctx(), opt(d))
 
+    def rt_structure():
+        # host buffers: NULL or real memory; the byte counts are the truth, too small, or wild (nothing may be written past them)
+        header = None if f.g.random() < 0.3 else (C.c_uint32 * lib.RT_STRUCTURE_HEADER_WORDS)()
+        tris, nodes = (C.c_uint8 * 480)(), (C.c_uint8 * 960)()
+        f.keep += [header, tris, nodes]
+        nbytes = lambda real: int(f.pick([real, real, 0, 1, real - 1, 2 ** 40, 2 ** 64 - 1]))
+        return L.sah_debug_rt_structure(ctx(), header, None if f.g.random() < 0.3 else tris, nbytes(480), None if f.g.random() < 0.3 else nodes, nbytes(960))
+
     L.sah_comm_unique_id.argtypes = [C.c_void_p]
     calls = {
         "sah_status_string": lambda: 0 if L.sah_status_string(int(f.g.integers(-50, 50))) is not None else -1,
@@ -253,6 +261,7 @@ def main():
         "sah_rtgi_trace": lambda: (lambda s: L.sah_rtgi_trace(ctx(), opt(f.random_bits(_abi.ViewData)), opt(f.random_bits(_abi.SunLightConstants)), opt(_abi.SkyLuts(f.plane(rgba16, (256, 64)), f.plane(rgba16, (200, 200)))), opt(f.plane(126, s)), opt(f.plane(rgba16, s)), opt(f.plane(37, (128, 128))), opt(f.plane(rgba16, s)), opt(f.plane(rgba16, s))))(size()),
         "sah_rt_set_rows": lambda: L.sah_rt_set_rows(ctx(), f.u32(), f.u32()),
         "sah_rt_set_bounces": lambda: L.sah_rt_set_bounces(ctx(), f.u32()),
+        "sah_debug_rt_structure": rt_structure,
         "sah_allgather_rows": lambda: L.sah_allgather_rows(ctx(), opt(f.plane(rgba16)), f.u32(), f.u32()),
         "sah_allgather_rows_reversed": lambda: L.sah_allgather_rows_reversed(ctx(), opt(f.plane(43)), f.u32(), f.u32()),
         "sah_allgather_bytes": lambda: L.sah_allgather_bytes(ctx(), f.addr(), int(f.g.integers(0, 2 ** 40))),
