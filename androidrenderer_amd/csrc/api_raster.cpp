@@ -60,12 +60,38 @@ bool geometry_ok(const sah_scene_geometry* g, bool need_attributes) {
     return g->num_primitives < (1u << 24);
 }
 
+// What the scratch of a pass looks like (raster_args.hpp: RasterPass).
+struct PassScratch {
+    int attr_slot;      // the buffer that holds one attribute record per raster record
+    size_t attr_bytes;  // ... of this size; 0: the pass writes none
+    size_t cell_bytes;  // per pixel of a split tile's merge buffer
+    bool seq_table;     // the resolve looks records up by sequence number
+};
+PassScratch scratch_of(sah::RasterPass pass, const sah_scene_geometry* scene) {
+    switch (pass) {
+        case sah::RasterPass::Shadow: {
+            // the alpha test of CUTOUT primitives needs their vertex colours and materials (lean records, raster_args.hpp)
+            const bool attrs = scene->vertex_data && scene->materials && scene->num_materials;
+            return {S_ATTRS, attrs ? sizeof(sah::ShadowAttr) : 0, sizeof(uint32_t), false};
+        }
+        case sah::RasterPass::GBuffer:
+        case sah::RasterPass::Rsm: return {S_ATTRS, sizeof(sah::RasterAttr), sizeof(unsigned long long), true};
+        // the motion-vectors pass carries its varying in records of its own; the G-buffer's attributes stay as they are
+        case sah::RasterPass::Motion: return {S_MOTION, sizeof(sah::MotionAttr), sizeof(uint32_t), true};
+    }
+    return {};
+}
+
 // Runs both stages; grows the scratch buffers and repeats the pass when a guess was too small.
-int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, bool gbuffer, uint32_t* stats) {
+int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, sah::RasterPass pass, uint32_t* stats) {
+    using namespace sah;  // Counter
     auto& r = ctx->raster;
+    a.pass = pass;
+    a.rsm = pass == RasterPass::Rsm;
+    const PassScratch ps = scratch_of(pass, scene);
     const uint32_t ntiles = a.tiles_x * a.tiles_y * a.num_views;
-    if (!r.host_counters) HIP_TRY(ctx, hipHostMalloc((void**)&r.host_counters, 16 * sizeof(uint32_t)));
-    if (int rc = ensure(ctx, S_COUNTERS, 16 * sizeof(uint32_t)); rc != SAH_OK) return rc;
+    if (!r.host_counters) HIP_TRY(ctx, hipHostMalloc((void**)&r.host_counters, C_WORDS * sizeof(uint32_t)));
+    if (int rc = ensure(ctx, S_COUNTERS, C_WORDS * sizeof(uint32_t)); rc != SAH_OK) return rc;
     if (int rc = ensure(ctx, S_TRI_BASE, (size_t)(scene->num_primitives + 1) * sizeof(uint32_t)); rc != SAH_OK) return rc;
     if (int rc = ensure(ctx, S_TILES, (size_t)ntiles * 3 * sizeof(uint32_t)); rc != SAH_OK) return rc;
     // First guesses: every index triple is drawn once per view and survives (instanced index ranges or clipping can exceed it); the
@@ -74,70 +100,64 @@ int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, bool 
     // and the pass repeated.  From the second frame of a scene on this is one iteration with no idle gap on the GPU.
     size_t want_records = (size_t)(scene->num_indices / 3) * a.num_views + 1024, want_clipped = want_records / 8 + 1024;
     size_t want_pairs = std::max<size_t>(r.buf[S_PAIRS].bytes / sizeof(uint32_t), 2 * want_records + 4 * (size_t)ntiles);
-    size_t want_seq = gbuffer ? std::max<size_t>(r.buf[S_SEQ].bytes / sizeof(uint32_t), (size_t)(scene->num_indices / 3) * 8 * a.num_views + 64) : 0;
+    size_t want_seq = ps.seq_table ? std::max<size_t>(r.buf[S_SEQ].bytes / sizeof(uint32_t), (size_t)(scene->num_indices / 3) * 8 * a.num_views + 64) : 0;
     for (int attempt = 0; attempt < 4; attempt++) {
         if (int rc = ensure(ctx, S_CLIPQ, want_clipped * sizeof(uint2)); rc != SAH_OK) return rc;
-        if (int rc = ensure(ctx, S_RECORDS, want_records * sizeof(sah::RasterRecord)); rc != SAH_OK) return rc;
-        // shadow pass: the alpha test of CUTOUT primitives needs their vertex colours and materials (lean records, raster_args.hpp)
-        const bool shadow_attrs = !gbuffer && scene->vertex_data && scene->materials && scene->num_materials;
-        if (gbuffer && !a.motion)
-            if (int rc = ensure(ctx, S_ATTRS, want_records * sizeof(sah::RasterAttr)); rc != SAH_OK) return rc;
-        if (a.motion)  // the motion-vectors pass carries its varying in records of its own; the G-buffer's attributes stay as they are
-            if (int rc = ensure(ctx, S_MOTION, want_records * sizeof(sah::MotionAttr)); rc != SAH_OK) return rc;
-        if (shadow_attrs)
-            if (int rc = ensure(ctx, S_ATTRS, want_records * sizeof(sah::ShadowAttr)); rc != SAH_OK) return rc;
+        if (int rc = ensure(ctx, S_RECORDS, want_records * sizeof(RasterRecord)); rc != SAH_OK) return rc;
+        if (ps.attr_bytes)
+            if (int rc = ensure(ctx, ps.attr_slot, want_records * ps.attr_bytes); rc != SAH_OK) return rc;
         if (int rc = ensure(ctx, S_PAIRS, want_pairs * sizeof(uint32_t)); rc != SAH_OK) return rc;
-        if (gbuffer)
+        if (ps.seq_table)
             if (int rc = ensure(ctx, S_SEQ, want_seq * sizeof(uint32_t)); rc != SAH_OK) return rc;
         a.clip_queue = (uint2*)r.buf[S_CLIPQ].ptr;
         a.clip_capacity = (uint32_t)std::min<size_t>(r.buf[S_CLIPQ].bytes / sizeof(uint2), 0xffffffffu);
         a.counters = (uint32_t*)r.buf[S_COUNTERS].ptr;
         a.tri_base = (uint32_t*)r.buf[S_TRI_BASE].ptr;
-        a.records = (sah::RasterRecord*)r.buf[S_RECORDS].ptr;
-        a.attrs = (sah::RasterAttr*)r.buf[S_ATTRS].ptr;
-        a.shadow_attrs = shadow_attrs ? (sah::ShadowAttr*)r.buf[S_ATTRS].ptr : nullptr;
-        a.record_capacity = (uint32_t)std::min<size_t>(r.buf[S_RECORDS].bytes / sizeof(sah::RasterRecord), 0xffffffffu);
-        if (gbuffer && !a.motion) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.buf[S_ATTRS].bytes / sizeof(sah::RasterAttr));
-        if (a.motion) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.buf[S_MOTION].bytes / sizeof(sah::MotionAttr));
-        a.motion_attrs = a.motion ? (sah::MotionAttr*)r.buf[S_MOTION].ptr : nullptr;
-        if (shadow_attrs) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.buf[S_ATTRS].bytes / sizeof(sah::ShadowAttr));
+        a.records = (RasterRecord*)r.buf[S_RECORDS].ptr;
+        a.record_capacity = (uint32_t)std::min<size_t>(r.buf[S_RECORDS].bytes / sizeof(RasterRecord), 0xffffffffu);
+        if (ps.attr_bytes) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.buf[ps.attr_slot].bytes / ps.attr_bytes);
+        void* attrs = ps.attr_bytes ? r.buf[ps.attr_slot].ptr : nullptr;
+        a.attrs = (RasterAttr*)r.buf[S_ATTRS].ptr;  // (read by the G-buffer and RSM passes only)
+        a.shadow_attrs = pass == RasterPass::Shadow ? (ShadowAttr*)attrs : nullptr;
+        a.motion_attrs = pass == RasterPass::Motion ? (MotionAttr*)attrs : nullptr;
         a.tile_count = (uint32_t*)r.buf[S_TILES].ptr;
         a.tile_cursor = a.tile_count + ntiles;
         a.tile_offset = a.tile_count + 2 * (size_t)ntiles;
         a.pairs = (uint32_t*)r.buf[S_PAIRS].ptr;
         a.pairs_capacity = (uint32_t)std::min<size_t>(r.buf[S_PAIRS].bytes / sizeof(uint32_t), 0xffffffffu);
         a.seq_to_record = (uint32_t*)r.buf[S_SEQ].ptr;
-        a.seq_capacity = gbuffer ? r.buf[S_SEQ].bytes / sizeof(uint32_t) : 0;
+        a.seq_capacity = ps.seq_table ? r.buf[S_SEQ].bytes / sizeof(uint32_t) : 0;
         // long bin lists are cut into parts of kRasterSplit entries: at most pairs / kRasterSplit further parts, and a merge buffer per split tile (the
         // number of those is capped: tiles beyond it are processed whole)
-        a.extra_capacity = a.pairs_capacity / sah::kRasterSplit + 1u;
+        a.extra_capacity = a.pairs_capacity / kRasterSplit + 1u;
         a.merge_capacity = std::min<uint32_t>(a.extra_capacity, ctx->raster_merge_cap);
-        const size_t tile_bytes = (size_t)kTile * kTile * (gbuffer && !a.motion ? 8 : 4);
         if (int rc = ensure(ctx, S_HEAVY, (size_t)ntiles * sizeof(uint32_t)); rc != SAH_OK) return rc;
         if (int rc = ensure(ctx, S_EXTRA, (size_t)a.extra_capacity * sizeof(uint2)); rc != SAH_OK) return rc;
         if (int rc = ensure(ctx, S_TICKETS, (size_t)a.merge_capacity * sizeof(uint32_t)); rc != SAH_OK) return rc;
-        if (int rc = ensure(ctx, S_MERGE, (size_t)a.merge_capacity * tile_bytes); rc != SAH_OK) return rc;
+        if (int rc = ensure(ctx, S_MERGE, (size_t)a.merge_capacity * kTile * kTile * ps.cell_bytes); rc != SAH_OK) return rc;
         a.heavy_slot = (uint32_t*)r.buf[S_HEAVY].ptr;
         a.extra_parts = (uint2*)r.buf[S_EXTRA].ptr;
         a.tickets = (uint32_t*)r.buf[S_TICKETS].ptr;
-        a.merge_depth = (uint32_t*)r.buf[S_MERGE].ptr;
-        a.merge_keys = (unsigned long long*)r.buf[S_MERGE].ptr;
-        a.merge_seq = (uint32_t*)r.buf[S_MERGE].ptr;
-        HIP_TRY(ctx, sah::launch_raster_setup(a, gbuffer, ctx->stream));
-        HIP_TRY(ctx, sah::launch_raster_tiles(a, gbuffer, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(r.host_counters, a.counters, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        // one buffer, typed by the pass's merge cell
+        a.merge_depth = pass == RasterPass::Shadow ? (uint32_t*)r.buf[S_MERGE].ptr : nullptr;
+        a.merge_keys = pass == RasterPass::GBuffer || pass == RasterPass::Rsm ? (unsigned long long*)r.buf[S_MERGE].ptr : nullptr;
+        a.merge_seq = pass == RasterPass::Motion ? (uint32_t*)r.buf[S_MERGE].ptr : nullptr;
+        HIP_TRY(ctx, launch_raster_setup(a, ctx->stream));
+        HIP_TRY(ctx, launch_raster_tiles(a, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(r.host_counters, a.counters, C_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        const size_t total_tris = r.host_counters[0], clipped = r.host_counters[3], pairs = r.host_counters[2];
+        const uint32_t* hc = r.host_counters;
+        const size_t total_tris = hc[C_TRIS], clipped = hc[C_CLIPPED], pairs = hc[C_PAIRS];
         if (total_tris >= (1u << 28)) return fail(ctx, SAH_ERR_UNSUPPORTED, "rasteriser: more than 2^28 triangles in one pass");
-        if (r.host_counters[13])
+        if (hc[C_BAD_TEXTURE])
             return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rasteriser: %u invalid texture slots or bindings (index beyond the table, more than %d levels, a level "
-                        "that is not R8G8B8A8_UNORM / _SRGB, a sampler enum out of range)", r.host_counters[13], SAH_MAX_TEXTURE_MIPS);
-        if (r.host_counters[12])
+                        "that is not R8G8B8A8_UNORM / _SRGB, a sampler enum out of range)", hc[C_BAD_TEXTURE], SAH_MAX_TEXTURE_MIPS);
+        if (hc[C_CUTOUT_NO_ATTR])
             return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "shadow_render: the scene has CUTOUT primitives (%u triangles): vertex_data and materials are needed "
-                        "for their alpha test (shadow_masked pipeline)", r.host_counters[12]);
+                        "for their alpha test (shadow_masked pipeline)", hc[C_CUTOUT_NO_ATTR]);
         // records: one slot per (view, triangle) plus the appended fans of the clipped ones
-        const size_t need_records = total_tris * a.num_views + r.host_counters[1];
-        const size_t need_seq = gbuffer ? total_tris * 8 * a.num_views + 1 : 0;
+        const size_t need_records = total_tris * a.num_views + hc[C_RECORDS];
+        const size_t need_seq = ps.seq_table ? total_tris * 8 * a.num_views + 1 : 0;
         if (need_records <= a.record_capacity && clipped <= a.clip_capacity && pairs <= a.pairs_capacity && need_seq <= a.seq_capacity) break;
         if (attempt == 3) return fail(ctx, SAH_ERR_HIP, "rasteriser: scratch buffers still too small after regrowing");
         // a short clip queue hides records and a short record buffer hides bin entries: size for the worst case of what was seen
@@ -146,8 +166,18 @@ int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, bool 
         want_pairs = std::max<size_t>(want_pairs, pairs + pairs / 4 + 16);
         want_seq = std::max<size_t>(want_seq, need_seq);
     }
-    if (stats) HIP_TRY(ctx, hipMemcpyAsync(stats, a.counters + 4, SAH_RASTER_STATS_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    if (stats) HIP_TRY(ctx, hipMemcpyAsync(stats, a.counters + C_STATS, SAH_RASTER_STATS_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
     return SAH_OK;
+}
+
+// the extent of every view of a pass and what follows from it
+void fill_extent(sah::RasterArgs& a, uint32_t width, uint32_t height) {
+    a.width = width;
+    a.height = height;
+    a.half_w = (float)width * 0.5f;
+    a.half_h = (float)height * 0.5f;
+    a.tiles_x = (width + kTile - 1) / kTile;
+    a.tiles_y = (height + kTile - 1) / kTile;
 }
 
 void fill_scene(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene) {
@@ -187,14 +217,9 @@ int sah_shadow_render(sah_ctx* ctx, const sah_scene_geometry* scene, const sah_s
     fill_scene(ctx, a, scene);
     a.num_views = num_cascades;
     for (uint32_t c = 0; c < num_cascades; c++) std::memcpy(a.clip_matrix[c], sun->cascade_matrices[c], 64);
-    a.width = shadowmap->width;
-    a.height = shadowmap->height;
-    a.half_w = (float)a.width * 0.5f;
-    a.half_h = (float)a.height * 0.5f;
-    a.tiles_x = (a.width + kTile - 1) / kTile;
-    a.tiles_y = (a.height + kTile - 1) / kTile;
+    fill_extent(a, shadowmap->width, shadowmap->height);
     a.shadowmap = varg(*shadowmap);
-    return run(ctx, a, scene, false, stats);
+    return run(ctx, a, scene, sah::RasterPass::Shadow, stats);
 }
 
 int sah_gbuffer_render(sah_ctx* ctx, const sah_scene_geometry* scene, const sah_view_data* view, const sah_gbuffer* out, uint32_t* stats) {
@@ -219,19 +244,14 @@ int sah_gbuffer_render(sah_ctx* ctx, const sah_scene_geometry* scene, const sah_
     a.shader_mip_bias = view->material_texture_mip_bias;
     std::memcpy(a.view_matrix, view->view, 64);
     std::memcpy(a.clip_matrix[0], view->projection, 64);
-    a.width = W;
-    a.height = H;
-    a.half_w = (float)W * 0.5f;
-    a.half_h = (float)H * 0.5f;
-    a.tiles_x = (W + kTile - 1) / kTile;
-    a.tiles_y = (H + kTile - 1) / kTile;
+    fill_extent(a, W, H);
     a.half_to_srgb8 = ctx->raster.half_to_srgb8;
     a.out_color = parg(&out->color);
     a.out_normals = parg(&out->normals);
     a.out_data = parg(&out->data);
     a.out_emission = parg(&out->emission);
     a.out_depth = parg(&out->depth);
-    return run(ctx, a, scene, true, stats);
+    return run(ctx, a, scene, sah::RasterPass::GBuffer, stats);
 }
 
 int sah_rsm_render(sah_ctx* ctx, const sah_scene_geometry* scene, const sah_sun_light_constants* sun, const sah_lpv_cascade_matrices* cascades,
@@ -256,19 +276,13 @@ int sah_rsm_render(sah_ctx* ctx, const sah_scene_geometry* scene, const sah_sun_
     fill_scene(ctx, a, scene);
     a.num_views = num_cascades;
     for (uint32_t c = 0; c < num_cascades; c++) std::memcpy(a.clip_matrix[c], cascades[c].rsm_vp, 64);
-    a.width = W;
-    a.height = H;
-    a.half_w = (float)W * 0.5f;
-    a.half_h = (float)H * 0.5f;
-    a.tiles_x = (W + kTile - 1) / kTile;
-    a.tiles_y = (H + kTile - 1) / kTile;
+    fill_extent(a, W, H);
     a.half_to_srgb8 = ctx->raster.half_to_srgb8;
-    a.rsm = 1;
     for (int k = 0; k < 3; k++) a.sun_direction[k] = sun->direction_and_tan_size[k];
     a.rsm_flux = varg(rsm->flux);
     a.rsm_normals = varg(rsm->normals);
     a.rsm_depth = varg(rsm->depth);
-    return run(ctx, a, scene, true, stats);
+    return run(ctx, a, scene, sah::RasterPass::Rsm, stats);
 }
 
 int sah_motion_vectors_render(sah_ctx* ctx, const sah_scene_geometry* scene, const sah_view_data* view, const sah_plane* depth,
@@ -294,7 +308,6 @@ int sah_motion_vectors_render(sah_ctx* ctx, const sah_scene_geometry* scene, con
     a.textures = nullptr;
     a.material_textures = nullptr;
     a.num_textures = 0;
-    a.motion = 1;
     a.num_views = 1;
     std::memcpy(a.view_matrix, view->view, 64);
     std::memcpy(a.clip_matrix[0], view->projection, 64);
@@ -302,15 +315,10 @@ int sah_motion_vectors_render(sah_ctx* ctx, const sah_scene_geometry* scene, con
     std::memcpy(a.prev_clip_matrix, view->last_frame_projection, 64);
     a.render_resolution[0] = view->render_resolution[0];
     a.render_resolution[1] = view->render_resolution[1];
-    a.width = W;
-    a.height = H;
-    a.half_w = (float)W * 0.5f;
-    a.half_h = (float)H * 0.5f;
-    a.tiles_x = (W + kTile - 1) / kTile;
-    a.tiles_y = (H + kTile - 1) / kTile;
+    fill_extent(a, W, H);
     a.mv_depth = parg(depth);
     a.out_motion = parg(motion_vectors);
-    return run(ctx, a, scene, true, stats);
+    return run(ctx, a, scene, sah::RasterPass::Motion, stats);
 }
 
 int sah_lpv_extract_vpls(sah_ctx* ctx, const sah_rsm_targets* rsm, const sah_lpv_cascade_matrices* cascades, uint32_t cascade_index,

@@ -80,9 +80,10 @@ hipError_t launch_probe_copy(const ProbeAtlasArgs& src, const ProbeAtlasArgs& ds
 hipError_t launch_probe_update(const ProbeAtlasArgs& atl, const VolumeArg& trace, const uint32_t* probes, uint32_t num_probes, uint32_t* slots,
                                hipStream_t st);
 
-// --- raster.hip
-hipError_t launch_raster_setup(const RasterArgs& a, bool gbuffer, hipStream_t st);
-hipError_t launch_raster_tiles(const RasterArgs& a, bool gbuffer, hipStream_t st);
+// --- raster_setup.hip, raster_tiles.hip (the pass is a.pass)
+hipError_t launch_raster_setup(const RasterArgs& a, hipStream_t st);
+void launch_raster_fill_bins(const RasterArgs& a, hipStream_t st);  // raster_setup.hip's k_bin<fill>, first kernel of launch_raster_tiles
+hipError_t launch_raster_tiles(const RasterArgs& a, hipStream_t st);
 
 // --- rt.hip
 hipError_t launch_rt_scan(const sah_primitive* prims, uint32_t n, uint32_t* tri_base, RtBuildState* st, hipStream_t s);

@@ -1,4 +1,4 @@
-// Kernel-argument block and scratch records of the scene rasteriser (raster.hip, api_raster.cpp).
+// Kernel-argument block and scratch records of the scene rasteriser (raster_setup.hip, raster_tiles.hip, api_raster.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,6 +17,18 @@ constexpr uint32_t kRasterTile = SAH_RASTER_TILE;
 #define SAH_RASTER_SPLIT 256  // bin lists longer than this are cut into parts of this many entries, one workgroup each (64 / 128 measured: dense shadow cascades 50 % / 15 % slower)
 #endif
 constexpr uint32_t kRasterSplit = SAH_RASTER_SPLIT;
+
+// What a call renders.  Host and device derive everything that differs between the passes from this one value: the attribute record the
+// set-up writes, the cell of a split tile's merge buffer, the fragment test and the resolve (the targets of raster_tiles.hip).
+enum class RasterPass : uint32_t {
+    Shadow,   // sah_shadow_render: D16 cascades, LESS; ShadowAttr for CUTOUT records when the scene has vertex data and materials
+    GBuffer,  // sah_gbuffer_render: reverse-Z depth + four colour targets; RasterAttr
+    Rsm,      // sah_rsm_render: the G-buffer path with per-view matrices, D16 LESS and the flux / normal targets (RasterArgs::rsm)
+    Motion,   // sah_motion_vectors_render: SOLID primitives only, compare EQUAL against mv_depth; MotionAttr
+};
+
+// RasterArgs::counters.  C_STATS .. C_STATS + 7 mirror SAH_RASTER_STATS_WORDS (C_EXTRA and C_HEAVY are statistics words 5 and 6).
+enum Counter { C_TRIS = 0, C_RECORDS = 1, C_PAIRS = 2, C_CLIPPED = 3, C_STATS = 4, C_EXTRA = 9, C_HEAVY = 10, C_CUTOUT_NO_ATTR = 12, C_BAD_TEXTURE = 13, C_WORDS = 16 };
 
 // One window-space triangle of one view: clipped, fanned, snapped to 1/256 pixel, oriented so that its area is positive.
 struct RasterRecord {
@@ -116,8 +128,8 @@ struct RasterArgs {
     // outputs
     VolumeArg shadowmap;
     PlaneArg out_color, out_normals, out_data, out_emission, out_depth;
-    // motion-vectors variant of the G-buffer path (sah_motion_vectors_render): SOLID primitives only, compare EQUAL against mv_depth
-    uint32_t motion;
+    RasterPass pass;
+    // motion-vectors pass (sah_motion_vectors_render)
     float prev_view_matrix[16], prev_clip_matrix[16];  // last_frame_view, last_frame_projection
     float render_resolution[2];
     MotionAttr* motion_attrs;  // one per record

@@ -17,6 +17,7 @@
 #include "launch.hpp"
 #include "numerics.hpp"
 #include "octahedral.hpp"
+#include "prim_scan.hpp"
 #include "rt_args.hpp"
 #include "texture_sample.hpp"
 
@@ -48,31 +49,8 @@ SAH_DEV float unordered(uint32_t u) { return __uint_as_float((u & 0x80000000u) ?
 // ---- build ------------------------------------------------------------------------------------------------------------------------
 // triangles per primitive -> exclusive offsets (one workgroup; a scene has thousands of primitives at most)
 __global__ __launch_bounds__(1024) void k_rt_scan(const sah_primitive* prims, uint32_t n, uint32_t* tri_base, RtBuildState* st) {
-    __shared__ uint32_t s_wave[16];
-    __shared__ uint32_t s_carry;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < n; base += 1024) {
-        const uint32_t i = base + tid;
-        const uint32_t v = i < n ? prims[i].index_count / 3u : 0u;
-        uint32_t incl = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d, 64);
-            if ((int)lane >= d) incl += up;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        uint32_t wave_base = 0;
-        for (uint32_t w = 0; w < wave; w++) wave_base += s_wave[w];
-        const uint32_t carry = s_carry;
-        if (i < n) tri_base[i] = carry + wave_base + incl - v;
-        __syncthreads();
-        if (tid == 1023) s_carry = carry + wave_base + incl;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        st->total = s_carry;
+    block_exclusive_scan<1>(n, [&](uint32_t i) { return prims[i].index_count / 3u; }, tri_base, &st->total);
+    if (threadIdx.x == 0) {
         st->kept = 0;
         st->dropped = 0;
         st->max_abs_bits = 0;
@@ -81,15 +59,6 @@ __global__ __launch_bounds__(1024) void k_rt_scan(const sah_primitive* prims, ui
             st->cmax[k] = 0u;
         }
     }
-}
-
-SAH_DEV uint32_t find_primitive(const uint32_t* tri_base, uint32_t n, uint32_t t) {  // last p with tri_base[p] <= t
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (tri_base[mid] <= t) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 SAH_DEV float mat_row3(const float* m, int r, float x, float y, float z) { return ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r]; }

@@ -1,4 +1,4 @@
-// Material texture sampling shared by the scene rasteriser (raster.hip: SampleBias with quad derivatives) and the any-hit stage of the
+// Material texture sampling shared by the scene rasteriser (raster_tiles.hip: SampleBias with quad derivatives) and the any-hit stage of the
 // ray tracer (rt.hip: SampleLevel 0).  The rules are the ones include/sah_hip.h lists under sah_texture.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -402,6 +402,63 @@ def test_hip_unsplit_bin_lists_take_several_rounds(monkeypatch):
 
 
 @pytest.mark.gpu
+def test_hip_split_bin_lists_equal_whole_lists(hip_ctx, monkeypatch):
+    """The shadow, G-buffer and RSM passes on the dense soup, once with their bin lists cut into parts and merged through global memory
+    (default context) and once with every list walked whole (SAH_RASTER_MERGE_CAPACITY=0): the same bytes in every plane."""
+    import torch
+    from androidrenderer_amd import lib
+    arrays = mesh.random_soup(31, triangles=1500, extent=1.5, size=(1.5, 4.0)).arrays()
+    view = _soup_view(128, 128, 31)
+    sun = scene.DirectionalLight(shadow_mode=_abi.SHADOW_MODE_CSM)
+    constants = sun.update_shadow_cascades(view, max_shadow_distance=16.0, resolution=128)
+    lpv = scene.LpvCascades()
+    lpv.update_cascade_transforms(view, sun)
+
+    def render_rsm(ctx):
+        dev = mesh.to_device(arrays)
+        keep = []
+        g = mesh.geometry(dev, keep)
+        t = {"flux": torch.full((4, 128, 128, 4), 9, dtype=torch.uint8, device="cuda"), "normals": torch.full((4, 128, 128, 4), 9, dtype=torch.uint8, device="cuda"),
+             "depth": torch.full((4, 128, 128), 9, dtype=torch.int16, device="cuda")}
+        desc = _abi.RsmTargets(images.volume(t["flux"], _abi.FORMAT_R8G8B8A8_SRGB), images.volume(t["normals"], _abi.FORMAT_R8G8B8A8_UNORM),
+                               images.volume(t["depth"], _abi.FORMAT_D16_UNORM))
+        stats = torch.zeros(_abi.RASTER_STATS_WORDS, dtype=torch.int32, device="cuda")
+        ctx.rsm_render(g, sun.constants, lpv.matrices, 4, desc, stats.data_ptr())
+        torch.cuda.synchronize()
+        return {k: v.cpu().numpy() for k, v in t.items()}, stats.cpu().numpy().view(np.uint32)
+
+    def render(ctx):
+        gb, gb_stats = _hip_gbuffer(ctx, arrays, view, 128, 128)
+        sm, sm_stats = _hip_shadow(ctx, arrays, constants, 4, (128, 128))
+        rsm, rsm_stats = render_rsm(ctx)
+        return gb, gb_stats, sm, sm_stats, rsm, rsm_stats
+
+    split = render(hip_ctx)
+    monkeypatch.setenv("SAH_RASTER_MERGE_CAPACITY", "0")
+    ctx = lib.Context(device=0)
+    ctx.set_stream(torch.cuda.current_stream().cuda_stream)
+    try:
+        whole = render(ctx)
+    finally:
+        torch.cuda.synchronize()
+        ctx.close()
+    for stats_split, stats_whole in ((split[1], whole[1]), (split[3], whole[3]), (split[5], whole[5])):
+        print("stats, split lists:", list(stats_split), "whole lists:", list(stats_whole))
+        assert stats_split[5] > 0  # parts were handed out
+        assert stats_whole[5] == 0 and stats_whole[6] >= 1
+        assert list(stats_split[:5]) == list(stats_whole[:5])
+    _assert_gbuffers_equal(split[0], whole[0])
+    assert np.array_equal(split[2], whole[2])
+    for k in ("depth", "flux", "normals"):
+        assert np.array_equal(split[4][k], whole[4][k]), f"rsm {k}: {(split[4][k] != whole[4][k]).sum()} bytes differ"
+    want_gb, _ = _oracle_gbuffer(arrays, view, 128, 128)
+    want_sm, _ = _oracle_shadow(arrays, constants, 4, (128, 128))
+    _assert_gbuffers_equal(split[0], want_gb)
+    assert np.array_equal(split[2], want_sm)
+    assert (split[4]["depth"].view(np.uint16) != 0xffff).any() and (want_sm != 0xffff).any() and (want_gb["depth"] > 0).any()
+
+
+@pytest.mark.gpu
 def test_hip_raster_rejects_bad_arguments(hip_ctx):
     import torch
     arrays = mesh.atrium().arrays()

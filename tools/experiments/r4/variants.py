@@ -185,7 +185,7 @@ for _n, _f, _src in (("prio_fast", ["-mllvm", "-amdgpu-set-wave-priority"], ["li
     FLAG_VARIANTS[_n] = _f
     VARIANTS[_n] = (_src, [])
 # ... and of every other translation unit with kernels in it, one at a time
-for _src in ("post.hip", "tonemap_tol.hip", "tonemap.hip", "rt.hip", "raster.hip", "lpv.hip", "probes.hip"):
+for _src in ("post.hip", "tonemap_tol.hip", "tonemap.hip", "rt.hip", "raster_setup.hip", "raster_tiles.hip", "lpv.hip", "probes.hip"):
     _n = "np_" + _src.split(".")[0]
     FLAG_VARIANTS[_n] = ["-mllvm", "-enable-post-misched=0"]
     VARIANTS[_n] = ([_src], [])

@@ -31,8 +31,23 @@ for line in out.splitlines():
         cur[k.strip()] = v.strip()
 if cur:
     rows.append(cur)
+
+
+def strip_arguments(name):
+    """The demangled name without its trailing argument list: `sah::(anonymous namespace)::k<true>(sah::Args)` keeps everything up to
+    the parenthesis that matches the last one."""
+    if not name.endswith(")"):
+        return name
+    depth = 0
+    for i in range(len(name) - 1, -1, -1):
+        depth += (name[i] == ")") - (name[i] == "(")
+        if depth == 0:
+            return name[:i]
+    return name
+
+
 for r in rows:
     name = subprocess.run(["c++filt", r["name"]], stdout=subprocess.PIPE, text=True).stdout.strip()
-    name = re.sub(r"\(.*", "", name)
+    name = strip_arguments(name)
     print(f"{name:60s} VGPR {r.get('VGPRs','?'):>4} AGPR {r.get('AGPRs','?'):>3} SGPR {r.get('TotalSGPRs', r.get('SGPRs','?')):>4} "
           f"scratch {r.get('ScratchSize [bytes/lane]','?'):>5} occ {r.get('Occupancy [waves/SIMD]','?'):>2} LDS {r.get('LDS Size [bytes/block]','?'):>6}")
