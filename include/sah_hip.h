@@ -347,7 +347,9 @@ int sah_probe_copy(sah_ctx* ctx, const sah_probe_atlases* src, const sah_probe_a
 
 /* probe_depth_update, probe_light_cache_update, probe_rtgi_update, probe_finalize, in that order, for `num_probes` probes.
  * trace_results: R16G16B16A16_SFLOAT 20 x 20 x num_probes (rgb = radiance, a = hit distance, <= 0: miss);
- * probes_to_update: DEVICE pointer to num_probes tightly packed uint32 triples (probe x, y, layer), all distinct. */
+ * probes_to_update: DEVICE pointer to num_probes tightly packed uint32 triples (probe x, y, layer), all distinct.
+ * Probe ids are expected below 32 per component.  An id outside the grid stores whatever of its blocks falls inside the atlases; the
+ * order of those stores against the stores of a listed neighbour inside the grid is unspecified. */
 int sah_probe_update(sah_ctx* ctx, const sah_probe_atlases* atlases, const sah_volume* trace_results, const uint32_t* probes_to_update,
                      uint32_t num_probes);
 
