@@ -1,10 +1,13 @@
-// C ABI: ray tracing — sah_rt_build, sah_rtao, sah_sun_shadow_mask (include/sah_hip.h "ray tracing"; kernels in rt.hip).
+// C ABI: ray tracing — sah_rt_build, sah_rtao, sah_sun_shadow_mask (include/sah_hip.h "ray tracing"; kernels in rt.hip) and sah_rt_refit
+// (include/sah_rt_refit.h; kernels in rt_refit.hip).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 #include "../../include/sah_hip.h"
+#include "../../include/sah_rt_refit.h"
 #include "ctx.hpp"
 #include "launch.hpp"
 
@@ -19,6 +22,26 @@ int ensure(sah_ctx* ctx, int slot, size_t bytes) {
     HIP_TRY(ctx, hipMalloc(&b.ptr, want));
     b.bytes = want;
     return SAH_OK;
+}
+
+// the device pointers and counts of a sah_scene_geometry, as the kernels take them
+sah::RtScene scene_args(const sah_ctx* ctx, const sah_scene_geometry* scene) {
+    sah::RtScene sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.positions = scene->vertex_positions;
+    sc.vertex_data = scene->vertex_data;
+    sc.indices = scene->indices;
+    sc.primitives = scene->primitives;
+    sc.materials = scene->materials;
+    sc.num_primitives = scene->num_primitives;
+    sc.num_indices = scene->num_indices;
+    sc.num_vertices = scene->num_vertices;
+    sc.num_materials = scene->num_materials;
+    sc.textures = scene->num_textures ? scene->textures : nullptr;
+    sc.material_textures = (scene->num_textures && scene->textures) ? scene->material_textures : nullptr;
+    sc.num_textures = scene->num_textures;
+    sc.luts = ctx->luts;
+    return sc;
 }
 
 bool plane_fmt(const sah_plane* p, uint32_t fmt, uint32_t bpp) {
@@ -63,21 +86,7 @@ int sah_rt_build(sah_ctx* ctx, const sah_scene_geometry* scene, uint32_t* stats)
     if (scene->num_primitives >= (1u << 24)) return fail(ctx, SAH_ERR_UNSUPPORTED, "too many primitives");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, sah_guard_touch(ctx, ctx->guard_rt));
-    RtScene sc;
-    memset(&sc, 0, sizeof(sc));
-    sc.positions = scene->vertex_positions;
-    sc.vertex_data = scene->vertex_data;
-    sc.indices = scene->indices;
-    sc.primitives = scene->primitives;
-    sc.materials = scene->materials;
-    sc.num_primitives = scene->num_primitives;
-    sc.num_indices = scene->num_indices;
-    sc.num_vertices = scene->num_vertices;
-    sc.num_materials = scene->num_materials;
-    sc.textures = scene->num_textures ? scene->textures : nullptr;
-    sc.material_textures = (scene->num_textures && scene->textures) ? scene->material_textures : nullptr;
-    sc.num_textures = scene->num_textures;
-    sc.luts = ctx->luts;
+    const RtScene sc = scene_args(ctx, scene);
     RtBvh bvh;
     memset(&bvh, 0, sizeof(bvh));
     RtBuildState host;
@@ -128,12 +137,41 @@ int sah_rt_build(sah_ctx* ctx, const sah_scene_geometry* scene, uint32_t* stats)
     rt.bvh = bvh;
     rt.scene = sc;
     rt.built = true;
+    rt.refitted = false;
     if (stats) {
         stats[0] = bvh.num_tris;
         stats[1] = host.dropped;
         stats[2] = bvh.num_levels;
         stats[3] = 0;
     }
+    return SAH_OK;
+}
+
+// include/sah_rt_refit.h.  Nothing of RtBvh changes on the host: the counts and the level table are the build's, and the pad the boxes
+// were made with stays in RtBuildState::max_abs_bits on the device (sah_debug_rt_structure reads it back from there).
+int sah_rt_refit(sah_ctx* ctx, const sah_scene_geometry* scene, uint32_t* stats) {
+    SAH_RANGE();
+    using namespace sah;
+    if (!ctx || !scene) return SAH_ERR_INVALID_ARGUMENT;
+    auto& rt = ctx->rt;
+    if (!rt.built) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sah_rt_build has not been called on this context");
+    if (scene->num_primitives != rt.scene.num_primitives || scene->num_vertices != rt.scene.num_vertices || scene->num_indices != rt.scene.num_indices)
+        return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sah_rt_refit: %u primitives, %u vertices, %u indices; the structure was built over %u, %u, %u",
+                    scene->num_primitives, scene->num_vertices, scene->num_indices, rt.scene.num_primitives, rt.scene.num_vertices, rt.scene.num_indices);
+    if (scene->num_primitives && (!scene->primitives || !scene->indices || !scene->vertex_positions))
+        return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "scene arrays are null");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, sah_guard_touch(ctx, ctx->guard_rt));
+    rt.scene = scene_args(ctx, scene);
+    if (rt.bvh.num_tris == 0) {
+        if (stats) HIP_TRY(ctx, hipMemsetAsync(stats, 0, 4 * sizeof(uint32_t), ctx->stream));
+        return SAH_OK;
+    }
+    auto* st = (RtBuildState*)rt.buf[R_STATE].ptr;
+    static_assert(offsetof(RtBuildState, kept) == 0 && offsetof(RtBuildState, max_abs_bits) == 8, "kept, dropped, max_abs_bits lead RtBuildState");
+    HIP_TRY(ctx, hipMemsetAsync(st, 0, 3 * sizeof(uint32_t), ctx->stream));
+    rt.refitted = true;
+    HIP_TRY(ctx, launch_rt_refit(rt.scene, rt.bvh, (RtTriangle*)rt.buf[R_SORTED].ptr, (RtNodeGroup*)rt.buf[R_NODES].ptr, st, stats, ctx->stream));
     return SAH_OK;
 }
 
@@ -162,11 +200,21 @@ int sah_debug_rt_structure(sah_ctx* ctx, uint32_t* header, void* triangles, uint
         if (triangles && tri_bytes) HIP_TRY(ctx, hipMemcpy(triangles, bvh.tris, tri_bytes, hipMemcpyDeviceToHost));
         if (nodes && node_bytes) HIP_TRY(ctx, hipMemcpy(nodes, bvh.nodes, node_bytes, hipMemcpyDeviceToHost));
     }
+    float pad = bvh.pad;
+    if (header && ctx->rt.refitted && bvh.num_tris) {  // a refit's pad never reached the host: S from the device, behind the stream
+        uint32_t s_bits = 0;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(&s_bits, &((const RtBuildState*)ctx->rt.buf[R_STATE].ptr)->max_abs_bits, 4, hipMemcpyDeviceToHost));
+        float S;
+        memcpy(&S, &s_bits, 4);
+        pad = S * 0x1p-16f;
+    }
     if (header) {
         header[0] = bvh.num_tris;
         header[1] = bvh.num_levels;
         header[2] = groups;
-        memcpy(&header[3], &bvh.pad, 4);
+        memcpy(&header[3], &pad, 4);
         for (uint32_t l = 0; l < kRtMaxLevels; l++) {
             header[4 + l] = bvh.level_offset[l];
             header[4 + kRtMaxLevels + l] = bvh.level_count[l];

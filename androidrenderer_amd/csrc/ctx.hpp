@@ -74,6 +74,7 @@ struct sah_ctx {
         sah::RtBvh bvh = {};
         sah::RtScene scene = {};
         bool built = false;
+        bool refitted = false;         // sah_rt_refit since the build: the boxes' pad is the device's (RtBuildState::max_abs_bits), not bvh.pad
         uint32_t row_begin = 0, row_end = 0;  // sah_rt_set_rows: the output rows the per-pixel ray generators write ((0, 0) = all)
         uint32_t num_bounces = 0;             // sah_rt_set_bounces: remaining_bounces of the GI generators' rays
     } rt;

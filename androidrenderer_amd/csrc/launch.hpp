@@ -96,6 +96,9 @@ hipError_t launch_noise_dirs(const PlaneArg& noise, const float* luts, float* ou
 hipError_t launch_probe_trace(const ProbeTraceArgs& a, const RtBvh& bvh, const RtScene& sc, hipStream_t s);
 hipError_t launch_rtgi_trace(const RtgiTraceArgs& a, const RtBvh& bvh, const RtScene& sc, hipStream_t s);
 
+// --- rt_refit.hip
+hipError_t launch_rt_refit(const RtScene& sc, const RtBvh& bvh, RtTriangle* tris, RtNodeGroup* nodes, RtBuildState* st, uint32_t* stats, hipStream_t s);
+
 // --- ipc.hip (direct exchange)
 struct IpcPeers {
     uint32_t* slot[SAH_IPC_MAX_WORLD];  // where to store (signal) / what to poll (wait); null: skipped

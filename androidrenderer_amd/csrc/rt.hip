@@ -19,6 +19,7 @@
 #include "octahedral.hpp"
 #include "prim_scan.hpp"
 #include "rt_args.hpp"
+#include "rt_build_common.hpp"
 #include "texture_sample.hpp"
 
 namespace sah {
@@ -27,9 +28,6 @@ namespace {
 SAH_DEV bool finite3r(float a, float b, float c) {
     const float inf = __builtin_inff();
     return __builtin_fabsf(a) < inf && __builtin_fabsf(b) < inf && __builtin_fabsf(c) < inf;
-}
-SAH_DEV bool finite3(const float v[3]) {
-    return __builtin_fabsf(v[0]) < __builtin_inff() && __builtin_fabsf(v[1]) < __builtin_inff() && __builtin_fabsf(v[2]) < __builtin_inff();
 }
 // v[k], k in {0, 1, 2}, as two selects on VALUES: written as a conditional expression on array elements it compiled to nested exec-mask
 // regions around single moves (eighteen per triangle test), and as selects of array elements to a dynamically indexed private array.
@@ -60,8 +58,6 @@ __global__ __launch_bounds__(1024) void k_rt_scan(const sah_primitive* prims, ui
         }
     }
 }
-
-SAH_DEV float mat_row3(const float* m, int r, float x, float y, float z) { return ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r]; }
 
 // one thread per triangle of every primitive: world-space vertices (the rasteriser's vertex stage), validity, scene extents
 __global__ __launch_bounds__(256) void k_rt_world(const RtScene sc, const uint32_t* tri_base, RtTriangle* out, RtBuildState* st) {
@@ -220,13 +216,6 @@ __global__ __launch_bounds__(256) void k_rt_sort_global(unsigned long long* keys
     if (a != a0) {
         keys[i] = a;
         keys[i | j] = b;
-    }
-}
-
-SAH_DEV void tri_box(const RtTriangle& r, float pad, float lo[3], float hi[3]) {
-    for (int c = 0; c < 3; c++) {
-        lo[c] = __builtin_fminf(__builtin_fminf(r.v0[c], r.v1[c]), r.v2[c]) - pad;
-        hi[c] = __builtin_fmaxf(__builtin_fmaxf(r.v0[c], r.v1[c]), r.v2[c]) + pad;
     }
 }
 
@@ -410,15 +399,6 @@ __global__ __launch_bounds__(768) void k_rt_refine(const RtTriangle* unsorted, u
         for (uint32_t pos = tid; pos < n_real; pos += 256u) keys[base + pos] = (keys[base + pos] & 0xffffffff00000000ull) | s_idx[s_perm[pos]];
 }
 
-// The lanes of a level's last group that stand for no node hold the box [+inf, +inf]^3, which no ray passes: RN((+inf - o) * inv) is
-// +inf on both planes of an axis where inv > 0 (entry = +inf > exit = min(tmax, +inf): make_ray keeps tmax FINITE, and the closest-hit
-// walk only ever lowers it) and -inf where inv < 0 (exit = -inf < entry); inv is never 0 or NaN for a ray that walks (non-finite rays do
-// not).  The walk then needs no "does this child exist" test.
-SAH_DEV void fill_absent(RtNodeGroup& g, uint32_t first_absent) {
-    if (first_absent == 0u) return;  // the group is full
-    for (uint32_t k = first_absent; k < kRtFanout; k++)
-        for (int c = 0; c < 3; c++) g.lo[c][k] = g.hi[c][k] = __builtin_inff();
-}
 // one thread per triangle: moves it into curve order and writes its padded box — the level-0 "node" of the hierarchy, so that the walk
 // meets a triangle's own box (part of the hit definition, sah_hip.h) like any other box
 __global__ __launch_bounds__(256) void k_rt_leaves(const RtTriangle* unsorted, const unsigned long long* keys, uint32_t num_tris, float pad,

@@ -43,6 +43,9 @@ MIP_CHAIN_EXPORTS = ["sah_mip_chain_generate"]
 MIP_CHAIN_MAX_LEVELS = 12     # SAH_MIP_CHAIN_MAX_LEVELS
 MIP_CHAIN_MAX_SOURCE = 4096   # SAH_MIP_CHAIN_MAX_SOURCE
 
+# the refit of the acceleration structure: exported, declared in include/sah_rt_refit.h (not sah_hip.h)
+RT_REFIT_EXPORTS = ["sah_rt_refit"]
+
 # the LPV mesh lights' entries: exported, declared in include/sah_lpv_mesh_lights.h (not sah_hip.h)
 ML_EXPORTS = ["sah_mesh_point_cloud", "sah_lpv_emissive_vpls", "sah_lpv_inject_emissive"]
 POINT_CLOUD_ON_SURFACE = 1    # SAH_POINT_CLOUD_ON_SURFACE
@@ -190,6 +193,7 @@ def load():
     lib.sah_vrsaa_measure_aliasing.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
     lib.sah_vrsaa_shading_rate_image.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.POINTER(_abi.ShadingRateParams)]
     lib.sah_mip_chain_generate.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32]
+    lib.sah_rt_refit.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.c_void_p]
     _lib = lib
     return lib
 
@@ -393,6 +397,13 @@ class Context:
         self._check(self.lib.sah_rt_build(self.handle, C.byref(scene), stats))
         self._rt_scene = scene  # keeps the descriptor's arrays alive
         return list(stats)
+
+    def rt_refit(self, scene, stats_ptr=None):
+        """sah_rt_refit (include/sah_rt_refit.h): refreshes the structure of the last rt_build from `scene` (_abi.SceneGeometry of device
+        addresses, same counts and topology; kept alive as rt_build keeps its scene) on the context's stream, without a host
+        synchronisation.  stats_ptr: device address of 4 words (present, absent, bits of S, 0) or None."""
+        self._check(self.lib.sah_rt_refit(self.handle, C.byref(scene), C.c_void_p(stats_ptr)))
+        self._rt_scene = scene
 
     def rtao(self, view, depth, normals, noise, samples_per_pixel, max_ray_distance, ao_out):
         self._check(self.lib.sah_rtao(self.handle, C.byref(view), C.byref(depth), C.byref(normals), C.byref(noise), samples_per_pixel, max_ray_distance,

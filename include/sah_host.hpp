@@ -31,6 +31,7 @@
 #include "sah_lpv_mesh_lights.h"
 #include "sah_mip_chain.h"
 #include "sah_motion_vectors.h"
+#include "sah_rt_refit.h"
 #include "sah_vrsaa.h"
 
 namespace sah {
@@ -664,17 +665,24 @@ struct ProceduralSky {
 
 // RenderCore/render/raytracing_scene.{hpp,cpp}: the TLAS over one instance per primitive.  add_primitive marks the scene dirty
 // (:15-43: the instance's transform, mask and opacity flags are already in sah_primitive), finalize() commits the pending build
-// (:45-170) — here one sah_rt_build over the scene's geometry pool.
+// (:45-170) — here one sah_rt_build over the scene's geometry pool.  The reference re-commits its TLAS with the instances' current
+// transforms over BLASes that persist; here the two levels are one structure, so a primitive that merely moved is reported with
+// update_primitive and finalize() refreshes the coordinates in place (sah_rt_refit: no host synchronisation, same ray results).
 class RaytracingScene {
 public:
+    enum class Commit { None, Build, Refit };  // what the last finalize() recorded
     explicit RaytracingScene(struct RenderScene& scene_in) : scene(scene_in) {}
     void add_primitive(uint32_t /*primitive index in scene.geometry.primitives*/) { is_dirty = true; }
+    // the primitive's model matrix or its vertices changed (already uploaded); topology and counts are as they were at the build
+    void update_primitive(uint32_t /*primitive index in scene.geometry.primitives*/) { is_moved = true; }
     void finalize(RenderGraph& graph);
     bool is_built() const { return built; }
+    Commit last_commit() const { return committed; }
 
 private:
     struct RenderScene& scene;
-    bool is_dirty = false, built = false;
+    bool is_dirty = false, is_moved = false, built = false;
+    Commit committed = Commit::None;
 };
 
 struct RenderScene {  // the slice of RenderCore/render/render_scene.hpp the hot path touches
@@ -769,9 +777,16 @@ public:
 };
 
 inline void RaytracingScene::finalize(RenderGraph& graph) {
-    if (!is_dirty) return;  // commit_tlas_builds: nothing to do
-    graph.add_pass(hip_pass("Build TLAS", [this](sah_ctx* ctx) { return sah_rt_build(ctx, &scene.geometry, nullptr); }));
-    is_dirty = false;
+    committed = Commit::None;
+    if (!is_dirty && !(built && is_moved)) return;  // commit_tlas_builds: nothing to do
+    if (is_dirty) {
+        graph.add_pass(hip_pass("Build TLAS", [this](sah_ctx* ctx) { return sah_rt_build(ctx, &scene.geometry, nullptr); }));
+        committed = Commit::Build;
+    } else {
+        graph.add_pass(hip_pass("Refit TLAS", [this](sah_ctx* ctx) { return sah_rt_refit(ctx, &scene.geometry, nullptr); }));
+        committed = Commit::Refit;
+    }
+    is_dirty = is_moved = false;  // (a build reads the current arrays: it covers every move before it)
     built = true;
 }
 

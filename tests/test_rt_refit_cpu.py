@@ -1,0 +1,159 @@
+"""CPU: sah_rt_refit's place in the ABI (a header of its own, an export list of its own, a NULL context refused without a device), and
+the checker of tests/rt_refit_check.py checked on structures synthesised from the reference: it passes a correct refit and names each
+planted fault."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from androidrenderer_amd import _abi, lib, synth
+from tests import rt_refit_check as rc
+from tests import rt_structure_check as check
+from tests import rt_structure_ref as ref
+from tests import rt_structure_scenes as scenes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_header_declares_exactly_sah_rt_refit():
+    text = open(os.path.join(ROOT, "include", "sah_rt_refit.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    assert '#include "sah_hip.h"' in text
+    assert re.findall(r"\b(sah_\w+)\s*\(", text) == ["sah_rt_refit"]
+    assert re.search(r"int\s+sah_rt_refit\s*\(\s*sah_ctx\s*\*\s*ctx\s*,\s*const\s+sah_scene_geometry\s*\*\s*scene\s*,\s*uint32_t\s*\*\s*stats\s*\)\s*;", text)
+    assert "sah_rt_refit" not in open(os.path.join(ROOT, "include", "sah_hip.h")).read()
+
+
+def test_library_exports_it_outside_the_base_list():
+    L = lib.load()
+    assert lib.RT_REFIT_EXPORTS == ["sah_rt_refit"] and hasattr(L, "sah_rt_refit")
+    assert "sah_rt_refit" not in lib.EXPORTS
+
+
+def test_null_context_is_refused_without_a_device():
+    L = lib.load()
+    scene = _abi.SceneGeometry()
+    assert L.sah_rt_refit(None, C.byref(scene), None) == _abi.SAH_ERR_INVALID_ARGUMENT
+    assert L.sah_rt_refit(None, None, None) == _abi.SAH_ERR_INVALID_ARGUMENT
+
+
+def test_refit_needs_a_structure():
+    """on a context without a build: the generators' error (here: a context without a device)"""
+    L = lib.load()
+    L.sah_debug_create_detached.argtypes = [C.POINTER(C.c_void_p)]
+    h = C.c_void_p()
+    if L.sah_debug_create_detached(C.byref(h)) == _abi.SAH_ERR_UNSUPPORTED:
+        return  # a HIP device is present: tests/test_rt_refit_gpu.py::test_arguments covers it there
+    scene = _abi.SceneGeometry()
+    assert L.sah_rt_refit(h, None, None) == _abi.SAH_ERR_INVALID_ARGUMENT
+    assert L.sah_rt_refit(h, C.byref(scene), None) == _abi.SAH_ERR_INVALID_ARGUMENT
+    assert b"sah_rt_build has not been called" in L.sah_last_error(h)
+    L.sah_destroy(h)
+
+
+def _pair(make, change, shuffle=True):
+    """(before, after arrays): a synthetic build of make(), and the arrays of change(make())"""
+    _, before = check.synthetic_structure(make().arrays(), synth.rng(3) if shuffle else None)
+    return before, change(make()).arrays()
+
+
+def _to_non_finite():
+    return _pair(lambda: scenes.soup(2049, seed=14), lambda m: scenes.non_finite())
+
+
+@pytest.mark.parametrize("scene", ["soup_1", "soup_5", "soup_2049", "many_primitives", "to_non_finite", "from_non_finite", "all_absent"])
+def test_checker_passes_a_correct_refit(scene):
+    if scene.startswith("soup_"):
+        n = int(scene[5:])
+        before, arrays = _pair(lambda: scenes.soup(n), rc.moved)
+    elif scene == "many_primitives":
+        before, arrays = _pair(lambda: scenes.many_primitives(1023), lambda m: rc.moved(m, displacement=0.0))
+    elif scene == "to_non_finite":
+        before, arrays = _to_non_finite()
+    elif scene == "from_non_finite":
+        before, arrays = _pair(scenes.non_finite, lambda m: scenes.soup(2049, seed=14))
+    else:
+        def all_nan(m):
+            for pos in m.positions:
+                pos[...] = np.nan
+            return m
+        before, arrays = _pair(lambda: scenes.soup(17), all_nan)
+    after = rc.synthetic_refit(before, arrays)
+    present = rc.check_refit(before, after, arrays)
+    if scene == "to_non_finite":
+        assert 150 < (~present).sum() < 450 and np.isinf(after["nodes"]).any() and np.isfinite(after["nodes"][-1][:, :, 0]).all()
+    elif scene == "all_absent":
+        assert not present.any() and (check._bits(after["nodes"]) == check.INF_BITS).all() and after["pad_bits"] == 0
+    else:
+        assert present.all()
+    s = max(np.float32(np.abs(after["tris"][k][present]).max()) for k in rc.VERTS) if present.any() else np.float32(0)
+    stats = [int(present.sum()), int((~present).sum()), int(np.array(s, np.float32).view(np.uint32)), 0]
+    rc.check_refit(before, after, arrays, stats)
+    with pytest.raises(AssertionError, match="stats"):
+        rc.check_refit(before, after, arrays, [stats[0], stats[1] + 1, stats[2], 0])
+
+
+def test_from_non_finite_the_left_out_triangles_stay_out():
+    before, arrays = _pair(scenes.non_finite, lambda m: scenes.soup(2049, seed=14))
+    assert before["num_tris"] < 2049 and rc.synthetic_refit(before, arrays)["num_tris"] == before["num_tris"]
+
+
+def test_soup_and_non_finite_share_topology_and_base_positions():
+    a, b = scenes.soup(2049, seed=14).arrays(), scenes.non_finite().arrays()
+    assert np.array_equal(a["indices"], b["indices"]) and a["primitives"].tobytes() == b["primitives"].tobytes()
+    same = a["positions"].view(np.uint32) == b["positions"].view(np.uint32)
+    assert (np.isfinite(b["positions"]) <= same).all() and not np.isfinite(b["positions"][~same]).any() and (~same).any()
+
+
+def test_checker_names_what_is_wrong():
+    def broken(change, message, pair=None):
+        before, arrays = pair() if pair else _pair(lambda: scenes.soup(2049), rc.moved)
+        after = rc.synthetic_refit(before, arrays)
+        after["tris"], after["nodes"], after["header"] = after["tris"].copy(), after["nodes"].copy(), list(after["header"])
+        change(before, after)
+        with pytest.raises(AssertionError, match=message):
+            rc.check_refit(before, after, arrays)
+
+    def stale_pad(before, after):  # the build's pad instead of this refit's
+        assert after["pad_bits"] != before["pad_bits"]
+        after["pad_bits"] = before["pad_bits"]
+    broken(stale_pad, "pad: ")
+
+    def swapped(before, after):  # a correct hierarchy over another order
+        order = np.arange(2049)
+        order[[5, 1030]] = order[[1030, 5]]
+        after["tris"] = after["tris"][order]
+    broken(swapped, "ids: 'triangle' changed at 2 positions")
+
+    def infinite_ancestor(before, after):  # max(hi) over an absent child's stored +inf
+        present, _ = rc.reference_triangles(after["tris"], scenes.non_finite().arrays())
+        i = int(np.flatnonzero(~present)[0])
+        after["nodes"][after["level_offset"][1] + i // 16, 1, :, (i // 4) % 4] = np.inf
+    broken(infinite_ancestor, "level 1 boxes: 1 of", _to_non_finite)
+
+    def absent_with_a_box(before, after):  # an absent triangle's lane keeps the finite box of the build
+        present, _ = rc.reference_triangles(after["tris"], scenes.non_finite().arrays())
+        i = int(np.flatnonzero(~present)[0])
+        after["nodes"][i // 4, :, :, i % 4] = before["nodes"][i // 4, :, :, i % 4]
+    broken(absent_with_a_box, "level 0 boxes: 1 of", _to_non_finite)
+
+    def old_vertices(before, after):
+        after["tris"]["v1"][77] = before["tris"]["v1"][77]
+    broken(old_vertices, "vertices: 1 present triangles are not the reference's \\(v1\\)")
+
+    def absent_not_zeroed(before, after):
+        present, _ = rc.reference_triangles(after["tris"], scenes.non_finite().arrays())
+        i = int(np.flatnonzero(~present)[0])
+        after["tris"]["v0"][i] = before["tris"]["v0"][i]
+    broken(absent_not_zeroed, "vertices: 1 absent triangles do not hold zeros", _to_non_finite)
+
+    def shrunk_upper(before, after):
+        off = after["level_offset"][3]
+        after["nodes"][off, 0, 0, 0] = np.nextafter(after["nodes"][off, 0, 0, 0], np.float32(np.inf))
+    broken(shrunk_upper, "level 3 boxes")
+
+    def trailing_lane(before, after):  # 2049 triangles: lanes 1 .. 3 of level 0's last group stand for nothing
+        after["nodes"][after["level_offset"][1] - 1, 1, 0, 2] = 0.0
+    broken(trailing_lane, "level 0: absent lanes")
