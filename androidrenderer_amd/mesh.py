@@ -147,6 +147,19 @@ class Mesh:
                 "material_textures": np.array(self.material_textures, dtype=np.uint32).reshape(-1, 4)}
 
 
+def _level_row_pitch(m):
+    """Row pitch in bytes of a texture level (h, w, 4) uint8, numpy or torch, from the array's row stride: a level given as a column slice of a
+    wider backing array has padded rows (include/sah_hip.h: sah_texture.mips[i].row_pitch_bytes).  Texels themselves must be packed."""
+    h, w = int(m.shape[0]), int(m.shape[1])
+    strides = tuple(s * m.element_size() for s in m.stride()) if hasattr(m, "data_ptr") else tuple(m.strides)
+    if tuple(m.shape[2:]) != (4,) or strides[2] != 1 or (w > 1 and strides[1] != 4):
+        raise ValueError(f"a texture level must be (h, w, 4) bytes with a texel stride of 4, got shape {tuple(m.shape)}, strides {strides}")
+    pitch = strides[0] if h > 1 else max(strides[0], w * 4)
+    if pitch < w * 4 or pitch % 4:
+        raise ValueError(f"texture level row stride {pitch} for {w} texels")
+    return pitch
+
+
 def geometry(arrays, keep=None):
     """sah_scene_geometry over `arrays` (numpy arrays -> host addresses for the oracle; torch uint8 tensors -> device addresses).
     `keep` collects the objects that must outlive the descriptor."""
@@ -173,7 +186,7 @@ def geometry(arrays, keep=None):
             for i, m in enumerate(mips):
                 on_device = on_device or hasattr(m, "data_ptr")
                 h, w = int(m.shape[0]), int(m.shape[1])
-                t.mips[i] = _abi.Plane(addr(m), w, h, w * 4, fmt)
+                t.mips[i] = _abi.Plane(addr(m), w, h, _level_row_pitch(m), fmt)
         if on_device:  # the kernels read the table itself: it has to live in device memory too
             import torch
             dev = textures[0][0][0].device

@@ -15,18 +15,23 @@ SENTINEL = 0xA5  # byte in the padding of a pitched plane / volume, and in rows 
 
 PLANE_FORMATS = {"color": _abi.FORMAT_R8G8B8A8_SRGB, "normals": _abi.FORMAT_R16G16B16A16_SFLOAT, "data": _abi.FORMAT_R8G8B8A8_UNORM,
                  "emission": _abi.FORMAT_R8G8B8A8_SRGB, "depth": _abi.FORMAT_D32_SFLOAT, "ao": _abi.FORMAT_R32_SFLOAT,
-                 "shadow_mask": _abi.FORMAT_R32_SFLOAT, "lit": _abi.FORMAT_R16G16B16A16_SFLOAT}
-VOLUME_FORMATS = {"lpv_r": _abi.FORMAT_R16G16B16A16_SFLOAT, "lpv_g": _abi.FORMAT_R16G16B16A16_SFLOAT, "lpv_b": _abi.FORMAT_R16G16B16A16_SFLOAT}
+                 "shadow_mask": _abi.FORMAT_R32_SFLOAT, "lit": _abi.FORMAT_R16G16B16A16_SFLOAT,
+                 "sky_t": _abi.FORMAT_R16G16B16A16_SFLOAT, "sky_v": _abi.FORMAT_R16G16B16A16_SFLOAT,
+                 "ray_buffer": _abi.FORMAT_R16G16B16A16_SFLOAT, "ray_irr": _abi.FORMAT_R16G16B16A16_SFLOAT, "noise": _abi.FORMAT_R8G8B8A8_UNORM}
+VOLUME_FORMATS = {"lpv_r": _abi.FORMAT_R16G16B16A16_SFLOAT, "lpv_g": _abi.FORMAT_R16G16B16A16_SFLOAT, "lpv_b": _abi.FORMAT_R16G16B16A16_SFLOAT,
+                  "shadowmap": _abi.FORMAT_D16_UNORM,  # (D32_SFLOAT when the array holds floats: the d32_shadowmap edit)
+                  "probe_irr": _abi.FORMAT_B10G11R11_UFLOAT_PACK32, "probe_depth": _abi.FORMAT_R16G16_SFLOAT, "probe_val": _abi.FORMAT_R8_UNORM}
 
 
 class Pitched:
     """A plane (H, W[, C]) or volume (D, H, W[, C]) stored in a backing buffer with a row pitch (and slice pitch) larger than the payload and an
-    optional byte offset of its base; every byte that is not payload holds SENTINEL.  Works on numpy arrays and on torch tensors alike.  The
+    optional byte offset of its base; every byte that is not payload holds `fill` (SENTINEL; 0xFF makes every half and float of the padding a
+    NaN, so that a padding read which reaches a result poisons it).  Works on numpy arrays and on torch tensors alike.  The
     descriptor is built by hand: images.plane() rightly refuses anything that is not tightly packed."""
 
-    def __init__(self, a, fmt, dims, row_pad=0, offset=0, slice_pad=0):
+    def __init__(self, a, fmt, dims, row_pad=0, offset=0, slice_pad=0, fill=SENTINEL):
         self.is_np = isinstance(a, np.ndarray)
-        self.logical, self.fmt, self.dims, self.offset = a, fmt, dims, offset
+        self.logical, self.fmt, self.dims, self.offset, self.fill = a, fmt, dims, offset, fill
         bpp = _abi.FORMAT_BPP[fmt]
         shape = tuple(a.shape)
         self.extent = shape[:dims]
@@ -39,14 +44,14 @@ class Pitched:
         size = offset + d * self.slice_pitch
         self._shape, self._strides = (d, h, self.row_bytes), (self.slice_pitch, self.row_pitch, 1)
         if self.is_np:
-            self.backing = np.full(size, SENTINEL, np.uint8)
+            self.backing = np.full(size, fill, np.uint8)
             mask = np.zeros(size, bool)
             self._payload(mask)[...] = True
             self.padding = ~mask
             self._payload(self.backing)[...] = np.ascontiguousarray(a).view(np.uint8).reshape(self._shape)
         else:
             import torch
-            self.backing = torch.full((size,), SENTINEL, dtype=torch.uint8, device=a.device)
+            self.backing = torch.full((size,), fill, dtype=torch.uint8, device=a.device)
             mask = torch.zeros(size, dtype=torch.bool, device=a.device)
             self._payload(mask)[...] = True
             self.padding = ~mask
@@ -71,13 +76,13 @@ class Pitched:
         return _abi.Volume(self.ptr, self.extent[2], self.extent[1], self.extent[0], self.row_pitch, self.slice_pitch, self.fmt)
 
     def read(self, dtype):
-        """the payload as a tight numpy array of `dtype`, in the logical array's shape"""
+        """a copy of the payload as a tight numpy array of `dtype`, in the logical array's shape"""
         p = self._payload(self.backing)
-        p = np.ascontiguousarray(p) if self.is_np else p.contiguous().cpu().numpy()
+        p = np.array(p) if self.is_np else p.contiguous().cpu().numpy()  # (a copy also where nothing is padded: later calls must not change it)
         return p.view(dtype).reshape(tuple(self.logical.shape))
 
     def padding_intact(self):
-        return bool((self.backing[self.padding] == SENTINEL).all())
+        return bool((self.backing[self.padding] == self.fill).all())
 
 
 # ---- view edits: a raw ViewData edited in place, after the camera's own update_transforms() -------------------------------------------
@@ -223,7 +228,8 @@ class MatrixFrame(util.LightingFrame):
         if spec is None:
             return a
         if k in VOLUME_FORMATS:
-            return Pitched(a, VOLUME_FORMATS[k], 3, **spec)
+            fmt = _abi.FORMAT_D32_SFLOAT if k == "shadowmap" and str(a.dtype).endswith("float32") else VOLUME_FORMATS[k]
+            return Pitched(a, fmt, 3, **spec)
         return Pitched(a, PLANE_FORMATS[k], 2, **spec) if k in PLANE_FORMATS else a
 
     def host_arrays(self):
@@ -253,12 +259,25 @@ class MatrixFrame(util.LightingFrame):
             d.ao.contents = arrays["ao"].plane()
         if isinstance(arrays.get("shadow_mask"), Pitched):
             d.shadow_mask.contents = arrays["shadow_mask"].plane()
-        if self.gi_kind == _abi.GI_LPV:
-            gi = d.gi.contents
-            for k, field in (("lpv_r", "lpv_red"), ("lpv_g", "lpv_green"), ("lpv_b", "lpv_blue")):
+        if isinstance(arrays.get("shadowmap"), Pitched):
+            sm = arrays["shadowmap"].volume()
+            d.shadowmap = C.pointer(sm)
+            keep.append(sm)
+        if self.has_sky:
+            sky = d.sky.contents
+            for k, field in (("sky_t", "transmittance"), ("sky_v", "sky_view")):
                 if isinstance(arrays[k], Pitched):
+                    setattr(sky, field, arrays[k].plane())
+        if self.gi_kind != _abi.GI_NONE:
+            gi = d.gi.contents
+            for k, field in (("lpv_r", "lpv_red"), ("lpv_g", "lpv_green"), ("lpv_b", "lpv_blue"), ("probe_irr", "probe_irradiance"),
+                             ("probe_depth", "probe_depth"), ("probe_val", "probe_validity")):
+                if isinstance(arrays.get(k), Pitched):
                     setattr(gi, field, arrays[k].volume())
-            if self.lpv_exposure is not None:
+            for k, field in (("ray_buffer", "ray_buffer"), ("ray_irr", "ray_irradiance"), ("noise", "noise")):
+                if isinstance(arrays.get(k), Pitched):
+                    setattr(gi, field, arrays[k].plane())
+            if self.gi_kind == _abi.GI_LPV and self.lpv_exposure is not None:
                 gi.lpv_exposure = self.lpv_exposure
         return d, keep
 

@@ -172,3 +172,104 @@ def test_hip_probe_update_with_adjacent_probes_in_one_list(hip_ctx, order):
         got = a_t[k].cpu().numpy()
         ref = want[k].view(np.uint16) if want[k].dtype == np.float16 else want[k]
         assert np.array_equal(got.view(ref.dtype).reshape(ref.shape), ref), f"atlas {k} differs"
+
+
+# ---- the five atlases, three texel sizes, on pitched and offset volumes (tests/layouts.py) ------------------------------------------------
+ATLAS_FORMATS = {"rtgi": (_abi.FORMAT_B10G11R11_UFLOAT_PACK32, 3), "light_cache": (_abi.FORMAT_B10G11R11_UFLOAT_PACK32, 3), "depth": (_abi.FORMAT_R16G16_SFLOAT, 3),
+                 "average": (_abi.FORMAT_B10G11R11_UFLOAT_PACK32, 3), "validity": (_abi.FORMAT_R8_UNORM, 3)}
+# csrc/api_probes.cpp: probe_vol_ok — every base a multiple of 4; row and slice pitch multiples of 4 except for the R8 validity atlas, which
+# takes any.  A: the smallest; B: no multiples of 16, slice paddings that are no multiples of the row pitch
+ATLAS_LAYOUTS = {
+    "A": {"rtgi": dict(row_pad=4, offset=4, slice_pad=4), "light_cache": dict(row_pad=4, slice_pad=4), "depth": dict(row_pad=4, offset=4),
+          "average": dict(row_pad=4, offset=4, slice_pad=4), "validity": dict(row_pad=1, offset=4, slice_pad=1)},
+    "B": {"rtgi": dict(row_pad=20, slice_pad=100), "light_cache": dict(row_pad=12, offset=8, slice_pad=52), "depth": dict(row_pad=36, offset=4, slice_pad=20),
+          "average": dict(row_pad=28, slice_pad=44), "validity": dict(row_pad=3, offset=8, slice_pad=7)},
+}
+# the destination of a copy: paddings that differ from the source's in every atlas
+ATLAS_LAYOUTS_DST = {
+    "A": {"rtgi": dict(row_pad=8), "light_cache": dict(row_pad=4, offset=4, slice_pad=8), "depth": dict(row_pad=8, slice_pad=4),
+          "average": dict(row_pad=8), "validity": dict(row_pad=2, slice_pad=3)},
+    "B": {"rtgi": dict(row_pad=44, offset=4, slice_pad=36), "light_cache": dict(row_pad=28, slice_pad=20), "depth": dict(row_pad=12, slice_pad=132),
+          "average": dict(row_pad=4, offset=12, slice_pad=20), "validity": dict(row_pad=5, offset=4, slice_pad=11)},
+}
+
+
+def atlases_desc(p):
+    """{name: tests.layouts.Pitched} -> _abi.ProbeAtlases"""
+    return _abi.ProbeAtlases(*[p[k].volume() for k in ("rtgi", "light_cache", "depth", "average", "validity")])
+
+
+def _device_atlases(a, spec):
+    from tests import layouts
+    return layouts.wrap({k: util.to_torch(v.view(np.uint16) if v.dtype == np.float16 else v) for k, v in a.items()}, ATLAS_FORMATS, spec)
+
+
+def _read_atlases(p):
+    return {k: p[k].read({1: np.uint8, 2: np.uint16, 4: np.uint32}[p[k].logical.element_size()]) for k in p}
+
+
+def _assert_atlases(got, want, what):
+    for k in want:
+        ref = want[k].view(np.uint16) if want[k].dtype == np.float16 else want[k]
+        g = got[k].read(ref.dtype).reshape(ref.shape)
+        assert np.array_equal(g, ref), f"{what}: atlas {k}: {int((g != ref).sum())} values differ"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["A", "B"])
+def test_hip_probe_copy_on_pitched_atlases(hip_ctx, layout):
+    """the second movement of test_hip_probe_copy_matches_oracle (scrolls, new probes, a cascade scrolled out); source and destination atlases
+    padded differently"""
+    import torch
+    from tests import layouts
+    movement = [[1.7, 0, 0], [-0.9, 0.9, 0], [0, 0, 0], [0, 9, 0]]
+    src, _, _ = synth.probe_maintenance_inputs(seed=25, num_probes=4)
+    src["rtgi"][3, 10, 20] = 0x7c1 | (0x7e3 << 11) | (0x3ff << 22)
+    src["rtgi"][3, 10, 21] = 0x7c0 | (0x7c0 << 11) | (0x3e0 << 22)
+    dst0 = synth.probe_maintenance_inputs(seed=26, num_probes=4)[0]
+    want = _copy_arrays(dst0)
+    _oracle_copy(src, want, movement)
+    results = []
+    for s_spec, d_spec in ((None, None), (ATLAS_LAYOUTS[layout], ATLAS_LAYOUTS_DST[layout])):
+        s_t, d_t = _device_atlases(src, s_spec), _device_atlases(dst0, d_spec)
+        hip_ctx.probe_copy(atlases_desc(s_t), atlases_desc(d_t), movement)
+        torch.cuda.synchronize()
+        layouts.assert_padding_intact(s_t, d_t, what="probe_copy")
+        layouts.assert_inputs_unchanged(s_t, what="probe_copy")
+        _assert_atlases(d_t, want, "probe_copy")
+        results.append(_read_atlases(d_t))
+    for k in results[0]:
+        assert np.array_equal(results[0][k], results[1][k]), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["A", "B"])
+@pytest.mark.parametrize("case", ["48_probes", "adjacent"])
+def test_hip_probe_update_on_pitched_atlases(hip_ctx, case, layout):
+    """48 scattered probes, and the clump of probes whose odd-sized blocks store into one another's cells (one list order of
+    test_hip_probe_update_with_adjacent_probes_in_one_list); the trace results are padded as well"""
+    import torch
+    from tests import layouts
+    if case == "48_probes":
+        atl, trace, ids = synth.probe_maintenance_inputs(seed=27, num_probes=48)
+    else:
+        atl, trace, _ = synth.probe_maintenance_inputs(seed=29, num_probes=8)
+        clump = np.array([(5, 5, 3), (6, 5, 3), (5, 6, 3), (6, 6, 3), (20, 9, 30), (21, 9, 30), (22, 9, 30), (0, 0, 0)], dtype=np.uint32)
+        ids = np.ascontiguousarray(clump[[3, 0, 6, 1, 7, 4, 2, 5]])
+    want = _copy_arrays(atl)
+    _oracle_update(want, trace, ids)
+    assert not np.array_equal(want["depth"].view(np.uint16), atl["depth"].view(np.uint16))
+    tr_spec = {"A": dict(row_pad=8, offset=8, slice_pad=8), "B": dict(row_pad=24, slice_pad=40)}[layout]
+    ids_t = torch.from_numpy(ids.view(np.int32)).cuda()
+    results = []
+    for spec, ts in ((None, None), (ATLAS_LAYOUTS[layout], tr_spec)):
+        a_t = _device_atlases(atl, spec)
+        tr = layouts.pitched(util.to_torch(trace.view(np.uint16)), _abi.FORMAT_R16G16B16A16_SFLOAT, 3, ts, fill=layouts.NAN_FILL)
+        hip_ctx.probe_update(atlases_desc(a_t), tr.volume(), ids_t.data_ptr(), len(ids))
+        torch.cuda.synchronize()
+        layouts.assert_padding_intact(a_t, tr, what="probe_update")
+        layouts.assert_inputs_unchanged(tr, what="probe_update")
+        _assert_atlases(a_t, want, "probe_update")
+        results.append(_read_atlases(a_t))
+    for k in results[0]:
+        assert np.array_equal(results[0][k], results[1][k]), k

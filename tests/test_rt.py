@@ -33,9 +33,18 @@ class RtCase:
         self.gbuffer = gbuffer
         self.sun = scene.DirectionalLight(shadow_mode=_abi.SHADOW_MODE_RT, num_shadow_samples=4.0)
 
+    @staticmethod
+    def _plane(a, fmt):
+        """descriptor of a tight array, or of an image laid out by hand (tests.layouts.Pitched)"""
+        return a.plane() if hasattr(a, "padding_intact") else images.plane(a, fmt)
+
+    @staticmethod
+    def _volume(a, fmt):
+        return a.volume() if hasattr(a, "padding_intact") else images.volume(a, fmt)
+
     def planes(self, depth, normals, noise, out):
-        return (images.plane(depth, _abi.FORMAT_D32_SFLOAT), images.plane(normals, _abi.FORMAT_R16G16B16A16_SFLOAT),
-                images.plane(noise, _abi.FORMAT_R8G8B8A8_UNORM), images.plane(out, _abi.FORMAT_R32_SFLOAT))
+        return (self._plane(depth, _abi.FORMAT_D32_SFLOAT), self._plane(normals, _abi.FORMAT_R16G16B16A16_SFLOAT),
+                self._plane(noise, _abi.FORMAT_R8G8B8A8_UNORM), self._plane(out, _abi.FORMAT_R32_SFLOAT))
 
     def oracle_rtao(self, spp=1, radius=1.0):
         out = np.zeros((self.height, self.width), np.float32)
@@ -58,11 +67,12 @@ class RtCase:
         return self._gi
 
     gi_seed = 3
+    pad_texture_levels = False  # set before the first device(): the HIP side's texture levels get padded rows
     cascade_centre = (0.0, 1.0, 0.0)
     cascade_spacing = 0.5
 
     def _sky(self, a):
-        return _abi.SkyLuts(images.plane(a["sky_t"], _abi.FORMAT_R16G16B16A16_SFLOAT), images.plane(a["sky_v"], _abi.FORMAT_R16G16B16A16_SFLOAT))
+        return _abi.SkyLuts(self._plane(a["sky_t"], _abi.FORMAT_R16G16B16A16_SFLOAT), self._plane(a["sky_v"], _abi.FORMAT_R16G16B16A16_SFLOAT))
 
     def probe_desc(self, a, probes_ptr, num_probes, noise, results):
         """_abi.ProbeTraceDesc over host or device arrays `a` (gi_arrays() keys); returns (desc, keepalive)"""
@@ -71,14 +81,14 @@ class RtCase:
             d.cascades[c].probe_spacing = spacing
             for i in range(3):
                 d.cascades[c].min[i] = cmin[i]
-        sky, nz = self._sky(a), images.plane(noise, _abi.FORMAT_R8G8B8A8_UNORM)
+        sky, nz = self._sky(a), self._plane(noise, _abi.FORMAT_R8G8B8A8_UNORM)
         d.probes_to_update, d.num_probes = probes_ptr, num_probes
         d.sun, d.sky, d.noise = C.pointer(self.sun.constants), C.pointer(sky), C.pointer(nz)
-        d.probe_irradiance = images.volume(a["irr"], _abi.FORMAT_B10G11R11_UFLOAT_PACK32)
-        d.probe_depth = images.volume(a["pdepth"], _abi.FORMAT_R16G16_SFLOAT)
-        d.probe_validity = images.volume(a["val"], _abi.FORMAT_R8_UNORM)
+        d.probe_irradiance = self._volume(a["irr"], _abi.FORMAT_B10G11R11_UFLOAT_PACK32)
+        d.probe_depth = self._volume(a["pdepth"], _abi.FORMAT_R16G16_SFLOAT)
+        d.probe_validity = self._volume(a["val"], _abi.FORMAT_R8_UNORM)
         d.probe_size[0], d.probe_size[1] = 5, 6
-        d.trace_results = images.volume(results, _abi.FORMAT_R16G16B16A16_SFLOAT)
+        d.trace_results = self._volume(results, _abi.FORMAT_R16G16B16A16_SFLOAT)
         return d, (sky, nz)
 
     def oracle_probe_trace(self, probes):
@@ -106,6 +116,10 @@ class RtCase:
             import torch
             from androidrenderer_amd.frame import to_torch
             dev_arrays = mesh.to_device(self.arrays)
+            self.texture_backing = []
+            if self.pad_texture_levels:  # every level a column slice of a wider array: padded rows
+                from tests import layouts
+                dev_arrays["textures"], self.texture_backing = layouts.pad_texture_levels(dev_arrays["textures"])
             keep = []
             self._dev = {"geo": mesh.geometry(dev_arrays, keep), "keep": keep,
                          "depth": torch.from_numpy(self.gbuffer["depth"]).cuda(), "normals": torch.from_numpy(self.gbuffer["normals"].view(np.int16)).cuda(),
@@ -154,6 +168,59 @@ class RtCase:
         ctx.sun_shadow_mask(self.view.gpu_data, self.sun.constants, d, n, z, o)
         torch.cuda.synchronize()
         return out.cpu().numpy()
+
+    # ---- the generators on pitched, offset images (tests/layouts.py) ----
+    LAYOUT_FORMATS = {"depth": (_abi.FORMAT_D32_SFLOAT, 2), "normals": (_abi.FORMAT_R16G16B16A16_SFLOAT, 2), "noise": (_abi.FORMAT_R8G8B8A8_UNORM, 2),
+                      "out": (_abi.FORMAT_R32_SFLOAT, 2), "ray_buffer": (_abi.FORMAT_R16G16B16A16_SFLOAT, 2), "ray_irradiance": (_abi.FORMAT_R16G16B16A16_SFLOAT, 2),
+                      "sky_t": (_abi.FORMAT_R16G16B16A16_SFLOAT, 2), "sky_v": (_abi.FORMAT_R16G16B16A16_SFLOAT, 2),
+                      "irr": (_abi.FORMAT_B10G11R11_UFLOAT_PACK32, 3), "pdepth": (_abi.FORMAT_R16G16_SFLOAT, 3), "val": (_abi.FORMAT_R8_UNORM, 3),
+                      "trace_results": (_abi.FORMAT_R16G16B16A16_SFLOAT, 3)}
+    OUT_F32, OUT_F16 = -7.0, 0x7bff  # payload of an output before the call, as in the tight runs above
+
+    def hip_pitched(self, ctx, entry, spec=None, spp=1, radius=1.0, probes=None):
+        """One run of `entry` ("rtao", "mask", "rtgi", "probe_trace") with every image it takes laid out as `spec` says ({name: dict(row_pad=,
+        offset=, slice_pad=)}, names as in LAYOUT_FORMATS; no entry: tight).  The padding of the inputs reads as NaN.  Afterwards no padding byte
+        and no input may have changed.  -> ({name: output as a tight numpy array}, {name: the wrapped outputs})"""
+        import torch
+        from tests import layouts
+        dv, spec = self.device(), spec or {}
+
+        def img(key, a, fill=layouts.NAN_FILL):
+            fmt, dims = self.LAYOUT_FORMATS[key]
+            return layouts.pitched(a, fmt, dims, spec.get(key), fill)
+
+        def new(key, shape, value, dtype):
+            return img(key, torch.full(shape, value, dtype=dtype, device="cuda"), layouts.SENTINEL)
+        ins = {k: img(k, dv[k]) for k in ("depth", "normals", "noise")}
+        hw = (self.height, self.width)
+        if entry in ("rtao", "mask"):
+            outs = {"out": new("out", hw, self.OUT_F32, torch.float32)}
+            d, n, z, o = self.planes(ins["depth"], ins["normals"], ins["noise"], outs["out"])
+            if entry == "rtao":
+                ctx.rtao(self.view.gpu_data, d, n, z, spp, radius, o)
+            else:
+                ctx.sun_shadow_mask(self.view.gpu_data, self.sun.constants, d, n, z, o)
+            dtypes = {"out": np.float32}
+        else:
+            ins.update({k: img(k, dv["gi"][k]) for k in ("sky_t", "sky_v")})
+            if entry == "rtgi":
+                outs = {k: new(k, hw + (4,), self.OUT_F16, torch.int16) for k in ("ray_buffer", "ray_irradiance")}
+                d, n, z, _ = self.planes(ins["depth"], ins["normals"], ins["noise"], torch.zeros((1, 1), dtype=torch.float32, device="cuda"))
+                ctx.rtgi_trace(self.view.gpu_data, self.sun.constants, self._sky(ins), d, n, z, outs["ray_buffer"].plane(), outs["ray_irradiance"].plane())
+                dtypes = {"ray_buffer": np.float16, "ray_irradiance": np.float16}
+            else:
+                assert entry == "probe_trace"
+                ins.update({k: img(k, dv["gi"][k]) for k in ("irr", "pdepth", "val")})
+                probes = np.ascontiguousarray(probes, np.uint32)
+                pd = torch.from_numpy(probes.view(np.int32).reshape(-1)).cuda()
+                outs = {"trace_results": new("trace_results", (len(probes), 20, 20, 4), self.OUT_F16, torch.int16)}
+                desc, keep = self.probe_desc(ins, pd.data_ptr(), len(probes), ins["noise"], outs["trace_results"])
+                ctx.probe_trace(desc)
+                dtypes = {"trace_results": np.float16}
+        torch.cuda.synchronize()
+        layouts.assert_padding_intact(ins, outs, what=entry)
+        layouts.assert_inputs_unchanged(ins, what=entry)
+        return {k: outs[k].read(dtypes[k]) for k in outs}, outs
 
 
 def _same_bits(a, b):
@@ -806,3 +873,125 @@ def test_hip_row_windows_trace_the_same_pixels(hip_ctx):
         hip_ctx.rt_set_rows(0, 0)
         torch.cuda.synchronize()
     assert np.array_equal(case.hip_rtao(hip_ctx, 1, 4.0), full[0])
+
+
+# ---- the generators on pitched, offset images ----------------------------------------------------------------------------------------
+# every image of a call has a padding of its own.  A: the smallest the argument checks admit (csrc/api_rt.cpp: plane_fmt, sah_probe_trace —
+# texel-size multiples; the probe atlases are not checked there, the R8 validity atlas takes a single byte); B: multiples of the texel size
+# that are no multiples of 16, slice paddings that are no multiples of the row pitch
+RT_LAYOUTS = {
+    "A": {"depth": dict(row_pad=4, offset=4), "normals": dict(row_pad=8, offset=8), "noise": dict(row_pad=4), "out": dict(row_pad=4, offset=4),
+          "ray_buffer": dict(row_pad=8), "ray_irradiance": dict(row_pad=8, offset=8), "sky_t": dict(row_pad=8, offset=8), "sky_v": dict(row_pad=8),
+          "irr": dict(row_pad=4, offset=4, slice_pad=4), "pdepth": dict(row_pad=4, slice_pad=4), "val": dict(row_pad=1, offset=4, slice_pad=1),
+          "trace_results": dict(row_pad=8, offset=8, slice_pad=8)},
+    "B": {"depth": dict(row_pad=20), "normals": dict(row_pad=24, offset=8), "noise": dict(row_pad=12, offset=4), "out": dict(row_pad=36, offset=12),
+          "ray_buffer": dict(row_pad=40, offset=8), "ray_irradiance": dict(row_pad=56), "sky_t": dict(row_pad=24), "sky_v": dict(row_pad=72, offset=24),
+          "irr": dict(row_pad=20, slice_pad=100), "pdepth": dict(row_pad=12, offset=4, slice_pad=52), "val": dict(row_pad=3, offset=4, slice_pad=7),
+          "trace_results": dict(row_pad=24, offset=8, slice_pad=40)},
+}
+RT_WINDOW = (10, 23)
+_golden_layout_case = []
+
+
+def _golden_case():
+    """the golden ray-tracing scene at 64 x 36 (its G-buffer rasterised by the oracle) and the oracle's planes, once per session"""
+    if not _golden_layout_case:
+        m, view, sun, noise = util.golden_rt_scene()
+        case = RtCase(m, 64, 36, view=view)
+        case.noise, case.sun = noise, sun
+        assert case.sun.constants.num_shadow_samples == 3.0
+        rb, ri = case.oracle_rtgi()
+        want = {"rtao": {"out": case.oracle_rtao(2, 3.0)}, "mask": {"out": case.oracle_mask()}, "rtgi": {"ray_buffer": rb, "ray_irradiance": ri}}
+        assert (case.gbuffer["depth"] == 0).any() and (case.gbuffer["depth"][RT_WINDOW[0]:RT_WINDOW[1]] != 0).any()
+        _golden_layout_case.append((case, want))
+    return _golden_layout_case[0]
+
+
+def _bits(a):
+    return a.view({2: np.uint16, 4: np.uint32}[a.dtype.itemsize])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["A", "B"])
+@pytest.mark.parametrize("window", [None, RT_WINDOW])
+@pytest.mark.parametrize("entry", ["rtao", "mask", "rtgi"])
+def test_hip_generators_on_pitched_planes(hip_ctx, entry, window, layout):
+    """rtao, the sun's shadow mask (three samples) and the GI ray per pixel with padded depth, normals, noise, sky LUTs and outputs: the oracle's
+    planes, the tight run's planes, nothing written outside the payload — whole frame and under sah_rt_set_rows, where the rows outside the
+    window (and, for the GI rays, the sky pixels) keep what the planes held"""
+    import torch
+    from tests import layouts
+    case, want = _golden_case()
+    case.hip_build(hip_ctx)
+    payload = np.uint16(case.OUT_F16) if entry == "rtgi" else np.float32(case.OUT_F32).view(np.uint32)
+    try:
+        if window:
+            hip_ctx.rt_set_rows(*window)
+        tight, _ = case.hip_pitched(hip_ctx, entry, None, spp=2, radius=3.0)
+        got, _ = case.hip_pitched(hip_ctx, entry, RT_LAYOUTS[layout], spp=2, radius=3.0)
+    finally:
+        hip_ctx.rt_set_rows(0, 0)
+        torch.cuda.synchronize()
+    r0, r1 = window or (0, case.height)
+    for k, ref in want[entry].items():
+        g, t, w = _bits(got[k]), _bits(tight[k]), _bits(ref)
+        assert np.array_equal(g[r0:r1], w[r0:r1]), f"{entry} {k}: {int((g[r0:r1] != w[r0:r1]).sum())} values differ from the oracle"
+        assert np.array_equal(g, t), f"{entry} {k}"
+        layouts.assert_rows_untouched(payload, g, r0, r1, what=f"{entry} {k}")
+        if entry == "rtgi":
+            assert (g[case.gbuffer["depth"] == 0] == payload).all()  # sky pixels are skipped
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["A", "B"])
+def test_hip_probe_trace_on_pitched_volumes_feeds_probe_update(hip_ctx, layout):
+    """the twelve golden probes traced into a trace_results volume with padded rows and slices, from padded irradiance / depth / validity
+    atlases, noise and sky LUTs; the padded results then go straight into sah_probe_update (padded atlases again), as
+    test_hip_probe_trace_feeds_probe_update chains them"""
+    import torch
+    from tests import layouts
+    from tests.test_probes import ATLAS_FORMATS, ATLAS_LAYOUTS, atlases_desc
+    case, _ = _golden_case()
+    case.hip_build(hip_ctx)
+    probes = util.golden_rt_gi_inputs()["probes"]
+    want = case.oracle_probe_trace(probes)
+    tight, _ = case.hip_pitched(hip_ctx, "probe_trace", None, probes=probes)
+    got, outs = case.hip_pitched(hip_ctx, "probe_trace", RT_LAYOUTS[layout], probes=probes)
+    assert np.array_equal(_bits(got["trace_results"]), _bits(want))
+    assert np.array_equal(_bits(got["trace_results"]), _bits(tight["trace_results"]))
+    # ... into the update: the probes inside the 32 x 32 x 32 grid (the twelfth lies outside the cascades)
+    n = 11
+    ids = np.ascontiguousarray(probes[:n])
+    assert (ids < 32).all()
+    atl = synth.probe_maintenance_inputs(seed=31, num_probes=n)[0]
+    o_atl = {k: v.copy() for k, v in atl.items()}
+    tv = images.volume(np.ascontiguousarray(want.view(np.uint16)), _abi.FORMAT_R16G16B16A16_SFLOAT)
+    assert util.oracle().orc_probe_update(C.byref(util.probe_atlases_desc(o_atl)), C.byref(tv), ids.ctypes.data, n) == 0
+    h_atl = layouts.wrap({k: util.to_torch(v.view(np.uint16) if v.dtype == np.float16 else v) for k, v in atl.items()}, ATLAS_FORMATS, ATLAS_LAYOUTS[layout])
+    pd = torch.from_numpy(ids.view(np.int32).reshape(-1)).cuda()
+    trace = outs["trace_results"]
+    hip_ctx.probe_update(atlases_desc(h_atl), trace.volume(), pd.data_ptr(), n)
+    torch.cuda.synchronize()
+    layouts.assert_padding_intact(h_atl, trace, what="probe_update")
+    assert np.array_equal(_bits(trace.read(np.float16)), _bits(want))  # the update only reads the results
+    for k in o_atl:
+        ref = o_atl[k].view(np.uint16) if o_atl[k].dtype == np.float16 else o_atl[k]
+        assert np.array_equal(h_atl[k].read(ref.dtype).reshape(ref.shape), ref), k
+
+
+@pytest.mark.gpu
+def test_hip_hit_stages_sample_texture_levels_with_padded_rows(hip_ctx):
+    """the golden scene's textures (base colour alpha in the shadow rays' any-hit stage, every slot in the GI rays' hit stage) from levels whose
+    row pitch is larger than their payload: the oracle's planes, i.e. those from tight levels"""
+    from tests import layouts
+    _, want = _golden_case()
+    m, view, sun, noise = util.golden_rt_scene()
+    case = RtCase(m, 64, 36, view=view)
+    case.noise, case.sun, case.pad_texture_levels = noise, sun, True
+    case.hip_build(hip_ctx)
+    assert case.texture_backing
+    mask = case.hip_mask(hip_ctx)
+    rb, ri = case.hip_rtgi(hip_ctx)
+    layouts.assert_texture_padding_intact(case.texture_backing)
+    assert _same_bits(mask, want["mask"]["out"])
+    assert np.array_equal(_bits(rb), _bits(want["rtgi"]["ray_buffer"])) and np.array_equal(_bits(ri), _bits(want["rtgi"]["ray_irradiance"]))

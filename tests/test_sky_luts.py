@@ -90,3 +90,43 @@ def test_generated_luts_feed_the_sky_fill(hip_ctx):
     assert d.max() <= 1, util.report_ulp("lighting with generated sky LUTs", d)
     sky = f.arrays["depth"] == 0
     assert sky.any() and (got[sky][:, :3] != 0).any()
+
+
+# ---- pitched, offset targets (tests/layouts.py) -------------------------------------------------------------------------------------------
+# RGBA16F: base and pitch multiples of 8 (csrc/ctx.hpp: rgba16f_ok); R32F: of 4 (csrc/api_probes.cpp: sah_ao_clear)
+SKY_LAYOUTS = {"A": [dict(row_pad=8, offset=8), dict(row_pad=8), dict(row_pad=8, offset=16)],
+               "B": [dict(row_pad=24), dict(row_pad=40, offset=8), dict(row_pad=56, offset=24)]}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["A", "B"])
+def test_hip_sky_luts_into_pitched_planes(hip_ctx, layout):
+    import torch
+    from tests import layouts
+    want = _oracle_luts(LIGHT)
+    results = []
+    for specs in ([None] * 3, SKY_LAYOUTS[layout]):
+        dev = [layouts.pitched(torch.full(a.shape, 0x7e01, dtype=torch.int16, device="cuda"), _abi.FORMAT_R16G16B16A16_SFLOAT, 2, s, fill=layouts.NAN_FILL)
+               for a, s in zip(want, specs)]
+        hip_ctx.sky_update_luts(dev[0].plane(), dev[1].plane(), dev[2].plane(), LIGHT)
+        torch.cuda.synchronize()
+        layouts.assert_padding_intact(dev, what="sky_update_luts")
+        results.append([p.read(np.uint16) for p in dev])
+    for name, w, t, g in zip(("transmittance", "multiscattering", "sky_view"), want, *results):
+        d = util.f16_ulp_diff(g, w)
+        assert d.max() <= 1, util.report_ulp(name, d)            # test_hip_sky_luts_match_oracle's bar
+        assert (d > 0).mean() < 1e-3, util.report_ulp(name, d)
+        assert np.array_equal(g, t), name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("spec", [dict(row_pad=4, offset=4), dict(row_pad=20, offset=12)])
+def test_hip_ao_clear_into_a_pitched_plane(hip_ctx, spec):
+    import torch
+    from tests import layouts
+    for w, h in ((161, 91), (9, 5)):
+        ao = layouts.pitched(torch.full((h, w), 7.0, dtype=torch.float32, device="cuda"), _abi.FORMAT_R32_SFLOAT, 2, spec)
+        hip_ctx.ao_clear(ao.plane())
+        torch.cuda.synchronize()
+        layouts.assert_padding_intact(ao, what="ao_clear")
+        assert (ao.read(np.float32).view(np.uint32) == np.float32(1.0).view(np.uint32)).all()
