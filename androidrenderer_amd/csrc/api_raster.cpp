@@ -146,6 +146,8 @@ int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, sah::
         HIP_TRY(ctx, launch_raster_tiles(a, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(r.host_counters, a.counters, C_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const uint32_t report[4] = {(uint32_t)attempt + 1u, a.record_capacity, a.clip_capacity, a.pairs_capacity};
+        std::memcpy(r.last_pass, report, sizeof(report));
         const uint32_t* hc = r.host_counters;
         const size_t total_tris = hc[C_TRIS], clipped = hc[C_CLIPPED], pairs = hc[C_PAIRS];
         if (total_tris >= (1u << 28)) return fail(ctx, SAH_ERR_UNSUPPORTED, "rasteriser: more than 2^28 triangles in one pass");
@@ -319,6 +321,14 @@ int sah_motion_vectors_render(sah_ctx* ctx, const sah_scene_geometry* scene, con
     a.mv_depth = parg(depth);
     a.out_motion = parg(motion_vectors);
     return run(ctx, a, scene, sah::RasterPass::Motion, stats);
+}
+
+// Debug / test hook: how the last rasteriser call of the context (shadow, G-buffer, RSM or motion vectors) went through run() — recorded
+// host side behind the synchronisation every attempt ends with; no device work.  All zero before the first call.
+int sah_debug_raster_last_pass(sah_ctx* ctx, uint32_t out[4]) {
+    if (!ctx || !out) return SAH_ERR_INVALID_ARGUMENT;
+    std::memcpy(out, ctx->raster.last_pass, sizeof(ctx->raster.last_pass));
+    return SAH_OK;
 }
 
 int sah_lpv_extract_vpls(sah_ctx* ctx, const sah_rsm_targets* rsm, const sah_lpv_cascade_matrices* cascades, uint32_t cascade_index,

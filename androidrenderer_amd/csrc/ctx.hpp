@@ -68,6 +68,7 @@ struct sah_ctx {
         SahBuffer buf[16];
         uint8_t* half_to_srgb8 = nullptr;
         uint32_t* host_counters = nullptr;  // pinned, 16 words
+        uint32_t last_pass[4] = {};         // debug hook (sah_debug_raster_last_pass): attempts of the last call, capacities of its last attempt
     } raster;
     struct RtState {                   // acceleration structure of sah_rt_build (api_rt.cpp); buffers grow on demand
         SahBuffer buf[7];              // tri_base, build state, unsorted triangles, sorted triangles, keys, nodes, noise directions

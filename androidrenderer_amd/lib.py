@@ -25,7 +25,7 @@ _lib = None
 EXPORTS = ["sah_abi_version", "sah_status_string", "sah_last_error", "sah_create", "sah_destroy", "sah_comm_unique_id", "sah_set_stream",
            "sah_sync", "sah_lighting", "sah_copy_scene", "sah_copy_scene_rows", "sah_copy_scene_bloom_mip0_rows", "sah_bloom", "sah_bloom_mip0_rows", "sah_bloom_from_mip0", "sah_bloom_mip_rows", "sah_bloom_from_mip", "sah_bloom_source_rows", "sah_tonemap", "sah_tonemap_ex", "sah_lpv_clear", "sah_lpv_propagate", "sah_probe_notify_updated",
            "sah_sky_update_luts", "sah_ao_clear", "sah_probe_copy", "sah_probe_update", "sah_shadow_render", "sah_gbuffer_render", "sah_rsm_render", "sah_lpv_extract_vpls",
-           "sah_lpv_inject_vpls", "sah_rt_build", "sah_rtao", "sah_sun_shadow_mask", "sah_probe_trace", "sah_rtgi_trace", "sah_rt_set_rows", "sah_rt_set_bounces", "sah_debug_rt_structure", "sah_allgather_rows", "sah_allgather_rows_reversed", "sah_allgather_bytes", "sah_comm_set_stream", "sah_comm_wait",
+           "sah_lpv_inject_vpls", "sah_rt_build", "sah_rtao", "sah_sun_shadow_mask", "sah_probe_trace", "sah_rtgi_trace", "sah_rt_set_rows", "sah_rt_set_bounces", "sah_debug_rt_structure", "sah_debug_raster_last_pass", "sah_allgather_rows", "sah_allgather_rows_reversed", "sah_allgather_bytes", "sah_comm_set_stream", "sah_comm_wait",
            "sah_ipc_open", "sah_ipc_connect", "sah_ipc_export", "sah_ipc_register", "sah_ipc_unregister", "sah_ipc_reset",
            "sah_chain_create", "sah_chain_submit", "sah_chain_flush", "sah_chain_counts", "sah_chain_destroy"]
 
@@ -161,6 +161,7 @@ def load():
     lib.sah_rt_set_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
     lib.sah_rt_set_bounces.argtypes = [C.c_void_p, C.c_uint32]
     lib.sah_debug_rt_structure.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
+    lib.sah_debug_raster_last_pass.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     lib.sah_probe_trace.argtypes = [C.c_void_p, C.POINTER(_abi.ProbeTraceDesc)]
     lib.sah_rtgi_trace.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData), C.POINTER(_abi.SunLightConstants), C.POINTER(_abi.SkyLuts)] + [C.POINTER(_abi.Plane)] * 5
     lib.sah_ipc_open.argtypes = [C.c_void_p, C.c_void_p]
@@ -360,6 +361,16 @@ class Context:
         """sah_motion_vectors_render (include/sah_motion_vectors.h): depth, out: _abi.Plane of device memory (D32_SFLOAT read only,
         R16G16_SFLOAT of the same extent); stats: device pointer to SAH_RASTER_STATS_WORDS words, or None."""
         self._check(self.lib.sah_motion_vectors_render(self.handle, C.byref(scene), C.byref(view), C.byref(depth), C.byref(out), C.c_void_p(stats)))
+
+    RASTER_PASS_FIELDS = ("attempts", "record_capacity", "clip_capacity", "pairs_capacity")
+
+    def raster_last_pass(self):
+        """Test hook (sah_debug_raster_last_pass): how the last shadow / G-buffer / RSM / motion-vectors call of this context sized its scratch,
+        as a dict — attempts (2 or more: a buffer was too small and the pass was rendered again) and the record, clip-queue and bin-list
+        capacities of the last attempt.  Recorded on the host: no device work, no synchronisation."""
+        out = (C.c_uint32 * len(self.RASTER_PASS_FIELDS))()
+        self._check(self.lib.sah_debug_raster_last_pass(self.handle, out))
+        return {k: int(v) for k, v in zip(self.RASTER_PASS_FIELDS, out)}
 
     def vrsaa_measure_aliasing(self, color, depth, contrast, rows=(0, 0)):
         """sah_vrsaa_measure_aliasing (include/sah_vrsaa.h): color R8G8B8A8_SRGB, depth D32_SFLOAT, contrast R16G16_SFLOAT, _abi.Plane of device

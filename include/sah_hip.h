@@ -668,6 +668,14 @@ int sah_rt_set_bounces(sah_ctx* ctx, uint32_t num_bounces);
 #define SAH_RT_NODE_GROUP_BYTES 96
 int sah_debug_rt_structure(sah_ctx* ctx, uint32_t* header, void* triangles, uint64_t triangles_bytes, void* nodes, uint64_t nodes_bytes);
 
+/* Debug / test hook (no reference counterpart): how the last rasteriser call of the context — sah_shadow_render, sah_gbuffer_render,
+ * sah_rsm_render or the motion-vectors pass of sah_motion_vectors.h — sized its scratch.  Such a call launches its pass with guessed buffer sizes, reads the
+ * counters back and, where a buffer was too small, grows it and renders the pass again; the images and the statistics words are those
+ * of the last attempt, so a repeated pass is visible only here.  Host side: launches nothing, waits for nothing, changes nothing.
+ *   out  HOST, 4 words: [0] attempts the call took (1: the first sizes were enough; 0: no rasteriser call yet), and of its last attempt
+ *        [1] the record capacity, [2] the clip-queue capacity, [3] the capacity of the bin lists (entries). */
+int sah_debug_raster_last_pass(sah_ctx* ctx, uint32_t out[4]);
+
 /* Multi-GPU exchange step (no reference counterpart: the reference drives one device, RenderCore/render/backend/render_backend.cpp:135-153;
  * BASELINE.json north_star: "RCCL all-gather over xGMI to reassemble the final image").
  * In-place all-gather of row blocks of `image` over RCCL on the context's stream: rank r owns rows [rows_per_rank*r, rows_per_rank*(r+1))

@@ -262,6 +262,7 @@ def main():
         "sah_rt_set_rows": lambda: L.sah_rt_set_rows(ctx(), f.u32(), f.u32()),
         "sah_rt_set_bounces": lambda: L.sah_rt_set_bounces(ctx(), f.u32()),
         "sah_debug_rt_structure": rt_structure,
+        "sah_debug_raster_last_pass": lambda: L.sah_debug_raster_last_pass(ctx(), None if f.g.random() < 0.3 else (C.c_uint32 * 4)()),
         "sah_allgather_rows": lambda: L.sah_allgather_rows(ctx(), opt(f.plane(rgba16)), f.u32(), f.u32()),
         "sah_allgather_rows_reversed": lambda: L.sah_allgather_rows_reversed(ctx(), opt(f.plane(43)), f.u32(), f.u32()),
         "sah_allgather_bytes": lambda: L.sah_allgather_bytes(ctx(), f.addr(), int(f.g.integers(0, 2 ** 40))),
