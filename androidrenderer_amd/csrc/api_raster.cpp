@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/sah_hip.h"
+#include "../../include/sah_gbuffer_motion.h"
 #include "../../include/sah_motion_vectors.h"
 #include "ctx.hpp"
 #include "launch.hpp"
@@ -62,22 +63,27 @@ bool geometry_ok(const sah_scene_geometry* g, bool need_attributes) {
 
 // What the scratch of a pass looks like (raster_args.hpp: RasterPass).
 struct PassScratch {
-    int attr_slot;      // the buffer that holds one attribute record per raster record
-    size_t attr_bytes;  // ... of this size; 0: the pass writes none
-    size_t cell_bytes;  // per pixel of a split tile's merge buffer
-    bool seq_table;     // the resolve looks records up by sequence number
+    struct {
+        int slot;      // a buffer that holds one attribute record per raster record
+        size_t bytes;  // ... of this size; 0: none
+    } attr[2];         // every pass but the fused one has one kind of attribute record
+    size_t cell_bytes[2];  // per pixel of a split tile's merge buffer, per tile stage (the second: 0 unless the pass has two)
+    bool seq_table;        // the resolve looks records up by sequence number
 };
 PassScratch scratch_of(sah::RasterPass pass, const sah_scene_geometry* scene) {
     switch (pass) {
         case sah::RasterPass::Shadow: {
             // the alpha test of CUTOUT primitives needs their vertex colours and materials (lean records, raster_args.hpp)
             const bool attrs = scene->vertex_data && scene->materials && scene->num_materials;
-            return {S_ATTRS, attrs ? sizeof(sah::ShadowAttr) : 0, sizeof(uint32_t), false};
+            return {{{S_ATTRS, attrs ? sizeof(sah::ShadowAttr) : 0}, {S_MOTION, 0}}, {sizeof(uint32_t), 0}, false};
         }
         case sah::RasterPass::GBuffer:
-        case sah::RasterPass::Rsm: return {S_ATTRS, sizeof(sah::RasterAttr), sizeof(unsigned long long), true};
+        case sah::RasterPass::Rsm: return {{{S_ATTRS, sizeof(sah::RasterAttr)}, {S_MOTION, 0}}, {sizeof(unsigned long long), 0}, true};
         // the motion-vectors pass carries its varying in records of its own; the G-buffer's attributes stay as they are
-        case sah::RasterPass::Motion: return {S_MOTION, sizeof(sah::MotionAttr), sizeof(uint32_t), true};
+        case sah::RasterPass::Motion: return {{{S_MOTION, sizeof(sah::MotionAttr)}, {S_ATTRS, 0}}, {sizeof(uint32_t), 0}, true};
+        // the fused pass owns both attribute buffers, and a merge cell and a ticket per tile stage
+        case sah::RasterPass::GBufferMotion:
+            return {{{S_ATTRS, sizeof(sah::RasterAttr)}, {S_MOTION, sizeof(sah::MotionAttr)}}, {sizeof(unsigned long long), sizeof(uint32_t)}, true};
     }
     return {};
 }
@@ -104,8 +110,9 @@ int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, sah::
     for (int attempt = 0; attempt < 4; attempt++) {
         if (int rc = ensure(ctx, S_CLIPQ, want_clipped * sizeof(uint2)); rc != SAH_OK) return rc;
         if (int rc = ensure(ctx, S_RECORDS, want_records * sizeof(RasterRecord)); rc != SAH_OK) return rc;
-        if (ps.attr_bytes)
-            if (int rc = ensure(ctx, ps.attr_slot, want_records * ps.attr_bytes); rc != SAH_OK) return rc;
+        for (const auto& at : ps.attr)
+            if (at.bytes)
+                if (int rc = ensure(ctx, at.slot, want_records * at.bytes); rc != SAH_OK) return rc;
         if (int rc = ensure(ctx, S_PAIRS, want_pairs * sizeof(uint32_t)); rc != SAH_OK) return rc;
         if (ps.seq_table)
             if (int rc = ensure(ctx, S_SEQ, want_seq * sizeof(uint32_t)); rc != SAH_OK) return rc;
@@ -115,11 +122,13 @@ int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, sah::
         a.tri_base = (uint32_t*)r.buf[S_TRI_BASE].ptr;
         a.records = (RasterRecord*)r.buf[S_RECORDS].ptr;
         a.record_capacity = (uint32_t)std::min<size_t>(r.buf[S_RECORDS].bytes / sizeof(RasterRecord), 0xffffffffu);
-        if (ps.attr_bytes) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.buf[ps.attr_slot].bytes / ps.attr_bytes);
-        void* attrs = ps.attr_bytes ? r.buf[ps.attr_slot].ptr : nullptr;
-        a.attrs = (RasterAttr*)r.buf[S_ATTRS].ptr;  // (read by the G-buffer and RSM passes only)
-        a.shadow_attrs = pass == RasterPass::Shadow ? (ShadowAttr*)attrs : nullptr;
-        a.motion_attrs = pass == RasterPass::Motion ? (MotionAttr*)attrs : nullptr;
+        for (const auto& at : ps.attr)
+            if (at.bytes) a.record_capacity = (uint32_t)std::min<size_t>(a.record_capacity, r.buf[at.slot].bytes / at.bytes);
+        const bool gbuffer_cells = pass == RasterPass::GBuffer || pass == RasterPass::Rsm || pass == RasterPass::GBufferMotion;
+        const bool motion_cells = pass == RasterPass::Motion || pass == RasterPass::GBufferMotion;
+        a.attrs = (RasterAttr*)r.buf[S_ATTRS].ptr;  // (read by the G-buffer, RSM and fused passes only)
+        a.shadow_attrs = pass == RasterPass::Shadow && ps.attr[0].bytes ? (ShadowAttr*)r.buf[S_ATTRS].ptr : nullptr;
+        a.motion_attrs = motion_cells ? (MotionAttr*)r.buf[S_MOTION].ptr : nullptr;
         a.tile_count = (uint32_t*)r.buf[S_TILES].ptr;
         a.tile_cursor = a.tile_count + ntiles;
         a.tile_offset = a.tile_count + 2 * (size_t)ntiles;
@@ -133,15 +142,18 @@ int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, sah::
         a.merge_capacity = std::min<uint32_t>(a.extra_capacity, ctx->raster_merge_cap);
         if (int rc = ensure(ctx, S_HEAVY, (size_t)ntiles * sizeof(uint32_t)); rc != SAH_OK) return rc;
         if (int rc = ensure(ctx, S_EXTRA, (size_t)a.extra_capacity * sizeof(uint2)); rc != SAH_OK) return rc;
-        if (int rc = ensure(ctx, S_TICKETS, (size_t)a.merge_capacity * sizeof(uint32_t)); rc != SAH_OK) return rc;
-        if (int rc = ensure(ctx, S_MERGE, (size_t)a.merge_capacity * kTile * kTile * ps.cell_bytes); rc != SAH_OK) return rc;
+        const size_t stages = ps.cell_bytes[1] ? 2 : 1, slot_cells = (size_t)a.merge_capacity * kTile * kTile;
+        if (int rc = ensure(ctx, S_TICKETS, stages * a.merge_capacity * sizeof(uint32_t)); rc != SAH_OK) return rc;
+        if (int rc = ensure(ctx, S_MERGE, slot_cells * (ps.cell_bytes[0] + ps.cell_bytes[1])); rc != SAH_OK) return rc;
         a.heavy_slot = (uint32_t*)r.buf[S_HEAVY].ptr;
         a.extra_parts = (uint2*)r.buf[S_EXTRA].ptr;
         a.tickets = (uint32_t*)r.buf[S_TICKETS].ptr;
-        // one buffer, typed by the pass's merge cell
+        // one buffer, typed by the pass's merge cell; the second tile stage of the fused pass has its cells behind the first's and
+        // its tickets behind the first's
         a.merge_depth = pass == RasterPass::Shadow ? (uint32_t*)r.buf[S_MERGE].ptr : nullptr;
-        a.merge_keys = pass == RasterPass::GBuffer || pass == RasterPass::Rsm ? (unsigned long long*)r.buf[S_MERGE].ptr : nullptr;
-        a.merge_seq = pass == RasterPass::Motion ? (uint32_t*)r.buf[S_MERGE].ptr : nullptr;
+        a.merge_keys = gbuffer_cells ? (unsigned long long*)r.buf[S_MERGE].ptr : nullptr;
+        a.merge_seq = motion_cells ? (uint32_t*)((uint8_t*)r.buf[S_MERGE].ptr + (stages == 2 ? slot_cells * ps.cell_bytes[0] : 0)) : nullptr;
+        a.motion_tickets = stages == 2 ? a.tickets + a.merge_capacity : nullptr;
         HIP_TRY(ctx, launch_raster_setup(a, ctx->stream));
         HIP_TRY(ctx, launch_raster_tiles(a, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(r.host_counters, a.counters, C_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -199,6 +211,45 @@ void fill_scene(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scen
     a.num_textures = textured ? scene->num_textures : 0;
     a.shader_mip_bias = 0.0f;
 }
+
+// the five targets of a G-buffer pass: format, the depth plane's extent, alignment; null: all are fine
+const char* bad_gbuffer_target(const sah_gbuffer* out, uint32_t W, uint32_t H) {
+    const struct { const sah_plane* p; uint32_t fmt; uint32_t align; const char* name; } targets[5] = {
+        {&out->color, SAH_FORMAT_R8G8B8A8_SRGB, 4, "color"},   {&out->normals, SAH_FORMAT_R16G16B16A16_SFLOAT, 8, "normals"},
+        {&out->data, SAH_FORMAT_R8G8B8A8_UNORM, 4, "data"},    {&out->emission, SAH_FORMAT_R8G8B8A8_SRGB, 4, "emission"},
+        {&out->depth, SAH_FORMAT_D32_SFLOAT, 4, "depth"}};
+    for (const auto& t : targets)
+        if (!plane_ok(t.p, t.fmt, t.fmt, W, H) || ((uintptr_t)t.p->ptr % t.align) || (t.p->row_pitch_bytes % t.align)) return t.name;
+    return nullptr;
+}
+bool motion_target_ok(const sah_plane* motion_vectors, uint32_t W, uint32_t H) {
+    return plane_ok(motion_vectors, SAH_FORMAT_R16G16_SFLOAT, SAH_FORMAT_R16G16_SFLOAT, W, H) && !((uintptr_t)motion_vectors->ptr % 4) &&
+           !(motion_vectors->row_pitch_bytes % 4);
+}
+
+// what a G-buffer pass takes from its view and its targets
+void fill_gbuffer(sah_ctx* ctx, sah::RasterArgs& a, const sah_view_data* view, const sah_gbuffer* out) {
+    a.num_views = 1;
+    a.shader_mip_bias = view->material_texture_mip_bias;
+    std::memcpy(a.view_matrix, view->view, 64);
+    std::memcpy(a.clip_matrix[0], view->projection, 64);
+    fill_extent(a, out->depth.width, out->depth.height);
+    a.half_to_srgb8 = ctx->raster.half_to_srgb8;
+    a.out_color = parg(&out->color);
+    a.out_normals = parg(&out->normals);
+    a.out_data = parg(&out->data);
+    a.out_emission = parg(&out->emission);
+    a.out_depth = parg(&out->depth);
+}
+// what a motion-vectors pass takes from its view and its planes beyond the extent and this frame's matrices
+void fill_motion(sah::RasterArgs& a, const sah_view_data* view, const sah_plane* depth, const sah_plane* motion_vectors) {
+    std::memcpy(a.prev_view_matrix, view->last_frame_view, 64);
+    std::memcpy(a.prev_clip_matrix, view->last_frame_projection, 64);
+    a.render_resolution[0] = view->render_resolution[0];
+    a.render_resolution[1] = view->render_resolution[1];
+    a.mv_depth = parg(depth);
+    a.out_motion = parg(motion_vectors);
+}
 }  // namespace
 
 extern "C" {
@@ -230,30 +281,39 @@ int sah_gbuffer_render(sah_ctx* ctx, const sah_scene_geometry* scene, const sah_
     if (!geometry_ok(scene, true) || !view || !out) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "gbuffer_render: bad scene, view or targets");
     const uint32_t W = out->depth.width, H = out->depth.height;
     if (W == 0 || H == 0 || W > kMaxExtent || H > kMaxExtent) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "gbuffer_render: extent must be 1..%u", kMaxExtent);
-    const struct { const sah_plane* p; uint32_t fmt; uint32_t align; const char* name; } targets[5] = {
-        {&out->color, SAH_FORMAT_R8G8B8A8_SRGB, 4, "color"},   {&out->normals, SAH_FORMAT_R16G16B16A16_SFLOAT, 8, "normals"},
-        {&out->data, SAH_FORMAT_R8G8B8A8_UNORM, 4, "data"},    {&out->emission, SAH_FORMAT_R8G8B8A8_SRGB, 4, "emission"},
-        {&out->depth, SAH_FORMAT_D32_SFLOAT, 4, "depth"}};
-    for (const auto& t : targets)
-        if (!plane_ok(t.p, t.fmt, t.fmt, W, H) || ((uintptr_t)t.p->ptr % t.align) || (t.p->row_pitch_bytes % t.align))
-            return fail(ctx, SAH_ERR_UNSUPPORTED_FORMAT, "gbuffer_render: target '%s' has the wrong format, extent or alignment", t.name);
+    if (const char* name = bad_gbuffer_target(out, W, H))
+        return fail(ctx, SAH_ERR_UNSUPPORTED_FORMAT, "gbuffer_render: target '%s' has the wrong format, extent or alignment", name);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, sah_guard_touch(ctx, ctx->guard_raster));
     if (int rc = ensure_srgb_table(ctx); rc != SAH_OK) return rc;
     sah::RasterArgs a{};
     fill_scene(ctx, a, scene);
-    a.num_views = 1;
-    a.shader_mip_bias = view->material_texture_mip_bias;
-    std::memcpy(a.view_matrix, view->view, 64);
-    std::memcpy(a.clip_matrix[0], view->projection, 64);
-    fill_extent(a, W, H);
-    a.half_to_srgb8 = ctx->raster.half_to_srgb8;
-    a.out_color = parg(&out->color);
-    a.out_normals = parg(&out->normals);
-    a.out_data = parg(&out->data);
-    a.out_emission = parg(&out->emission);
-    a.out_depth = parg(&out->depth);
+    fill_gbuffer(ctx, a, view, out);
     return run(ctx, a, scene, sah::RasterPass::GBuffer, stats);
+}
+
+// sah_gbuffer_motion.h: sah_gbuffer_render, then sah_motion_vectors_render against the depth it wrote, with one set-up, one set of bin
+// lists and one read-back of the counters
+int sah_gbuffer_motion_render(sah_ctx* ctx, const sah_scene_geometry* scene, const sah_view_data* view, const sah_gbuffer* out,
+                              const sah_plane* motion_vectors, uint32_t* stats) {
+    SAH_RANGE();
+    if (!ctx) return SAH_ERR_INVALID_ARGUMENT;
+    if (!geometry_ok(scene, true) || !view || !out || !motion_vectors)
+        return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "gbuffer_motion_render: bad scene, view or targets");
+    const uint32_t W = out->depth.width, H = out->depth.height;
+    if (W == 0 || H == 0 || W > kMaxExtent || H > kMaxExtent) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "gbuffer_motion_render: extent must be 1..%u", kMaxExtent);
+    if (const char* name = bad_gbuffer_target(out, W, H))
+        return fail(ctx, SAH_ERR_UNSUPPORTED_FORMAT, "gbuffer_motion_render: target '%s' has the wrong format, extent or alignment", name);
+    if (!motion_target_ok(motion_vectors, W, H))
+        return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "gbuffer_motion_render: 'motion_vectors' must be an R16G16_SFLOAT plane of the depth plane's extent, 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, sah_guard_touch(ctx, ctx->guard_raster));
+    if (int rc = ensure_srgb_table(ctx); rc != SAH_OK) return rc;
+    sah::RasterArgs a{};
+    fill_scene(ctx, a, scene);
+    fill_gbuffer(ctx, a, view, out);
+    fill_motion(a, view, &out->depth, motion_vectors);
+    return run(ctx, a, scene, sah::RasterPass::GBufferMotion, stats);
 }
 
 int sah_rsm_render(sah_ctx* ctx, const sah_scene_geometry* scene, const sah_sun_light_constants* sun, const sah_lpv_cascade_matrices* cascades,
@@ -298,8 +358,7 @@ int sah_motion_vectors_render(sah_ctx* ctx, const sah_scene_geometry* scene, con
     if (!plane_ok(depth, SAH_FORMAT_D32_SFLOAT, SAH_FORMAT_D32_SFLOAT, W, H) || ((uintptr_t)depth->ptr % 4) || (depth->row_pitch_bytes % 4))
         return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_vectors_render: 'depth' must be a D32_SFLOAT plane, 4-byte aligned, its pitch at least a row");
     // (r.MotionVectors.FullRes, a target of another extent than the depth buffer, is not supported: DESIGN.md §8)
-    if (!plane_ok(motion_vectors, SAH_FORMAT_R16G16_SFLOAT, SAH_FORMAT_R16G16_SFLOAT, W, H) || ((uintptr_t)motion_vectors->ptr % 4) ||
-        (motion_vectors->row_pitch_bytes % 4))
+    if (!motion_target_ok(motion_vectors, W, H))
         return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_vectors_render: 'motion_vectors' must be an R16G16_SFLOAT plane of the depth plane's extent, 4-byte aligned");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, sah_guard_touch(ctx, ctx->guard_raster));
@@ -313,17 +372,12 @@ int sah_motion_vectors_render(sah_ctx* ctx, const sah_scene_geometry* scene, con
     a.num_views = 1;
     std::memcpy(a.view_matrix, view->view, 64);
     std::memcpy(a.clip_matrix[0], view->projection, 64);
-    std::memcpy(a.prev_view_matrix, view->last_frame_view, 64);
-    std::memcpy(a.prev_clip_matrix, view->last_frame_projection, 64);
-    a.render_resolution[0] = view->render_resolution[0];
-    a.render_resolution[1] = view->render_resolution[1];
     fill_extent(a, W, H);
-    a.mv_depth = parg(depth);
-    a.out_motion = parg(motion_vectors);
+    fill_motion(a, view, depth, motion_vectors);
     return run(ctx, a, scene, sah::RasterPass::Motion, stats);
 }
 
-// Debug / test hook: how the last rasteriser call of the context (shadow, G-buffer, RSM or motion vectors) went through run() — recorded
+// Debug / test hook: how the last rasteriser call of the context (shadow, G-buffer, RSM, motion vectors or the fused pass) went through run() — recorded
 // host side behind the synchronisation every attempt ends with; no device work.  All zero before the first call.
 int sah_debug_raster_last_pass(sah_ctx* ctx, uint32_t out[4]) {
     if (!ctx || !out) return SAH_ERR_INVALID_ARGUMENT;

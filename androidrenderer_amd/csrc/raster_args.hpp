@@ -25,6 +25,10 @@ enum class RasterPass : uint32_t {
     GBuffer,  // sah_gbuffer_render: reverse-Z depth + four colour targets; RasterAttr
     Rsm,      // sah_rsm_render: the G-buffer path with per-view matrices, D16 LESS and the flux / normal targets (RasterArgs::rsm)
     Motion,   // sah_motion_vectors_render: SOLID primitives only, compare EQUAL against mv_depth; MotionAttr
+    // sah_gbuffer_motion_render (sah_gbuffer_motion.h): the G-buffer pass, whose set-up also writes the MotionAttr of every SOLID record,
+    // then a second tile stage with the motion target over the same bin lists (mv_depth = out_depth), with tickets and a merge buffer of
+    // its own (motion_tickets, merge_seq)
+    GBufferMotion,
 };
 
 // RasterArgs::counters.  C_STATS .. C_STATS + 7 mirror SAH_RASTER_STATS_WORDS (C_EXTRA and C_HEAVY are statistics words 5 and 6).
@@ -132,9 +136,11 @@ struct RasterArgs {
     // motion-vectors pass (sah_motion_vectors_render)
     float prev_view_matrix[16], prev_clip_matrix[16];  // last_frame_view, last_frame_projection
     float render_resolution[2];
-    MotionAttr* motion_attrs;  // one per record
+    MotionAttr* motion_attrs;  // one per record (GBufferMotion: written for the SOLID ones)
     uint32_t* merge_seq;       // per slot: kRasterTile^2 winners (seq + 1, 0 = none) of a split list
     PlaneArg mv_depth, out_motion;
+    // fused G-buffer + motion pass (sah_gbuffer_motion_render)
+    uint32_t* motion_tickets;  // GBufferMotion: the tickets of the second tile stage (`tickets` are spent by the first); null otherwise
 };
 
 }  // namespace sah

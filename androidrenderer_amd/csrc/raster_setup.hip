@@ -132,12 +132,35 @@ struct SetupStats {
 
 // The set-up kernels are instantiated per attribute record, which is what tells the passes apart at this stage: ShadowAttr (shadow
 // cascades: no near / far clipping, attributes for CUTOUT records only and only when the scene brought them), RasterAttr (G-buffer and
-// RSM, told apart by a.rsm at run time) and MotionAttr (motion vectors: SOLID primitives only).
+// RSM, told apart by a.rsm at run time) and MotionAttr (motion vectors: SOLID primitives only).  kWithMotion beside RasterAttr is the
+// set-up of sah_gbuffer_motion_render: the G-buffer's, which also writes the MotionAttr of every record of a SOLID primitive.  Slot,
+// sequence number and RasterRecord of such a record are the stand-alone motion pass's: both count every primitive in the running
+// triangle number (k_setup skips a CUTOUT one only after `t` is fixed), both run clip_vertex / clip_polygon / to_window on the same
+// inputs (a.rsm is 0 in both), and emit_triangle derives the record from those alone.  One difference remains: the G-buffer's range
+// check reads the material, the motion pass's does not (sah_gbuffer_motion.h says what follows).
 template <class Attr> constexpr bool kShadowSetup = std::is_same_v<Attr, ShadowAttr>;
 template <class Attr> constexpr bool kMotionSetup = std::is_same_v<Attr, MotionAttr>;
 
+// motion_vectors.vert.slang:27-31: the same model matrix serves both frames
+SAH_DEV void write_motion_attr(const RasterArgs& a, const sah_primitive& prim, uint32_t tri, const WindowVertex& v0, const WindowVertex& v1, const WindowVertex& v2,
+                               uint32_t r) {
+    MotionAttr ma;
+    ma.inv_w[0] = v0.inv_w; ma.inv_w[1] = v1.inv_w; ma.inv_w[2] = v2.inv_w;
+    for (int k = 0; k < 3; k++) { ma.bary[0][k] = v0.bary[k]; ma.bary[1][k] = v1.bary[k]; ma.bary[2][k] = v2.bary[k]; }
+    for (int k = 0; k < 3; k++) {
+        const float* pos = a.positions + 3 * ((int64_t)prim.vertex_offset + a.indices[prim.first_index + 3 * tri + k]);
+        const float local[4] = {pos[0], pos[1], pos[2], 1.0f};
+        float world[4], vs[4], prev[4];
+        mat_vec(prim.model, local, world);
+        mat_vec(a.prev_view_matrix, world, vs);
+        mat_vec(a.prev_clip_matrix, vs, prev);
+        ma.prev[k][0] = prev[0]; ma.prev[k][1] = prev[1]; ma.prev[k][2] = prev[3];
+    }
+    a.motion_attrs[r] = ma;
+}
+
 // One window-space triangle of the fan: facing, bounding box, record.
-template <class Attr>
+template <class Attr, bool kWithMotion>
 SAH_DEV void emit_triangle(const RasterArgs& a, SetupStats& st, uint32_t view, uint32_t p, const sah_primitive& prim, uint32_t tri, uint32_t seq,
                            const WindowVertex& v0, WindowVertex v1, WindowVertex v2, uint32_t slot) {
     if (!v0.finite || !v1.finite || !v2.finite) { st.dropped++; return; }
@@ -186,21 +209,7 @@ SAH_DEV void emit_triangle(const RasterArgs& a, SetupStats& st, uint32_t view, u
             atomicAdd(&a.counters[C_CUTOUT_NO_ATTR], 1u);  // the host turns this into SAH_ERR_INVALID_ARGUMENT (api_raster.cpp)
         }
     }
-    if (kMotionSetup<Attr>) {  // motion_vectors.vert.slang:27-31: the same model matrix serves both frames
-        MotionAttr ma;
-        ma.inv_w[0] = v0.inv_w; ma.inv_w[1] = v1.inv_w; ma.inv_w[2] = v2.inv_w;
-        for (int k = 0; k < 3; k++) { ma.bary[0][k] = v0.bary[k]; ma.bary[1][k] = v1.bary[k]; ma.bary[2][k] = v2.bary[k]; }
-        for (int k = 0; k < 3; k++) {
-            const float* pos = a.positions + 3 * ((int64_t)prim.vertex_offset + a.indices[prim.first_index + 3 * tri + k]);
-            const float local[4] = {pos[0], pos[1], pos[2], 1.0f};
-            float world[4], vs[4], prev[4];
-            mat_vec(prim.model, local, world);
-            mat_vec(a.prev_view_matrix, world, vs);
-            mat_vec(a.prev_clip_matrix, vs, prev);
-            ma.prev[k][0] = prev[0]; ma.prev[k][1] = prev[1]; ma.prev[k][2] = prev[3];
-        }
-        a.motion_attrs[r] = ma;
-    }
+    if (kMotionSetup<Attr> || (kWithMotion && prim.type == SAH_PRIMITIVE_TYPE_SOLID)) write_motion_attr(a, prim, tri, v0, v1, v2, r);
     if (std::is_same_v<Attr, RasterAttr>) {
         RasterAttr at;
         at.inv_w[0] = v0.inv_w; at.inv_w[1] = v1.inv_w; at.inv_w[2] = v2.inv_w;
@@ -242,7 +251,7 @@ SAH_DEV ClipVertex clip_vertex(const RasterArgs& a, const sah_primitive& prim, u
 
 // Rare path: the triangle crosses a clipping plane.  k_setup queues it and this kernel, launched right after, clips and fans it, so
 // that the polygon arrays (scratch memory) and their registers burden only the triangles that need them.
-template <class Attr>
+template <class Attr, bool kWithMotion = false>
 __global__ __launch_bounds__(64) void k_setup_clipped(const RasterArgs a) {
     // the polygons live in LDS, 12 vertices per lane and buffer: dynamically indexed private arrays would sit in scratch memory,
     // and the clipping loop is one long chain of dependent accesses to them
@@ -262,7 +271,7 @@ __global__ __launch_bounds__(64) void k_setup_clipped(const RasterArgs a) {
         WindowVertex prev = to_window(poly[1], a.half_w, a.half_h);
         for (int i = 1; i + 1 < n; i++) {
             const WindowVertex next = to_window(poly[i + 1], a.half_w, a.half_h);
-            emit_triangle<Attr>(a, st, view, p, prim, tri, t * 8u + (uint32_t)(i - 1), v0, prev, next, kAppend);
+            emit_triangle<Attr, kWithMotion>(a, st, view, p, prim, tri, t * 8u + (uint32_t)(i - 1), v0, prev, next, kAppend);
             prev = next;
         }
     }
@@ -271,7 +280,7 @@ __global__ __launch_bounds__(64) void k_setup_clipped(const RasterArgs a) {
     block_flush<4>(&a.counters[C_STATS], local, s_acc);
 }
 
-template <class Attr>
+template <class Attr, bool kWithMotion = false>
 __global__ __launch_bounds__(256) void k_setup(const RasterArgs a) {
     const uint32_t total = a.counters[C_TRIS];
     const uint64_t work = (uint64_t)total * a.num_views;
@@ -303,7 +312,7 @@ __global__ __launch_bounds__(256) void k_setup(const RasterArgs a) {
             inside = inside && plane_distance(c0, plane) >= 0.0f && plane_distance(c1, plane) >= 0.0f && plane_distance(c2, plane) >= 0.0f;
         if (!finite) { st.dropped++; continue; }
         if (inside) {
-            emit_triangle<Attr>(a, st, view, p, prim, tri, t * 8u, to_window(c0, a.half_w, a.half_h), to_window(c1, a.half_w, a.half_h),
+            emit_triangle<Attr, kWithMotion>(a, st, view, p, prim, tri, t * 8u, to_window(c0, a.half_w, a.half_h), to_window(c1, a.half_w, a.half_h),
                                    to_window(c2, a.half_w, a.half_h), w < a.record_capacity ? (uint32_t)w : a.record_capacity);
         } else {
             const uint32_t q = wave_alloc(&a.counters[C_CLIPPED], true);
@@ -413,10 +422,10 @@ __global__ __launch_bounds__(256) void k_check_textures(const RasterArgs a) {
     if (bad) atomicAdd(&a.counters[C_BAD_TEXTURE], 1u);
 }
 
-template <class Attr>
+template <class Attr, bool kWithMotion = false>
 void launch_setup_kernels(const RasterArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(k_setup<Attr>, dim3(1024), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_setup_clipped<Attr>, dim3(256), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((k_setup<Attr, kWithMotion>), dim3(1024), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_setup_clipped<Attr, kWithMotion>), dim3(256), dim3(64), 0, st, a);
 }
 
 }  // namespace
@@ -436,6 +445,7 @@ hipError_t launch_raster_setup(const RasterArgs& a, hipStream_t st) {
         case RasterPass::GBuffer:
         case RasterPass::Rsm: launch_setup_kernels<RasterAttr>(a, st); break;
         case RasterPass::Motion: launch_setup_kernels<MotionAttr>(a, st); break;
+        case RasterPass::GBufferMotion: launch_setup_kernels<RasterAttr, true>(a, st); break;
     }
     hipLaunchKernelGGL(k_bin<false>, dim3(1024), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, st, (const sah_primitive*)nullptr, (const uint32_t*)a.tile_count, ntiles, a.tile_offset, &a.counters[C_PAIRS]);

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "launch.hpp"
 #include "numerics.hpp"
 #include "raster_args.hpp"
@@ -275,6 +277,13 @@ struct SeqCell {  // sequence number + 1 of the latest fragment that matched the
     static SAH_DEV T* buffer(const RasterArgs& a) { return a.merge_seq; }
     static SAH_DEV void fold(T* into, T v) { atomicMax(into, v); }
 };
+// The fused G-buffer + motion pass (sah_gbuffer_motion.h) walks the same split lists twice: k_split sets up the G-buffer's cell and, in
+// the same launch, the second stage's cell and tickets (a second k_split would count C_HEAVY and C_EXTRA twice).
+struct KeyAndSeqCell : KeyCell {
+    using Second = SeqCell;
+};
+template <class Merge, class = void> struct SecondCell { using type = void; };
+template <class Merge> struct SecondCell<Merge, std::void_t<typename Merge::Second>> { using type = typename Merge::Second; };
 
 // ---- targets --------------------------------------------------------------------------------------------------------------------------
 // A target is what differs between the passes in the tile kernel: Merge (the cell above), Cells (the tile in LDS: merged[] plus what
@@ -444,6 +453,14 @@ struct MotionTarget {
     }
 };
 
+// The second tile stage of the fused pass: the motion target over the G-buffer's bin lists, which also hold the CUTOUT records the
+// stand-alone motion pass never sets up (scene.draw_opaque draws none of them); the walk drops them where it loads the record.
+struct SharedMotionTarget : MotionTarget {
+    static constexpr bool kSkipCutout = true;
+};
+template <class Target, class = void> constexpr bool kSkipsCutout = false;
+template <class Target> constexpr bool kSkipsCutout<Target, std::void_t<decltype(Target::kSkipCutout)>> = Target::kSkipCutout;
+
 // ---- the walk over a bin list -----------------------------------------------------------------------------------------------------------
 // a covered pixel: its depth and cell, then the target's test
 template <class Target>
@@ -525,22 +542,25 @@ SAH_DEV void walk_list(const RasterArgs& a, const TileWork& w, typename Target::
         if (li < w.count) {
             rec_index = a.pairs[w.begin + li];
             const RasterRecord rec = a.records[rec_index];
-            x0 = max((int32_t)rec.x0, w.tile_x); x1 = min((int32_t)rec.x1, w.tile_x + kTile - 1);
-            y0 = max((int32_t)rec.y0, w.tile_y); y1 = min((int32_t)rec.y1, w.tile_y + kTile - 1);
-            area = (uint32_t)((x1 - x0 + 1) * (y1 - y0 + 1));
-            mine = edge_setup(rec);  // every lane sets up its own record: 64 set-ups for the price of one
-            medium_rec = area > kSmallArea && area <= kMediumArea;
-            if (area <= kSmallArea) {
-                for (int32_t py = y0; py <= y1; py++)
-                    for (int32_t px = x0; px <= x1; px++) test_pixel<Target>(a, w, s, mine, rec_index, px, py);
-            } else if (area > kMediumArea) {
-                const uint32_t slot = atomicAdd(&s_nbig, 1u);
-                if (slot < kBigSlots) {
-                    s_big[slot].e = mine;
-                    s_big[slot].rec_index = rec_index;
-                    s_big[slot].x0 = x0; s_big[slot].x1 = x1; s_big[slot].y0 = y0; s_big[slot].y1 = y1;
-                } else {
-                    medium_rec = true;  // list full: the wave does it
+            // (the motion stage of the fused pass drops the CUTOUT records of the shared list before any coverage work)
+            if (!(kSkipsCutout<Target> && rec.cutout)) {
+                x0 = max((int32_t)rec.x0, w.tile_x); x1 = min((int32_t)rec.x1, w.tile_x + kTile - 1);
+                y0 = max((int32_t)rec.y0, w.tile_y); y1 = min((int32_t)rec.y1, w.tile_y + kTile - 1);
+                area = (uint32_t)((x1 - x0 + 1) * (y1 - y0 + 1));
+                mine = edge_setup(rec);  // every lane sets up its own record: 64 set-ups for the price of one
+                medium_rec = area > kSmallArea && area <= kMediumArea;
+                if (area <= kSmallArea) {
+                    for (int32_t py = y0; py <= y1; py++)
+                        for (int32_t px = x0; px <= x1; px++) test_pixel<Target>(a, w, s, mine, rec_index, px, py);
+                } else if (area > kMediumArea) {
+                    const uint32_t slot = atomicAdd(&s_nbig, 1u);
+                    if (slot < kBigSlots) {
+                        s_big[slot].e = mine;
+                        s_big[slot].rec_index = rec_index;
+                        s_big[slot].x0 = x0; s_big[slot].x1 = x1; s_big[slot].y0 = y0; s_big[slot].y1 = y1;
+                    } else {
+                        medium_rec = true;  // list full: the wave does it
+                    }
                 }
             }
         }
@@ -602,8 +622,10 @@ __global__ __launch_bounds__(kTileThreads, Target::kMinWaves) void k_raster_tile
 
 // Cuts long bin lists into parts: a tile with more than kSplit entries gets a merge buffer (initialised here to the identity of its
 // depth test), a ticket, and one extra workgroup per further part.  Tiles beyond the scratch capacity stay unsplit (slower, not wrong).
+// A Merge with a Second cell (KeyAndSeqCell) also arms the second tile stage: its tickets and its buffer, under the same slots.
 template <class Merge>
 __global__ __launch_bounds__(256) void k_split(const RasterArgs a) {
+    using Second = typename SecondCell<Merge>::type;
     const uint32_t ntiles = a.tiles_x * a.tiles_y * a.num_views;
     const uint32_t tile = blockIdx.x;  // one workgroup per tile: the merge buffer of a heavy tile is initialised by all 256 threads
     __shared__ uint32_t s_slot;
@@ -619,6 +641,7 @@ __global__ __launch_bounds__(256) void k_split(const RasterArgs a) {
                 if ((uint64_t)e + parts - 1u <= a.extra_capacity) {
                     slot = h;
                     a.tickets[h] = 0u;
+                    if constexpr (!std::is_void_v<Second>) a.motion_tickets[h] = 0u;
                     for (uint32_t p = 1; p < parts; p++) a.extra_parts[e + p - 1u] = make_uint2(tile, p);
                 }
             }
@@ -630,6 +653,10 @@ __global__ __launch_bounds__(256) void k_split(const RasterArgs a) {
     if (s_slot == ~0u) return;
     typename Merge::T* merged = Merge::buffer(a) + (size_t)s_slot * (kTile * kTile);
     for (uint32_t i = threadIdx.x; i < kTile * kTile; i += 256) merged[i] = Merge::kClear;
+    if constexpr (!std::is_void_v<Second>) {
+        typename Second::T* second = Second::buffer(a) + (size_t)s_slot * (kTile * kTile);
+        for (uint32_t i = threadIdx.x; i < kTile * kTile; i += 256) second[i] = Second::kClear;
+    }
 }
 
 // seq -> record index for the appended records (fans of clipped triangles; G-buffer resolve)
@@ -642,11 +669,18 @@ __global__ __launch_bounds__(256) void k_seq_table(const RasterArgs a) {
     }
 }
 
-template <class Target>
+template <class Target, class Split = typename Target::Merge>
 void launch_tile_kernels(const RasterArgs& a, uint32_t ntiles, hipStream_t st) {
     // every tile gets its heavy_slot (~0 when its list stays whole), also for an empty scene
-    hipLaunchKernelGGL(k_split<typename Target::Merge>, dim3(ntiles), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_split<Split>, dim3(ntiles), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_raster_tiles<Target>, dim3(ntiles + a.extra_capacity), dim3(kTileThreads), 0, st, a);
+}
+// The second tile stage of the fused pass: the same bin lists, heavy_slot and extra_parts; the tickets k_split armed for it.  Stream
+// order makes the depth plane the first stage wrote visible to it.
+void launch_shared_motion_tiles(const RasterArgs& a, uint32_t ntiles, hipStream_t st) {
+    RasterArgs m = a;
+    m.tickets = a.motion_tickets;
+    hipLaunchKernelGGL(k_raster_tiles<SharedMotionTarget>, dim3(ntiles + a.extra_capacity), dim3(kTileThreads), 0, st, m);
 }
 
 }  // namespace
@@ -669,6 +703,11 @@ hipError_t launch_raster_tiles(const RasterArgs& a, hipStream_t st) {
             else launch_tile_kernels<GBufferTarget<false>>(a, ntiles, st);
             break;
         case RasterPass::Motion: launch_tile_kernels<MotionTarget>(a, ntiles, st); break;
+        case RasterPass::GBufferMotion:
+            if (a.textures) launch_tile_kernels<GBufferTarget<true>, KeyAndSeqCell>(a, ntiles, st);
+            else launch_tile_kernels<GBufferTarget<false>, KeyAndSeqCell>(a, ntiles, st);
+            launch_shared_motion_tiles(a, ntiles, st);
+            break;
     }
     return hipGetLastError();
 }

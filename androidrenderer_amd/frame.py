@@ -179,11 +179,12 @@ class LightingInputs:
         return from_torch(lit, np.uint16)
 
 
-def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, stats_ptr=None, vrsaa=None):
+def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, stats_ptr=None, vrsaa=None, fused_motion=False):
     """The rasterised part of a frame: sah_gbuffer_render into `gbuffer` (dict of device arrays: color, normals, data, emission, depth)
     and — only when a `motion_vectors` target (H, W, 2) int16 device array is given — sah_motion_vectors_render against the depth the
     G-buffer pass has just written, as the reference runs its motion-vectors phase after its depth pass (scene_renderer.cpp:308-316).
-    Without the target the frame is what it always was.
+    Without the target the frame is what it always was.  `fused_motion` (off by default) with a target: the two passes as the one call
+    sah_gbuffer_motion_render, which gives the same bytes with one rasteriser set-up (include/sah_gbuffer_motion.h).
 
     `vrsaa` (off by default): a dict with "rates" [(x, y), ...] and "texel_size" (x, y), and optionally the device arrays "contrast"
     (H, W, 2) int16 — the LAST frame's contrast image — and "shading_rate_image" (uint8, the extent of
@@ -203,8 +204,11 @@ def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, sta
             sri = torch.zeros((sh, sw), dtype=torch.uint8, device=gbuffer["depth"].device)
         contrast_p = images.plane(contrast, _abi.FORMAT_R16G16_SFLOAT)
         ctx.vrsaa_shading_rate_image(contrast_p, images.plane(sri, _abi.FORMAT_R8_UINT), scene.shading_rate_params((w, h), (sw, sh), vrsaa["rates"]))
-    ctx.gbuffer_render(geometry, view_data, images.gbuffer(gbuffer), stats_ptr)
-    if motion_vectors is not None:
+    if fused_motion and motion_vectors is not None:
+        ctx.gbuffer_motion_render(geometry, view_data, images.gbuffer(gbuffer), images.plane(motion_vectors, _abi.FORMAT_R16G16_SFLOAT), stats_ptr)
+    else:
+        ctx.gbuffer_render(geometry, view_data, images.gbuffer(gbuffer), stats_ptr)
+    if motion_vectors is not None and not fused_motion:
         ctx.motion_vectors_render(geometry, view_data, images.plane(gbuffer["depth"], _abi.FORMAT_D32_SFLOAT),
                                   images.plane(motion_vectors, _abi.FORMAT_R16G16_SFLOAT))
     if vrsaa is not None:

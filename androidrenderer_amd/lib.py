@@ -35,6 +35,9 @@ GV_EXPORTS = ["sah_lpv_inject_rsm_gv", "sah_lpv_inject_scene_gv", "sah_lpv_propa
 # the motion-vectors pass: exported, declared in include/sah_motion_vectors.h (not sah_hip.h)
 MV_EXPORTS = ["sah_motion_vectors_render"]
 
+# the fused G-buffer + motion-vectors pass: exported, declared in include/sah_gbuffer_motion.h (not sah_hip.h)
+GBUFFER_MOTION_EXPORTS = ["sah_gbuffer_motion_render"]
+
 # the VRSAA passes: exported, declared in include/sah_vrsaa.h (not sah_hip.h)
 VRSAA_EXPORTS = ["sah_vrsaa_measure_aliasing", "sah_vrsaa_shading_rate_image"]
 
@@ -146,6 +149,8 @@ def load():
                                       C.POINTER(_abi.Volume), C.c_void_p]
     lib.sah_gbuffer_render.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.POINTER(_abi.ViewData), C.POINTER(_abi.GBuffer), C.c_void_p]
     lib.sah_motion_vectors_render.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.POINTER(_abi.ViewData), C.POINTER(_abi.Plane), C.POINTER(_abi.Plane),
+                                              C.c_void_p]
+    lib.sah_gbuffer_motion_render.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.POINTER(_abi.ViewData), C.POINTER(_abi.GBuffer), C.POINTER(_abi.Plane),
                                               C.c_void_p]
     lib.sah_rsm_render.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.POINTER(_abi.SunLightConstants), C.POINTER(_abi.LpvCascadeMatrices),
                                    C.c_uint32, C.POINTER(_abi.RsmTargets), C.c_void_p]
@@ -361,6 +366,12 @@ class Context:
         """sah_motion_vectors_render (include/sah_motion_vectors.h): depth, out: _abi.Plane of device memory (D32_SFLOAT read only,
         R16G16_SFLOAT of the same extent); stats: device pointer to SAH_RASTER_STATS_WORDS words, or None."""
         self._check(self.lib.sah_motion_vectors_render(self.handle, C.byref(scene), C.byref(view), C.byref(depth), C.byref(out), C.c_void_p(stats)))
+
+    def gbuffer_motion_render(self, scene, view, gbuffer, out, stats=None):
+        """sah_gbuffer_motion_render (include/sah_gbuffer_motion.h): gbuffer_render into `gbuffer` (_abi.GBuffer) and motion_vectors_render
+        against its depth plane into `out` (_abi.Plane, R16G16_SFLOAT of the same extent) with one rasteriser set-up; stats: device pointer to
+        SAH_RASTER_STATS_WORDS words (the G-buffer pass's), or None."""
+        self._check(self.lib.sah_gbuffer_motion_render(self.handle, C.byref(scene), C.byref(view), C.byref(gbuffer), C.byref(out), C.c_void_p(stats)))
 
     RASTER_PASS_FIELDS = ("attempts", "record_capacity", "clip_capacity", "pairs_capacity")
 

@@ -30,6 +30,7 @@
 #include "sah_lpv_gv.h"
 #include "sah_lpv_mesh_lights.h"
 #include "sah_mip_chain.h"
+#include "sah_gbuffer_motion.h"
 #include "sah_motion_vectors.h"
 #include "sah_rt_refit.h"
 #include "sah_vrsaa.h"
@@ -1263,16 +1264,14 @@ private:
 // ---- LightingPhase (RenderCore/render/phase/lighting_phase.hpp:17-57, .cpp:34-134) -------------------------------------
 // RenderCore/render/phase/gbuffer_phase.cpp:17-97 (and the depth pre-pass it relies on, phase/depth_culling_phase.cpp): visibility and
 // the four G-buffer targets in one compute pass.  The indirect draw buffers of the reference (GPU culling results) have no
-// counterpart: every primitive of the scene is submitted.
+// counterpart: every primitive of the scene is submitted.  Given a MotionVectorsPhase that wants its vectors and shares this phase's
+// set-up (share_gbuffer_setup), the one pass "gbuffer + motion_vectors" — sah_gbuffer_motion_render — writes that phase's target too,
+// and MotionVectorsPhase::render then records nothing.
+class MotionVectorsPhase;
 class GbufferPhase {
 public:
-    void render(RenderGraph& graph, const RenderScene& scene, const GBuffer& gbuffer, const SceneView& player_view) {
-        graph.add_pass(hip_pass("gbuffer", [&scene, &gbuffer, &player_view](sah_ctx* ctx) {
-                            const sah_gbuffer g = {gbuffer.color->plane(), gbuffer.normals->plane(), gbuffer.data->plane(), gbuffer.emission->plane(),
-                                                   gbuffer.depth->plane()};
-                            return sah_gbuffer_render(ctx, &scene.geometry, &player_view.get_gpu_data(), &g, nullptr);
-                        }));
-    }
+    inline void render(RenderGraph& graph, const RenderScene& scene, const GBuffer& gbuffer, const SceneView& player_view,
+                       const MotionVectorsPhase* motion_vectors_phase = nullptr);
 };
 
 // RenderCore/render/phase/motion_vectors_phase.hpp:13-33, .cpp:27-107; SceneRenderer runs it after the depth pre-pass when
@@ -1280,9 +1279,12 @@ public:
 // GbufferPhase::render, which is where this library's depth comes from.  Off by default: AA = None needs no motion vectors and the
 // default frame stays as it is.  r.MotionVectors.FullRes (a target of the output resolution) is not supported: the target always has
 // the render resolution, and the output resolution is only taken for the signature's sake.
+// share_gbuffer_setup (off by default: the frame records the passes it always did): the vectors come from the fused pass that
+// GbufferPhase::render records when it is handed this phase — the same bytes, one rasteriser set-up (sah_gbuffer_motion.h).
 class MotionVectorsPhase {
 public:
     bool needs_motion_vectors = false;
+    bool share_gbuffer_setup = false;
     explicit MotionVectorsPhase(ResourceAllocator& allocator_in) : allocator(allocator_in) {}
     static bool render_full_res() { return false; }
     void set_render_resolution(const uint32_t resolution[2], const uint32_t /*output_resolution*/[2]) {
@@ -1291,7 +1293,7 @@ public:
     }
     // the indirect draw buffers of the reference have no counterpart (GbufferPhase): every SOLID primitive of the scene is drawn
     void render(RenderGraph& graph, const RenderScene& scene, const SceneView& player_view, TextureHandle depth_buffer) {
-        if (!needs_motion_vectors) return;
+        if (!needs_motion_vectors || share_gbuffer_setup) return;
         TextureHandle target = motion_vectors;
         graph.add_pass(hip_pass("motion_vectors", [&scene, &player_view, depth_buffer, target](sah_ctx* ctx) {
                             if (!target) return (int)SAH_ERR_INVALID_ARGUMENT;  // set_render_resolution has not been called
@@ -1305,6 +1307,26 @@ private:
     ResourceAllocator& allocator;
     TextureHandle motion_vectors = nullptr;
 };
+
+inline void GbufferPhase::render(RenderGraph& graph, const RenderScene& scene, const GBuffer& gbuffer, const SceneView& player_view,
+                                 const MotionVectorsPhase* motion_vectors_phase) {
+    if (motion_vectors_phase && motion_vectors_phase->needs_motion_vectors && motion_vectors_phase->share_gbuffer_setup) {
+        TextureHandle target = motion_vectors_phase->get_motion_vectors();
+        graph.add_pass(hip_pass("gbuffer + motion_vectors", [&scene, &gbuffer, &player_view, target](sah_ctx* ctx) {
+                            if (!target) return (int)SAH_ERR_INVALID_ARGUMENT;  // set_render_resolution has not been called
+                            const sah_gbuffer g = {gbuffer.color->plane(), gbuffer.normals->plane(), gbuffer.data->plane(), gbuffer.emission->plane(),
+                                                   gbuffer.depth->plane()};
+                            const sah_plane m = target->plane();
+                            return sah_gbuffer_motion_render(ctx, &scene.geometry, &player_view.get_gpu_data(), &g, &m, nullptr);
+                        }));
+        return;
+    }
+    graph.add_pass(hip_pass("gbuffer", [&scene, &gbuffer, &player_view](sah_ctx* ctx) {
+                        const sah_gbuffer g = {gbuffer.color->plane(), gbuffer.normals->plane(), gbuffer.data->plane(), gbuffer.emission->plane(),
+                                               gbuffer.depth->plane()};
+                        return sah_gbuffer_render(ctx, &scene.geometry, &player_view.get_gpu_data(), &g, nullptr);
+                    }));
+}
 
 // RenderCore/render/phase/sampling_rate_calculator.hpp / .cpp:11-175.  SceneRenderer makes one when AntiAliasingType::VRSAA is selected
 // (scene_renderer.cpp:142-154), calls generate_shading_rate_image before the G-buffer pass (:357-361: it reads the LAST frame's contrast

@@ -1,0 +1,47 @@
+"""The fused G-buffer + motion-vectors call (include/sah_gbuffer_motion.h) without a GPU: the library exports the entry its header
+declares and no other header or export list changed for it, the header compiles as C and as C++, and malformed calls are refused with the
+status codes of the two calls it replaces before anything is launched."""
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+from androidrenderer_amd import lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_library_exports_the_entry_its_header_declares():
+    L = lib.load()
+    assert all(hasattr(L, s) for s in lib.GBUFFER_MOTION_EXPORTS)
+    header = open(os.path.join(ROOT, "include", "sah_gbuffer_motion.h")).read()
+    assert sorted(re.findall(r"^int (sah_\w+)\(", header, re.M)) == sorted(lib.GBUFFER_MOTION_EXPORTS) == ["sah_gbuffer_motion_render"]
+    assert not set(lib.GBUFFER_MOTION_EXPORTS) & (set(lib.EXPORTS) | set(lib.MV_EXPORTS))
+    # sah_hip.h, its ABI version and sah_motion_vectors.h stay as they are: the new entry lives in a header of its own, which includes both
+    for other in ("sah_hip.h", "sah_motion_vectors.h"):
+        assert "gbuffer_motion" not in open(os.path.join(ROOT, "include", other)).read(), other
+        assert f'#include "{other}"' in header
+
+
+@pytest.mark.parametrize("language", ["c", "c++"])
+def test_header_compiles_as_c_and_as_cpp(tmp_path, language):
+    src = tmp_path / ("use.c" if language == "c" else "use.cpp")
+    src.write_text('#include "sah_gbuffer_motion.h"\n'
+                   "int use(sah_ctx* c, const sah_scene_geometry* s, const sah_view_data* v, const sah_gbuffer* g, const sah_plane* m) {\n"
+                   "    return sah_gbuffer_motion_render(c, s, v, g, m, 0) + sah_motion_vectors_render(c, s, v, &g->depth, m, 0);\n}\n")
+    clang = "/opt/rocm/llvm/bin/clang" if os.path.exists("/opt/rocm/llvm/bin/clang") else "cc"
+    subprocess.check_call([clang, "-x", language, "-std=c11" if language == "c" else "-std=c++17", "-Wall", "-Werror", "-fsyntax-only",
+                           "-I", os.path.join(ROOT, "include"), str(src)], timeout=120)
+
+
+@pytest.mark.parametrize("seed", [41, 42])
+def test_malformed_calls_are_refused_and_launch_nothing(seed):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "gbuffer_motion_fuzz_child.py"), str(seed), "3000"], stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True, timeout=600)
+    tail = "\n".join(r.stdout.splitlines()[-10:])
+    if "SKIP:" in r.stdout:
+        pytest.skip(r.stdout.strip().splitlines()[-1])
+    assert r.returncode == 0, f"the fuzz child ended with code {r.returncode}:\n{tail}"
+    assert "OK: 3000 iterations" in r.stdout, tail
