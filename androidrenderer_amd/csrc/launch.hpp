@@ -6,6 +6,7 @@
 
 #include "../../include/sah_hip.h"
 #include "../../include/sah_mip_chain.h"
+#include "../../include/sah_taa.h"
 #include "../../include/sah_vrsaa.h"
 #include "params.hpp"
 #include "post_args.hpp"
@@ -46,6 +47,14 @@ hipError_t launch_vrsaa_contrast(const PlaneArg& color, const PlaneArg& depth, c
                                  uint32_t row_end, const float* luts, hipStream_t st);
 hipError_t launch_vrsaa_shading_rate(const PlaneArg& contrast, uint32_t cw, uint32_t ch, const PlaneArg& out, uint32_t sw, uint32_t sh, uint32_t d,
                                      const sah_shading_rate_params& params, hipStream_t st);
+
+// --- taa.hip
+struct TaaArgs {
+    PlaneArg lit, depth, mv, history, out;  // history: null without a history (the kernel then copies lit)
+    uint32_t W, H, row_begin, row_end;
+    float blend, djx, djy;                  // dj = previous_jitter - jitter
+};
+hipError_t launch_taa_resolve(const TaaArgs& a, bool history, bool hdr_weights, hipStream_t st);
 
 // --- mip_chain.hip
 struct MipChainArgs {

@@ -215,3 +215,38 @@ def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, sta
         ctx.vrsaa_measure_aliasing(images.plane(gbuffer["color"], _abi.FORMAT_R8G8B8A8_SRGB), images.plane(gbuffer["depth"], _abi.FORMAT_D32_SFLOAT), contrast_p)
         return contrast, sri
     return None
+
+
+class TemporalResolver:
+    """Temporal anti-aliasing over successive frames (include/sah_taa.h): owns the two ping-pong targets — this frame's output is the next
+    frame's history — and the previous frame's jitter.  The first frame, and the first after reset() (a camera cut), passes
+    SAH_TAA_HISTORY_INVALID: the output is then the lit frame."""
+
+    def __init__(self, ctx, width, height, blend=0.1, hdr_weights=True, device="cuda"):
+        import torch
+        self.ctx, self.width, self.height, self.blend, self.hdr_weights = ctx, width, height, blend, hdr_weights
+        self.targets = [torch.zeros((height, width, 4), dtype=torch.int16, device=device) for _ in range(2)]
+        self.current = 0  # index of the target the last resolve() wrote
+        self.previous_jitter = (0.0, 0.0)
+        self.history_valid = False
+
+    def reset(self):
+        self.history_valid = False
+
+    def resolve(self, lit, depth, motion_vectors, jitter, rows=(0, 0)):
+        """lit (H, W, 4) int16, depth (H, W) float32, motion_vectors (H, W, 2) int16 device arrays, `jitter` the (x, y) this frame was rendered
+        with.  Returns the resolved frame: one of the two targets, valid until the call after the next."""
+        params = _abi.TaaParams()
+        params.blend = self.blend
+        params.jitter[:] = [float(jitter[0]), float(jitter[1])]
+        params.previous_jitter[:] = self.previous_jitter if self.history_valid else params.jitter[:]
+        params.flags = (_abi.TAA_HDR_WEIGHTS if self.hdr_weights else 0) | (0 if self.history_valid else _abi.TAA_HISTORY_INVALID)
+        history, out = self.targets[self.current], self.targets[1 - self.current]
+        self.ctx.taa_resolve(images.plane(lit, _abi.FORMAT_R16G16B16A16_SFLOAT), images.plane(depth, _abi.FORMAT_D32_SFLOAT),
+                             images.plane(motion_vectors, _abi.FORMAT_R16G16_SFLOAT),
+                             images.plane(history, _abi.FORMAT_R16G16B16A16_SFLOAT) if self.history_valid else None,
+                             images.plane(out, _abi.FORMAT_R16G16B16A16_SFLOAT), params, rows)
+        self.current = 1 - self.current
+        self.previous_jitter = (params.jitter[0], params.jitter[1])
+        self.history_valid = True
+        return out

@@ -33,6 +33,7 @@
 #include "sah_gbuffer_motion.h"
 #include "sah_motion_vectors.h"
 #include "sah_rt_refit.h"
+#include "sah_taa.h"
 #include "sah_vrsaa.h"
 
 namespace sah {
@@ -497,6 +498,12 @@ public:
     float get_near() const { return near_value; }
     const sah_view_data& get_gpu_data() const { return gpu_data; }
     BufferHandle get_buffer() const { return &buffer; }  // scene_view.hpp: the ViewDataGPU uniform buffer
+    // scene_view.cpp:115-126: in pixels; the next update_transforms puts it into the projection (:163-164)
+    void set_jitter(float x, float y) {
+        gpu_data.previous_jitter[0] = gpu_data.jitter[0], gpu_data.previous_jitter[1] = gpu_data.jitter[1];
+        gpu_data.jitter[0] = x, gpu_data.jitter[1] = y;
+    }
+    std::array<float, 2> get_jitter() const { return {gpu_data.jitter[0], gpu_data.jitter[1]}; }
     void update_transforms() {
         forward = {std::cos(pitch) * std::sin(yaw), std::sin(pitch), std::cos(pitch) * std::cos(yaw)};
         const float half_pi = 3.14159265358979f / 2.0f;
@@ -510,6 +517,10 @@ public:
         const float t = 1.0f / std::tan(fov * 3.14159265358979f / 180.0f * 0.5f);
         Mat4 proj{};
         proj[0] = t / aspect; proj[5] = t; proj[11] = -1.0f; proj[14] = near_value;
+        if (gpu_data.jitter[0] != 0.f || gpu_data.jitter[1] != 0.f) {  // (without a jitter the matrix is what it always was, whatever the resolution holds)
+            proj[8] += gpu_data.jitter[0] * 2.f / gpu_data.render_resolution[0];
+            proj[9] += gpu_data.jitter[1] * 2.f / gpu_data.render_resolution[1];
+        }
         std::memcpy(gpu_data.last_frame_projection, gpu_data.projection, 64);
         std::memcpy(gpu_data.projection, proj.data(), 64);
         std::memcpy(gpu_data.inverse_projection, mat_inverse(proj).data(), 64);
@@ -1541,6 +1552,107 @@ inline void evaluate_antialiasing_none(RenderGraph& graph, TextureHandle lit_sce
                         return sah_copy_scene(ctx, &a, &b);
                     }));
 }
+
+// ---- HaltonSequence (RenderCore/core/halton_sequence.hpp:3-13, .cpp:8-22) --------------------------------------------------------------
+class HaltonSequence {
+public:
+    explicit HaltonSequence(float base_in) : base(base_in) {}
+    float get_next_value() {
+        const float x = d - n;
+        if (std::fabs(x - 1.f) < 1.1920929e-7f) {  // FLT_EPSILON
+            n = 1;
+            d *= base;
+        } else {
+            float y = d / base;
+            while (x <= y) y /= base;
+            n = (base + 1) * y - x;
+        }
+        return n / d;
+    }
+
+private:
+    float base, n = 0, d = 1;
+};
+
+// ---- IUpscaler (RenderCore/render/upscaling/upscaler.hpp:12-32): the seam the reference's anti-aliasing modes plug into -------------------
+// SceneRenderer asks it for the render resolution and the frame's jitter (scene_renderer.cpp:684-691) and calls evaluate in place of
+// "Copy scene" (:483-497).  The reference's three implementations (FSR3, DLSS, XeSS) are vendor SDKs and have no counterpart here.
+class IUpscaler {
+public:
+    virtual ~IUpscaler() = default;
+    virtual void initialize(const uint32_t output_resolution[2], uint32_t frame_number) = 0;
+    virtual std::array<uint32_t, 2> get_optimal_render_resolution() const = 0;
+    virtual void set_constants(const SceneView& scene_view, const uint32_t render_resolution[2]) = 0;
+    virtual std::array<float, 2> get_jitter() { return {jitter_sequence_x.get_next_value(), jitter_sequence_y.get_next_value()}; }
+    virtual void evaluate(RenderGraph& graph, const SceneView& view, const GBuffer& gbuffer, TextureHandle color_in, TextureHandle color_out,
+                          TextureHandle motion_vectors_in) = 0;
+
+private:
+    HaltonSequence jitter_sequence_x{2}, jitter_sequence_y{3};
+};
+
+// Temporal anti-aliasing behind that seam (include/sah_taa.h; builder-owned, no reference counterpart): render resolution == output
+// resolution, the jitter is the base class's Halton (2, 3) point minus a half over a repeating cycle of 8, and evaluate records the pass
+// "Temporal AA": color_in resolved against the history into color_out, which is also kept as the next frame's history.  Not
+// instantiated by the default frame (AA = None: evaluate_antialiasing_none).  The first evaluate, and the first after reset_history() (a
+// camera cut), has no history: color_out is then color_in.
+class TemporalAntiAliasing : public IUpscaler {
+public:
+    static constexpr uint32_t kJitterCycle = 8;
+    float blend = 0.1f;
+    bool hdr_weights = true;
+    explicit TemporalAntiAliasing(ResourceAllocator& allocator_in) : allocator(allocator_in) {}
+    void initialize(const uint32_t output_resolution[2], uint32_t frame_number) override {
+        resolution = {output_resolution[0], output_resolution[1]};
+        for (auto& h : history) h = allocator.create_texture("TAA history", SAH_FORMAT_R16G16B16A16_SFLOAT, resolution[0], resolution[1]);
+        if (cycle.empty())
+            for (uint32_t i = 0; i < kJitterCycle; i++) {
+                const auto j = IUpscaler::get_jitter();
+                cycle.push_back({j[0] - 0.5f, j[1] - 0.5f});
+            }
+        frame = frame_number;
+        history_valid = false;
+    }
+    std::array<uint32_t, 2> get_optimal_render_resolution() const override { return resolution; }
+    // what the pass needs of the view — this frame's and the last frame's jitter — is read from it when the pass runs
+    void set_constants(const SceneView&, const uint32_t /*render_resolution*/[2]) override {}
+    std::array<float, 2> get_jitter() override {
+        if (cycle.empty()) throw std::runtime_error("TemporalAntiAliasing: initialize has not been called");
+        return cycle[frame++ % kJitterCycle];
+    }
+    void reset_history() { history_valid = false; }
+    void evaluate(RenderGraph& graph, const SceneView& view, const GBuffer& gbuffer, TextureHandle color_in, TextureHandle color_out,
+                  TextureHandle motion_vectors_in) override {
+        TextureHandle depth = gbuffer.depth, previous = history[current], next = history[1 - current];
+        const bool use_history = history_valid;
+        graph.add_pass(hip_pass("Temporal AA", [this, &view, depth, color_in, color_out, motion_vectors_in, previous, next, use_history](sah_ctx* ctx) {
+                            if (!previous || !next || !depth || !color_in || !color_out || !motion_vectors_in) return (int)SAH_ERR_INVALID_ARGUMENT;
+                            const sah_view_data& v = view.get_gpu_data();
+                            sah_taa_params p{};
+                            p.blend = blend;
+                            p.jitter[0] = v.jitter[0], p.jitter[1] = v.jitter[1];
+                            p.previous_jitter[0] = v.previous_jitter[0], p.previous_jitter[1] = v.previous_jitter[1];
+                            p.flags = (hdr_weights ? SAH_TAA_HDR_WEIGHTS : 0u) | (use_history ? 0u : SAH_TAA_HISTORY_INVALID);
+                            const sah_plane l = color_in->plane(), d = depth->plane(), m = motion_vectors_in->plane(), h = previous->plane(), o = next->plane();
+                            if (int rc = sah_taa_resolve(ctx, &l, &d, &m, use_history ? &h : nullptr, &o, &p, 0, 0); rc != SAH_OK) return rc;
+                            // The history stays with this object; the caller's target gets a copy, on the context's stream: without a
+                            // history the pass stores its input's bits.
+                            p.flags |= SAH_TAA_HISTORY_INVALID;
+                            const sah_plane out = color_out->plane();
+                            return sah_taa_resolve(ctx, &o, &d, &m, nullptr, &out, &p, 0, 0);
+                        }));
+        current = 1 - current;  // swap the history
+        history_valid = true;
+    }
+
+private:
+    ResourceAllocator& allocator;
+    std::array<uint32_t, 2> resolution = {0, 0};
+    TextureHandle history[2] = {nullptr, nullptr};
+    std::vector<std::array<float, 2>> cycle;
+    uint32_t frame = 0, current = 0;
+    bool history_valid = false;
+};
 
 // ---- the row-sharded frame (no reference counterpart: north_star's "frames shard by screen-tile rows across the 8 GPUs") ------------------
 // Which rows a rank shades, copies, reduces and composites so that the two exchanges of sah_chain_submit — the quarter-resolution bloom

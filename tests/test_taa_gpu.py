@@ -1,0 +1,349 @@
+"""GPU: sah_taa_resolve (include/sah_taa.h) against the numpy restatement (tests/taa_ref.py) and its committed fixture, bit for bit; the
+Python TemporalResolver and the C++ façade's TemporalAntiAliasing over successive frames; and a rendered frame end to end.  The kernel's
+tile is 64 x 16 pixels."""
+import faulthandler
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from androidrenderer_amd import _abi, frame, lib, mesh, scene
+from tests import mv_reproject, util
+from tests import taa_ref as ref
+from tests.test_vrsaa_gpu import Image
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE = os.path.join(ROOT, "tests", "golden", "taa_69x21.npz")
+RGBA16F, D32, RG16F = _abi.FORMAT_R16G16B16A16_SFLOAT, _abi.FORMAT_D32_SFLOAT, _abi.FORMAT_R16G16_SFLOAT
+HDR, NO_HISTORY = _abi.TAA_HDR_WEIGHTS, _abi.TAA_HISTORY_INVALID
+
+
+@pytest.fixture(autouse=True)
+def _time_limit():
+    faulthandler.dump_traceback_later(120, exit=True)  # each test under a limit of its own: an overrun ends the process
+    yield
+    faulthandler.cancel_dump_traceback_later()
+
+
+@pytest.fixture(scope="module")
+def fixture():
+    return np.load(FIXTURE)
+
+
+def _params(blend, jitter, previous_jitter, flags):
+    p = _abi.TaaParams()
+    p.blend, p.flags = blend, flags
+    p.jitter[:] = [float(v) for v in jitter]
+    p.previous_jitter[:] = [float(v) for v in previous_jitter]
+    return p
+
+
+def _fixture_params(fx, flags):
+    return _params(float(fx["blend"]), fx["jitter"], fx["previous_jitter"], flags)
+
+
+class Planes:
+    """the five device planes of one call; pitches / offsets in the order lit, depth, motion vectors, history, out"""
+
+    def __init__(self, lit, depth, mv, history, pitches=(None,) * 5, offsets=(0,) * 5, out=None):
+        h, w = depth.shape
+        self.w, self.h = w, h
+        self.lit = Image(RGBA16F, w, h, pitches[0], lit, offsets[0])
+        self.depth = Image(D32, w, h, pitches[1], depth, offsets[1])
+        self.mv = Image(RG16F, w, h, pitches[2], mv, offsets[2])
+        self.history = None if history is None else Image(RGBA16F, w, h, pitches[3], history, offsets[3])
+        self.out = out or Image(RGBA16F, w, h, pitches[4], None, offsets[4])
+
+    def resolve(self, ctx, params, rows=(0, 0)):
+        import torch
+        ctx.taa_resolve(self.lit.plane, self.depth.plane, self.mv.plane, None if self.history is None else self.history.plane, self.out.plane, params, rows)
+        torch.cuda.synchronize()
+        assert self.lit.unchanged() and self.depth.unchanged() and self.mv.unchanged() and (self.history is None or self.history.unchanged())
+        return self.out.texels(np.uint16).reshape(self.h, self.w, 4)
+
+
+def _differs(got, want):
+    bad = (got != want).any(-1)
+    return f"{int(bad.sum())} of {bad.size} texels differ, first (y, x) at {np.argwhere(bad)[:4].tolist()}"
+
+
+# ---- the fixture --------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("flags,key", [(0, "out_plain"), (HDR, "out_hdr")])
+def test_fixture_bit_for_bit_and_repeatable(hip_ctx, fixture, flags, key):
+    fx = fixture
+    got = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"]).resolve(hip_ctx, _fixture_params(fx, flags))
+    assert np.array_equal(got, fx[key]), _differs(got, fx[key])
+    again = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"]).resolve(hip_ctx, _fixture_params(fx, flags))
+    assert again.tobytes() == got.tobytes()
+
+
+def test_without_history_the_output_is_lit(hip_ctx, fixture):
+    fx = fixture
+    for history in (None, fx["history"]):  # not read, given or not
+        got = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], history).resolve(hip_ctx, _fixture_params(fx, NO_HISTORY | HDR))
+        assert np.array_equal(got, fx["lit"]), _differs(got, fx["lit"])
+
+
+# (65, 17): one tile plus one pixel in both axes; (129, 33): two tiles plus one
+@pytest.mark.parametrize("extent", [(1, 1), (1, 9), (9, 1), (8, 8), (65, 17), (129, 33)])
+@pytest.mark.parametrize("flags", [0, HDR])
+def test_small_extents(hip_ctx, extent, flags):
+    w, h = extent
+    lit, depth, mv, history = ref.random_inputs(w, h, 11 + w)
+    jitter, previous = (0.3, -0.2), (-0.25, 0.4)
+    got = Planes(lit, depth, mv, history).resolve(hip_ctx, _params(0.1, jitter, previous, flags))
+    want, info = ref.resolve_ex(lit, depth, mv, history, 0.1, jitter, previous, flags)
+    assert np.array_equal(got, want), _differs(got, want)
+    if w * h >= 64:
+        assert info["valid"].any() and (want[..., :3] != lit[..., :3]).any()
+
+
+# pitches and offsets in bytes: lit, depth, motion vectors, history, out
+@pytest.mark.parametrize("pitches,offsets", [((69 * 8 + 4, 69 * 4 + 12, 69 * 4 + 20, 69 * 8 + 12, 69 * 8 + 4), (4, 8, 12, 4, 12)),  # no plane 16-byte aligned
+                                             ((560, 288, 304, 576, 560), (0, 0, 16, 32, 0)),                                        # padded, 16-byte aligned: the 16-byte path
+                                             ((560, 288, 304, 576, 560), (0, 0, 0, 8, 0))])                                         # one plane 8-byte aligned only
+def test_pitches_offsets_sentinels_and_inputs(hip_ctx, fixture, pitches, offsets):
+    fx = fixture
+    p = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"], pitches, offsets)
+    got = p.resolve(hip_ctx, _fixture_params(fx, HDR))  # (asserts the inputs unchanged)
+    assert np.array_equal(got, fx["out_hdr"]), _differs(got, fx["out_hdr"])
+    assert p.out.padding_intact()
+
+
+def test_row_bands_compose_to_the_whole(hip_ctx, fixture):
+    fx = fixture
+    W, H, pitch = 69, 21, 576
+    whole = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"], (None, None, None, None, pitch))
+    whole.resolve(hip_ctx, _fixture_params(fx, HDR))
+    out = Image(RGBA16F, W, H, pitch)
+    p = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"], out=out)
+    for rows in ((9, 10), (0, 9), (10, H)):
+        before = out.bytes().copy()
+        p.resolve(hip_ctx, _fixture_params(fx, HDR), rows)
+        changed = out.bytes() != before
+        body = changed[:H * pitch].reshape(H, pitch)
+        assert not body[:rows[0]].any() and not body[rows[1]:].any() and not body[:, W * 8:].any() and not changed[H * pitch:].any()
+    assert out.bytes().tobytes() == whole.out.bytes().tobytes()
+    assert np.array_equal(out.texels(np.uint16).reshape(H, W, 4), fx["out_hdr"])
+    before = out.bytes().copy()
+    p.resolve(hip_ctx, _fixture_params(fx, 0), (5, 5))  # an empty band writes nothing
+    assert (out.bytes() == before).all()
+
+
+# ---- sequences ------------------------------------------------------------------------------------------------------------------------------
+def _sequence(frames, w, h, seed):
+    """[(lit, depth, mv)] of a scene that changes a little from frame to frame, and the jitters of the façade's cycle"""
+    out = []
+    for i in range(frames):
+        lit, depth, mv, _ = ref.random_inputs(w, h, seed + i, specials=(i % 3 == 1))
+        out.append((lit, depth, mv))
+    return out, ref.jitter_cycle(8)
+
+
+def _restated_sequence(seq, jitters, blend, hdr):
+    outs, history, previous = [], None, None
+    for i, (lit, depth, mv) in enumerate(seq):
+        j = jitters[i % len(jitters)]
+        flags = (HDR if hdr else 0) | (NO_HISTORY if history is None else 0)
+        history = ref.resolve(lit, depth, mv, history, blend, j, j if previous is None else previous, flags)
+        previous = j
+        outs.append(history)
+    return outs
+
+
+def test_eight_frames_of_ping_pong_match_the_restatement_frame_by_frame(hip_ctx):
+    import torch
+    W, H, blend = 64, 36, 0.1
+    seq, jitters = _sequence(8, W, H, 300)
+    want = _restated_sequence(seq, jitters, blend, True)
+    resolver = frame.TemporalResolver(hip_ctx, W, H, blend=blend, hdr_weights=True)
+    for i, (lit, depth, mv) in enumerate(seq):
+        out = resolver.resolve(util.to_torch(lit), torch.from_numpy(depth).cuda(), util.to_torch(mv), jitters[i])
+        torch.cuda.synchronize()
+        got = util.from_torch(out, np.uint16)
+        assert np.array_equal(got, want[i]), f"frame {i}: " + _differs(got, want[i])
+    assert np.array_equal(want[0], seq[0][0]) and not np.array_equal(want[7], seq[7][0])
+    # after a cut the next frame is the lit frame again
+    resolver.reset()
+    out = resolver.resolve(util.to_torch(seq[3][0]), torch.from_numpy(seq[3][1]).cuda(), util.to_torch(seq[3][2]), jitters[0])
+    torch.cuda.synchronize()
+    assert np.array_equal(util.from_torch(out, np.uint16), seq[3][0])
+
+
+def _host_program(tmp_path):
+    built = os.path.join(ROOT, "tests", "cpp", "host_taa")
+    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_taa.h")]
+    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
+        return built
+    exe, libdir = str(tmp_path / "host_taa"), os.path.join(ROOT, "androidrenderer_amd")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
+                           f"-Wl,-rpath,{libdir}"], timeout=600)
+    return exe
+
+
+def test_three_frames_through_the_cpp_facade_match_the_python_resolver(tmp_path, hip_ctx):
+    import torch
+    W, H, blend = 64, 36, 0.25
+    seq, jitters = _sequence(3, W, H, 500)
+    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
+    with open(inp, "wb") as f:
+        f.write(np.array([W, H, 3, 1], np.uint32).tobytes())
+        f.write(np.float32(blend).tobytes())
+        for lit, depth, mv in seq:
+            f.write(lit.tobytes() + depth.tobytes() + mv.tobytes())
+    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    blob = open(outp, "rb").read()
+    size = 8 + W * H * 8
+    assert len(blob) == 3 * size
+    resolver = frame.TemporalResolver(hip_ctx, W, H, blend=blend, hdr_weights=True)
+    want = _restated_sequence(seq, jitters, blend, True)
+    for i, (lit, depth, mv) in enumerate(seq):
+        jitter = np.frombuffer(blob[i * size:i * size + 8], np.float32)
+        assert jitter.tobytes() == np.array(jitters[i], np.float32).tobytes(), f"frame {i}: the façade's jitter {jitter} is not {jitters[i]}"
+        facade = np.frombuffer(blob[i * size + 8:(i + 1) * size], np.uint16).reshape(H, W, 4)
+        out = resolver.resolve(util.to_torch(lit), torch.from_numpy(depth).cuda(), util.to_torch(mv), jitters[i])
+        torch.cuda.synchronize()
+        got = util.from_torch(out, np.uint16)
+        assert np.array_equal(facade, got), f"frame {i}: " + _differs(facade, got)
+        assert np.array_equal(got, want[i])
+
+
+# ---- the call contract ----------------------------------------------------------------------------------------------------------------------
+def test_side_stream_without_host_sync_and_under_capture(fixture):
+    import torch
+    fx = fixture
+    s = torch.cuda.Stream()
+    ctx = lib.Context(0)
+    try:
+        ctx.set_stream(s.cuda_stream)
+        a = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"])
+        second = Image(RGBA16F, 69, 21)
+        p1, p2 = _fixture_params(fx, HDR), _params(float(fx["blend"]), fx["previous_jitter"], fx["jitter"], 0)
+        want2 = ref.resolve(fx["lit"], fx["depth"], fx["motion_vectors"], fx["out_hdr"], float(fx["blend"]), fx["previous_jitter"], fx["jitter"], 0)
+
+        def two_frames():  # the second call's history is the first call's output: no host synchronisation in between
+            ctx.taa_resolve(a.lit.plane, a.depth.plane, a.mv.plane, a.history.plane, a.out.plane, p1)
+            ctx.taa_resolve(a.lit.plane, a.depth.plane, a.mv.plane, a.out.plane, second.plane, p2)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(s):
+            two_frames()
+        s.synchronize()
+        assert np.array_equal(a.out.texels(np.uint16).reshape(21, 69, 4), fx["out_hdr"])
+        assert np.array_equal(second.texels(np.uint16).reshape(21, 69, 4), want2)
+        # one captured graph, a linear chain; replayed over other input contents
+        lit2, depth2, mv2, history2 = ref.random_inputs(69, 21, 77)
+        b = Planes(lit2, depth2, mv2, history2)
+        direct1 = ref.resolve(lit2, depth2, mv2, history2, float(fx["blend"]), fx["jitter"], fx["previous_jitter"], HDR)
+        direct2 = ref.resolve(lit2, depth2, mv2, direct1, float(fx["blend"]), fx["previous_jitter"], fx["jitter"], 0)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=s):
+            two_frames()
+        for dst, src in ((a.lit, b.lit), (a.depth, b.depth), (a.mv, b.mv), (a.history, b.history)):
+            dst.t.copy_(src.t)
+        torch.cuda.synchronize()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert np.array_equal(a.out.texels(np.uint16).reshape(21, 69, 4), direct1)
+        assert np.array_equal(second.texels(np.uint16).reshape(21, 69, 4), direct2)
+        assert not np.array_equal(direct2, want2)
+    finally:
+        torch.cuda.synchronize()
+        ctx.close()
+
+
+def test_no_side_effects_on_the_context(hip_ctx, fixture):
+    fx = fixture
+    f = util.LightingFrame(64, 36, seed=5, sun_mode=_abi.SHADOW_MODE_CSM, gi=_abi.GI_LPV, flavour="atrium")
+    f.run_hip(hip_ctx)
+
+    def state():
+        return hip_ctx.cache_epoch(), hip_ctx.lighting_dispatch(), hip_ctx.copy_rebuilds()
+    before = state()
+    got = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"]).resolve(hip_ctx, _fixture_params(fx, 0))
+    assert state() == before
+    assert np.array_equal(got, fx["out_plain"])
+
+
+def test_refusals_launch_nothing(hip_ctx, fixture):
+    """(tests/test_taa_cpu.py runs the whole list on a context without a device; here: the target keeps its bytes)"""
+    import torch
+    fx = fixture
+    p = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"])
+    ok = _fixture_params(fx, 0)
+    lit, depth, mv, history, out = p.lit.plane, p.depth.plane, p.mv.plane, p.history.plane, p.out.plane
+
+    def retyped(plane, fmt):
+        return _abi.Plane(plane.ptr, plane.width, plane.height, plane.row_pitch_bytes, fmt)
+    INVALID, FORMAT = _abi.SAH_ERR_INVALID_ARGUMENT, _abi.SAH_ERR_UNSUPPORTED_FORMAT
+    cases = [((lit, depth, mv, history, retyped(out, _abi.FORMAT_R32_SFLOAT), ok), FORMAT),
+             ((lit, retyped(depth, _abi.FORMAT_R32_SFLOAT), mv, history, out, ok), FORMAT),
+             ((lit, depth, mv, None, out, ok), INVALID),
+             ((lit, depth, mv, history, out, ok, (0, 22)), INVALID),
+             ((lit, depth, mv, history, out, ok, (9, 3)), INVALID),
+             ((lit, depth, mv, history, out, _fixture_params(fx, 4)), INVALID),
+             ((lit, depth, mv, history, out, _params(0.0, (0, 0), (0, 0), 0)), INVALID),
+             ((lit, depth, mv, history, out, _params(0.5, (float("nan"), 0), (0, 0), 0)), INVALID),
+             ((lit, depth, mv, out, out, ok), INVALID),
+             ((out, depth, mv, history, out, ok), INVALID),
+             ((lit, depth, mv, history, _abi.Plane(out.ptr, 68, 21, 69 * 8, RGBA16F), ok), INVALID)]
+    for args, status in cases:
+        with pytest.raises(lib.SahError) as e:
+            hip_ctx.taa_resolve(*args)
+        assert e.value.status == status, args
+    torch.cuda.synchronize()
+    assert p.out.unchanged()
+
+
+# ---- end to end -------------------------------------------------------------------------------------------------------------------------------
+def test_rendered_frames_end_to_end(hip_ctx):
+    """The atrium through sah_gbuffer_motion_render and sah_lighting for two views of a camera that stands still and changes its jitter,
+    then the resolve: the output is the restatement's on the device's own planes, and with the jitter taken out the history is read where
+    the pixel is — |q - centre| within DEVIATION_FACTOR x FIXTURE_EXCESS_PIXELS (what the motion vectors are allowed against the fp64
+    reprojection, tests/mv_reproject.py) plus half an fp16 spacing below 1 (the vectors' store; |jitter - previous_jitter| < 1), over the
+    SOLID-covered pixels but MAX_LEFT_OUT of them."""
+    import torch
+    W, H, blend = 192, 108, 0.1
+    j0, j1 = (0.3, -0.2), (-0.25, 0.4)
+    keep = []
+    geo = mesh.geometry(mesh.to_device(mesh.atrium(2).arrays()), keep)
+    view = scene.SceneView()
+    view.rotate(0.0, math.radians(90.0))
+    view.set_position([-7.0, 1.0, 0.0])
+    view.set_render_resolution(W, H)
+    view.set_perspective_projection(75.0, float(W) / float(H), 0.05)
+    resolver = frame.TemporalResolver(hip_ctx, W, H, blend=blend, hdr_weights=True)
+    shapes = {"color": (4, torch.uint8), "normals": (4, torch.int16), "data": (4, torch.uint8), "emission": (4, torch.uint8), "depth": (0, torch.float32)}
+    frames = []
+    for jitter in (j0, j1):
+        view.jitter = np.array(jitter, np.float32)
+        view.update_transforms()
+        gb = {k: torch.zeros((H, W) + ((c,) if c else ()), dtype=t, device="cuda") for k, (c, t) in shapes.items()}
+        mv = torch.zeros((H, W, 2), dtype=torch.int16, device="cuda")
+        frame.rasterised_frame(hip_ctx, geo, view.gpu_data, gb, motion_vectors=mv, fused_motion=True)
+        torch.cuda.synchronize()
+        gb_np = {k: v.cpu().numpy() for k, v in gb.items()}
+        gb_np["normals"] = gb_np["normals"].view(np.uint16)
+        inputs = frame.LightingInputs(W, H, gbuffer=gb_np, seed=3, sun_mode=_abi.SHADOW_MODE_RT, gi=_abi.GI_NONE)
+        inputs.view = view
+        lit = inputs.run_hip(hip_ctx)
+        out = resolver.resolve(util.to_torch(lit), gb["depth"], mv, jitter)
+        torch.cuda.synchronize()
+        frames.append((lit, gb_np["depth"], util.from_torch(mv, np.uint16), util.from_torch(out, np.uint16)))
+    (lit0, _, _, out0), (lit1, depth1, mv1, out1) = frames
+    assert np.array_equal(out0, lit0)
+    want, info = ref.resolve_ex(lit1, depth1, mv1, out0, blend, j1, j0, HDR)
+    assert np.array_equal(out1, want), _differs(out1, want)
+    assert info["valid"].mean() > 0.9 and (out1[..., :3] != lit1[..., :3]).any()
+    solid = depth1 > 0
+    assert solid.mean() > 0.5
+    centre = np.stack(np.meshgrid(np.arange(W) + 0.5, np.arange(H) + 0.5), -1)
+    off = np.abs(info["q"].astype(np.float64) - centre).max(-1)
+    bound = mv_reproject.DEVIATION_FACTOR * mv_reproject.FIXTURE_EXCESS_PIXELS + 2.0 ** -12
+    left_out = (off[solid] > bound).mean()
+    print(f"end to end: {float(solid.mean()):.2f} of the pixels SOLID-covered, max |q - centre| {float(off[solid].max()):.5f} (bound {bound:.5f}), "
+          f"{float(left_out):.4f} left out")
+    assert left_out <= mv_reproject.MAX_LEFT_OUT
