@@ -51,6 +51,10 @@ class TaaParams(C.Structure):  # sah_taa_params (include/sah_taa.h): 24 bytes
     _fields_ = [("blend", C.c_float), ("jitter", C.c_float * 2), ("previous_jitter", C.c_float * 2), ("flags", C.c_uint32)]
 
 
+class TaaUpscaleParams(C.Structure):  # sah_taa_upscale_params (include/sah_taa_upscale.h): 28 bytes; flags are the TAA_* bits
+    _fields_ = [("blend", C.c_float), ("min_confidence", C.c_float), ("jitter", C.c_float * 2), ("previous_jitter", C.c_float * 2), ("flags", C.c_uint32)]
+
+
 class ShadingRateParams(C.Structure):  # sah_shading_rate_params (include/sah_vrsaa.h): 92 bytes
     _fields_ = [("contrast_image_resolution", C.c_uint32 * 2), ("shading_rate_image_resolution", C.c_uint32 * 2), ("max_rate", C.c_uint32 * 2),
                 ("num_shading_rates", C.c_uint32), ("rates", (C.c_uint32 * 2) * 8)]

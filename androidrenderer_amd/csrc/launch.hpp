@@ -7,6 +7,7 @@
 #include "../../include/sah_hip.h"
 #include "../../include/sah_mip_chain.h"
 #include "../../include/sah_taa.h"
+#include "../../include/sah_taa_upscale.h"
 #include "../../include/sah_vrsaa.h"
 #include "params.hpp"
 #include "post_args.hpp"
@@ -55,6 +56,15 @@ struct TaaArgs {
     float blend, djx, djy;                  // dj = previous_jitter - jitter
 };
 hipError_t launch_taa_resolve(const TaaArgs& a, bool history, bool hdr_weights, hipStream_t st);
+
+// --- taa_upscale.hip
+struct TaaUpscaleArgs {
+    PlaneArg lit, depth, mv, history, out;  // lit, depth, mv: w x h; history (null without a history), out: W x H
+    uint32_t w, h, W, H, row_begin, row_end;
+    float blend, min_confidence, jx, jy, djx, djy;  // j = jitter, dj = previous_jitter - jitter
+    float sx, sy, rx, ry;                           // fl(w / W), fl(h / H), fl(W / w), fl(H / h)
+};
+hipError_t launch_taa_upscale(const TaaUpscaleArgs& a, bool history, bool hdr_weights, hipStream_t st);
 
 // --- mip_chain.hip
 struct MipChainArgs {

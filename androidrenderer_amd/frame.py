@@ -250,3 +250,40 @@ class TemporalResolver:
         self.previous_jitter = (params.jitter[0], params.jitter[1])
         self.history_valid = True
         return out
+
+
+class TemporalUpscaler:
+    """Temporal upscaling over successive frames (include/sah_taa_upscale.h): the frame is rendered, jittered, at `render` and resolved to
+    `output`.  Owns the two ping-pong targets of the output extent and the previous frame's jitter, like TemporalResolver.  The first frame,
+    and the first after reset() (a camera cut), passes SAH_TAA_HISTORY_INVALID: the output is then the bilinear upsample of the lit frame."""
+
+    def __init__(self, ctx, render, output, blend=0.1, min_confidence=0.05, hdr_weights=True, device="cuda"):
+        import torch
+        self.ctx, self.render, self.output = ctx, tuple(render), tuple(output)
+        self.blend, self.min_confidence, self.hdr_weights = blend, min_confidence, hdr_weights
+        self.targets = [torch.zeros((self.output[1], self.output[0], 4), dtype=torch.int16, device=device) for _ in range(2)]
+        self.current = 0  # index of the target the last resolve() wrote
+        self.previous_jitter = (0.0, 0.0)
+        self.history_valid = False
+
+    def reset(self):
+        self.history_valid = False
+
+    def resolve(self, lit, depth, motion_vectors, jitter, rows=(0, 0)):
+        """lit (h, w, 4) int16, depth (h, w) float32, motion_vectors (h, w, 2) int16 device arrays of the render extent, `jitter` the (x, y)
+        in render pixels this frame was rendered with.  Returns the resolved (H, W, 4) frame: one of the two targets, valid until the call
+        after the next."""
+        params = _abi.TaaUpscaleParams()
+        params.blend, params.min_confidence = self.blend, self.min_confidence
+        params.jitter[:] = [float(jitter[0]), float(jitter[1])]
+        params.previous_jitter[:] = self.previous_jitter if self.history_valid else params.jitter[:]
+        params.flags = (_abi.TAA_HDR_WEIGHTS if self.hdr_weights else 0) | (0 if self.history_valid else _abi.TAA_HISTORY_INVALID)
+        history, out = self.targets[self.current], self.targets[1 - self.current]
+        self.ctx.taa_upscale(images.plane(lit, _abi.FORMAT_R16G16B16A16_SFLOAT), images.plane(depth, _abi.FORMAT_D32_SFLOAT),
+                             images.plane(motion_vectors, _abi.FORMAT_R16G16_SFLOAT),
+                             images.plane(history, _abi.FORMAT_R16G16B16A16_SFLOAT) if self.history_valid else None,
+                             images.plane(out, _abi.FORMAT_R16G16B16A16_SFLOAT), params, rows)
+        self.current = 1 - self.current
+        self.previous_jitter = (params.jitter[0], params.jitter[1])
+        self.history_valid = True
+        return out

@@ -44,6 +44,9 @@ VRSAA_EXPORTS = ["sah_vrsaa_measure_aliasing", "sah_vrsaa_shading_rate_image"]
 # temporal anti-aliasing: exported, declared in include/sah_taa.h (not sah_hip.h)
 TAA_EXPORTS = ["sah_taa_resolve"]
 
+# temporal upscaling: exported, declared in include/sah_taa_upscale.h (not sah_hip.h)
+TAA_UPSCALE_EXPORTS = ["sah_taa_upscale"]
+
 # the mip-chain generator: exported, declared in include/sah_mip_chain.h (not sah_hip.h)
 MIP_CHAIN_EXPORTS = ["sah_mip_chain_generate"]
 MIP_CHAIN_MAX_LEVELS = 12     # SAH_MIP_CHAIN_MAX_LEVELS
@@ -202,6 +205,7 @@ def load():
     lib.sah_vrsaa_measure_aliasing.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
     lib.sah_vrsaa_shading_rate_image.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.POINTER(_abi.ShadingRateParams)]
     lib.sah_taa_resolve.argtypes = [C.c_void_p] + [C.POINTER(_abi.Plane)] * 5 + [C.POINTER(_abi.TaaParams), C.c_uint32, C.c_uint32]
+    lib.sah_taa_upscale.argtypes = [C.c_void_p] + [C.POINTER(_abi.Plane)] * 5 + [C.POINTER(_abi.TaaUpscaleParams), C.c_uint32, C.c_uint32]
     lib.sah_mip_chain_generate.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32]
     lib.sah_rt_refit.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.c_void_p]
     _lib = lib
@@ -397,6 +401,13 @@ class Context:
         of device memory, one extent; params an _abi.TaaParams.  history may be None with _abi.TAA_HISTORY_INVALID in params.flags.  rows
         (begin, end) of `out`, (0, 0) = all."""
         self._check(self.lib.sah_taa_resolve(self.handle, C.byref(lit), C.byref(depth), C.byref(motion_vectors), None if history is None else C.byref(history),
+                                             C.byref(out), C.byref(params), rows[0], rows[1]))
+
+    def taa_upscale(self, lit, depth, motion_vectors, history, out, params, rows=(0, 0)):
+        """sah_taa_upscale (include/sah_taa_upscale.h): lit R16G16B16A16_SFLOAT, depth D32_SFLOAT, motion_vectors R16G16_SFLOAT of the render
+        extent, history and out R16G16B16A16_SFLOAT of the output extent (no smaller), _abi.Plane of device memory; params an
+        _abi.TaaUpscaleParams.  history may be None with _abi.TAA_HISTORY_INVALID in params.flags.  rows (begin, end) of `out`, (0, 0) = all."""
+        self._check(self.lib.sah_taa_upscale(self.handle, C.byref(lit), C.byref(depth), C.byref(motion_vectors), None if history is None else C.byref(history),
                                              C.byref(out), C.byref(params), rows[0], rows[1]))
 
     def vrsaa_shading_rate_image(self, contrast, sri, params):

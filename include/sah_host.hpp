@@ -34,6 +34,7 @@
 #include "sah_motion_vectors.h"
 #include "sah_rt_refit.h"
 #include "sah_taa.h"
+#include "sah_taa_upscale.h"
 #include "sah_vrsaa.h"
 
 namespace sah {
@@ -1648,6 +1649,79 @@ public:
 private:
     ResourceAllocator& allocator;
     std::array<uint32_t, 2> resolution = {0, 0};
+    TextureHandle history[2] = {nullptr, nullptr};
+    std::vector<std::array<float, 2>> cycle;
+    uint32_t frame = 0, current = 0;
+    bool history_valid = false;
+};
+
+// Temporal upscaling behind the same seam (include/sah_taa_upscale.h; builder-owned): the frame is rendered at the output resolution divided
+// by `scale` (>= 1) — get_optimal_render_resolution() = max(1, uint32(float(W) / scale + 0.5f)) per axis — and resolved to the output
+// resolution.  A lower render resolution needs more sample positions to cover an output pixel, so the jitter cycle has ceil(8 W^2 / w^2)
+// phases: the base class's Halton (2, 3) points minus a half, in render pixels.  evaluate records the pass "Temporal upscale": color_in,
+// gbuffer.depth and motion_vectors_in at the render resolution, color_out at the output resolution; the history stays with this object.  Not
+// instantiated by the default frame.  The first evaluate, and the first after reset_history(), has no history: color_out is then the bilinear
+// upsample of color_in.
+class TemporalUpscaling : public IUpscaler {
+public:
+    float blend = 0.1f, min_confidence = 0.05f;
+    bool hdr_weights = true;
+    TemporalUpscaling(ResourceAllocator& allocator_in, float scale_in) : allocator(allocator_in), scale(scale_in) {
+        if (!(scale >= 1.f)) throw std::invalid_argument("TemporalUpscaling: the scale must be at least 1");
+    }
+    void initialize(const uint32_t output_resolution[2], uint32_t frame_number) override {
+        output = {output_resolution[0], output_resolution[1]};
+        for (int a = 0; a < 2; a++) render[a] = std::max<uint32_t>(1u, (uint32_t)((float)output[a] / scale + 0.5f));
+        for (auto& h : history) h = allocator.create_texture("Upscaler history", SAH_FORMAT_R16G16B16A16_SFLOAT, output[0], output[1]);
+        const uint64_t W2 = (uint64_t)output[0] * output[0], w2 = (uint64_t)render[0] * render[0];
+        const uint64_t phases = (8 * W2 + w2 - 1) / w2;
+        if (phases > (1u << 20)) throw std::invalid_argument("TemporalUpscaling: more than 2^20 jitter phases");
+        HaltonSequence x{2}, y{3};  // the base class's sequences from their start: the cycle is a function of the resolutions alone
+        cycle.clear();
+        for (uint64_t i = 0; i < phases; i++) {
+            const float jx = x.get_next_value(), jy = y.get_next_value();
+            cycle.push_back({jx - 0.5f, jy - 0.5f});
+        }
+        frame = frame_number;
+        history_valid = false;
+    }
+    std::array<uint32_t, 2> get_optimal_render_resolution() const override { return render; }
+    uint32_t get_jitter_phase_count() const { return (uint32_t)cycle.size(); }
+    // what the pass needs of the view — this frame's and the last frame's jitter — is read from it when the pass runs
+    void set_constants(const SceneView&, const uint32_t /*render_resolution*/[2]) override {}
+    std::array<float, 2> get_jitter() override {
+        if (cycle.empty()) throw std::runtime_error("TemporalUpscaling: initialize has not been called");
+        return cycle[frame++ % cycle.size()];
+    }
+    void reset_history() { history_valid = false; }
+    void evaluate(RenderGraph& graph, const SceneView& view, const GBuffer& gbuffer, TextureHandle color_in, TextureHandle color_out,
+                  TextureHandle motion_vectors_in) override {
+        TextureHandle depth = gbuffer.depth, previous = history[current], next = history[1 - current];
+        const bool use_history = history_valid;
+        graph.add_pass(hip_pass("Temporal upscale", [this, &view, depth, color_in, color_out, motion_vectors_in, previous, next, use_history](sah_ctx* ctx) {
+                            if (!previous || !next || !depth || !color_in || !color_out || !motion_vectors_in) return (int)SAH_ERR_INVALID_ARGUMENT;
+                            const sah_view_data& v = view.get_gpu_data();
+                            sah_taa_upscale_params p{};
+                            p.blend = blend, p.min_confidence = min_confidence;
+                            p.jitter[0] = v.jitter[0], p.jitter[1] = v.jitter[1];
+                            p.previous_jitter[0] = v.previous_jitter[0], p.previous_jitter[1] = v.previous_jitter[1];
+                            p.flags = (hdr_weights ? SAH_TAA_HDR_WEIGHTS : 0u) | (use_history ? 0u : SAH_TAA_HISTORY_INVALID);
+                            const sah_plane l = color_in->plane(), d = depth->plane(), m = motion_vectors_in->plane(), h = previous->plane(), o = next->plane();
+                            if (int rc = sah_taa_upscale(ctx, &l, &d, &m, use_history ? &h : nullptr, &o, &p, 0, 0); rc != SAH_OK) return rc;
+                            // The history stays with this object and the caller's target gets the same frame.  The C ABI has no copy of a
+                            // plane that keeps every bit pattern at the output resolution, so the target is resolved from the same inputs:
+                            // the same bits, on the context's stream, without a synchronisation.
+                            const sah_plane out = color_out->plane();
+                            return sah_taa_upscale(ctx, &l, &d, &m, use_history ? &h : nullptr, &out, &p, 0, 0);
+                        }));
+        current = 1 - current;  // swap the history
+        history_valid = true;
+    }
+
+private:
+    ResourceAllocator& allocator;
+    float scale;
+    std::array<uint32_t, 2> output = {0, 0}, render = {0, 0};
     TextureHandle history[2] = {nullptr, nullptr};
     std::vector<std::array<float, 2>> cycle;
     uint32_t frame = 0, current = 0;

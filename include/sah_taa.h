@@ -9,8 +9,8 @@
  * conventions as sah_hip.h (this header includes it).
  *
  * The call runs on the context's stream, does no host synchronisation, allocates nothing, leaves its inputs and every cache and epoch of
- * the context untouched, and may be recorded under stream capture.  Upscaling (render resolution != output resolution), a bicubic history
- * tap and depth-based disocclusion tests are not part of it.
+ * the context untouched, and may be recorded under stream capture.  A bicubic history tap and depth-based disocclusion tests are not part
+ * of it.  Upscaling (render resolution != output resolution) is sah_taa_upscale's, in sah_taa_upscale.h.
  */
 #ifndef SAH_TAA_H
 #define SAH_TAA_H

@@ -1,0 +1,412 @@
+"""Temporal upscaling (include/sah_taa_upscale.h) without a GPU: the export and the header, the 28-byte parameter block, every refusal the
+header lists, and the numpy restatement (tests/taa_upscale_ref.py) — its committed fixture with every planted case asserted to take its
+branch, what the kernel's staging relies on (monotone nearest texels, the footprint of a tile, the upsample's taps inside the 3 x 3
+neighbourhood), the sign of the jitter against the fp64 reprojection, and convergence on an analytic scene."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from androidrenderer_amd import _abi, lib, scene
+from tests import mv_reproject
+from tests import taa_upscale_ref as ref
+from tests.test_taa_cpu import _stripes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import gen_golden_taa_upscale as gen  # noqa: E402
+
+f32 = np.float32
+RGBA16F, D32, RG16F = _abi.FORMAT_R16G16B16A16_SFLOAT, _abi.FORMAT_D32_SFLOAT, _abi.FORMAT_R16G16_SFLOAT
+
+
+# ---- exports, header, struct ----------------------------------------------------------------------------------------------------------
+def test_library_exports_the_entry_its_header_declares():
+    L = lib.load()
+    assert all(hasattr(L, s) for s in lib.TAA_UPSCALE_EXPORTS)
+    header = open(os.path.join(ROOT, "include", "sah_taa_upscale.h")).read()
+    assert sorted(re.findall(r"^int (sah_\w+)\(", header, re.M)) == sorted(lib.TAA_UPSCALE_EXPORTS) == ["sah_taa_upscale"]
+    assert not set(lib.TAA_UPSCALE_EXPORTS) & (set(lib.EXPORTS) | set(lib.TAA_EXPORTS))
+    assert '#include "sah_taa.h"' in header and "ABI-defined" in header
+    flat = " ".join(header.split())
+    assert "under row sharding the history must be whole" in flat and "j(row_begin) - 1 .. j(row_end - 1) + 1" in flat
+    assert "sah_taa_upscale.h" in open(os.path.join(ROOT, "include", "sah_taa.h")).read()
+    assert "upscale" not in open(os.path.join(ROOT, "include", "sah_hip.h")).read().lower()  # declared apart from sah_hip.h
+
+
+@pytest.mark.parametrize("language", ["c", "c++"])
+def test_header_compiles_and_the_parameter_block_is_28_bytes(tmp_path, language):
+    src = tmp_path / ("use.c" if language == "c" else "use.cpp")
+    check = "_Static_assert" if language == "c" else "static_assert"
+    src.write_text('#include "sah_taa_upscale.h"\n'
+                   f'{check}(sizeof(sah_taa_upscale_params) == 28, "sah_taa_upscale_params");\n'
+                   f'{check}(SAH_TAA_HISTORY_INVALID == 1u && SAH_TAA_HDR_WEIGHTS == 2u, "flags");\n'
+                   "int use(sah_ctx* c, const sah_plane* p, const sah_taa_upscale_params* s) { return sah_taa_upscale(c, p, p, p, p, p, s, 0, 0); }\n")
+    clang = "/opt/rocm/llvm/bin/clang" if os.path.exists("/opt/rocm/llvm/bin/clang") else "cc"
+    subprocess.check_call([clang, "-x", language, "-std=c11" if language == "c" else "-std=c++17", "-Wall", "-Werror", "-fsyntax-only",
+                           "-I", os.path.join(ROOT, "include"), str(src)], timeout=120)
+    P = _abi.TaaUpscaleParams
+    assert C.sizeof(P) == 28
+    assert [(n, getattr(P, n).offset) for n, _ in P._fields_] == [("blend", 0), ("min_confidence", 4), ("jitter", 8), ("previous_jitter", 16), ("flags", 24)]
+
+
+# ---- refusals ---------------------------------------------------------------------------------------------------------------------------
+OK, INVALID, FORMAT = "well-formed", _abi.SAH_ERR_INVALID_ARGUMENT, _abi.SAH_ERR_UNSUPPORTED_FORMAT
+NAMES = ("lit", "depth", "motion_vectors", "history", "out")
+FORMATS = {"lit": RGBA16F, "depth": D32, "motion_vectors": RG16F, "history": RGBA16F, "out": RGBA16F}
+RENDER_PLANES = NAMES[:3]
+
+
+def _plane(base, fmt, w, h, pitch=None, ptr=True, offset=0, bpp=None):
+    bpp = _abi.FORMAT_BPP[fmt] if bpp is None else bpp
+    return _abi.Plane((base + offset) if ptr else None, w, h, w * bpp if pitch is None else pitch, fmt)
+
+
+def _params(blend=0.1, min_confidence=0.05, jitter=(0.25, -0.125), previous_jitter=(-0.25, 0.375), flags=0):
+    p = _abi.TaaUpscaleParams()
+    p.blend, p.min_confidence, p.flags = blend, min_confidence, flags
+    p.jitter[:] = jitter
+    p.previous_jitter[:] = previous_jitter
+    return p
+
+
+def _cases(base):
+    """(name, [lit, depth, motion_vectors, history, out, params], rows, expected)"""
+    (w, h), (W, H) = (16, 12), (24, 16)
+    where = {n: base + (i << 16) for i, n in enumerate(NAMES)}
+    extent = {n: (w, h) if n in RENDER_PLANES else (W, H) for n in NAMES}
+
+    def call(params=None, **kw):
+        p = {n: _plane(where[n], FORMATS[n], *extent[n]) for n in NAMES}
+        p.update(kw)
+        return [p[n] for n in NAMES] + [_params() if params is None else params]
+    yield "whole", call(), (0, 0), OK
+    yield "band", call(), (3, 9), OK
+    yield "empty band", call(), (5, 5), OK
+    yield "hdr weights", call(_params(flags=2)), (0, 0), OK
+    yield "blend 1", call(_params(blend=1.0)), (0, 0), OK
+    yield "min_confidence 0", call(_params(min_confidence=0.0)), (0, 0), OK
+    yield "min_confidence 1", call(_params(min_confidence=1.0)), (0, 0), OK
+    yield "no history, none given", call(_params(flags=1), history=None), (0, 0), OK
+    yield "no history, one given but not looked at", call(_params(flags=3), history=_plane(where["history"], D32, 3, 0, ptr=False)), (0, 0), OK
+    yield "padded pitches", call(lit=_plane(where["lit"], RGBA16F, w, h, pitch=w * 8 + 4), depth=_plane(where["depth"], D32, w, h, pitch=w * 4 + 12)), (0, 0), OK
+    yield "render == output", call(history=_plane(where["history"], RGBA16F, w, h), out=_plane(where["out"], RGBA16F, w, h)), (0, 0), OK
+    yield "upscaled in x alone", call(history=_plane(where["history"], RGBA16F, W, h), out=_plane(where["out"], RGBA16F, W, h)), (0, 0), OK
+    yield "history NULL with a valid history", call(history=None), (0, 0), INVALID
+    yield "params NULL", call()[:5] + [None], (0, 0), INVALID
+    for n in NAMES:
+        fmt, bpp, (pw, ph) = FORMATS[n], _abi.FORMAT_BPP[FORMATS[n]], extent[n]
+        if n != "history":
+            p = call()
+            p[NAMES.index(n)] = None
+            yield f"{n}: null plane", p, (0, 0), INVALID
+        yield f"{n}: null pointer", call(**{n: _plane(where[n], fmt, pw, ph, ptr=False)}), (0, 0), INVALID
+        other = D32 if fmt != D32 else _abi.FORMAT_R32_SFLOAT
+        yield f"{n}: wrong format", call(**{n: _plane(where[n], other, pw, ph, bpp=bpp)}), (0, 0), FORMAT
+        yield f"{n}: short pitch", call(**{n: _plane(where[n], fmt, pw, ph, pitch=pw * bpp - 4)}), (0, 0), INVALID
+        yield f"{n}: zero width", call(**{n: _plane(where[n], fmt, 0, ph)}), (0, 0), INVALID
+        yield f"{n}: zero height", call(**{n: _plane(where[n], fmt, pw, 0)}), (0, 0), INVALID
+        yield f"{n}: misaligned pointer", call(**{n: _plane(where[n], fmt, pw, ph, offset=2)}), (0, 0), INVALID
+        yield f"{n}: pitch not a multiple of 4", call(**{n: _plane(where[n], fmt, pw, ph, pitch=pw * bpp + 2)}), (0, 0), INVALID
+    # the render planes share one extent, history and out share one extent
+    for n in ("depth", "motion_vectors", "history"):
+        fmt, bpp, (pw, ph) = FORMATS[n], _abi.FORMAT_BPP[FORMATS[n]], extent[n]
+        yield f"{n}: other width", call(**{n: _plane(where[n], fmt, pw - 1, ph)}), (0, 0), INVALID
+        yield f"{n}: other height", call(**{n: _plane(where[n], fmt, pw, ph + 1)}), (0, 0), INVALID
+    yield "lit: other width than depth and motion_vectors", call(lit=_plane(where["lit"], RGBA16F, w - 1, h)), (0, 0), INVALID
+    yield "out: other height than history", call(out=_plane(where["out"], RGBA16F, W, H - 1)), (0, 0), INVALID
+    yield "history at the render extent", call(history=_plane(where["history"], RGBA16F, w, h)), (0, 0), INVALID
+    # downscaling, in either axis or both
+    for name, (ow, oh) in (("narrower", (w - 1, H)), ("lower", (W, h - 1)), ("smaller", (w - 1, h - 1))):
+        yield f"output {name} than the render", call(history=_plane(where["history"], RGBA16F, ow, oh), out=_plane(where["out"], RGBA16F, ow, oh)), (0, 0), INVALID
+        yield f"output {name} than the render, no history", call(_params(flags=1), history=None, out=_plane(where["out"], RGBA16F, ow, oh)), (0, 0), INVALID
+    yield "lit as R16G16_SFLOAT", call(lit=_plane(where["lit"], RG16F, w, h, bpp=8)), (0, 0), FORMAT
+    yield "row_begin > row_end", call(), (9, 3), INVALID
+    yield "row_end > H", call(), (0, H + 1), INVALID
+    yield "row_end == H (beyond h)", call(), (h + 1, H), OK
+    for blend in (0.0, -0.5, 1.0000001, float("nan"), float("inf")):
+        yield f"blend {blend}", call(_params(blend=blend)), (0, 0), INVALID
+    for mc in (-1e-6, -1.0, 1.0000001, float("nan"), float("inf"), float("-inf")):
+        yield f"min_confidence {mc}", call(_params(min_confidence=mc)), (0, 0), INVALID
+    for k in range(4):
+        for v in (float("nan"), float("inf"), float("-inf")):
+            j = [0.25, -0.125, -0.25, 0.375]
+            j[k] = v
+            yield f"jitter component {k} = {v}", call(_params(jitter=j[:2], previous_jitter=j[2:])), (0, 0), INVALID
+    for flags in (4, 8, 0x80000000, 7):
+        yield f"flags {flags:#x}", call(_params(flags=flags)), (0, 0), INVALID
+    # out's byte range against every input's: the same memory, its last byte on the input's first, its first on the input's last
+    size = {n: extent[n][1] * extent[n][0] * _abi.FORMAT_BPP[FORMATS[n]] for n in NAMES}
+    for n in NAMES[:4]:
+        yield f"out is {n}'s memory", call(out=_plane(where[n], RGBA16F, W, H)), (0, 0), INVALID
+        yield f"out ends inside {n}", call(out=_plane(where[n] - size["out"] + 4, RGBA16F, W, H)), (0, 0), INVALID
+        yield f"out begins inside {n}", call(out=_plane(where[n] + size[n] - 4, RGBA16F, W, H)), (0, 0), INVALID
+        yield f"out ends where {n} begins", call(out=_plane(where[n] - size["out"], RGBA16F, W, H)), (0, 0), OK
+    yield "out is the unread history's memory", call(_params(flags=1), out=_plane(where["history"], RGBA16F, W, H)), (0, 0), OK
+
+
+def test_every_refusal_of_the_header_on_a_context_without_a_device():
+    """A malformed call answers its status; a well-formed one gets as far as selecting the device, which a detached context does not have
+    (SAH_ERR_HIP) — so nothing is launched and the made-up addresses are never used."""
+    L = lib.load()
+    L.sah_debug_create_detached.argtypes = [C.POINTER(C.c_void_p)]
+    h = C.c_void_p()
+    rc = L.sah_debug_create_detached(C.byref(h))
+    if rc == _abi.SAH_ERR_UNSUPPORTED:
+        pytest.skip("a HIP device is present (made-up addresses must not reach a GPU); tests/test_taa_upscale_gpu.py checks the refusals there")
+    assert rc == 0 and h.value
+    ref_of = lambda a: None if a is None else C.byref(a)  # noqa: E731
+    n = 0
+    try:
+        for name, args, rows, want in _cases(0x10000000):
+            got = L.sah_taa_upscale(h, *[ref_of(a) for a in args], *rows)
+            assert got == (_abi.SAH_ERR_HIP if want == OK else want), f"{name}: status {got}"
+            n += 1
+        ok = next(_cases(0x10000000))[1]
+        assert L.sah_taa_upscale(None, *[C.byref(a) for a in ok], 0, 0) == INVALID
+    finally:
+        L.sah_destroy(h)
+    assert n > 100
+
+
+# ---- the fixture ------------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def fixture():
+    return np.load(gen.FIXTURE)
+
+
+def test_generator_reproduces_the_committed_fixture(fixture):
+    got = gen.generate(int(fixture["seed"]))
+    assert sorted(got) == sorted(fixture.files)
+    for k in fixture.files:
+        assert np.asarray(got[k]).dtype == fixture[k].dtype and np.asarray(got[k]).tobytes() == fixture[k].tobytes(), k
+    (w, h), (W, H) = gen.RENDER, gen.OUTPUT
+    assert fixture["lit"].shape == (h, w, 4) == (23, 89, 4) and fixture["history"].shape == fixture["out_hdr"].shape == (H, W, 4) == (35, 133, 4)
+    assert -(-W // ref.TILE[0]) == 3 and -(-H // ref.TILE[1]) == 3  # 3 x 3 tiles
+    assert (W * h) % (w * H) != 0 and W % w != 0 and H % h != 0     # the ratios differ and neither is an integer
+    assert os.path.getsize(gen.FIXTURE) < 200 * 1024
+
+
+def test_every_planted_case_of_the_fixture_takes_its_branch(fixture):
+    fx = fixture
+    (w, h), (W, H) = gen.RENDER, gen.OUTPUT
+    args = (fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"], gen.OUTPUT, float(fx["blend"]), float(fx["min_confidence"]), fx["jitter"],
+            fx["previous_jitter"])
+    plain, info = ref.upscale_ex(*args, 0)
+    hdr, _ = ref.upscale_ex(*args, ref.HDR_WEIGHTS)
+    bare, bare_info = ref.upscale_ex(*args, ref.HISTORY_INVALID)
+    assert plain.tobytes() == fx["out_plain"].tobytes() and hdr.tobytes() == fx["out_hdr"].tobytes() and bare.tobytes() == fx["out_no_history"].tobytes()
+    assert ((plain != hdr).any(-1)).mean() > 0.5
+    i, j, q, valid, in_range, fallback = info["i"], info["j"], info["q"], info["valid"], info["in_range"], info["fallback"]
+    nearest = fx["lit"][j][:, i]
+    # every branch of Store: the blend, the upsample, the nearest texel's bits — with a history and without
+    blended, upsampled, copied = ~fallback, info["used_bilinear"], info["used_nearest"]
+    assert blended.sum() > 1000 and upsampled.sum() > 50 and copied.sum() >= 4 and (blended ^ upsampled ^ copied).all() and not (blended & upsampled).any()
+    assert (plain[copied][:, :3] == nearest[copied][:, :3]).all() and (plain[upsampled][:, :3] == bare[upsampled][:, :3]).all()
+    assert (plain[blended][:, :3] != bare[blended][:, :3]).any(-1).mean() > 0.9
+    assert bare_info["used_bilinear"].sum() > 4000 and bare_info["used_nearest"].sum() >= 4
+    assert (bare[bare_info["used_nearest"]][:, :3] == nearest[bare_info["used_nearest"]][:, :3]).all()
+    for out in (plain, hdr, bare):  # alpha: the nearest texel's bits, always
+        assert (out[..., 3] == nearest[..., 3]).all()
+    # the pixels of a planted motion vector: the output pixels whose nearest texel is the planted one (constant depth: every tap ties)
+    by, bx = ref.dilated_texel(fx["depth"])
+
+    def pixels(x, y):
+        assert (by[y, x], bx[y, x]) == (y, x)
+        m = (j[:, None] == y) & (i[None, :] == x)
+        assert m.any(), (x, y)
+        return m
+    rx, ry = f32(W) / f32(w), f32(H) / f32(h)
+    m = pixels(84, 5)   # no motion: q = centre + dj * r, dj = (-0.5, 0.5)
+    ys, xs = np.nonzero(m)
+    assert np.array_equal(q[m][:, 0], (xs.astype(f32) + f32(0.5)) + f32(-0.5) * rx) and np.array_equal(q[m][:, 1], (ys.astype(f32) + f32(0.5)) + f32(0.5) * ry)
+    assert valid[m].all() and not fallback[m].any()
+    m = pixels(5, 12)   # (1.5, -0.5) + dj = (1, 0): one render texel to the right, rx output pixels
+    ys, xs = np.nonzero(m)
+    assert np.array_equal(q[m][:, 0], (xs.astype(f32) + f32(0.5)) + rx) and np.array_equal(q[m][:, 1], ys.astype(f32) + f32(0.5)) and valid[m].all()
+    for x, y in ((3, 9), (85, 14)):  # finite, outside
+        m = pixels(x, y)
+        assert np.isfinite(q[m]).all() and not in_range[m].any()
+    assert np.isinf(q[pixels(4, 15)][:, 0]).all() and np.isinf(q[pixels(84, 7)][:, 1]).all()
+    assert np.isnan(q[pixels(6, 10)][:, 0]).all() and np.isnan(q[pixels(83, 11)][:, 1]).all()
+    for x, y in ((3, 9), (85, 14), (4, 15), (84, 7), (6, 10), (83, 11)):  # no usable history: the upsample is stored
+        m = pixels(x, y)
+        assert upsampled[m].all() and (plain[m] == bare[m]).all()
+    # a history with NaN and inf texels: in range, and refused for the tap's value
+    assert (in_range & ~info["history_finite"]).sum() >= 3
+    # lit: inf, NaN and -0 are there; a non-finite current colour under a valid history does not blend
+    lit16 = fx["lit"].view(np.float16)[..., :3]
+    assert np.isinf(lit16).sum() >= 2 and np.isnan(lit16).sum() >= 2 and (fx["lit"][..., :3] == 0x8000).sum() >= 2
+    assert (valid & fallback).sum() >= 3 and not np.isfinite(nearest.view(np.float16)[..., :3][valid & fallback]).all(-1).any()
+    assert (valid & copied).any() and (~valid & copied).any()
+    assert (np.signbit(info["lo"]) & (info["lo"] == 0)).any()  # -0 decides a bound somewhere
+    # depth: ties with a nearer neighbour, sky, NaN, inf
+    d = fx["depth"]
+    moved = (by != np.arange(h)[:, None]) | (bx != np.arange(w)[None, :])
+    assert moved[5:14, 36:50].any() and (d == 0).sum() >= 40 and np.isnan(d).sum() == 1 and np.isposinf(d).sum() == 1 and np.isneginf(d).sum() == 1
+    assert (by[10:13, 32:35] == 11).all() and (bx[10:13, 32:35] == 33).all() and (by[7, 18], bx[7, 18]) == (7, 18)
+    assert info["clamped"].sum() > 100 and (valid & ~info["clamped"]).sum() > 100
+    # Confidence: in [min_confidence, 1], both ends nearly reached (samples near the pixel's centre, and half a texel away)
+    conf = info["conf"]
+    assert conf.min() == f32(fx["min_confidence"]) and conf.max() > 0.95 and ((conf > 0.05) & (conf < 0.95)).mean() > 0.3
+
+
+# ---- what the kernel's staging relies on ----------------------------------------------------------------------------------------------------
+SCALES = (1.0, 65.0 / 64.0, 1.3, 1.5, 2.0, 3.0, 256.0)
+
+
+def _axis_cases():
+    """(n_out, n_render) of one axis: both axes of the GPU test's extents and of the fixture, and outputs of several sizes at every scale"""
+    pairs = set()
+    for (w, h), (W, H) in ref.EXTENTS + [(gen.RENDER, gen.OUTPUT)]:
+        pairs |= {(W, w), (H, h)}
+    for s in SCALES:
+        for n in (1, 16, 17, 64, 65, 129, 133, 256, 1000, 3840):
+            pairs.add((n, ref.render_resolution((n, n), s)[0]))
+    return sorted(pairs)
+
+
+def _jitters(n_out, n_render):
+    cycle = ref.upscale_jitter_cycle(n_out, n_render) if ref.jitter_phases(n_out, n_render) <= 128 else ref.jitter_cycle(128)
+    return [0.0, 0.5, -0.5, 0.25, -0.25] + [float(v) for p in cycle for v in p]
+
+
+def test_nearest_texels_are_monotone_and_a_tiles_footprint_is_bounded():
+    """i(X) never decreases, so the nearest texels of a tile lie between those of its first and last pixel, and with one texel of halo they
+    span at most 67 cells for a 64-pixel tile and 19 for a 16-pixel one."""
+    widest = {64: 0, 16: 0}
+    for n_out, n_render in _axis_cases():
+        for jitter in _jitters(n_out, n_render):
+            u, i = ref.sample_positions(n_out, n_render, jitter)
+            assert (np.diff(u) >= 0).all() and (np.diff(i) >= 0).all(), (n_out, n_render, jitter)
+            for tile, cells in zip(ref.TILE, ref.FOOTPRINT):
+                first = np.arange(0, n_out, tile)
+                last = np.minimum(first + tile, n_out) - 1
+                span = int((i[last] - i[first]).max()) + 3
+                assert span <= cells, (n_out, n_render, jitter, tile, span)
+                widest[tile] = max(widest[tile], span)
+    # 63 sx <= 63, so in exact arithmetic the first and last texel are at most 63 apart: 66 and 18 cells, reached at scale 1; the 67th and
+    # the 19th are what fp32 rounding may add
+    assert 66 <= widest[64] <= 67 and 18 <= widest[16] <= 19
+
+
+def test_the_upsamples_taps_lie_in_the_3x3_neighbourhood_of_the_nearest_texel():
+    """floor(fl(u - 0.5)) is floor(u) - 1 or floor(u) for every finite float, so the clamped taps are among clamp(i - 1), i, clamp(i + 1): no
+    exceptions for the kernel to handle.  Over the same cases, jitters far outside the image and floats around every power of two."""
+    for n_out, n_render in _axis_cases():
+        for jitter in _jitters(n_out, n_render) + [1e9, -1e9, 3e38, -3e38, 7.25, -1234.5]:
+            u, i = ref.sample_positions(n_out, n_render, jitter)
+            a, b, _ = ref.bilinear_axis(u, n_render)
+            near = [np.clip(i - 1, 0, n_render - 1), i, np.clip(i + 1, 0, n_render - 1)]
+            assert ((a == near[0]) | (a == near[1])).all() and ((b == near[1]) | (b == near[2])).all(), (n_out, n_render, jitter)
+    g = np.random.default_rng(3)
+    u = np.concatenate([np.ldexp(f32(1) + g.random(64).astype(f32) * f32(2.0 ** -20), e) * sign for e in range(-30, 40) for sign in (f32(1), f32(-1))] +
+                       [np.atleast_1d(np.nextafter(f32(v), f32(d))) for v in (0, 0.5, 1, 2, 8388608, 16777216, 2147483648) for d in (-np.inf, np.inf)]).astype(f32)
+    lower = ref.floor_to_int(u - f32(0.5))
+    assert ((lower == ref.floor_to_int(u) - 1) | (lower == ref.floor_to_int(u))).all()
+
+
+def test_rows_read_are_those_the_header_names():
+    (w, h), (W, H) = gen.RENDER, gen.OUTPUT
+    _, j = ref.sample_positions(H, h, -0.125)
+    assert ref.render_rows_read(0, H, H, h, -0.125) == (0, h - 1)
+    first, last = ref.render_rows_read(16, 24, H, h, -0.125)
+    assert (first, last) == (int(j[16]) - 1, int(j[23]) + 1) and 0 < first < last < h - 1
+
+
+def test_a_window_of_rows_restates_what_the_whole_image_does():
+    """upscale_ex(window=...) exists for the image that is too high to restate whole (tests/test_taa_upscale_gpu.py, rows beyond 2^28): on an
+    image that is not, a window gives the rows of the whole, with and without a history."""
+    from tests import taa_ref
+    (w, h), (W, H) = (37, 50), (53, 77)
+    lit, depth, mv, _ = taa_ref.random_inputs(w, h, 21, specials=False)
+    history = taa_ref.random_inputs(W, H, 22, specials=False)[3]
+    Y0, rows, h0, history0 = 40, 37, 20, 30
+    for flags in (0, ref.HDR_WEIGHTS, ref.HISTORY_INVALID):
+        whole, info = ref.upscale_ex(lit, depth, mv, history, (W, H), 0.1, 0.05, (0.25, -0.125), (-0.25, 0.375), flags)
+        part, part_info = ref.upscale_ex(lit[h0:], depth[h0:], mv[h0:], history[history0:], (W, H), 0.1, 0.05, (0.25, -0.125), (-0.25, 0.375), flags,
+                                         window=(Y0, rows, h0, h, history0))
+        assert part.shape == (rows, W, 4) and np.array_equal(part, whole[Y0:Y0 + rows]) and np.array_equal(part_info["j"], info["j"][Y0:Y0 + rows])
+        if not flags & ref.HISTORY_INVALID:
+            assert (~part_info["fallback"]).mean() > 0.8 and np.array_equal(part_info["q"], info["q"][Y0:Y0 + rows])
+
+
+# ---- the sign of dj and of the jitter -------------------------------------------------------------------------------------------------------
+def test_a_static_cameras_history_is_read_at_the_output_pixels_own_centre():
+    """SceneView at the render resolution twice with different jitters and no motion: the fp64 reprojection of every render pixel
+    (tests/mv_reproject.py) is jitter - previous_jitter, in render pixels.  Fed those vectors, the restatement reads the history at the
+    output pixel's own centre: |q - centre| within half an fp16 spacing below 1 (the vectors' store) times rx, whatever the jitters."""
+    (w, h), (W, H) = (64, 36), (96, 54)
+    j0, j1 = np.array([0.3, -0.2], f32), np.array([-0.25, 0.4], f32)
+    v = scene.SceneView.default(w, h)
+    v.jitter = j0
+    v.update_transforms()
+    v.jitter = j1
+    v.update_transforms()
+    depth = np.random.default_rng(1).uniform(0.001, 0.9, (h, w)).astype(f32)
+    mv = mv_reproject.reproject(v.gpu_data, depth)
+    want = (j1.astype(np.float64) - j0.astype(np.float64))
+    assert np.abs(mv - want).max() < 1e-3, (mv[0, 0], want)
+    lit, _, _, _ = ref_inputs(w, h, 4)
+    history = np.zeros((H, W, 4), np.uint16)
+    mv16 = np.broadcast_to(want.astype(np.float16), (h, w, 2)).copy().view(np.uint16)
+    _, info = ref.upscale_ex(lit, depth, mv16, history, (W, H), 0.1, 0.05, j1, j0, 0)
+    centre = np.stack(np.meshgrid(np.arange(W) + 0.5, np.arange(H) + 0.5), -1)
+    assert np.abs(info["q"] - centre).max() <= 2.0 ** -12 * 1.5 + 1e-5
+    # and the sample position: the jitter shifts the raster by -jitter render pixels
+    ux, _ = info["u"]
+    assert np.abs(ux - ((np.arange(W) + 0.5) * (w / W) - float(j1[0]))).max() < 1e-5
+    # the opposite sign would miss by 2 |dj| rx
+    _, wrong = ref.upscale_ex(lit, depth, mv16, history, (W, H), 0.1, 0.05, j0, j1, 0)
+    assert np.abs(wrong["q"] - centre).max() > 1.0
+
+
+def ref_inputs(w, h, seed):
+    from tests import taa_ref
+    return taa_ref.random_inputs(w, h, seed, specials=False)
+
+
+# ---- convergence --------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("output,blend,min_confidence,flags", [((96, 54), 0.1, 0.05, ref.HDR_WEIGHTS), ((128, 72), 0.25, 0.05, ref.HDR_WEIGHTS),
+                                                               ((128, 72), 0.25, 0.0, 0), ((83, 47), 0.25, 0.05, ref.HDR_WEIGHTS)])
+def test_a_static_camera_converges_towards_the_supersampled_image(output, blend, min_confidence, flags):
+    """Render 64 x 36, four cycles of the façade's jitter (ceil(8 W^2 / w^2) centred Halton phases), every frame point-sampled at
+    centre + jitter in render pixels with mv = fp16(jitter - previous_jitter).  Against a 16 x 16 box supersample at the output pixels, the
+    RMSE of each resolved frame of the last cycle is at most 0.75 of the smallest RMSE that any single frame's bilinear upsample (the
+    SAH_TAA_HISTORY_INVALID output) has."""
+    (w, h), (W, H) = (64, 36), output
+    ys, xs = np.mgrid[0:h, 0:w]
+    Ys, Xs = np.mgrid[0:H, 0:W]
+    sub = (np.arange(16) + 0.5) / 16
+    truth = _stripes((Xs[..., None, None] + sub[None, None, None, :]) * (w / W), (Ys[..., None, None] + sub[None, None, :, None]) * (h / H)).mean((-1, -2))
+    jitters = ref.upscale_jitter_cycle(W, w)
+    phases = len(jitters)
+    assert phases == -(-8 * W * W // (w * w))
+    depth = np.full((h, w), 0.5, f32)
+    single, resolved = [], []
+    history, previous = None, None
+
+    def rmse(bits):
+        return float(np.sqrt(((bits.view(np.float16)[..., 0].astype(np.float64) - truth) ** 2).mean()))
+    for n in range(4 * phases):
+        j = jitters[n % phases]
+        value = _stripes(xs + 0.5 + float(j[0]), ys + 0.5 + float(j[1]))
+        lit = np.stack([value, value, value, np.ones_like(value)], -1).astype(np.float16).view(np.uint16)
+        still = np.zeros((h, w, 2), np.uint16)
+        upsampled = ref.upscale(lit, depth, still, None, output, blend, min_confidence, j, j, flags | ref.HISTORY_INVALID)
+        single.append(rmse(upsampled))
+        if history is None:
+            history = upsampled
+        else:
+            mv = np.broadcast_to(np.array([j[0] - previous[0], j[1] - previous[1]], f32).astype(np.float16), (h, w, 2)).copy().view(np.uint16)
+            history = ref.upscale(lit, depth, mv, history, output, blend, min_confidence, j, previous, flags)
+        previous = j
+        resolved.append(rmse(history))
+    ratios = [r / min(single) for r in resolved[-phases:]]
+    print(f"{w} x {h} -> {W} x {H}, {phases} phases, flags {flags}, blend {blend}, min_confidence {min_confidence}: single-frame RMSE "
+          f"{min(single):.4f} .. {max(single):.4f}, last cycle resolved / best single {min(ratios):.3f} .. {max(ratios):.3f}")
+    assert max(ratios) <= 0.75
