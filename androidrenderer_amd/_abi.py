@@ -51,6 +51,19 @@ class TaaParams(C.Structure):  # sah_taa_params (include/sah_taa.h): 24 bytes
     _fields_ = [("blend", C.c_float), ("jitter", C.c_float * 2), ("previous_jitter", C.c_float * 2), ("flags", C.c_uint32)]
 
 
+class SsaoParams(C.Structure):  # sah_ssao_params (include/sah_ssao.h): 40 bytes; default() = the reference's CACAO settings
+    _fields_ = [("radius", C.c_float), ("max_radius_pixels", C.c_float), ("shadow_multiplier", C.c_float), ("shadow_clamp", C.c_float),
+                ("horizon_angle_threshold", C.c_float), ("fade_out_from", C.c_float), ("fade_out_to", C.c_float), ("edge_sharpness", C.c_float),
+                ("blur_passes", C.c_uint32), ("flags", C.c_uint32)]
+
+    @classmethod
+    def default(cls, **changes):
+        values = dict(radius=8.0, max_radius_pixels=32.0, shadow_multiplier=1.0, shadow_clamp=0.98, horizon_angle_threshold=0.06, fade_out_from=50.0,
+                      fade_out_to=300.0, edge_sharpness=50.0, blur_passes=2, flags=0)
+        values.update(changes)
+        return cls(**values)
+
+
 class TaaUpscaleParams(C.Structure):  # sah_taa_upscale_params (include/sah_taa_upscale.h): 28 bytes; flags are the TAA_* bits
     _fields_ = [("blend", C.c_float), ("min_confidence", C.c_float), ("jitter", C.c_float * 2), ("previous_jitter", C.c_float * 2), ("flags", C.c_uint32)]
 

@@ -6,6 +6,7 @@
 
 #include "../../include/sah_hip.h"
 #include "../../include/sah_mip_chain.h"
+#include "../../include/sah_ssao.h"
 #include "../../include/sah_taa.h"
 #include "../../include/sah_taa_upscale.h"
 #include "../../include/sah_vrsaa.h"
@@ -65,6 +66,19 @@ struct TaaUpscaleArgs {
     float sx, sy, rx, ry;                           // fl(w / W), fl(h / H), fl(W / w), fl(H / h)
 };
 hipError_t launch_taa_upscale(const TaaUpscaleArgs& a, bool history, bool hdr_weights, hipStream_t st);
+
+// --- ssao.hip
+struct SsaoArgs {
+    PlaneArg depth, normals, raw, out;  // raw: what the raw pass writes and the blur reads (scratch; ao_out itself without a blur)
+    uint32_t W, H;
+    uint32_t raw_begin, raw_end;        // rows of `raw` the raw pass writes: the band widened by the blur's reach, clipped to the image
+    uint32_t row_begin, row_end;        // rows of `out`
+    float m[9];                         // the 3 x 3 of view, column major: m[3 * column + row]
+    float p20, p21, ipx, ipy, tx, ty;   // 1 / P00, 1 / P11, 2 / W, 2 / H
+    float sx, rs, z_near;               // (0.5 W) P00, radius * sx
+    float max_radius_pixels, threshold, shadow_multiplier, shadow_clamp, fade_to, fade_span, edge_sharpness;
+};
+hipError_t launch_ssao(const SsaoArgs& a, uint32_t blur_passes, hipStream_t st);
 
 // --- mip_chain.hip
 struct MipChainArgs {

@@ -287,3 +287,24 @@ class TemporalUpscaler:
         self.previous_jitter = (params.jitter[0], params.jitter[1])
         self.history_valid = True
         return out
+
+
+class ScreenSpaceAO:
+    """Screen-space ambient occlusion (include/sah_ssao.h) for frames of one extent: owns the AO plane sah_lighting reads and the scratch plane
+    of the raw, unblurred result, which the library does not allocate.  `settings` are fields of _abi.SsaoParams; the defaults are the
+    reference's CACAO settings."""
+
+    def __init__(self, ctx, width, height, device="cuda", **settings):
+        import torch
+        self.ctx, self.width, self.height = ctx, width, height
+        self.params = _abi.SsaoParams.default(**settings)
+        self.ao = torch.ones((height, width), dtype=torch.float32, device=device)
+        self.scratch = torch.ones((height, width), dtype=torch.float32, device=device)
+
+    def generate(self, view_data, depth, normals, rows=(0, 0)):
+        """depth (H, W) float32 and normals (H, W, 4) int16 device arrays (the G-buffer's), view_data the frame's _abi.ViewData.  Returns the
+        AO plane, (H, W) float32: the same array every call."""
+        scratch = images.plane(self.scratch, _abi.FORMAT_R32_SFLOAT) if self.params.blur_passes else None
+        self.ctx.ssao(view_data, images.plane(depth, _abi.FORMAT_D32_SFLOAT), images.plane(normals, _abi.FORMAT_R16G16B16A16_SFLOAT), scratch,
+                      images.plane(self.ao, _abi.FORMAT_R32_SFLOAT), self.params, rows)
+        return self.ao

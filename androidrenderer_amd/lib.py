@@ -47,6 +47,9 @@ TAA_EXPORTS = ["sah_taa_resolve"]
 # temporal upscaling: exported, declared in include/sah_taa_upscale.h (not sah_hip.h)
 TAA_UPSCALE_EXPORTS = ["sah_taa_upscale"]
 
+# screen-space ambient occlusion: exported, declared in include/sah_ssao.h (not sah_hip.h)
+SSAO_EXPORTS = ["sah_ssao"]
+
 # the mip-chain generator: exported, declared in include/sah_mip_chain.h (not sah_hip.h)
 MIP_CHAIN_EXPORTS = ["sah_mip_chain_generate"]
 MIP_CHAIN_MAX_LEVELS = 12     # SAH_MIP_CHAIN_MAX_LEVELS
@@ -206,6 +209,7 @@ def load():
     lib.sah_vrsaa_shading_rate_image.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.POINTER(_abi.ShadingRateParams)]
     lib.sah_taa_resolve.argtypes = [C.c_void_p] + [C.POINTER(_abi.Plane)] * 5 + [C.POINTER(_abi.TaaParams), C.c_uint32, C.c_uint32]
     lib.sah_taa_upscale.argtypes = [C.c_void_p] + [C.POINTER(_abi.Plane)] * 5 + [C.POINTER(_abi.TaaUpscaleParams), C.c_uint32, C.c_uint32]
+    lib.sah_ssao.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData)] + [C.POINTER(_abi.Plane)] * 4 + [C.POINTER(_abi.SsaoParams), C.c_uint32, C.c_uint32]
     lib.sah_mip_chain_generate.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32]
     lib.sah_rt_refit.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.c_void_p]
     _lib = lib
@@ -409,6 +413,13 @@ class Context:
         _abi.TaaUpscaleParams.  history may be None with _abi.TAA_HISTORY_INVALID in params.flags.  rows (begin, end) of `out`, (0, 0) = all."""
         self._check(self.lib.sah_taa_upscale(self.handle, C.byref(lit), C.byref(depth), C.byref(motion_vectors), None if history is None else C.byref(history),
                                              C.byref(out), C.byref(params), rows[0], rows[1]))
+
+    def ssao(self, view_data, depth, normals, scratch, ao_out, params, rows=(0, 0)):
+        """sah_ssao (include/sah_ssao.h): depth D32_SFLOAT, normals R16G16B16A16_SFLOAT, scratch and ao_out R32_SFLOAT, _abi.Plane of device
+        memory, one extent; params an _abi.SsaoParams.  scratch may be None with params.blur_passes == 0.  rows (begin, end) of `ao_out`,
+        (0, 0) = all."""
+        self._check(self.lib.sah_ssao(self.handle, C.byref(view_data), C.byref(depth), C.byref(normals), None if scratch is None else C.byref(scratch),
+                                      C.byref(ao_out), C.byref(params), rows[0], rows[1]))
 
     def vrsaa_shading_rate_image(self, contrast, sri, params):
         """sah_vrsaa_shading_rate_image: contrast R16G16_SFLOAT, sri R8_UINT (_abi.Plane of device memory), params an _abi.ShadingRateParams

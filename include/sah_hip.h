@@ -318,8 +318,9 @@ int sah_sky_update_luts(sah_ctx* ctx, const sah_plane* transmittance, const sah_
                         const float light_vector[3]);
 
 /* AmbientOcclusionPhase::generate_ao with r.AO.Mode = Off — RenderCore/render/phase/ambient_occlusion_phase.cpp:167-179: the AO
- * target (R32_SFLOAT) is cleared to 1.0.  RTAO / CACAO need the scene BVH and stay in the renderer; their output is the `ao` input
- * plane of sah_lighting. */
+ * target (R32_SFLOAT) is cleared to 1.0.  The other two modes fill the same plane, the `ao` input of sah_lighting: RTAO is sah_rtao
+ * (below; it needs the acceleration structure of sah_rt_build), and the CACAO slot — a vendor SDK in the reference — is taken by
+ * sah_ssao (sah_ssao.h), which needs depth and normals only. */
 int sah_ao_clear(sah_ctx* ctx, const sah_plane* ao);
 
 /* Irradiance-cache probe maintenance (a11) — RenderCore/render/gi/irradiance_cache.cpp:455-486 (copy_probes_to_new_texture)

@@ -33,6 +33,7 @@
 #include "sah_gbuffer_motion.h"
 #include "sah_motion_vectors.h"
 #include "sah_rt_refit.h"
+#include "sah_ssao.h"
 #include "sah_taa.h"
 #include "sah_taa_upscale.h"
 #include "sah_vrsaa.h"
@@ -1244,13 +1245,29 @@ private:
 };
 
 // RenderCore/render/phase/ambient_occlusion_phase.cpp:157-189: r.AO.Mode = Off clears the target to 1.0 (:167-179), RTAO traces one
-// occlusion ray per pixel (evaluate_rtao, :357-397); CACAO is a vendor SDK and hands its result over as the AO plane.
-enum class AoTechnique { Off = 0, CACAO = 1, RTAO = 2 };
+// occlusion ray per pixel (evaluate_rtao, :357-397); CACAO is a vendor SDK and hands its result over as the AO plane.  ScreenSpace is this
+// library's own pass for the CACAO slot (include/sah_ssao.h; builder-owned, no reference counterpart): it needs neither the noise
+// texture nor a built acceleration structure.
+enum class AoTechnique { Off = 0, CACAO = 1, RTAO = 2, ScreenSpace = 3 };
+// The settings of sah_ssao_params under the names and with the defaults the reference gives CACAO (ambient_occlusion_phase.cpp:302-320);
+// the radius is the phase's ao_radius (r.AO.MaxRayDistance).
+struct ScreenSpaceAoSettings {
+    float max_radius_pixels = 32.f;
+    float shadow_multiplier = 1.f, shadow_clamp = 0.98f, horizon_angle_threshold = 0.06f;
+    float fade_out_from = 50.f, fade_out_to = 300.f;
+    float edge_sharpness = 50.f;
+    uint32_t blur_passes = 2;
+};
 class AmbientOcclusionPhase {
 public:
     AoTechnique technique = AoTechnique::RTAO;  // r.AO (ambient_occlusion_phase.cpp:15-17: RTAO is the reference's default)
     uint32_t rtao_samples = 1;                  // r.AO.RTAO.SamplesPerPixel (:19-21)
     float ao_radius = 8.0f;                     // r.AO.MaxRayDistance (:23-25)
+    ScreenSpaceAoSettings screen_space;
+    AmbientOcclusionPhase() = default;
+    // ScreenSpace keeps the raw, unblurred result in a texture of its own, which needs an allocator: on a default-constructed phase
+    // generate_ao throws std::logic_error when it is asked for ScreenSpace with screen_space.blur_passes > 0 (the default is 2)
+    explicit AmbientOcclusionPhase(ResourceAllocator& allocator_in) : allocator(&allocator_in) {}
     void generate_ao(RenderGraph& graph, TextureHandle ao_out) {  // the Off path (no scene needed)
         graph.add_pass(hip_pass("Clear AO", [ao_out](sah_ctx* ctx) {
                             const sah_plane p = ao_out->plane();
@@ -1260,6 +1277,7 @@ public:
     // ambient_occlusion_phase.hpp: generate_ao(graph, view, scene, noise, gbuffer_normals, gbuffer_depth, ao_out)
     void generate_ao(RenderGraph& graph, const SceneView& view, const RenderScene& scene, const NoiseTexture& noise, TextureHandle gbuffer_normals,
                      TextureHandle gbuffer_depth, TextureHandle ao_out) {
+        if (technique == AoTechnique::ScreenSpace) return generate_screen_space(graph, view, gbuffer_normals, gbuffer_depth, ao_out);
         if (technique != AoTechnique::RTAO || !scene.get_raytracing_scene().is_built()) return generate_ao(graph, ao_out);
         TextureHandle layer = noise.get_layer(frame_index);
         frame_index++;
@@ -1270,6 +1288,30 @@ public:
     }
 
 private:
+    // The scratch texture is (re-)created when the target's extent changes; without a blur none is needed.
+    void generate_screen_space(RenderGraph& graph, const SceneView& view, TextureHandle gbuffer_normals, TextureHandle gbuffer_depth, TextureHandle ao_out) {
+        if (screen_space.blur_passes > 0 && !allocator)
+            throw std::logic_error("AmbientOcclusionPhase: ScreenSpace with blur_passes > 0 needs the phase constructed with an allocator");
+        if (ao_out && screen_space.blur_passes > 0 && (!scratch || scratch->desc.width != ao_out->desc.width || scratch->desc.height != ao_out->desc.height))
+            scratch = allocator->create_texture("SSAO raw", SAH_FORMAT_R32_SFLOAT, ao_out->desc.width, ao_out->desc.height);
+        TextureHandle raw = scratch;
+        graph.add_pass(hip_pass("Screen-space ambient occlusion", [this, &view, raw, gbuffer_normals, gbuffer_depth, ao_out](sah_ctx* ctx) {
+                            if (!gbuffer_depth || !gbuffer_normals || !ao_out) return (int)SAH_ERR_INVALID_ARGUMENT;
+                            sah_ssao_params p{};
+                            p.radius = ao_radius;
+                            p.max_radius_pixels = screen_space.max_radius_pixels;
+                            p.shadow_multiplier = screen_space.shadow_multiplier, p.shadow_clamp = screen_space.shadow_clamp;
+                            p.horizon_angle_threshold = screen_space.horizon_angle_threshold;
+                            p.fade_out_from = screen_space.fade_out_from, p.fade_out_to = screen_space.fade_out_to;
+                            p.edge_sharpness = screen_space.edge_sharpness;
+                            p.blur_passes = screen_space.blur_passes;
+                            const sah_plane d = gbuffer_depth->plane(), n = gbuffer_normals->plane(), o = ao_out->plane();
+                            const sah_plane s = raw ? raw->plane() : sah_plane{};
+                            return sah_ssao(ctx, &view.get_gpu_data(), &d, &n, raw ? &s : nullptr, &o, &p, 0, 0);  // (no scratch with a blur: refused)
+                        }));
+    }
+    ResourceAllocator* allocator = nullptr;
+    TextureHandle scratch = nullptr;
     uint32_t frame_index = 0;
 };
 
