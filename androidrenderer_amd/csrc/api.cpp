@@ -15,6 +15,7 @@
 
 #include "../../include/sah_hip.h"
 #include "ctx.hpp"
+#include "fast_pixel_map.hpp"
 #include "launch.hpp"
 
 namespace {
@@ -474,6 +475,9 @@ int lighting_fast_layout(sah_ctx* ctx, const sah_lighting_desc* d, const Lightin
         const uint64_t gpr = W / (uint32_t)ppt, threads = (gpr * (r1 - r0) + 255) / 256 * 256;
         fast.row_magic = (gpr >= 2 && threads * gpr < (1ull << 32)) ? (uint32_t)((1ull << 32) / gpr) + 1u : 0u;
     }
+    // which pixels a wave owns: a tile instead of a strip where the kernel gathers (shadow-map taps, the LPV footprint) — a permutation of the same
+    // thread indices, so the grid, the segments and the sky workgroups above stand as they are (fast_pixel_map.hpp)
+    fast.tile_rows = fast_tile_rows_for(call.sun_mode == SAH_SHADOW_MODE_CSM || call.gi_kind == SAH_GI_LPV, W, r1 - r0, (uint32_t)ppt);
     fast.state = ctx->state;
     fast.hint_slot = ctx->hint_slot;  // (FrameState::deferred_hint: consecutive calls take the two words in turn)
     ctx->hint_slot ^= 1u;

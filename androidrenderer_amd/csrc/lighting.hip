@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "../../include/sah_hip.h"
+#include "fast_pixel_map.hpp"
 #include "lighting_common.hpp"
 #include "lighting_fast.hpp"
 #include "launch.hpp"
@@ -116,9 +117,9 @@ __global__ void __launch_bounds__(256) k_lighting_fixup(const LightingArgs a, co
         for (uint32_t step = kFixupSegs / 2; step >= 1; step >>= 1)
             if (s_pref[s + step] <= i) s += step;
         const uint32_t code = f.seg_list[(size_t)(seg0 + s) * f.seg_stride + (i - s_pref[s])];
-        const uint32_t g = (seg0 + s) * 64u + code / PPT;
-        const uint32_t ry = g / groups_per_row;
-        const uint32_t y = a.row_begin + ry, x = (g - ry * groups_per_row) * PPT + code % PPT;
+        const uint32_t g = (seg0 + s) * 64u + code / PPT;  // the thread of the fast kernel that listed the pixel: the same map back
+        const FastPixel at = fast_pixel_of(g, groups_per_row, a.row_end - a.row_begin, PPT, f.tile_rows, f.row_magic);
+        const uint32_t y = a.row_begin + at.row, x = at.x0 + code % PPT;
         Px p;
         p.color = *reinterpret_cast<const uint32_t*>(a.color.ptr + (size_t)y * a.color.pitch + (size_t)x * 4);
         p.data = *reinterpret_cast<const uint32_t*>(a.data.ptr + (size_t)y * a.data.pitch + (size_t)x * 4);
@@ -220,12 +221,13 @@ __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const Lighti
     if (SKY) {
         if (blockIdx.x < f.sky_first) {
             const uint32_t ratio = f.sky_ratio;
-            const uint32_t groups_per_row = a.width / PPT, total = groups_per_row * (a.row_end - a.row_begin);
+            const uint32_t groups_per_row = a.width / PPT, rows = a.row_end - a.row_begin, total = groups_per_row * rows;
 #pragma unroll 1
             for (uint32_t k = 0; k < ratio; k++) {
                 const uint32_t gid = (blockIdx.x * ratio + k) * 256u + threadIdx.x;
                 if (gid >= total) break;
-                const uint32_t ry = gid / groups_per_row, y = a.row_begin + ry, x0 = (gid - ry * groups_per_row) * PPT;
+                const FastPixel at = fast_pixel_of(gid, groups_per_row, rows, PPT, f.tile_rows, f.row_magic);  // (the surface workgroups' map)
+                const uint32_t y = a.row_begin + at.row, x0 = at.x0;
                 uint32_t wz[PPT];
                 load_words<PPT>(a.depth.ptr + (size_t)y * a.depth.pitch + (size_t)x0 * 4, wz);
 #pragma unroll 1
@@ -245,9 +247,11 @@ __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const Lighti
     const uint32_t gid = block_id * 256u + threadIdx.x;
     const uint32_t rows = a.row_end - a.row_begin;
     const bool active = gid < groups_per_row * rows;
-    const uint32_t ry = active ? (f.row_magic ? __umulhi(gid, f.row_magic) : gid / groups_per_row) : 0u;
-    const uint32_t y = a.row_begin + ry;
-    const uint32_t x0 = active ? (gid - ry * groups_per_row) * PPT : 0u;
+    // which pixels the thread owns: a strip of its row, or — where the launch gathers — its place in the wave's 64-pixel-wide tile (fast_pixel_map.hpp)
+    FastPixel at = {0u, 0u};
+    if (active) at = fast_pixel_of(gid, groups_per_row, rows, PPT, f.tile_rows, f.row_magic);
+    const uint32_t y = a.row_begin + at.row;
+    const uint32_t x0 = at.x0;
     const bool lpv_bad = (GI == SAH_GI_LPV) ? (f.state->nonfinite != 0u) : false;
     const bool div_shared = (SUN == SAH_SHADOW_MODE_CSM || GI == SAH_GI_LPV) ? pos_div_shared_of(f) : false;
 

@@ -110,6 +110,7 @@ struct FastArgs {
     uint32_t sky_ratio;  // surface workgroups per sky workgroup of k_lighting_fast's grid (lighting.hip); >= 1
     uint32_t sky_first;  // the number of sky workgroups, which lead the grid: ceil(surface workgroups / sky_ratio) with a sky bound, else 0
     uint32_t row_magic;  // floor(2^32 / groups per row) + 1 when mulhi(gid, row_magic) == gid / groups_per_row for every thread of the call, else 0
+    uint32_t tile_rows;  // 0: a wave is a strip of one row; R: a wave is a tile of 64 pixels x R rows (fast_pixel_map.hpp, where the host's rule stands too)
     uint32_t repack;       // 1: this call rebuilds the gather copy first
     const float* colx_tab; // per-column view-space x numerators (k_colx_table): [0, width) the GLSL flavour, [colx_stride, ..) the Slang one; or null
     uint32_t colx_stride;
