@@ -308,3 +308,53 @@ class ScreenSpaceAO:
         self.ctx.ssao(view_data, images.plane(depth, _abi.FORMAT_D32_SFLOAT), images.plane(normals, _abi.FORMAT_R16G16B16A16_SFLOAT), scratch,
                       images.plane(self.ao, _abi.FORMAT_R32_SFLOAT), self.params, rows)
         return self.ao
+
+
+class RayTracedDenoiser:
+    """The temporal and edge-aware filter for a one-channel ray-traced plane (include/sah_rt_denoise.h) over successive frames of one
+    extent: owns the two ping-ponged accumulation / sample-count pairs — this frame's accum_out and length_out are the next frame's history
+    — the kept copy of the last frame's depth, and the `denoised` plane sah_lighting reads; tracks the previous jitter and whether there
+    is a history, like TemporalResolver.  The first frame, and the first after reset() (a camera cut), passes
+    SAH_RT_DENOISE_HISTORY_INVALID.  `settings` are fields of _abi.RtDenoiseParams.  One instance per plane (AO, the sun's mask).  The
+    depth is kept with a device copy on torch's current stream, which must be the context's."""
+
+    def __init__(self, ctx, width, height, device="cuda", **settings):
+        import torch
+        self.ctx, self.width, self.height = ctx, width, height
+        self.params = _abi.RtDenoiseParams.default(**settings)
+        self.accum = [torch.zeros((height, width), dtype=torch.float32, device=device) for _ in range(2)]
+        self.length = [torch.zeros((height, (width + 1) // 2 * 2), dtype=torch.float16, device=device) for _ in range(2)]  # pitch: a multiple of 4
+        self.previous_depth = torch.zeros((height, width), dtype=torch.float32, device=device)
+        self.denoised = torch.ones((height, width), dtype=torch.float32, device=device)
+        self.current = 0  # index of the pair the last denoise() wrote
+        self.previous_jitter = (0.0, 0.0)
+        self.history_valid = False
+
+    def reset(self):
+        self.history_valid = False
+
+    def _length_plane(self, t):
+        return _abi.Plane(t.data_ptr(), self.width, self.height, t.shape[1] * 2, _abi.FORMAT_R16_SFLOAT)
+
+    def denoise(self, view_data, noisy, depth, normals, motion_vectors, jitter):
+        """noisy and depth (H, W) float32, normals (H, W, 4) int16, motion_vectors (H, W, 2) int16 device arrays of this frame, view_data its
+        _abi.ViewData, `jitter` the (x, y) it was rendered with.  Returns the denoised plane, (H, W) float32: the same array every call."""
+        p = self.params
+        p.jitter[:] = [float(jitter[0]), float(jitter[1])]
+        p.previous_jitter[:] = self.previous_jitter if self.history_valid else p.jitter[:]
+        p.flags = 0 if self.history_valid else _abi.RT_DENOISE_HISTORY_INVALID
+        old, new = self.current, 1 - self.current
+        R32F, D32 = _abi.FORMAT_R32_SFLOAT, _abi.FORMAT_D32_SFLOAT
+        previous = dict(previous_depth=images.plane(self.previous_depth, D32), history=images.plane(self.accum[old], R32F),
+                        history_length=self._length_plane(self.length[old])) if self.history_valid else {}
+        desc = _abi.RtDenoiseDesc.of(noisy=images.plane(noisy, R32F), depth=images.plane(depth, D32),
+                                     normals=images.plane(normals, _abi.FORMAT_R16G16B16A16_SFLOAT),
+                                     motion_vectors=images.plane(motion_vectors, _abi.FORMAT_R16G16_SFLOAT),
+                                     accum_out=images.plane(self.accum[new], R32F), length_out=self._length_plane(self.length[new]),
+                                     denoised=images.plane(self.denoised, R32F), **previous)
+        self.ctx.rt_denoise(view_data, desc, p)
+        self.previous_depth.copy_(depth)
+        self.current = new
+        self.previous_jitter = (p.jitter[0], p.jitter[1])
+        self.history_valid = True
+        return self.denoised

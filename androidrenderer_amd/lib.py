@@ -50,6 +50,9 @@ TAA_UPSCALE_EXPORTS = ["sah_taa_upscale"]
 # screen-space ambient occlusion: exported, declared in include/sah_ssao.h (not sah_hip.h)
 SSAO_EXPORTS = ["sah_ssao"]
 
+# the filter for the ray-traced masks: exported, declared in include/sah_rt_denoise.h (not sah_hip.h)
+RT_DENOISE_EXPORTS = ["sah_rt_denoise"]
+
 # the mip-chain generator: exported, declared in include/sah_mip_chain.h (not sah_hip.h)
 MIP_CHAIN_EXPORTS = ["sah_mip_chain_generate"]
 MIP_CHAIN_MAX_LEVELS = 12     # SAH_MIP_CHAIN_MAX_LEVELS
@@ -210,7 +213,8 @@ def load():
     lib.sah_taa_resolve.argtypes = [C.c_void_p] + [C.POINTER(_abi.Plane)] * 5 + [C.POINTER(_abi.TaaParams), C.c_uint32, C.c_uint32]
     lib.sah_taa_upscale.argtypes = [C.c_void_p] + [C.POINTER(_abi.Plane)] * 5 + [C.POINTER(_abi.TaaUpscaleParams), C.c_uint32, C.c_uint32]
     lib.sah_ssao.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData)] + [C.POINTER(_abi.Plane)] * 4 + [C.POINTER(_abi.SsaoParams), C.c_uint32, C.c_uint32]
-    lib.sah_mip_chain_generate.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32]
+    lib.sah_rt_denoise.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData), C.POINTER(_abi.RtDenoiseDesc), C.POINTER(_abi.RtDenoiseParams), C.c_uint32, C.c_uint32]
+    lib.sah_mip_chain_generate.argtypes =[C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32]
     lib.sah_rt_refit.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.c_void_p]
     _lib = lib
     return lib
@@ -420,6 +424,12 @@ class Context:
         (0, 0) = all."""
         self._check(self.lib.sah_ssao(self.handle, C.byref(view_data), C.byref(depth), C.byref(normals), None if scratch is None else C.byref(scratch),
                                       C.byref(ao_out), C.byref(params), rows[0], rows[1]))
+
+    def rt_denoise(self, view_data, desc, params, rows=(0, 0)):
+        """sah_rt_denoise (include/sah_rt_denoise.h): desc an _abi.RtDenoiseDesc (RtDenoiseDesc.of(noisy=..., ...), _abi.Plane of device
+        memory, one extent), params an _abi.RtDenoiseParams.  previous_depth, history and history_length may be None with
+        RT_DENOISE_HISTORY_INVALID in params.flags.  rows (begin, end) of `denoised`, (0, 0) = all."""
+        self._check(self.lib.sah_rt_denoise(self.handle, C.byref(view_data), C.byref(desc), C.byref(params), rows[0], rows[1]))
 
     def vrsaa_shading_rate_image(self, contrast, sri, params):
         """sah_vrsaa_shading_rate_image: contrast R16G16_SFLOAT, sri R8_UINT (_abi.Plane of device memory), params an _abi.ShadingRateParams

@@ -584,7 +584,8 @@ int sah_rt_build(sah_ctx* ctx, const sah_scene_geometry* scene, uint32_t* stats)
  * END_SEARCH | RAY_FLAG_CULL_NON_OPAQUE (CUTOUT primitives are invisible to it); ao = (spp - hits) / spp.  Kept quirks: every one of
  * the samples_per_pixel rays reads the same noise texel, so they are one ray; no depth == 0 test (a sky pixel's origin is not finite,
  * nothing is hit, ao = 1); the unused rotation matrix.  noise: R8G8B8A8_UNORM (a blue-noise layer, RenderCore/render/noise_texture.cpp),
- * extent <= 65535; samples_per_pixel <= 4096.  depth: D32_SFLOAT, normals: R16G16B16A16_SFLOAT, both of ao_out's extent. */
+ * extent <= 65535; samples_per_pixel <= 4096.  depth: D32_SFLOAT, normals: R16G16B16A16_SFLOAT, both of ao_out's extent.  The plane is
+ * 0 or 1 per pixel; the filter that makes it (and the sun's mask below) something to light from is declared in sah_rt_denoise.h. */
 int sah_rtao(sah_ctx* ctx, const sah_view_data* view, const sah_plane* depth, const sah_plane* normals, const sah_plane* noise,
              uint32_t samples_per_pixel, float max_ray_distance, const sah_plane* ao_out);
 

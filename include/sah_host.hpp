@@ -32,6 +32,7 @@
 #include "sah_mip_chain.h"
 #include "sah_gbuffer_motion.h"
 #include "sah_motion_vectors.h"
+#include "sah_rt_denoise.h"
 #include "sah_rt_refit.h"
 #include "sah_ssao.h"
 #include "sah_taa.h"
@@ -1258,12 +1259,84 @@ struct ScreenSpaceAoSettings {
     float edge_sharpness = 50.f;
     uint32_t blur_passes = 2;
 };
+// The settings of sah_rt_denoise_params (include/sah_rt_denoise.h) with the header's defaults; the jitters come from the view.
+struct RtDenoiseSettings {
+    float max_history = 32.f, depth_tolerance = 0.1f, depth_sharpness = 50.f;
+    uint32_t normal_squarings = 5, passes = 3;
+};
+// The temporal and edge-aware filter for a one-channel ray-traced plane (include/sah_rt_denoise.h; builder-owned, no reference
+// counterpart) over successive frames: owns the two ping-ponged accumulation / sample-count pairs and the kept copy of the last
+// frame's depth, (re-)created when the target's extent changes.  denoise records the pass "Ray-traced denoise" and an image copy that
+// keeps the depth.  The first denoise, the first after reset_history() (a camera cut) and the first of another extent have no history.
+// One instance per plane.
+class RayTracedDenoiser {
+public:
+    RtDenoiseSettings settings;
+    explicit RayTracedDenoiser(ResourceAllocator& allocator_in) : allocator(allocator_in) {}
+    void reset_history() { history_valid = false; }
+    void denoise(RenderGraph& graph, const SceneView& view, TextureHandle noisy, TextureHandle gbuffer_depth, TextureHandle gbuffer_normals,
+                 TextureHandle motion_vectors, TextureHandle denoised) {
+        if (!noisy || !gbuffer_depth || !gbuffer_normals || !motion_vectors || !denoised) {
+            graph.add_pass(hip_pass("Ray-traced denoise", [](sah_ctx*) { return (int)SAH_ERR_INVALID_ARGUMENT; }));
+            return;
+        }
+        const uint32_t w = denoised->desc.width, h = denoised->desc.height;
+        if (!previous_depth || previous_depth->desc.width != w || previous_depth->desc.height != h) {
+            for (int i = 0; i < 2; i++) {
+                accum[i] = allocator.create_texture("Denoiser accumulation", SAH_FORMAT_R32_SFLOAT, w, h);
+                length[i] = allocator.create_texture("Denoiser sample count", SAH_FORMAT_R16_SFLOAT, w, h);
+            }
+            previous_depth = allocator.create_texture("Denoiser previous depth", SAH_FORMAT_D32_SFLOAT, w, h);
+            history_valid = false;
+        }
+        TextureHandle old_accum = accum[current], old_length = length[current], new_accum = accum[1 - current], new_length = length[1 - current];
+        TextureHandle kept = previous_depth;
+        const bool use_history = history_valid;
+        graph.add_pass(hip_pass("Ray-traced denoise", [=, &view](sah_ctx* ctx) {
+                            const sah_view_data& v = view.get_gpu_data();
+                            sah_rt_denoise_params p{};
+                            p.max_history = settings.max_history, p.depth_tolerance = settings.depth_tolerance, p.depth_sharpness = settings.depth_sharpness;
+                            p.normal_squarings = settings.normal_squarings, p.passes = settings.passes;
+                            p.jitter[0] = v.jitter[0], p.jitter[1] = v.jitter[1];
+                            p.previous_jitter[0] = use_history ? v.previous_jitter[0] : v.jitter[0];
+                            p.previous_jitter[1] = use_history ? v.previous_jitter[1] : v.jitter[1];
+                            p.flags = use_history ? 0u : SAH_RT_DENOISE_HISTORY_INVALID;
+                            const sah_plane s = noisy->plane(), d = gbuffer_depth->plane(), n = gbuffer_normals->plane(), m = motion_vectors->plane();
+                            const sah_plane pd = kept->plane(), ha = old_accum->plane(), hl = old_length->plane();
+                            const sah_plane na = new_accum->plane(), nl = new_length->plane(), o = denoised->plane();
+                            sah_rt_denoise_desc desc{};
+                            desc.noisy = &s, desc.depth = &d, desc.normals = &n, desc.motion_vectors = &m;
+                            if (use_history) desc.previous_depth = &pd, desc.history = &ha, desc.history_length = &hl;
+                            desc.accum_out = &na, desc.length_out = &nl, desc.denoised = &o;
+                            return sah_rt_denoise(ctx, &v, &desc, &p, 0, 0);
+                        }));
+        graph.add_copy_pass(ImageCopyPass{"Keep depth for the denoiser", previous_depth, gbuffer_depth});
+        current = 1 - current;  // swap the history
+        history_valid = true;
+    }
+
+private:
+    ResourceAllocator& allocator;
+    TextureHandle accum[2] = {nullptr, nullptr}, length[2] = {nullptr, nullptr}, previous_depth = nullptr;
+    uint32_t current = 0;
+    bool history_valid = false;
+};
+
 class AmbientOcclusionPhase {
 public:
     AoTechnique technique = AoTechnique::RTAO;  // r.AO (ambient_occlusion_phase.cpp:15-17: RTAO is the reference's default)
     uint32_t rtao_samples = 1;                  // r.AO.RTAO.SamplesPerPixel (:19-21)
     float ao_radius = 8.0f;                     // r.AO.MaxRayDistance (:23-25)
     ScreenSpaceAoSettings screen_space;
+    // Opt-in, RTAO only, off by default: the rays' plane goes to a texture of the phase's own and ao_out gets it denoised
+    // (RayTracedDenoiser; include/sah_rt_denoise.h).  It needs the frame's motion vectors in denoise_motion_vectors and a phase
+    // constructed with the allocator: without either generate_ao throws std::logic_error.
+    bool denoise = false;
+    RtDenoiseSettings denoise_settings;
+    TextureHandle denoise_motion_vectors = nullptr;
+    void reset_denoise_history() {
+        if (denoiser) denoiser->reset_history();
+    }
     AmbientOcclusionPhase() = default;
     // ScreenSpace keeps the raw, unblurred result in a texture of its own, which needs an allocator: on a default-constructed phase
     // generate_ao throws std::logic_error when it is asked for ScreenSpace with screen_space.blur_passes > 0 (the default is 2)
@@ -1278,13 +1351,26 @@ public:
     void generate_ao(RenderGraph& graph, const SceneView& view, const RenderScene& scene, const NoiseTexture& noise, TextureHandle gbuffer_normals,
                      TextureHandle gbuffer_depth, TextureHandle ao_out) {
         if (technique == AoTechnique::ScreenSpace) return generate_screen_space(graph, view, gbuffer_normals, gbuffer_depth, ao_out);
+        if (technique == AoTechnique::RTAO && denoise && (!allocator || !denoise_motion_vectors))
+            throw std::logic_error("AmbientOcclusionPhase: denoise needs the phase constructed with an allocator and denoise_motion_vectors set");
         if (technique != AoTechnique::RTAO || !scene.get_raytracing_scene().is_built()) return generate_ao(graph, ao_out);
         TextureHandle layer = noise.get_layer(frame_index);
         frame_index++;
-        graph.add_pass(hip_pass("Ray traced ambient occlusion", [this, &view, layer, gbuffer_normals, gbuffer_depth, ao_out](sah_ctx* ctx) {
-                            const sah_plane d = gbuffer_depth->plane(), n = gbuffer_normals->plane(), z = layer->plane(), o = ao_out->plane();
+        TextureHandle rays_out = ao_out;
+        if (denoise && ao_out) {
+            if (!raw_rtao || raw_rtao->desc.width != ao_out->desc.width || raw_rtao->desc.height != ao_out->desc.height)
+                raw_rtao = allocator->create_texture("RTAO raw", SAH_FORMAT_R32_SFLOAT, ao_out->desc.width, ao_out->desc.height);
+            rays_out = raw_rtao;
+        }
+        graph.add_pass(hip_pass("Ray traced ambient occlusion", [this, &view, layer, gbuffer_normals, gbuffer_depth, rays_out](sah_ctx* ctx) {
+                            const sah_plane d = gbuffer_depth->plane(), n = gbuffer_normals->plane(), z = layer->plane(), o = rays_out->plane();
                             return sah_rtao(ctx, &view.get_gpu_data(), &d, &n, &z, rtao_samples, ao_radius, &o);
                         }));
+        if (denoise && ao_out) {
+            if (!denoiser) denoiser = std::make_unique<RayTracedDenoiser>(*allocator);
+            denoiser->settings = denoise_settings;
+            denoiser->denoise(graph, view, raw_rtao, gbuffer_depth, gbuffer_normals, denoise_motion_vectors, ao_out);
+        }
     }
 
 private:
@@ -1311,7 +1397,8 @@ private:
                         }));
     }
     ResourceAllocator* allocator = nullptr;
-    TextureHandle scratch = nullptr;
+    TextureHandle scratch = nullptr, raw_rtao = nullptr;
+    std::unique_ptr<RayTracedDenoiser> denoiser;
     uint32_t frame_index = 0;
 };
 
