@@ -282,6 +282,14 @@ __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const Lighti
     __shared__ __attribute__((aligned(16))) float s_lut[TAB_SIZE];
     stage_fast_tables<SUN == SAH_SHADOW_MODE_CSM, GI == SAH_GI_LPV>(s_lut, a, csm, f);
     __syncthreads();
+    // each wave's LPV texel box (lighting_fast.hpp: LpvBox): kLpvBoxBytes, 3 KB, per wave beside the table, written and read by that wave alone
+    LpvBox box;
+    box.lds = nullptr;
+    box.valid = false;
+    if constexpr (GI == SAH_GI_LPV) {
+        __shared__ __attribute__((aligned(16))) uint8_t s_box[4 * kLpvBoxBytes];
+        box.lds = s_box + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * kLpvBoxBytes;
+    }
 
     // per-row / per-column terms of the view-space position (two texcoord conventions, see lighting_common.hpp): from the table where
     // the host has built one (uniform branch), else computed
@@ -324,7 +332,8 @@ __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const Lighti
             if (SUN == SAH_SHADOW_MODE_CSM || GI == SAH_GI_LPV) colx_glsl = colx_glsl_of(a, f, x);
             if (SUN == SAH_SHADOW_MODE_RT) colx_slang = colx_slang_of(a, f, x);
         }
-        const FastPixelOut r = shade_pixel_fast_sl<SUN, GI>(a, csm, lpv, f, colx_glsl, rowy_glsl, colx_slang, rowy_slang, p, s_lut, lpv_bad, emissive_wave, div_shared);
+        const FastPixelOut r = shade_pixel_fast_sl<SUN, GI>(a, csm, lpv, f, colx_glsl, rowy_glsl, colx_slang, rowy_slang, p, s_lut, lpv_bad, emissive_wave, div_shared, box, i == 0,
+                                                                   lpv_box_centre_lane(PPT));
         out[2 * i] = r.lit.x;
         out[2 * i + 1] = r.lit.y;
         if (r.deferred) deferred_mask |= 1u << i;

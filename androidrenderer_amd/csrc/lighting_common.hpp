@@ -6,10 +6,13 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sah_hip.h"
+#include "lpv_box.hpp"
 #include "numerics.hpp"
 #include "params.hpp"
 
 namespace sah {
+
+static_assert(kLpvBoxSrcTexel == kLpvPackTexel && kLpvBoxPad == kLpvPackBorder, "lpv_box.hpp restates the gather copy's texel and border");
 
 // (non-temporal forms of these loads / stores were measured and lose: off/none 0.0614 -> 0.0686 ms, headline 0.1728 -> 0.1795 ms —
 //  profiles/r3_lpv_pack32_experiment.txt, second table)
@@ -353,6 +356,46 @@ SAH_DEV void lpv_fetch_packed(const LpvArgs& L, const uint8_t* packed, uint32_t 
             a[1] = fma_mix_hi(wt[k], lo, a[1]);
             a[2] = fma_mix_lo(wt[k], hi, a[2]);
             a[3] = fma_mix_hi(wt[k], hi, a[3]);
+        }
+        out[c] = dot4(a, n);
+    }
+}
+
+// The footprint base of lpv_fetch_packed() for the same coordinate: (x0, y0, z0) in the copy's padded coordinates, each in [0, size + 2]
+SAH_DEV void lpv_packed_base(const LpvArgs& L, float u, float v, float w, uint32_t (&base)[3]) {
+    const int W = (int)L.red.width, H = (int)L.red.height, D = (int)L.red.depth;
+    const float px = u * (float)W - 0.5f, py = v * (float)H - 0.5f, pz = w * (float)D - 0.5f;
+    const float fx0 = __builtin_floorf(px), fy0 = __builtin_floorf(py), fz0 = __builtin_floorf(pz);
+    const int b = (int)kLpvPackBorder;
+    base[0] = (uint32_t)(min(max(clamp_to_int(fx0), -b), W) + b);
+    base[1] = (uint32_t)(min(max(clamp_to_int(fy0), -b), H) + b);
+    base[2] = (uint32_t)(min(max(clamp_to_int(fz0), -b), D) + b);
+}
+
+// lpv_fetch_packed() for a pixel whose eight taps lie in the wave's fp32 texel box in LDS (lpv_box.hpp; staged by lighting_fast.hpp:
+// lpv_box_write): `box_px` points at the texel of the pixel's first tap.  The same weights, the same tap order and the same dot4; a tap is
+// fma(w, t32, acc) with t32 the exactly widened half, which is what v_fma_mix_f32 computes from the half itself — the same bits, as plain
+// v_fma_f32 after 8 ds_read_b128 per channel quad instead of 12 global loads and 96 mixed-precision fmas.
+SAH_DEV void lpv_fetch_box(const LpvArgs& L, const uint8_t* box_px, float u, float v, float w, const Fn (&n)[4], Fn (&out)[3]) {
+    const int W = (int)L.red.width, H = (int)L.red.height, D = (int)L.red.depth;
+    const float px = u * (float)W - 0.5f, py = v * (float)H - 0.5f, pz = w * (float)D - 0.5f;
+    const float fx0 = __builtin_floorf(px), fy0 = __builtin_floorf(py), fz0 = __builtin_floorf(pz);
+    const float fx = px - fx0, fy = py - fy0, fz = pz - fz0;
+    const float gx = 1.0f - fx, gy = 1.0f - fy, gz = 1.0f - fz;
+    const float wxy[4] = {gx * gy, fx * gy, gx * fy, fx * fy};
+    float wt[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) wt[k] = wxy[k & 3] * ((k >> 2) ? fz : gz);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        float a[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 8; k++) {  // tap order: x fastest, then y, then z
+            const float4 t = *reinterpret_cast<const float4*>(box_px + lpv_box_lds_row((uint32_t)k >> 1) + (uint32_t)(k & 1) * kLpvBoxTexel + 16u * (uint32_t)c);
+            a[0] = __builtin_fmaf(wt[k], t.x, a[0]);
+            a[1] = __builtin_fmaf(wt[k], t.y, a[1]);
+            a[2] = __builtin_fmaf(wt[k], t.z, a[2]);
+            a[3] = __builtin_fmaf(wt[k], t.w, a[3]);
         }
         out[c] = dot4(a, n);
     }

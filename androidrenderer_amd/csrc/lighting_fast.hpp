@@ -71,6 +71,41 @@ struct FastPixelOut {
     bool deferred;
 };
 
+// The wave's LPV texel box (lpv_box.hpp): 4 x 4 x 4 texels of the gather copy around the footprint base of one reference lane of the thread's
+// first pixel slot, widened once to fp32 in the wave's own kLpvBoxBytes of LDS.  A slot whose surface lanes all have both taps of every axis
+// inside it taps from there (lighting_common.hpp: lpv_fetch_box) instead of gathering 192 bytes per lane through the texture path; any other
+// slot, and every slot of a wave whose first slot does not fit one box, gathers as before (lpv_fetch_packed): the vote is wave-uniform.
+// No workgroup barrier: a wave reads only what it wrote itself, and LDS serves one wave's operations in order.
+struct LpvBox {
+    uint8_t* lds;   // the wave's region
+    bool valid;     // (wave-uniform) the first slot staged the box
+    uint32_t o[3];  // (wave-uniform) its origin in the copy's padded coordinates
+    uint4 q[2];     // the lane's two 16-byte chunks of the copy, between lpv_box_request() and lpv_box_write()
+};
+// chunks `lane` and 64 + (lane & 31) of the 96: lanes 32-63 fetch and write what lanes 0-31 do a second time, the same bytes to the same place
+SAH_DEV void lpv_box_request(LpvBox& box, const FastArgs& f) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t c[2] = {lane, 64u + (lane & 31u)};
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+        box.q[i] = *reinterpret_cast<const uint4*>(f.lpv_packed + lpv_box_chunk_src(c[i], box.o[0], box.o[1], box.o[2], f.pk_row_pitch, f.pk_slice_pitch));
+}
+SAH_DEV void lpv_box_write(const LpvBox& box) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t c[2] = {lane, 64u + (lane & 31u)};
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const uint4 q = box.q[i];
+        float4* dst = reinterpret_cast<float4*>(box.lds + lpv_box_chunk_dst(c[i]));
+        dst[0] = make_float4(h2f((uint16_t)q.x), h2f((uint16_t)(q.x >> 16)), h2f((uint16_t)q.y), h2f((uint16_t)(q.y >> 16)));
+        dst[1] = make_float4(h2f((uint16_t)q.z), h2f((uint16_t)(q.z >> 16)), h2f((uint16_t)q.w), h2f((uint16_t)(q.w >> 16)));
+    }
+    // the wave's own reads follow its writes: LDS keeps one wave's operations in order, the fence keeps the compiler from moving a read ahead
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // fp32 ("GLSL") geometry shared by the CSM sun, the LPV overlay and the point lights: normalised normal, world-space position with
 // the shader's (x + 1) / W texcoord quirk, view-space depth, and the view vector.  `ok` is cleared when an operand leaves the domain of a
 // restricted-range operator (the caller then evaluates the general restatement for that pixel).
@@ -263,7 +298,8 @@ SAH_DEV void fast_lpv_overlay(const LpvArgs& lpv, const FastArgs& f, const float
 template <int SUN, int GI>
 SAH_DEV FastPixelOut shade_pixel_fast_sl(const LightingArgs& a, const CsmArgs& csm, const LpvArgs& lpv, const FastArgs& f, float colx_glsl,
                                          float rowy_glsl, float colx_slang, float rowy_slang, const Px& p, const float* tab,
-                                         bool lpv_has_nonfinite, bool emissive_wave, bool div_shared) {
+                                         bool lpv_has_nonfinite, bool emissive_wave, bool div_shared, LpvBox& box, bool first_slot,
+                                         uint32_t centre_lane) {
     const float* lut = tab;
     const float D = p.depth;
     const bool sky_px = D == 0.f;
@@ -299,6 +335,8 @@ SAH_DEV FastPixelOut shade_pixel_fast_sl(const LightingArgs& a, const CsmArgs& c
     // LPV: cascade selection and the gather coordinate
     Fn nc[4];
     float lpv_u = 0.f, lpv_v = 0.f, lpv_w = 0.f;
+    bool box_tap = false;             // (wave-uniform) this slot taps from the wave's box
+    const uint8_t* box_px = nullptr;  // the lane's first tap in it
     if constexpr (GI == SAH_GI_LPV) {
         // selected = smallest i whose unit box contains the point (overlay.frag:97-103 scans down and overwrites; 0 if none).
         // Cascade 0 is tested first: when every lane of the wave is inside it (coherent near-field pixels) the other
@@ -341,6 +379,28 @@ SAH_DEV FastPixelOut shade_pixel_fast_sl(const LightingArgs& a, const CsmArgs& c
         lpv_u = cpx.v;
         lpv_v = cpy.v;
         lpv_w = cpz.v;
+        // The wave's texel box (lpv_box.hpp).  The first slot places it around the base of its reference lane and stages it if all its surface
+        // lanes are served (and the wave is whole: every lane stages a part); each slot then votes once.
+        uint32_t lb[3];
+        lpv_packed_base(lpv, lpv_u, lpv_v, lpv_w, lb);
+        const uint32_t size[3] = {lpv.red.width, lpv.red.height, lpv.red.depth};
+        if (first_slot) {
+            box.valid = false;
+            box.o[0] = box.o[1] = box.o[2] = 0u;
+            if (act) {
+                const uint32_t ref = lpv_box_reference_lane(act, centre_lane);
+#pragma unroll
+                for (int k = 0; k < 3; k++) box.o[k] = lpv_box_origin((uint32_t)__builtin_amdgcn_readlane((int)lb[k], (int)ref), size[k]);
+            }
+        }
+        const uint32_t dx = lpv_box_delta(lb[0], box.o[0]), dy = lpv_box_delta(lb[1], box.o[1]), dz = lpv_box_delta(lb[2], box.o[2]);
+        const lanemask unserved = lanes(max(max(dx, dy), dz) > kLpvBoxEdge - 2u) & act;  // (max3: lpv_box_served() of the three)
+        if (first_slot && act != 0ull && unserved == 0ull && lanes(true) == ~0ull) {
+            box.valid = true;
+            lpv_box_request(box, f);  // ahead of the sun term, whose PCF and BRDF cover the latency
+        }
+        box_tap = box.valid && unserved == 0ull;
+        box_px = box.lds + lpv_box_lds_base(lpv_box_clamp_delta(dx), lpv_box_clamp_delta(dy), lpv_box_clamp_delta(dz));
     }
 
     // ---------------- a1: sun, CSM mode ----------------
@@ -363,7 +423,9 @@ SAH_DEV FastPixelOut shade_pixel_fast_sl(const LightingArgs& a, const CsmArgs& c
     // ---------------- a3: LPV overlay ----------------
     if constexpr (GI == SAH_GI_LPV) {
         Fn indirect[3];
-        lpv_fetch_packed(lpv, f.lpv_packed, f.pk_row_pitch, f.pk_slice_pitch, lpv_u, lpv_v, lpv_w, nc, indirect);
+        if (first_slot && box.valid) lpv_box_write(box);
+        if (box_tap) lpv_fetch_box(lpv, box_px, lpv_u, lpv_v, lpv_w, nc, indirect);
+        else lpv_fetch_packed(lpv, f.lpv_packed, f.pk_row_pitch, f.pk_slice_pitch, lpv_u, lpv_v, lpv_w, nc, indirect);
         // Fd(surface, N, N) == diffuse_color * (1/pi) exactly when N is a finite normalised vector, and the specular term
         // is (finite) * (finite * 0) == +-0 when roughness > 0 and the volumes are finite (DESIGN.md "Fast path proofs").
         const Fn dielectric_f0 = Fn(0.04f);

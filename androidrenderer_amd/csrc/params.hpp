@@ -133,7 +133,10 @@ struct FastArgs {
     uint32_t pk_row_pitch, pk_slice_pitch;
     uint32_t lpv_fast;  // tiled kernel: the LPV part of the fast-path check holds too and the gather copy is there (lpv_s / lpv_t, lpv_packed, state valid)
 };
-// (an fp32 copy — 48-byte texels, plain v_fma_f32 taps — was measured and loses 67 %: profiles/r3_lpv_pack32_experiment.txt)
+// (an fp32 copy IN GLOBAL MEMORY — 48-byte texels, plain v_fma_f32 taps — was measured and loses 67 %: doubling the gather's bytes through the
+//  texture path costs far more than the cheaper fma saves, profiles/r3_lpv_pack32_experiment.txt.  In LDS fp32 wins: a wave of the fast kernel
+//  widens the 4 x 4 x 4 texels its pixels share once and taps them with ds_read_b128 + v_fma_f32 — lpv_box.hpp, profiles/lpv_box_ab.txt: -7 % on
+//  the 4K frame, and 3 % ahead of the same box kept as fp16 with v_fma_mix_f32 taps.)
 constexpr uint32_t kLpvPackTexel = 24, kLpvPackBorder = 2;
 struct LpvGvStep {  // use_gv = 1 in a propagation step (lpv.hip): the geometry volume and its precomputed factors (k_gv_factors)
     VolumeArg gv;

@@ -9,7 +9,12 @@ cascade and footprint) over the workload's own frame: good for statistics, not f
   - the same for one row load of the LPV footprint (48 bytes per lane; mean over the four rows),
   - the share of (wave, pixel slot) pairs whose vote runs the PCF (a lane with ndotl > 0) and the BRDF (a lit lane whose shadow is not 0),
     against the share of pixels that need them,
-  - the share of waves that hold sky and surface pixels at once."""
+  - the share of waves that hold sky and surface pixels at once,
+  - the share of (wave, pixel slot) pairs with a surface pixel that the wave's LPV texel box serves, under exactly the kernel's rule
+    (csrc/lpv_box.hpp: a 4 x 4 x 4-texel box around the footprint base of one reference lane of slot 0, valid when every surface lane of slot 0 is
+    served; a slot taps from the box when the box is valid and all its surface lanes are served), for both choices of the reference lane: the first
+    surface lane, and the first surface lane at or behind the tile's centre lane (else the last before it), which the kernel keeps.  Every pixel
+    that is not sky counts as a surface pixel here: the few the kernel defers are not modelled."""
 import os
 import sys
 
@@ -28,7 +33,8 @@ PPT = 4
 
 
 def geometry(fr):
-    """per pixel: surface, lit (PCF needed), brdf (BRDF needed), byte offsets of the four PCF taps and of the four LPV footprint rows"""
+    """per pixel: surface, lit (PCF needed), brdf (BRDF needed), byte offsets of the four PCF taps and of the four LPV footprint rows, the
+    footprint's base texel (x0, y0, z0) in the gather copy's padded coordinates and the volume's extents (w, h, d)"""
     W, H = fr.width, fr.height
     g = fr.view.gpu_data
     P, V = np.array(g.inverse_projection[:], f32), np.array(g.inverse_view[:], f32)
@@ -89,7 +95,7 @@ def geometry(fr):
         lslice = lrow * (lh + 4)
         base = t0[2] * lslice + t0[1] * lrow + t0[0] * 24
         rows = [base, base + lrow, base + lslice, base + lslice + lrow]
-    return surface, lit, brdf, taps, rows
+    return surface, lit, brdf, taps, rows, t0, (lw, lh, ld)
 
 
 def per_wave(a, tw, th):
@@ -104,25 +110,55 @@ def distinct(lines):
     return 1 + (s[..., 1:] != s[..., :-1]).sum(-1)
 
 
+def box_served(base, extents, w_surf, tw, th, centre_rule):
+    """share of (wave, slot) pairs with a surface pixel that tap from the wave's box (csrc/lpv_box.hpp)"""
+    b = [per_wave(t, tw, th) for t in base]  # (waves, PPT, 64) per axis
+    act0 = w_surf[:, 0, :]
+    has0 = act0.any(-1)
+    lane = np.arange(64)
+    first = np.where(act0, lane, 64).min(-1)
+    if centre_rule:
+        centre = (th // 2) * (tw // PPT) + tw // (2 * PPT)
+        behind = np.where(act0 & (lane >= centre), lane, 64).min(-1)
+        last = np.where(act0, lane, -1).max(-1)
+        ref = np.where(behind < 64, behind, last)
+    else:
+        ref = first
+    ref = np.clip(ref, 0, 63)
+    waves = np.arange(act0.shape[0])
+    served = np.ones(w_surf.shape, bool)
+    for axis, e in enumerate(extents):
+        r = b[axis][waves, 0, ref]
+        o = np.clip(r - 1, 0, e + 4 - 4)
+        d = b[axis] - o[:, None, None]
+        served &= (d >= 0) & (d <= 2)
+    slot_ok = (served | ~w_surf).all(-1)  # every surface lane of the slot served
+    valid = has0 & slot_ok[:, 0]
+    pairs = w_surf.any(-1)
+    return (pairs & slot_ok & valid[:, None]).sum() / max(1, pairs.sum())
+
+
 def main():
     name = sys.argv[1] if len(sys.argv) > 1 else "4k_deferred_gi"
     (W, H), flavour, shadow = WORKLOADS[name]
     fr = frame.LightingInputs(W, H, seed=2, sun_mode=_abi.SHADOW_MODE_CSM, gi=_abi.GI_LPV, flavour=flavour, shadowmap_res=4096, shadow=shadow)
-    surface, lit, brdf, taps, rows = geometry(fr)
+    surface, lit, brdf, taps, rows, base, extents = geometry(fr)
     print(f"{name}: {W} x {H}, {flavour} G-buffer, shadow map '{shadow}'; pixels that need the PCF {100 * lit.mean():.1f} %, the BRDF {100 * brdf.mean():.1f} %, "
           f"sky {100 * (fr.arrays['depth'] == 0).mean():.1f} %")
-    print("| wave footprint (px) | 128-B lines per PCF tap load | per LPV row load (48 B/lane) | wave slots that run the PCF | the BRDF | waves mixing sky and surface |")
-    print("|---|---|---|---|---|---|")
+    print("| wave footprint (px) | 128-B lines per PCF tap load | per LPV row load (48 B/lane) | wave slots that run the PCF | the BRDF | waves mixing sky and surface | "
+          "LPV box serves: reference = first surface lane | = surface lane at the centre |")
+    print("|---|---|---|---|---|---|---|---|")
     for tw, th in SHAPES:
         if W % tw or H % th:
-            print(f"| {tw}x{th} | (the extent is not whole tiles) | | | | |")
+            print(f"| {tw}x{th} | (the extent is not whole tiles) | | | | | | |")
             continue
         w_lit, w_brdf, w_surf = per_wave(lit, tw, th).any(-1), per_wave(brdf, tw, th).any(-1), per_wave(surface, tw, th)
         pcf_lines = np.mean([distinct(per_wave(t, tw, th) >> 7)[w_lit].mean() for t in taps])
         run_lpv = w_surf.any(-1)
         lpv_lines = np.mean([distinct(np.concatenate([per_wave(r, tw, th) >> 7, per_wave(r + 47, tw, th) >> 7], -1))[run_lpv].mean() for r in rows])
         any_surf, all_surf = w_surf.any((1, 2)), w_surf.all((1, 2))
-        print(f"| {tw}x{th} | {pcf_lines:.1f} | {lpv_lines:.1f} | {100 * w_lit.mean():.1f} % | {100 * w_brdf.mean():.1f} % | {100 * (any_surf & ~all_surf).mean():.1f} % |")
+        print(f"| {tw}x{th} | {pcf_lines:.1f} | {lpv_lines:.1f} | {100 * w_lit.mean():.1f} % | {100 * w_brdf.mean():.1f} % | {100 * (any_surf & ~all_surf).mean():.1f} % | "
+              f"{100 * box_served(base, extents, w_surf, tw, th, False):.1f} % | {100 * box_served(base, extents, w_surf, tw, th, True):.1f} % |")
 
 
 if __name__ == "__main__":
