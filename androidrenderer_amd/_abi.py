@@ -64,6 +64,24 @@ class SsaoParams(C.Structure):  # sah_ssao_params (include/sah_ssao.h): 40 bytes
         return cls(**values)
 
 
+EXPOSURE_HISTORY_INVALID = 1  # SAH_EXPOSURE_HISTORY_INVALID (include/sah_exposure.h)
+
+
+class ExposureParams(C.Structure):  # sah_exposure_params (include/sah_exposure.h): 32 bytes; default() = the header's defaults
+    _fields_ = [("key", C.c_float), ("low_fraction", C.c_float), ("high_fraction", C.c_float), ("min_exposure", C.c_float), ("max_exposure", C.c_float),
+                ("adaptation", C.c_float), ("max_workgroups", C.c_uint32), ("flags", C.c_uint32)]
+
+    @classmethod
+    def default(cls, **changes):
+        values = dict(key=0.18, low_fraction=0.5, high_fraction=0.95, min_exposure=1.0 / 64.0, max_exposure=64.0, adaptation=1.0, max_workgroups=0, flags=0)
+        values.update(changes)
+        return cls(**values)
+
+
+class ExposureState(C.Structure):  # sah_exposure_state: 16 bytes of device memory
+    _fields_ = [("exposure", C.c_float), ("adapted", C.c_float), ("metered", C.c_uint32), ("window", C.c_uint32)]
+
+
 RT_DENOISE_HISTORY_INVALID = 1  # SAH_RT_DENOISE_HISTORY_INVALID
 
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/sah_exposure.h"
 #include "../../include/sah_hip.h"
 #include "../../include/sah_mip_chain.h"
 #include "../../include/sah_rt_denoise.h"
@@ -80,6 +81,21 @@ struct SsaoArgs {
     float max_radius_pixels, threshold, shadow_multiplier, shadow_clamp, fade_to, fade_span, edge_sharpness;
 };
 hipError_t launch_ssao(const SsaoArgs& a, uint32_t blur_passes, hipStream_t st);
+
+// --- exposure.hip
+struct ExposureArgs {
+    PlaneArg scene, out;              // out: exposed_out of the fused form / out of apply; unused by the metering alone
+    uint32_t W, H;
+    uint32_t row_begin, row_end;      // apply: rows of `out`
+    uint32_t tiles_x, tiles;          // set by the launchers
+    uint32_t* work;                   // SAH_EXPOSURE_WORK_BYTES: 256 bins, then the ticket word
+    const sah_exposure_state* state_in;  // null without a history (meter); the state apply multiplies by
+    sah_exposure_state* state_out;
+    float key, low_fraction, high_fraction, min_exposure, max_exposure, adaptation;
+    bool history;                     // SAH_EXPOSURE_HISTORY_INVALID is clear
+};
+hipError_t launch_exposure_meter(const ExposureArgs& a, bool apply, uint32_t max_workgroups, hipStream_t st);
+hipError_t launch_exposure_apply(const ExposureArgs& a, hipStream_t st);
 
 // --- rt_denoise.hip
 struct RtDenoiseArgs {

@@ -310,6 +310,62 @@ class ScreenSpaceAO:
         return self.ao
 
 
+def adaptation_from(dt, speed):
+    """The `adaptation` weight of a frame that took `dt` seconds at `speed` per second: 1 - exp(-dt * speed), clamped into (0, 1]."""
+    a = 1.0 - math.exp(-float(dt) * float(speed))
+    return min(max(a, float(np.finfo(np.float32).tiny)), 1.0)
+
+
+class AutoExposure:
+    """Histogram auto-exposure (include/sah_exposure.h) over successive frames: owns the histogram's work buffer, the two ping-ponged states
+    and the exposed plane, which is re-created (and the history dropped) when a scene of another extent arrives.  The first frame, and the first after reset() (a cut), is metered and then exposed by its own
+    exposure (sah_exposure_meter with SAH_EXPOSURE_HISTORY_INVALID, then sah_exposure_apply); later frames take the fused call and are
+    exposed by what the frame before metered.  `settings` are fields of _abi.ExposureParams; set `params.adaptation` per frame from
+    adaptation_from(dt, speed)."""
+
+    def __init__(self, ctx, width, height, device="cuda", **settings):
+        import torch
+        self.ctx, self.width, self.height = ctx, width, height
+        self.params = _abi.ExposureParams.default(**settings)
+        self.work = torch.zeros(260, dtype=torch.int32, device=device)  # SAH_EXPOSURE_WORK_BYTES
+        self.states = [torch.zeros(4, dtype=torch.float32, device=device) for _ in range(2)]
+        self.exposed = torch.zeros((height, width, 4), dtype=torch.int16, device=device)
+        self.current = 0  # index of the state the last expose() wrote
+        self.history_valid = False
+
+    def reset(self):
+        self.history_valid = False
+
+    def state(self):
+        """the state the last expose() wrote, as an _abi.ExposureState (synchronises)"""
+        return _abi.ExposureState.from_buffer_copy(self.states[self.current].cpu().numpy().tobytes())
+
+    def histogram(self):
+        """the last frame's 256-bin histogram (synchronises)"""
+        return self.work[:256].cpu().numpy().view(np.uint32)
+
+    def expose(self, scene):
+        """scene (H, W, 4) int16 device array.  Returns the exposed plane, (H, W, 4) int16: the same array every call."""
+        p = self.params
+        if tuple(scene.shape[:2]) != (self.height, self.width):  # another extent: a new exposed plane, and no history
+            import torch
+            self.height, self.width = int(scene.shape[0]), int(scene.shape[1])
+            self.exposed = torch.zeros((self.height, self.width, 4), dtype=torch.int16, device=self.exposed.device)
+            self.history_valid = False
+        scene_p, out_p = images.plane(scene, _abi.FORMAT_R16G16B16A16_SFLOAT), images.plane(self.exposed, _abi.FORMAT_R16G16B16A16_SFLOAT)
+        old, new = self.current, 1 - self.current
+        if self.history_valid:
+            p.flags &= ~_abi.EXPOSURE_HISTORY_INVALID
+            self.ctx.exposure_meter(scene_p, self.states[old].data_ptr(), self.states[new].data_ptr(), self.work.data_ptr(), out_p, p)
+        else:
+            p.flags |= _abi.EXPOSURE_HISTORY_INVALID
+            self.ctx.exposure_meter(scene_p, None, self.states[new].data_ptr(), self.work.data_ptr(), None, p)
+            self.ctx.exposure_apply(scene_p, self.states[new].data_ptr(), out_p)
+        self.current = new
+        self.history_valid = True
+        return self.exposed
+
+
 class RayTracedDenoiser:
     """The temporal and edge-aware filter for a one-channel ray-traced plane (include/sah_rt_denoise.h) over successive frames of one
     extent: owns the two ping-ponged accumulation / sample-count pairs — this frame's accum_out and length_out are the next frame's history

@@ -53,6 +53,11 @@ SSAO_EXPORTS = ["sah_ssao"]
 # the filter for the ray-traced masks: exported, declared in include/sah_rt_denoise.h (not sah_hip.h)
 RT_DENOISE_EXPORTS = ["sah_rt_denoise"]
 
+# histogram auto-exposure: exported, declared in include/sah_exposure.h (not sah_hip.h)
+EXPOSURE_EXPORTS = ["sah_exposure_meter", "sah_exposure_apply"]
+EXPOSURE_WORK_BYTES = 1040    # SAH_EXPOSURE_WORK_BYTES
+EXPOSURE_BINS = 256           # SAH_EXPOSURE_BINS
+
 # the mip-chain generator: exported, declared in include/sah_mip_chain.h (not sah_hip.h)
 MIP_CHAIN_EXPORTS = ["sah_mip_chain_generate"]
 MIP_CHAIN_MAX_LEVELS = 12     # SAH_MIP_CHAIN_MAX_LEVELS
@@ -214,6 +219,8 @@ def load():
     lib.sah_taa_upscale.argtypes = [C.c_void_p] + [C.POINTER(_abi.Plane)] * 5 + [C.POINTER(_abi.TaaUpscaleParams), C.c_uint32, C.c_uint32]
     lib.sah_ssao.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData)] + [C.POINTER(_abi.Plane)] * 4 + [C.POINTER(_abi.SsaoParams), C.c_uint32, C.c_uint32]
     lib.sah_rt_denoise.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData), C.POINTER(_abi.RtDenoiseDesc), C.POINTER(_abi.RtDenoiseParams), C.c_uint32, C.c_uint32]
+    lib.sah_exposure_meter.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.ExposureParams)]
+    lib.sah_exposure_apply.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
     lib.sah_mip_chain_generate.argtypes =[C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32]
     lib.sah_rt_refit.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.c_void_p]
     _lib = lib
@@ -430,6 +437,18 @@ class Context:
         memory, one extent), params an _abi.RtDenoiseParams.  previous_depth, history and history_length may be None with
         RT_DENOISE_HISTORY_INVALID in params.flags.  rows (begin, end) of `denoised`, (0, 0) = all."""
         self._check(self.lib.sah_rt_denoise(self.handle, C.byref(view_data), C.byref(desc), C.byref(params), rows[0], rows[1]))
+
+    def exposure_meter(self, scene, state_in, state_out, work, exposed_out, params):
+        """sah_exposure_meter (include/sah_exposure.h): scene and exposed_out R16G16B16A16_SFLOAT _abi.Plane of device memory, one extent;
+        state_in, state_out (16 bytes each) and work (EXPOSURE_WORK_BYTES) device addresses; params an _abi.ExposureParams.  state_in may be
+        None with _abi.EXPOSURE_HISTORY_INVALID in params.flags; exposed_out None = meter only, a plane = the fused form."""
+        self._check(self.lib.sah_exposure_meter(self.handle, C.byref(scene), C.c_void_p(state_in), C.c_void_p(state_out), C.c_void_p(work),
+                                                None if exposed_out is None else C.byref(exposed_out), C.byref(params)))
+
+    def exposure_apply(self, scene, state, out, rows=(0, 0)):
+        """sah_exposure_apply: out.rgb = scene.rgb * state->exposure; state a device address; out may be the plane `scene` itself.  rows
+        (begin, end) of `out`, (0, 0) = all."""
+        self._check(self.lib.sah_exposure_apply(self.handle, C.byref(scene), C.c_void_p(state), C.byref(out), rows[0], rows[1]))
 
     def vrsaa_shading_rate_image(self, contrast, sri, params):
         """sah_vrsaa_shading_rate_image: contrast R16G16_SFLOAT, sri R8_UINT (_abi.Plane of device memory), params an _abi.ShadingRateParams

@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <optional>
 #include <random>
@@ -26,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "sah_exposure.h"
 #include "sah_hip.h"
 #include "sah_lpv_gv.h"
 #include "sah_lpv_mesh_lights.h"
@@ -1400,6 +1402,84 @@ private:
     TextureHandle scratch = nullptr, raw_rtao = nullptr;
     std::unique_ptr<RayTracedDenoiser> denoiser;
     uint32_t frame_index = 0;
+};
+
+// ---- AutoExposure (include/sah_exposure.h; builder-owned, no reference counterpart: the reference's scale is a set of literals) ----------
+// The settings of sah_exposure_params with the header's defaults; `adaptation` is the caller's, per frame, from its frame time.
+struct AutoExposureSettings {
+    float key = 0.18f, low_fraction = 0.5f, high_fraction = 0.95f, min_exposure = 1.0f / 64.0f, max_exposure = 64.0f, adaptation = 1.0f;
+    static float adaptation_from(float dt, float speed) {  // 1 - exp(-dt * speed), clamped into (0, 1]
+        const float a = 1.0f - std::exp(-dt * speed);
+        return a > 0.0f ? (a < 1.0f ? a : 1.0f) : std::numeric_limits<float>::min();
+    }
+};
+// Histogram auto-exposure over successive frames: sits between the upscaler (or TAA) and Bloomer::fill_bloom_tex.  Owns the histogram's
+// work buffer, the two ping-ponged states and the exposed texture, (re-)created when the scene's extent changes.  expose records the
+// passes and returns the exposed texture.  The first frame, the first after reset_history() (a cut) and the first of another extent are
+// metered and then exposed by their own exposure ("Auto-exposure: meter", "Auto-exposure: apply"); later frames take the fused pass
+// ("Auto-exposure") and are exposed by what the frame before metered.  Off unless a caller constructs one and calls it: no existing
+// phase uses it.
+class AutoExposure {
+public:
+    AutoExposureSettings settings;
+    explicit AutoExposure(ResourceAllocator& allocator_in) : allocator(allocator_in) {}
+    void reset_history() { history_valid = false; }
+    TextureHandle get_exposed() const { return exposed; }
+    // the state the last recorded frame writes (16 bytes of device memory: exposure, adapted, metered, window) and its histogram (256 words)
+    const sah_exposure_state* get_state() const { return state(current); }
+    const uint32_t* get_histogram() const { return buffers ? reinterpret_cast<const uint32_t*>(work()) : nullptr; }
+    TextureHandle expose(RenderGraph& graph, TextureHandle scene) {
+        if (!scene) {
+            graph.add_pass(hip_pass("Auto-exposure", [](sah_ctx*) { return (int)SAH_ERR_INVALID_ARGUMENT; }));
+            return nullptr;
+        }
+        const uint32_t w = scene->desc.width, h = scene->desc.height;
+        if (!exposed || exposed->desc.width != w || exposed->desc.height != h) {
+            exposed = allocator.create_texture("Exposed scene", SAH_FORMAT_R16G16B16A16_SFLOAT, w, h);
+            if (!buffers) buffers = allocator.create_texture("Auto-exposure states and histogram", SAH_FORMAT_R32_SFLOAT, (kWorkOffset + SAH_EXPOSURE_WORK_BYTES) / 4, 1);
+            history_valid = false;
+        }
+        const sah_exposure_state* in = state(current);
+        sah_exposure_state* out = state(1 - current);
+        void* wk = work();
+        TextureHandle target = exposed;
+        const AutoExposureSettings s = settings;
+        const auto params = [s](uint32_t flags) {
+            sah_exposure_params p{};
+            p.key = s.key, p.low_fraction = s.low_fraction, p.high_fraction = s.high_fraction;
+            p.min_exposure = s.min_exposure, p.max_exposure = s.max_exposure, p.adaptation = s.adaptation, p.flags = flags;
+            return p;
+        };
+        if (history_valid) {
+            graph.add_pass(hip_pass("Auto-exposure", [=](sah_ctx* ctx) {
+                                const sah_exposure_params p = params(0);
+                                const sah_plane sc = scene->plane(), o = target->plane();
+                                return sah_exposure_meter(ctx, &sc, in, out, wk, &o, &p);
+                            }));
+        } else {
+            graph.add_pass(hip_pass("Auto-exposure: meter", [=](sah_ctx* ctx) {
+                                const sah_exposure_params p = params(SAH_EXPOSURE_HISTORY_INVALID);
+                                const sah_plane sc = scene->plane();
+                                return sah_exposure_meter(ctx, &sc, nullptr, out, wk, nullptr, &p);
+                            }));
+            graph.add_pass(hip_pass("Auto-exposure: apply", [=](sah_ctx* ctx) {
+                                const sah_plane sc = scene->plane(), o = target->plane();
+                                return sah_exposure_apply(ctx, &sc, out, &o, 0, 0);
+                            }));
+        }
+        current = 1 - current;
+        history_valid = true;
+        return exposed;
+    }
+
+private:
+    static constexpr uint32_t kWorkOffset = 64;  // the two states at 0 and 16, the work buffer 16-byte aligned behind them
+    sah_exposure_state* state(uint32_t i) const { return buffers ? reinterpret_cast<sah_exposure_state*>(static_cast<char*>(buffers->desc.ptr) + 16 * i) : nullptr; }
+    void* work() const { return static_cast<char*>(buffers->desc.ptr) + kWorkOffset; }
+    ResourceAllocator& allocator;
+    TextureHandle exposed = nullptr, buffers = nullptr;
+    uint32_t current = 0;
+    bool history_valid = false;
 };
 
 // ---- LightingPhase (RenderCore/render/phase/lighting_phase.hpp:17-57, .cpp:34-134) -------------------------------------
