@@ -117,6 +117,46 @@ class RtDenoiseDesc(C.Structure):  # sah_rt_denoise_desc: ten plane pointers; of
         return self
 
 
+RTGI_DENOISE_HISTORY_INVALID = 1  # SAH_RTGI_DENOISE_HISTORY_INVALID
+FORMAT_R32G32_SFLOAT = 103        # include/sah_rtgi_denoise.h: accepted by sah_rtgi_denoise only
+FORMAT_R32G32B32A32_SFLOAT = 109
+FORMAT_BPP.update({FORMAT_R32G32_SFLOAT: 8, FORMAT_R32G32B32A32_SFLOAT: 16})
+
+
+class RtgiDenoiseParams(C.Structure):  # sah_rtgi_denoise_params (include/sah_rtgi_denoise.h): 52 bytes; default() = the header's defaults
+    _fields_ = [("max_history", C.c_float), ("min_history", C.c_float), ("depth_tolerance", C.c_float), ("depth_sharpness", C.c_float),
+                ("normal_squarings", C.c_uint32), ("passes", C.c_uint32), ("luminance_sigma", C.c_float), ("luminance_floor", C.c_float),
+                ("jitter", C.c_float * 2), ("previous_jitter", C.c_float * 2), ("flags", C.c_uint32)]
+
+    @classmethod
+    def default(cls, **changes):
+        values = dict(max_history=32.0, min_history=4.0, depth_tolerance=0.1, depth_sharpness=50.0, normal_squarings=5, passes=3, luminance_sigma=4.0,
+                      luminance_floor=1e-6, jitter=(0.0, 0.0), previous_jitter=(0.0, 0.0), flags=0)
+        values.update(changes)
+        for k in ("jitter", "previous_jitter"):
+            values[k] = (C.c_float * 2)(*values[k])
+        return cls(**values)
+
+
+class RtgiDenoiseDesc(C.Structure):  # sah_rtgi_denoise_desc: twelve plane pointers; of() keeps the planes alive with the descriptor
+    PLANES = ("ray_buffer", "ray_irradiance", "depth", "normals", "motion_vectors", "previous_depth", "history", "history_moments", "accum_out",
+              "moments_out", "denoised_ray_buffer", "denoised_irradiance")
+    _fields_ = [(name, C.POINTER(Plane)) for name in PLANES]
+
+    @classmethod
+    def of(cls, **planes):
+        """planes by field name, each an _abi.Plane or None (NULL)"""
+        unknown = set(planes) - set(cls.PLANES)
+        if unknown:
+            raise TypeError(f"not planes of sah_rtgi_denoise_desc: {sorted(unknown)}")
+        self = cls()
+        self._planes = dict(planes)
+        for name, p in planes.items():
+            if p is not None:
+                setattr(self, name, C.pointer(p))
+        return self
+
+
 class TaaUpscaleParams(C.Structure):  # sah_taa_upscale_params (include/sah_taa_upscale.h): 28 bytes; flags are the TAA_* bits
     _fields_ = [("blend", C.c_float), ("min_confidence", C.c_float), ("jitter", C.c_float * 2), ("previous_jitter", C.c_float * 2), ("flags", C.c_uint32)]
 

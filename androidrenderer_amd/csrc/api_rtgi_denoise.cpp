@@ -1,0 +1,106 @@
+// C ABI: temporal accumulation and variance-guided filter for the RTGI ray planes (include/sah_rtgi_denoise.h; kernels in rtgi_denoise.hip).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "../../include/sah_rtgi_denoise.h"
+#include "ctx.hpp"
+#include "launch.hpp"
+
+namespace {
+// 0, or the status a plane of `format` with `bpp`-byte texels earns (the alignment rules of sah_taa_resolve)
+int plane_status(const sah_plane* p, uint32_t format, uint32_t bpp) {
+    if (!p || !p->ptr) return SAH_ERR_INVALID_ARGUMENT;
+    if (p->format != format) return SAH_ERR_UNSUPPORTED_FORMAT;
+    if (!p->width || !p->height || (uint64_t)p->row_pitch_bytes < (uint64_t)p->width * bpp || ((uintptr_t)p->ptr % 4) || (p->row_pitch_bytes % 4))
+        return SAH_ERR_INVALID_ARGUMENT;
+    return SAH_OK;
+}
+struct Checked {
+    const sah_plane* p;
+    uint32_t format, bpp;
+    bool output, previous;  // previous: one of the three planes SAH_RTGI_DENOISE_HISTORY_INVALID excuses
+    const char* what;
+};
+bool overlap(const Checked& a, const Checked& b) {
+    const uintptr_t a0 = (uintptr_t)a.p->ptr, a1 = a0 + (uint64_t)(a.p->height - 1) * a.p->row_pitch_bytes + (uint64_t)a.p->width * a.bpp;
+    const uintptr_t b0 = (uintptr_t)b.p->ptr, b1 = b0 + (uint64_t)(b.p->height - 1) * b.p->row_pitch_bytes + (uint64_t)b.p->width * b.bpp;
+    return a0 < b1 && b0 < a1;
+}
+}  // namespace
+
+extern "C" int sah_rtgi_denoise(sah_ctx* ctx, const sah_view_data* view, const sah_rtgi_denoise_desc* desc, const sah_rtgi_denoise_params* params,
+                                uint32_t row_begin, uint32_t row_end) {
+    SAH_RANGE();
+    static_assert(sizeof(sah_rtgi_denoise_params) == 52, "sah_rtgi_denoise_params is 52 bytes");
+    static_assert(sizeof(sah_rtgi_denoise_desc) == 12 * sizeof(void*), "sah_rtgi_denoise_desc is twelve pointers");
+    if (!ctx) return SAH_ERR_INVALID_ARGUMENT;
+    if (!view || !desc || !params) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: view, desc or params is null");
+    const sah_rtgi_denoise_params& s = *params;
+    if (s.flags & ~SAH_RTGI_DENOISE_HISTORY_INVALID) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: unknown flag bits");
+    const bool history = !(s.flags & SAH_RTGI_DENOISE_HISTORY_INVALID);
+    if (s.passes > 3 || s.normal_squarings > 7) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: passes must be 0..3 and normal_squarings 0..7");
+    constexpr uint32_t RGBA16 = SAH_FORMAT_R16G16B16A16_SFLOAT, RGBA32 = SAH_FORMAT_R32G32B32A32_SFLOAT, RG32 = SAH_FORMAT_R32G32_SFLOAT;
+    constexpr int kPlanes = 12;
+    const Checked planes[kPlanes] = {{desc->ray_buffer, RGBA16, 8, false, false, "ray_buffer must be an R16G16B16A16_SFLOAT plane"},
+                                     {desc->ray_irradiance, RGBA16, 8, false, false, "ray_irradiance must be an R16G16B16A16_SFLOAT plane"},
+                                     {desc->depth, SAH_FORMAT_D32_SFLOAT, 4, false, false, "depth must be a D32_SFLOAT plane"},
+                                     {desc->normals, RGBA16, 8, false, false, "normals must be an R16G16B16A16_SFLOAT plane"},
+                                     {desc->motion_vectors, SAH_FORMAT_R16G16_SFLOAT, 4, false, false, "motion_vectors must be an R16G16_SFLOAT plane"},
+                                     {desc->previous_depth, SAH_FORMAT_D32_SFLOAT, 4, false, true, "previous_depth must be a D32_SFLOAT plane"},
+                                     {desc->history, RGBA32, 16, false, true, "history must be an R32G32B32A32_SFLOAT plane"},
+                                     {desc->history_moments, RG32, 8, false, true, "history_moments must be an R32G32_SFLOAT plane"},
+                                     {desc->accum_out, RGBA32, 16, true, false, "accum_out must be an R32G32B32A32_SFLOAT plane"},
+                                     {desc->moments_out, RG32, 8, true, false, "moments_out must be an R32G32_SFLOAT plane"},
+                                     {desc->denoised_ray_buffer, RGBA16, 8, true, false, "denoised_ray_buffer must be an R16G16B16A16_SFLOAT plane"},
+                                     {desc->denoised_irradiance, RGBA16, 8, true, false, "denoised_irradiance must be an R16G16B16A16_SFLOAT plane"}};
+    const auto used = [history](const Checked& c) { return history || !c.previous; };  // (a previous-frame plane that is not used is not looked at)
+    for (const Checked& c : planes)
+        if (used(c))
+            if (const int rc = plane_status(c.p, c.format, c.bpp); rc != SAH_OK)
+                return fail(ctx, rc, "rtgi_denoise: %s, 4-byte aligned, with a pitch of at least a row that is a multiple of 4", c.what);
+    const uint32_t w = desc->denoised_irradiance->width, h = desc->denoised_irradiance->height;
+    for (const Checked& c : planes)
+        if (used(c) && (c.p->width != w || c.p->height != h)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: the planes must have one extent");
+    if (((w | h) >> 31) || (uint64_t)w * h >= (1ull << 32)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: 2^32 texels or more");
+    if (row_begin == 0 && row_end == 0) row_end = h;
+    if (row_end > h || row_begin > row_end) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: bad row range");
+    if (!(s.max_history >= 1.0f && s.max_history <= 256.0f)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: max_history must be in [1, 256]");
+    if (!(s.min_history >= 1.0f && s.min_history <= 256.0f)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: min_history must be in [1, 256]");
+    if (!(std::isfinite(s.depth_tolerance) && s.depth_tolerance > 0.0f)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: depth_tolerance must be finite and positive");
+    if (!(std::isfinite(s.depth_sharpness) && s.depth_sharpness >= 0.0f)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: depth_sharpness must be finite and not negative");
+    if (!(std::isfinite(s.luminance_sigma) && s.luminance_sigma >= 0.0f)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: luminance_sigma must be finite and not negative");
+    if (!(std::isfinite(s.luminance_floor) && s.luminance_floor > 0.0f)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: luminance_floor must be finite and positive");
+    for (const float v : {s.jitter[0], s.jitter[1], s.previous_jitter[0], s.previous_jitter[1]})
+        if (!std::isfinite(v)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: a jitter is not finite");
+    const float* P = view->projection;
+    const float* IV = view->inverse_view;
+    const float* L = view->last_frame_view;
+    for (const float v : {P[0], P[5], P[8], P[9], view->z_near, IV[0], IV[1], IV[2], IV[4], IV[5], IV[6], IV[8], IV[9], IV[10], IV[12], IV[13], IV[14], L[2], L[6], L[10], L[14]})
+        if (std::isnan(v)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: a field of the view that the pass reads is NaN");
+    if (!(std::isfinite(view->z_near) && view->z_near > 0.0f)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: z_near must be finite and positive");
+    for (int o = 0; o < kPlanes; o++)
+        for (int i = 0; planes[o].output && i < kPlanes; i++)
+            if (i != o && used(planes[i]) && overlap(planes[o], planes[i])) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rtgi_denoise: an output overlaps an input or another output");
+    sah::RtgiDenoiseArgs a{};
+    a.rays = parg(desc->ray_buffer), a.irr = parg(desc->ray_irradiance), a.depth = parg(desc->depth), a.normals = parg(desc->normals), a.mv = parg(desc->motion_vectors);
+    if (history) a.prev_depth = parg(desc->previous_depth), a.history = parg(desc->history), a.hist_mom = parg(desc->history_moments);
+    a.accum = parg(desc->accum_out), a.moments = parg(desc->moments_out), a.out_rays = parg(desc->denoised_ray_buffer), a.out_irr = parg(desc->denoised_irradiance);
+    a.W = w, a.H = h, a.row_begin = row_begin, a.row_end = row_end;
+    const uint32_t reach = (1u << s.passes) - 1;
+    a.acc_begin = row_begin - std::min(row_begin, reach);
+    a.acc_end = std::min(h, row_end + reach);
+    for (int c = 0; c < 4; c++)
+        for (int r = 0; r < 3; r++) a.iv[3 * c + r] = IV[4 * c + r];
+    for (int c = 0; c < 4; c++) a.l2[c] = L[4 * c + 2];
+    const float wf = (float)w, hf = (float)h;
+    a.p20 = P[8], a.p21 = P[9], a.ipx = 1.0f / P[0], a.ipy = 1.0f / P[5], a.tx = 2.0f / wf, a.ty = 2.0f / hf;
+    a.z_near = view->z_near;
+    a.djx = s.previous_jitter[0] - s.jitter[0], a.djy = s.previous_jitter[1] - s.jitter[1];
+    a.max_history = s.max_history, a.min_history = s.min_history, a.depth_tolerance = s.depth_tolerance, a.depth_sharpness = s.depth_sharpness;
+    a.luminance_sigma = s.luminance_sigma, a.luminance_floor = s.luminance_floor, a.normal_squarings = s.normal_squarings;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, sah::launch_rtgi_denoise(a, s.passes, history, ctx->stream));
+    return SAH_OK;
+}

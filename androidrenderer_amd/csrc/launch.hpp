@@ -8,6 +8,7 @@
 #include "../../include/sah_hip.h"
 #include "../../include/sah_mip_chain.h"
 #include "../../include/sah_rt_denoise.h"
+#include "../../include/sah_rtgi_denoise.h"
 #include "../../include/sah_ssao.h"
 #include "../../include/sah_taa.h"
 #include "../../include/sah_taa_upscale.h"
@@ -111,6 +112,21 @@ struct RtDenoiseArgs {
     uint32_t normal_squarings;
 };
 hipError_t launch_rt_denoise(const RtDenoiseArgs& a, uint32_t passes, bool history, hipStream_t st);
+
+// --- rtgi_denoise.hip
+struct RtgiDenoiseArgs {
+    PlaneArg rays, irr, depth, normals, mv, prev_depth, history, hist_mom, accum, moments, out_rays, out_irr;
+    uint32_t W, H;
+    uint32_t acc_begin, acc_end;      // rows of `accum` and `moments` the temporal kernel writes: the band widened by the filter's reach, clipped to the image
+    uint32_t row_begin, row_end;      // rows of `out_rays` and `out_irr`
+    float iv[12];                     // rows 0..2 of inverse_view, column major: iv[3 * column + row]
+    float l2[4];                      // row 2 of last_frame_view
+    float p20, p21, ipx, ipy, tx, ty;  // 1 / P00, 1 / P11, 2 / W, 2 / H
+    float z_near, djx, djy;           // previous_jitter - jitter
+    float max_history, min_history, depth_tolerance, depth_sharpness, luminance_sigma, luminance_floor;
+    uint32_t normal_squarings;
+};
+hipError_t launch_rtgi_denoise(const RtgiDenoiseArgs& a, uint32_t passes, bool history, hipStream_t st);
 
 // --- mip_chain.hip
 struct MipChainArgs {

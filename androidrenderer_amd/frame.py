@@ -414,3 +414,53 @@ class RayTracedDenoiser:
         self.previous_jitter = (p.jitter[0], p.jitter[1])
         self.history_valid = True
         return self.denoised
+
+
+class RtgiDenoiser:
+    """The temporal accumulation and variance-guided filter for the RTGI ray planes (include/sah_rtgi_denoise.h) over successive frames of
+    one extent: owns the two ping-ponged accumulation / moments pairs — this frame's accum_out and moments_out are the next frame's history
+    — the kept copy of the last frame's depth, and the two denoised planes sah_lighting reads as gi.ray_buffer and gi.ray_irradiance; tracks
+    the previous jitter and whether there is a history, like RayTracedDenoiser.  The first frame, and the first after reset() (a camera cut),
+    passes SAH_RTGI_DENOISE_HISTORY_INVALID.  `settings` are fields of _abi.RtgiDenoiseParams.  The depth is kept with a device copy on
+    torch's current stream, which must be the context's."""
+
+    def __init__(self, ctx, width, height, device="cuda", **settings):
+        import torch
+        self.ctx, self.width, self.height = ctx, width, height
+        self.params = _abi.RtgiDenoiseParams.default(**settings)
+        self.accum = [torch.zeros((height, width, 4), dtype=torch.float32, device=device) for _ in range(2)]
+        self.moments = [torch.zeros((height, width, 2), dtype=torch.float32, device=device) for _ in range(2)]
+        self.previous_depth = torch.zeros((height, width), dtype=torch.float32, device=device)
+        self.denoised_ray_buffer = torch.zeros((height, width, 4), dtype=torch.int16, device=device)
+        self.denoised_irradiance = torch.zeros((height, width, 4), dtype=torch.int16, device=device)
+        self.current = 0  # index of the pair the last denoise() wrote
+        self.previous_jitter = (0.0, 0.0)
+        self.history_valid = False
+
+    def reset(self):
+        self.history_valid = False
+
+    def denoise(self, view_data, ray_buffer, ray_irradiance, depth, normals, motion_vectors, jitter):
+        """ray_buffer, ray_irradiance and normals (H, W, 4) int16, depth (H, W) float32, motion_vectors (H, W, 2) int16 device arrays of this
+        frame, view_data its _abi.ViewData, `jitter` the (x, y) it was rendered with.  Returns (denoised_ray_buffer, denoised_irradiance),
+        (H, W, 4) int16: the same arrays every call."""
+        p = self.params
+        p.jitter[:] = [float(jitter[0]), float(jitter[1])]
+        p.previous_jitter[:] = self.previous_jitter if self.history_valid else p.jitter[:]
+        p.flags = 0 if self.history_valid else _abi.RTGI_DENOISE_HISTORY_INVALID
+        old, new = self.current, 1 - self.current
+        RGBA16F, RGBA32F, RG32F, D32 = _abi.FORMAT_R16G16B16A16_SFLOAT, _abi.FORMAT_R32G32B32A32_SFLOAT, _abi.FORMAT_R32G32_SFLOAT, _abi.FORMAT_D32_SFLOAT
+        previous = dict(previous_depth=images.plane(self.previous_depth, D32), history=images.plane(self.accum[old], RGBA32F),
+                        history_moments=images.plane(self.moments[old], RG32F)) if self.history_valid else {}
+        desc = _abi.RtgiDenoiseDesc.of(ray_buffer=images.plane(ray_buffer, RGBA16F), ray_irradiance=images.plane(ray_irradiance, RGBA16F),
+                                       depth=images.plane(depth, D32), normals=images.plane(normals, RGBA16F),
+                                       motion_vectors=images.plane(motion_vectors, _abi.FORMAT_R16G16_SFLOAT),
+                                       accum_out=images.plane(self.accum[new], RGBA32F), moments_out=images.plane(self.moments[new], RG32F),
+                                       denoised_ray_buffer=images.plane(self.denoised_ray_buffer, RGBA16F),
+                                       denoised_irradiance=images.plane(self.denoised_irradiance, RGBA16F), **previous)
+        self.ctx.rtgi_denoise(view_data, desc, p)
+        self.previous_depth.copy_(depth)
+        self.current = new
+        self.previous_jitter = (p.jitter[0], p.jitter[1])
+        self.history_valid = True
+        return self.denoised_ray_buffer, self.denoised_irradiance

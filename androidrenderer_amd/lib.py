@@ -53,6 +53,9 @@ SSAO_EXPORTS = ["sah_ssao"]
 # the filter for the ray-traced masks: exported, declared in include/sah_rt_denoise.h (not sah_hip.h)
 RT_DENOISE_EXPORTS = ["sah_rt_denoise"]
 
+# the filter for the RTGI ray planes: exported, declared in include/sah_rtgi_denoise.h (not sah_hip.h)
+RTGI_DENOISE_EXPORTS = ["sah_rtgi_denoise"]
+
 # histogram auto-exposure: exported, declared in include/sah_exposure.h (not sah_hip.h)
 EXPOSURE_EXPORTS = ["sah_exposure_meter", "sah_exposure_apply"]
 EXPOSURE_WORK_BYTES = 1040    # SAH_EXPOSURE_WORK_BYTES
@@ -219,6 +222,7 @@ def load():
     lib.sah_taa_upscale.argtypes = [C.c_void_p] + [C.POINTER(_abi.Plane)] * 5 + [C.POINTER(_abi.TaaUpscaleParams), C.c_uint32, C.c_uint32]
     lib.sah_ssao.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData)] + [C.POINTER(_abi.Plane)] * 4 + [C.POINTER(_abi.SsaoParams), C.c_uint32, C.c_uint32]
     lib.sah_rt_denoise.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData), C.POINTER(_abi.RtDenoiseDesc), C.POINTER(_abi.RtDenoiseParams), C.c_uint32, C.c_uint32]
+    lib.sah_rtgi_denoise.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData), C.POINTER(_abi.RtgiDenoiseDesc), C.POINTER(_abi.RtgiDenoiseParams), C.c_uint32, C.c_uint32]
     lib.sah_exposure_meter.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.ExposureParams)]
     lib.sah_exposure_apply.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
     lib.sah_mip_chain_generate.argtypes =[C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32]
@@ -437,6 +441,12 @@ class Context:
         memory, one extent), params an _abi.RtDenoiseParams.  previous_depth, history and history_length may be None with
         RT_DENOISE_HISTORY_INVALID in params.flags.  rows (begin, end) of `denoised`, (0, 0) = all."""
         self._check(self.lib.sah_rt_denoise(self.handle, C.byref(view_data), C.byref(desc), C.byref(params), rows[0], rows[1]))
+
+    def rtgi_denoise(self, view_data, desc, params, rows=(0, 0)):
+        """sah_rtgi_denoise (include/sah_rtgi_denoise.h): desc an _abi.RtgiDenoiseDesc (RtgiDenoiseDesc.of(ray_buffer=..., ...), _abi.Plane of
+        device memory, one extent), params an _abi.RtgiDenoiseParams.  previous_depth, history and history_moments may be None with
+        RTGI_DENOISE_HISTORY_INVALID in params.flags.  rows (begin, end) of the two denoised planes, (0, 0) = all."""
+        self._check(self.lib.sah_rtgi_denoise(self.handle, C.byref(view_data), C.byref(desc), C.byref(params), rows[0], rows[1]))
 
     def exposure_meter(self, scene, state_in, state_out, work, exposed_out, params):
         """sah_exposure_meter (include/sah_exposure.h): scene and exposed_out R16G16B16A16_SFLOAT _abi.Plane of device memory, one extent;

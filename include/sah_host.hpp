@@ -36,6 +36,7 @@
 #include "sah_motion_vectors.h"
 #include "sah_rt_denoise.h"
 #include "sah_rt_refit.h"
+#include "sah_rtgi_denoise.h"
 #include "sah_ssao.h"
 #include "sah_taa.h"
 #include "sah_taa_upscale.h"
@@ -77,7 +78,8 @@ inline uint32_t format_bytes(uint32_t f) {
     switch (f) {
         case SAH_FORMAT_R8_UNORM: case SAH_FORMAT_R8_UINT: return 1;
         case SAH_FORMAT_R16_SFLOAT: case SAH_FORMAT_D16_UNORM: return 2;
-        case SAH_FORMAT_R16G16B16A16_SFLOAT: return 8;
+        case SAH_FORMAT_R16G16B16A16_SFLOAT: case SAH_FORMAT_R32G32_SFLOAT: return 8;
+        case SAH_FORMAT_R32G32B32A32_SFLOAT: return 16;
         default: return 4;
     }
 }
@@ -1179,10 +1181,79 @@ private:
     TextureHandle own_trace_results{};
 };
 
+// The settings of sah_rtgi_denoise_params (include/sah_rtgi_denoise.h) with the header's defaults; the jitters come from the view.
+struct RtgiDenoiseSettings {
+    float max_history = 32.f, min_history = 4.f, depth_tolerance = 0.1f, depth_sharpness = 50.f;
+    uint32_t normal_squarings = 5, passes = 3;
+    float luminance_sigma = 4.f, luminance_floor = 1e-6f;
+};
+// The temporal accumulation and variance-guided filter for the two RTGI ray planes (include/sah_rtgi_denoise.h; builder-owned, no
+// reference counterpart) over successive frames: owns the two ping-ponged accumulation / moments pairs and the kept copy of the last
+// frame's depth, (re-)created when the targets' extent changes.  denoise records the pass "RTGI denoise" and an image copy that keeps
+// the depth.  The first denoise, the first after reset_history() (a camera cut) and the first of another extent have no history.
+class RtgiDenoiser {
+public:
+    RtgiDenoiseSettings settings;
+    explicit RtgiDenoiser(ResourceAllocator& allocator_in) : allocator(allocator_in) {}
+    void reset_history() { history_valid = false; }
+    void denoise(RenderGraph& graph, const SceneView& view, TextureHandle ray_buffer, TextureHandle ray_irradiance, TextureHandle gbuffer_depth,
+                 TextureHandle gbuffer_normals, TextureHandle motion_vectors, TextureHandle denoised_ray_buffer, TextureHandle denoised_irradiance) {
+        if (!ray_buffer || !ray_irradiance || !gbuffer_depth || !gbuffer_normals || !motion_vectors || !denoised_ray_buffer || !denoised_irradiance) {
+            graph.add_pass(hip_pass("RTGI denoise", [](sah_ctx*) { return (int)SAH_ERR_INVALID_ARGUMENT; }));
+            return;
+        }
+        const uint32_t w = denoised_irradiance->desc.width, h = denoised_irradiance->desc.height;
+        if (!previous_depth || previous_depth->desc.width != w || previous_depth->desc.height != h) {
+            for (int i = 0; i < 2; i++) {
+                accum[i] = allocator.create_texture("RTGI denoiser accumulation", SAH_FORMAT_R32G32B32A32_SFLOAT, w, h);
+                moments[i] = allocator.create_texture("RTGI denoiser moments", SAH_FORMAT_R32G32_SFLOAT, w, h);
+            }
+            previous_depth = allocator.create_texture("RTGI denoiser previous depth", SAH_FORMAT_D32_SFLOAT, w, h);
+            history_valid = false;
+        }
+        TextureHandle old_accum = accum[current], old_moments = moments[current], new_accum = accum[1 - current], new_moments = moments[1 - current];
+        TextureHandle kept = previous_depth;
+        const bool use_history = history_valid;
+        const RtgiDenoiseSettings st = settings;
+        graph.add_pass(hip_pass("RTGI denoise", [=, &view](sah_ctx* ctx) {
+                            const sah_view_data& v = view.get_gpu_data();
+                            sah_rtgi_denoise_params p{};
+                            p.max_history = st.max_history, p.min_history = st.min_history, p.depth_tolerance = st.depth_tolerance, p.depth_sharpness = st.depth_sharpness;
+                            p.normal_squarings = st.normal_squarings, p.passes = st.passes;
+                            p.luminance_sigma = st.luminance_sigma, p.luminance_floor = st.luminance_floor;
+                            p.jitter[0] = v.jitter[0], p.jitter[1] = v.jitter[1];
+                            p.previous_jitter[0] = use_history ? v.previous_jitter[0] : v.jitter[0];
+                            p.previous_jitter[1] = use_history ? v.previous_jitter[1] : v.jitter[1];
+                            p.flags = use_history ? 0u : SAH_RTGI_DENOISE_HISTORY_INVALID;
+                            const sah_plane rb = ray_buffer->plane(), ri = ray_irradiance->plane(), d = gbuffer_depth->plane(), n = gbuffer_normals->plane();
+                            const sah_plane m = motion_vectors->plane(), pd = kept->plane(), ha = old_accum->plane(), hm = old_moments->plane();
+                            const sah_plane na = new_accum->plane(), nm = new_moments->plane(), ob = denoised_ray_buffer->plane(), oi = denoised_irradiance->plane();
+                            sah_rtgi_denoise_desc desc{};
+                            desc.ray_buffer = &rb, desc.ray_irradiance = &ri, desc.depth = &d, desc.normals = &n, desc.motion_vectors = &m;
+                            if (use_history) desc.previous_depth = &pd, desc.history = &ha, desc.history_moments = &hm;
+                            desc.accum_out = &na, desc.moments_out = &nm, desc.denoised_ray_buffer = &ob, desc.denoised_irradiance = &oi;
+                            return sah_rtgi_denoise(ctx, &v, &desc, &p, 0, 0);
+                        }));
+        graph.add_copy_pass(ImageCopyPass{"Keep depth for the RTGI denoiser", previous_depth, gbuffer_depth});
+        current = 1 - current;  // swap the history
+        history_valid = true;
+    }
+
+private:
+    ResourceAllocator& allocator;
+    TextureHandle accum[2] = {nullptr, nullptr}, moments[2] = {nullptr, nullptr}, previous_depth = nullptr;
+    uint32_t current = 0;
+    bool history_valid = false;
+};
+
 // RenderCore/render/gi/rtgi.{hpp,cpp}: post_render (:69-139) traces one GI ray per pixel (sah_rtgi_trace) into the two per-pixel
 // textures — ray direction + distance, ray irradiance — that the reconstruction overlay (rtgi.cpp:160-188,
 // gi/rtgi/overlay.frag.slang:68-117) binds in the NEXT frame's Lighting pass.  It owns an IrradianceCache, as the reference does
 // (rtgi.hpp: irradiance_cache).  set_ray_textures() remains for ray textures produced elsewhere.
+// Opt-in, off by default: with `denoise` post_render records sah_rtgi_denoise after the trace (RtgiDenoiser; include/sah_rtgi_denoise.h)
+// and render_to_lit_scene binds the denoised pair instead of the raw one.  It needs the frame's motion vectors in
+// denoise_motion_vectors: without them post_render throws std::logic_error.  set_reconstruction keeps its meaning (the overlay's extra
+// taps then read the denoised pair).
 class RayTracedGlobalIllumination : public IGlobalIlluminator {
 public:
     explicit RayTracedGlobalIllumination(RenderBackend& backend) : cache(backend), allocator(&backend.get_global_allocator()) {}
@@ -1201,10 +1272,19 @@ public:
     IrradianceCache& get_irradiance_cache() { return cache; }
     TextureHandle get_ray_texture() const { return ray_texture; }
     TextureHandle get_ray_irradiance() const { return ray_irradiance; }
+    bool denoise = false;
+    RtgiDenoiseSettings denoise_settings;
+    TextureHandle denoise_motion_vectors = nullptr;
+    void reset_denoise_history() {
+        if (denoiser) denoiser->reset_history();
+    }
+    TextureHandle get_denoised_ray_texture() const { return denoised_ray_texture; }
+    TextureHandle get_denoised_ray_irradiance() const { return denoised_ray_irradiance; }
     void pre_render(RenderGraph& graph, const SceneView& view, const RenderScene& scene, TextureHandle noise_tex) override {
         cache.pre_render(graph, view, scene, noise_tex);  // rtgi.cpp:60-75: the cache updates first
     }
     void post_render(RenderGraph& graph, const SceneView& view, const RenderScene& scene, const GBuffer& gbuffer, TextureHandle noise_tex) override {
+        if (denoise && !denoise_motion_vectors) throw std::logic_error("RayTracedGlobalIllumination: denoise needs denoise_motion_vectors set");
         if (!scene.get_raytracing_scene().is_built() || !noise_tex || !scene.sky.transmittance_lut || !scene.sky.sky_view_lut) return;
         const uint32_t w = gbuffer.depth->desc.width, h = gbuffer.depth->desc.height;
         if (ray_texture == nullptr || ray_texture->desc.width != w || ray_texture->desc.height != h)
@@ -1220,6 +1300,15 @@ public:
                             sah_rt_set_bounces(ctx, 0);  // (the context's setting also governs the irradiance cache's probe rays)
                             return rc;
                         }));
+        denoised_now = denoise;
+        if (!denoise) return;
+        if (denoised_ray_texture == nullptr || denoised_ray_texture->desc.width != w || denoised_ray_texture->desc.height != h) {  // (a new extent: the denoiser starts over too)
+            denoised_ray_texture = allocator->create_texture("rtgi_params_denoised", SAH_FORMAT_R16G16B16A16_SFLOAT, w, h);
+            denoised_ray_irradiance = allocator->create_texture("rtgi_irradiance_denoised", SAH_FORMAT_R16G16B16A16_SFLOAT, w, h);
+        }
+        if (!denoiser) denoiser = std::make_unique<RtgiDenoiser>(*allocator);
+        denoiser->settings = denoise_settings;
+        denoiser->denoise(graph, view, ray_texture, ray_irradiance, gbuffer.depth, gbuffer.normals, denoise_motion_vectors, denoised_ray_texture, denoised_ray_irradiance);
     }
     void get_lighting_resource_usages(TextureUsageList& textures, BufferUsageList& buffers) const override {
         cache.get_lighting_resource_usages(textures, buffers);
@@ -1231,8 +1320,9 @@ public:
         gi = sah_gi{};
         commands.lighting.has_gi = true;
         gi.kind = SAH_GI_RTGI;
-        gi.ray_buffer = ray_texture->plane();
-        gi.ray_irradiance = ray_irradiance->plane();
+        const bool denoised = denoise && denoised_now && denoised_ray_texture;  // (the pair the last post_render denoised)
+        gi.ray_buffer = (denoised ? denoised_ray_texture : ray_texture)->plane();
+        gi.ray_irradiance = (denoised ? denoised_ray_irradiance : ray_irradiance)->plane();
         if (noise_tex) gi.noise = noise_tex->plane();
         gi.num_extra_rays = noise_tex ? num_extra_rays : 0;
         gi.extra_ray_radius = extra_ray_radius;
@@ -1241,7 +1331,9 @@ public:
 private:
     IrradianceCache cache;
     ResourceAllocator* allocator = nullptr;
-    TextureHandle ray_texture{}, ray_irradiance{};
+    TextureHandle ray_texture{}, ray_irradiance{}, denoised_ray_texture{}, denoised_ray_irradiance{};
+    std::unique_ptr<RtgiDenoiser> denoiser;
+    bool denoised_now = false;
     uint32_t forwarded_bounces = 0;
     uint32_t num_extra_rays = 0;
     float extra_ray_radius = 16.f;

@@ -7,9 +7,9 @@
  * tests/golden/rt_denoise_*.npz.  Parity unpinned: there is no reference output to compare with.  Same conventions as sah_hip.h (this
  * header includes it).
  *
- * NOT part of it: variance-guided or history-length-adaptive filter widths, a previous-normals test, bicubic history, RGB planes
- * (ray_irradiance), feeding the filtered value back into the history, sah_chain_* integration, any change to sah_rtao or
- * sah_sun_shadow_mask.
+ * NOT part of it: variance-guided or history-length-adaptive filter widths and RGB planes (ray_irradiance) — those are
+ * sah_rtgi_denoise.h's — a previous-normals test, bicubic history, feeding the filtered value back into the history, sah_chain_*
+ * integration, any change to sah_rtao or sah_sun_shadow_mask.
  *
  * The call runs on the context's stream, does no host synchronisation, allocates nothing and asks no scratch of the caller (the filter's
  * iterations chain through LDS), leaves its inputs and every cache and epoch of the context untouched, may be recorded under stream
