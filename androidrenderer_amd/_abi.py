@@ -31,6 +31,9 @@ LIGHTING_BRUTE_FORCE_LIGHTS = 1 << 1
 LIGHTING_DEFAULT_FLAGS = LIGHTING_QUIRK_SUN_BLEND
 MAX_BLOOM_MIPS = 8
 TONEMAP_TOLERANCE_1CODE = 1 << 0
+# sah_debug_set's `strays` (a test hook, not in sah_hip.h): who shades the pixels the fast Lighting kernel lists — the context's record of recent
+# calls decides, always the fix-up launch, always the fast kernel itself.  Word 12 of sah_debug_lighting_dispatch reports 1 + (in-kernel) for a fast call.
+DEBUG_STRAYS_AUTO, DEBUG_STRAYS_LAUNCH, DEBUG_STRAYS_INLINE = 0, 1, 2
 GENERATION_TRACKED = 0xFFFFFFFF  # sah_gi::lpv_generation / probe_generation: the context keeps its gather copies current itself
 
 

@@ -60,9 +60,9 @@ namespace {
 // The words of sah_debug_lighting_dispatch, named after and in the order of Context.DISPATCH_FIELDS (androidrenderer_amd/lib.py)
 enum DispatchField {
     kDispFamily, kDispPpt, kDispPosDivNr, kDispNcascPow2, kDispRowMagic, kDispSkyRatio, kDispSkyWorkgroups, kDispTiledFastGeom, kDispTiledFastLpv,
-    kDispRepack, kDispTableRebuilt, kDispPosDivShared, kDispFields
+    kDispRepack, kDispTableRebuilt, kDispPosDivShared, kDispStrays, kDispFields
 };
-static_assert(kDispFields == sizeof(sah_ctx::last_dispatch) / sizeof(uint32_t), "sah_debug_lighting_dispatch reports uint32_t[12]");
+static_assert(kDispFields == sizeof(sah_ctx::last_dispatch) / sizeof(uint32_t), "sah_debug_lighting_dispatch reports uint32_t[13]");
 
 // What the stages of one call share about it
 struct LightingCall {
@@ -514,6 +514,25 @@ int lighting_colx_table(sah_ctx* ctx, const LightingCall& call, const LightingAr
     return SAH_OK;
 }
 
+// How the fast kernel's strays are finished (FastArgs::strays_inline): by the context's record (ctx_cache.hpp: SahStraysRecord, where the rule
+// stands), or as sah_debug_set says.  A body that cannot finish its own strays (lighting.hip), an empty row range and a capturing stream take
+// the fix-up launch whatever is asked; a captured call leaves the record alone.
+int lighting_strays(sah_ctx* ctx, const LightingCall& call, const SkyArgs& sky, int ppt, FastArgs& fast) {
+    fast.strays_record = ctx->strays.rec;
+    fast.strays_inline = 0u;
+    if (!lighting_fast_finishes_strays(sky.enabled != 0u) || call.r1 <= call.r0) return SAH_OK;
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(ctx->stream, &capturing) != hipSuccess) {  // (the query itself is refused, e.g. on the null stream beside a capture: the launches will say so)
+        (void)hipGetLastError();
+        return SAH_OK;
+    }
+    if (capturing != hipStreamCaptureStatusNone) return SAH_OK;
+    const uint32_t key[7] = {call.sun_mode, call.gi_kind, (uint32_t)ppt, sky.enabled, call.W, call.r0, call.r1};
+    const bool predicted_clean = ctx->strays.take(key);
+    fast.strays_inline = ctx->force_strays == 0 ? (predicted_clean ? 1u : 0u) : (ctx->force_strays == 2 ? 1u : 0u);
+    return SAH_OK;
+}
+
 void lighting_report(sah_ctx* ctx, const LightingCall& call, const FastPath& path, int ppt, const FastArgs& fast, bool table_rebuilt) {
     uint32_t* w = ctx->last_dispatch;
     w[kDispFamily] = path.family;
@@ -528,6 +547,7 @@ void lighting_report(sah_ctx* ctx, const LightingCall& call, const FastPath& pat
     w[kDispRepack] = fast.repack;
     w[kDispTableRebuilt] = table_rebuilt ? 1u : 0u;
     w[kDispPosDivShared] = fast.pos_div_shared;  // (the host's half: sah_debug_lighting_dispatch adds the table's)
+    w[kDispStrays] = path.use_fast ? 1u + fast.strays_inline : 0u;
 }
 
 }  // namespace
@@ -608,6 +628,7 @@ int sah_create(sah_ctx** out, int device, int rank, int world, const void* comm_
         sah_destroy(ctx);
         return SAH_ERR_HIP;
     }
+    ctx->strays.create();
     // (kept: read once per context, selects code that ships — every bin list whole — and is how tests/test_raster.py reaches it)
     const char* mc = getenv("SAH_RASTER_MERGE_CAPACITY");
     if (mc) ctx->raster_merge_cap = (uint32_t)atoi(mc);
@@ -648,6 +669,7 @@ void sah_destroy(sah_ctx* ctx) {
     for (SahBuffer* b : buffers) b->release();
     ctx->tm_codes.release();
     ctx->mip_chain_counter.release();
+    ctx->strays.release();
     for (SahCacheGuard* g : {&ctx->guard_lighting, &ctx->guard_tonemap, &ctx->guard_raster, &ctx->guard_rt, &ctx->guard_mip_chain})
         if (g->done) (void)hipEventDestroy(g->done);
     if (ctx->raster.half_to_srgb8) (void)hipFree(ctx->raster.half_to_srgb8);
@@ -676,11 +698,15 @@ int sah_set_stream(sah_ctx* ctx, void* hip_stream) {
 
 void* sah_get_stream(sah_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
-// Testing / tuning hooks (not part of the reference-facing ABI): force the general kernel, force pixels-per-thread.
-int sah_debug_set(sah_ctx* ctx, int force_general, int force_ppt) {
+// Testing / tuning hooks (not part of the reference-facing ABI): force the general kernel, force pixels-per-thread, and say how the fast
+// kernel's strays are finished — `strays` 0: by the context's record of recent calls (SahStraysRecord), 1: always the fix-up launch, 2: always
+// in the fast kernel, where its body can (lighting.hip).  Any other value is refused and changes nothing.
+int sah_debug_set(sah_ctx* ctx, int force_general, int force_ppt, int strays) {
     if (!ctx) return SAH_ERR_INVALID_ARGUMENT;
+    if (strays < 0 || strays > 2) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "strays must be 0 (auto), 1 (launch) or 2 (inline), not %d", strays);
     ctx->force_general = force_general != 0;
     ctx->force_ppt = force_ppt;
+    ctx->force_strays = strays;
     return SAH_OK;
 }
 
@@ -723,7 +749,8 @@ int sah_debug_cache_epoch(sah_ctx* ctx, uint64_t* out) {
 //   [11] pos_div_shared: the call shared one reciprocal among the position divides through the condition for zeros of either sign (0 where
 //   pos_div_nr is 1).  The kernel decides this from FrameState::colx_neg_zero, so this word alone reads device memory: where the host's half
 //   of the condition held, the stream is synchronised and the table's word fetched.
-int sah_debug_lighting_dispatch(sah_ctx* ctx, uint32_t out[12]) {
+//   [12] the fast kernel's strays: 1 the fix-up launch followed, 2 the fast kernel finished them itself, no second launch (0: not the fast kernel)
+int sah_debug_lighting_dispatch(sah_ctx* ctx, uint32_t out[13]) {
     if (!ctx || !out) return SAH_ERR_INVALID_ARGUMENT;
     memcpy(out, ctx->last_dispatch, sizeof(ctx->last_dispatch));
     if (out[sah::kDispPosDivShared] && ctx->state) {
@@ -779,6 +806,7 @@ int sah_lighting(sah_ctx* ctx, const sah_lighting_desc* d) {
     }
     if (path.use_fast) {
         if (const int rc = lighting_fast_layout(ctx, d, call, ppt, lpv, sky, fast); rc != SAH_OK) return rc;
+        if (const int rc = lighting_strays(ctx, call, sky, ppt, fast); rc != SAH_OK) return rc;
     }
     bool table_rebuilt = false;
     if (const int rc = lighting_colx_table(ctx, call, a, path, ppt, fast, &table_rebuilt); rc != SAH_OK) return rc;

@@ -42,6 +42,7 @@ struct sah_ctx {
     bool comm_pending = false;          // a gather on comm_stream has not been joined by sah_comm_wait yet
     int force_ppt = 0;      // tuning/testing hook: 0 = auto
     bool force_general = false;  // testing hook: always run the general kernel
+    int force_strays = 0;   // testing hook: how the fast kernel's strays are finished — 0 by the record's rule (SahStraysRecord), 1 always the fix-up launch, 2 always in-kernel
     sah::FrameState* state = nullptr;  // device
     // ---- derived device state (ctx_cache.hpp): its operations are the only writers of these members and of cache_epoch
     SahBuffer list;                    // deferred-pixel list
@@ -55,6 +56,7 @@ struct sah_ctx {
     SahKeyedTable tm_axis;             // axis set-ups of the tolerance-mode composite (tonemap_tol.hip); key: output extent, mip extents, number of mips
     SahTonemapCodeTables tm_codes;
     SahTicketCounter mip_chain_counter;  // sah_mip_chain_generate (mip_chain.hip)
+    SahStraysRecord strays;            // whether a fast Lighting launch goes without its fix-up launch (never moves the epoch)
     // Raised whenever something changes that a launch of sah_lighting / sah_tonemap_ex DEPENDS on beyond its arguments: a context buffer is
     // reallocated, a table is rebuilt for other extents, a gather copy that calls were re-using is dropped or has to be rebuilt.  While it
     // stands, the same call enqueues the same kernels with the same kernel arguments — what sah_chain's captured graphs rely on (api_chain.cpp).
@@ -63,7 +65,7 @@ struct sah_ctx {
     uint32_t dbg_lpv_packs = 0, dbg_irr_unpacks = 0;  // full rebuilds of the two gather copies by sah_lighting (debug hook sah_debug_copy_rebuilds)
     const uint16_t* last_seg_count = nullptr;  // debug hook (sah_debug_deferred_pixels)
     uint32_t last_num_segments = 0;
-    uint32_t last_dispatch[12] = {};   // debug hook (sah_debug_lighting_dispatch): what the last sah_lighting call decided, host side
+    uint32_t last_dispatch[13] = {};   // debug hook (sah_debug_lighting_dispatch): what the last sah_lighting call decided, host side
     struct RasterScratch {             // device buffers of the scene rasteriser, grown on demand (api_raster.cpp)
         SahBuffer buf[16];
         uint8_t* half_to_srgb8 = nullptr;

@@ -2,7 +2,8 @@
 //
 // Four kinds: the two gather copies of the Lighting pass (SahLpvCopy, SahIrr32Copy), the keyed tables (SahKeyedTable: the fast kernel's column
 // table, the tolerance composite's axis tables; SahTonemapCodeTables), grow-only scratch (SahBuffer) and the mip-chain generator's ticket counter
-// (SahTicketCounter).  Plain structs of host values and device pointers, members of sah_ctx (ctx.hpp).  An operation that can change what the NEXT identical call would enqueue takes the context's
+// (SahTicketCounter); and, beside them, the record of the fast Lighting kernel's strays (SahStraysRecord), which decides between two ways of
+// enqueueing the same image and never moves the epoch.  Plain structs of host values and device pointers, members of sah_ctx (ctx.hpp).  An operation that can change what the NEXT identical call would enqueue takes the context's
 // `cache_epoch` and raises it; nothing outside this header writes the epoch, a generation, or the extent / all-zero record of the LPV copy.
 // While the epoch stands, the same call enqueues the same kernels with the same kernel arguments — what sah_chain's captured graphs rely on
 // (api_chain.cpp reads it, never writes it).
@@ -224,6 +225,61 @@ struct SahTicketCounter {
     void release() {
         if (word) (void)hipFree(word);
         word = nullptr;
+    }
+};
+
+// Whether a fast Lighting launch needs the fix-up launch behind it (lighting.hip: k_lighting_fixup, which shades the pixels the fast kernel
+// listed): in the frames a renderer produces nothing is listed, and the launch is a few microseconds of workgroups that read one word and
+// return.  The fast kernel can finish its own strays instead (FastArgs::strays_inline) — slower where there are many, the same bytes always —
+// so the launcher leaves the fix-up launch out when the recent past says there will be none:
+//     the last kCleanCalls fast launches the GPU has started for this context listed nothing,
+//     they were launches of the same kernel variant, width and row range as this one,
+//     and the stream is not capturing (a captured call is always the two launches, and leaves this record alone: what a graph holds does not
+//     depend on when it was captured, and the cache epoch has nothing to do with this).
+// A launch that lists after all finishes in-kernel once; the calls behind it launch the fix-up again until kCleanCalls have been clean.
+// The device half is sah::StraysRecord, in host memory the kernel stores to and `take` reads without waiting for anything, and the launch
+// numbers of FrameState::call_no.  The host counts the launches it enqueues; the device's count runs ahead where captured launches are
+// replayed, which `take` notices (started > issued) and takes as the end of what it knew.  No ticket, no atomic, no read-back: the record is
+// a prediction, and a wrong one costs time, never a pixel.
+struct SahStraysRecord {
+    static constexpr uint32_t kCleanCalls = 4;
+    sah::StraysRecord* rec = nullptr;  // hipHostMalloc; null after a failed allocation: the context then keeps the two launches for its whole life
+    uint32_t issued = 0;     // the launch number (FrameState::call_no) the last launch enqueued outside a capture is expected to have
+    uint32_t key[7] = {};    // sun mode, GI kind, pixels per thread, sky bound, width, row range of the launches numbered key_first .. issued
+    uint32_t key_first = 0;
+    bool have_key = false;
+
+    // with the context, so that no call allocates (a capturing stream forbids it); a failure is not an error
+    void create() {
+        if (hipHostMalloc((void**)&rec, sizeof(sah::StraysRecord)) != hipSuccess) {
+            (void)hipGetLastError();
+            rec = nullptr;
+            return;
+        }
+        rec->started = rec->listed = 0;
+    }
+    // A fast launch with key `k` is about to be enqueued, outside a capture: counts it, and tells whether it may go without the fix-up launch
+    bool take(const uint32_t (&k)[7]) {
+        if (!rec) return false;
+        const uint32_t started = __atomic_load_n(&rec->started, __ATOMIC_RELAXED), listed = __atomic_load_n(&rec->listed, __ATOMIC_RELAXED);
+        // (launch numbers are compared by their signed difference: they wrap after 2^32 launches)
+        auto ahead = [](uint32_t a, uint32_t b) { return (int32_t)(a - b); };
+        if (ahead(started, issued) > 0) {  // launches this record did not count have run (replays of a captured graph): of whatever extent, with whatever strays
+            issued = started;
+            have_key = false;
+        }
+        if (!have_key || memcmp(k, key, sizeof(key)) != 0) {
+            memcpy(key, k, sizeof(key));
+            key_first = issued + 1;
+            have_key = true;
+        }
+        issued++;
+        // launches started - kCleanCalls + 1 .. started: all of this key, none of them listed
+        return ahead(started, key_first) >= (int32_t)kCleanCalls - 1 && ahead(started, listed) >= (int32_t)kCleanCalls;
+    }
+    void release() {
+        if (rec) (void)hipHostFree(rec);
+        rec = nullptr;
     }
 };
 

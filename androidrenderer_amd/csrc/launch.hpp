@@ -28,6 +28,7 @@ hipError_t launch_lighting(const LightingArgs& a, const CsmArgs& csm, const LpvA
                            hipStream_t st);
 hipError_t launch_lighting_tiled(const LightingArgs& a, const CsmArgs& csm, const LpvArgs& lpv, const CacheArgs& cache, const RtgiArgs& rtgi,
                                  const SkyArgs& sky, int sun_mode, int gi, bool brute_force_lights, const FastArgs* fast, hipStream_t st);
+bool lighting_fast_finishes_strays(bool sky_bound);  // whether that body of the fast kernel honours FastArgs::strays_inline (lighting.hip)
 hipError_t launch_colx_table(const LightingArgs& a, const FastArgs& f, float* out, uint32_t stride, uint32_t row_stride, hipStream_t st);
 hipError_t launch_probe_irr_unpack(const VolumeArg& src, uint8_t* dst, hipStream_t st);
 hipError_t launch_probe_irr_unpack_probes(const VolumeArg& src, uint8_t* dst, const uint32_t* probes, uint32_t num_probes, hipStream_t st);

@@ -83,11 +83,40 @@ constexpr uint32_t kFixupSegs = 16;
 // (at most this many workgroups, striding over the groups of segments: 512 leave an empty list 0.7 us sooner than 2,048, but take
 //  3.7 % longer over a frame that lists 29 K pixels — tools/experiments/r5/ab_fixup_grid.sh)
 constexpr uint32_t kFixupMaxWorkgroups = 2048;
+
+// One listed pixel, `code` of segment `seg`: back to its place through the map of the fast kernel's thread that listed it, its planes read, shaded
+// with the general restatement, stored.  The fix-up kernel's loop body, and the fast kernel's where it finishes its own strays (FastArgs::strays_inline).
+template <int SUN, int GI, int PPT, bool SKY_FILL = true>
+SAH_DEV void shade_listed_pixel(const LightingArgs& a, const CsmArgs& csm, const LpvArgs& lpv, const SkyArgs& sky, const FastArgs& f, uint32_t seg,
+                                uint32_t code, const float* s_lut) {
+    const uint32_t g = seg * 64u + code / PPT;  // the thread of the fast kernel that listed the pixel: the same map back
+    const FastPixel at = fast_pixel_of(g, a.width / PPT, a.row_end - a.row_begin, PPT, f.tile_rows, f.row_magic);
+    const uint32_t y = a.row_begin + at.row, x = at.x0 + code % PPT;
+    Px p;
+    p.color = *reinterpret_cast<const uint32_t*>(a.color.ptr + (size_t)y * a.color.pitch + (size_t)x * 4);
+    p.data = *reinterpret_cast<const uint32_t*>(a.data.ptr + (size_t)y * a.data.pitch + (size_t)x * 4);
+    p.emission = *reinterpret_cast<const uint32_t*>(a.emission.ptr + (size_t)y * a.emission.pitch + (size_t)x * 4);
+    p.depth = *reinterpret_cast<const float*>(a.depth.ptr + (size_t)y * a.depth.pitch + (size_t)x * 4);
+    const uint2 n = *reinterpret_cast<const uint2*>(a.normals.ptr + (size_t)y * a.normals.pitch + (size_t)x * 8);
+    p.n01 = n.x;
+    p.n23 = n.y;
+    p.ao = (GI == SAH_GI_LPV && a.has_ao) ? *reinterpret_cast<const float*>(a.ao.ptr + (size_t)y * a.ao.pitch + (size_t)x * 4) : 1.0f;
+    p.mask = (SUN == SAH_SHADOW_MODE_RT && a.has_mask)
+                 ? *reinterpret_cast<const float*>(a.shadow_mask.ptr + (size_t)y * a.shadow_mask.pitch + (size_t)x * 4)
+                 : 1.0f;
+    const uint2 r = shade_pixel_general<SUN, GI, SKY_FILL>(a, csm, lpv, sky, x, y, p, s_lut);
+    *reinterpret_cast<uint2*>(const_cast<uint8_t*>(a.lit.ptr) + (size_t)y * a.lit.pitch + (size_t)x * 8) = r;
+}
+
 template <int SUN, int GI, int PPT>
 __global__ void __launch_bounds__(256) k_lighting_fixup(const LightingArgs a, const CsmArgs csm, const LpvArgs lpv, const SkyArgs sky,
                                                         const FastArgs f) {
     // nothing listed by any wave (FrameState::deferred_hint): every workgroup leaves here
     if (__hip_atomic_load(&f.state->deferred_hint[f.hint_slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;
+    // ... and something was: one thread says so in the host's record (StraysRecord) for the 20 K waves of a frame full of strays.  The fast kernel
+    // in front of this launch has left its own number in the next launch's word (FrameState::call_no).
+    if (blockIdx.x == 0u && threadIdx.x == 0u && f.strays_record)
+        __hip_atomic_store(&f.strays_record->listed, f.state->call_no[f.hint_slot ^ 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __shared__ uint32_t s_pref[kFixupSegs + 1];
     __shared__ float s_lut[512];
     stage_format_tables(s_lut, a.luts);
@@ -110,30 +139,13 @@ __global__ void __launch_bounds__(256) k_lighting_fixup(const LightingArgs a, co
     __syncthreads();
     const uint32_t total = s_pref[kFixupSegs];
     if (total == 0) continue;
-    const uint32_t groups_per_row = a.width / PPT;
     for (uint32_t i = threadIdx.x; i < total; i += 256u) {
         uint32_t s = 0;  // last segment whose prefix is <= i (counts are small: a 4-step search over 16 LDS words)
 #pragma unroll
         for (uint32_t step = kFixupSegs / 2; step >= 1; step >>= 1)
             if (s_pref[s + step] <= i) s += step;
         const uint32_t code = f.seg_list[(size_t)(seg0 + s) * f.seg_stride + (i - s_pref[s])];
-        const uint32_t g = (seg0 + s) * 64u + code / PPT;  // the thread of the fast kernel that listed the pixel: the same map back
-        const FastPixel at = fast_pixel_of(g, groups_per_row, a.row_end - a.row_begin, PPT, f.tile_rows, f.row_magic);
-        const uint32_t y = a.row_begin + at.row, x = at.x0 + code % PPT;
-        Px p;
-        p.color = *reinterpret_cast<const uint32_t*>(a.color.ptr + (size_t)y * a.color.pitch + (size_t)x * 4);
-        p.data = *reinterpret_cast<const uint32_t*>(a.data.ptr + (size_t)y * a.data.pitch + (size_t)x * 4);
-        p.emission = *reinterpret_cast<const uint32_t*>(a.emission.ptr + (size_t)y * a.emission.pitch + (size_t)x * 4);
-        p.depth = *reinterpret_cast<const float*>(a.depth.ptr + (size_t)y * a.depth.pitch + (size_t)x * 4);
-        const uint2 n = *reinterpret_cast<const uint2*>(a.normals.ptr + (size_t)y * a.normals.pitch + (size_t)x * 8);
-        p.n01 = n.x;
-        p.n23 = n.y;
-        p.ao = (GI == SAH_GI_LPV && a.has_ao) ? *reinterpret_cast<const float*>(a.ao.ptr + (size_t)y * a.ao.pitch + (size_t)x * 4) : 1.0f;
-        p.mask = (SUN == SAH_SHADOW_MODE_RT && a.has_mask)
-                     ? *reinterpret_cast<const float*>(a.shadow_mask.ptr + (size_t)y * a.shadow_mask.pitch + (size_t)x * 4)
-                     : 1.0f;
-        const uint2 r = shade_pixel_general<SUN, GI>(a, csm, lpv, sky, x, y, p, s_lut);
-        *reinterpret_cast<uint2*>(const_cast<uint8_t*>(a.lit.ptr) + (size_t)y * a.lit.pitch + (size_t)x * 8) = r;
+        shade_listed_pixel<SUN, GI, PPT>(a, csm, lpv, sky, f, seg0 + s, code, s_lut);
     }
     }
 }
@@ -200,8 +212,17 @@ __global__ void __launch_bounds__(256) k_colx_table(const LightingArgs a, const 
 // worse: DESIGN.md §5 "Deferred pixels ... and the sky" —; small launches fewer, so that a thread of a sky workgroup over an all-sky stretch walks
 // fewer pixels one after the other: that walk is the launch's critical path when the launch is short)
 
+// Which bodies of the fast kernel have a twin that finishes its own strays (FINISH; FastArgs::strays_inline): the ones with a sky bound.  The
+// general restatement wants 135-207 VGPRs (k_lighting_fixup), and a kernel has one register count.  A SKY body is held at 128 by its launch
+// bound, so the finish — a region at the kernel's end, behind a wave-uniform vote, where nothing of the hot path is live — spills what it must,
+// where only a wave with strays goes, and the hot path keeps its registers and its occupancy.  A body without a sky has no bound: with the
+// finish it would take the restatement's count and lose one to five waves per SIMD for every wave of every frame.  Those keep the fix-up launch.
+// A twin, not a branch of the one body: compiled into the body that runs in front of a fix-up launch, the finish moved that body's SGPR spills
+// and cost it 1.1-1.8 % in every launch, strays or none (profiles/strays_inline_ab.txt).  The body in front of a fix-up launch is the kernel it was.
+constexpr bool strays_inline_body(bool sky) { return sky; }
+
 // ---- fast kernel (per-pixel body: lighting_fast.hpp) ----------------------------------------------------------------------
-template <int SUN, int GI, int PPT, bool SKY>
+template <int SUN, int GI, int PPT, bool SKY, bool FINISH = false>
 // (106 VGPRs at 4 px/thread = 4 waves per SIMD.  Forcing 5 or 6 with amdgpu_waves_per_eu spills 36-44 bytes per lane and is 12-20 %
 // slower, measured.)
 // (The sky path — two fp64 transcendentals per pixel — wants 126-137 VGPRs whatever stands next to it, and a kernel has ONE register count: left
@@ -368,12 +389,35 @@ __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const Lighti
                 front += (uint32_t)__builtin_popcountll(m);
             }
         }
+        // The FINISH body — the launcher has taken it and enqueues no fix-up launch behind it (FastArgs::strays_inline): the wave shades what it
+        // has just listed, dealt densely to its lanes like the fix-up kernel deals a group of segments — n listed pixels are ceil(n / 64) passes.
+        // It reads back only its own segment, and overwrites only lit pixels it stored itself: its stores above have to be done first.  A wave's
+        // memory operations are in order, and a wave-level fence keeps the compiler from moving a read ahead, as in lpv_box_write(); the wait
+        // for the stores' acknowledgements is there besides, in a region that runs for strays only.  (No sky here: the sky workgroups own the
+        // depth == 0 pixels of a SKY body.)
+        if constexpr (FINISH) {
+            static_assert(strays_inline_body(SKY), "no such body");
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            // (the host's record, StraysRecord: nobody else tells it here.  One store per listing wave of a launch that was predicted to have none)
+            if (lane == 0u && f.strays_record)
+                __hip_atomic_store(&f.strays_record->listed, f.state->call_no[f.hint_slot] + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#pragma unroll 1
+            for (uint32_t i = lane; i < front; i += 64u) shade_listed_pixel<SUN, GI, PPT, false>(a, csm, lpv, sky, f, seg, seg_codes[i], s_lut);
+        }
     }
     if (lane == 0 && seg < f.num_segments) {
         f.seg_count[seg] = (uint16_t)front;
         if (front != 0u) f.state->deferred_hint[f.hint_slot] = 1u;  // (see FrameState: the fix-up kernel's workgroups leave at once without it)
     }
-    if (gid == 0u) f.state->deferred_hint[f.hint_slot ^ 1u] = 0u;  // the next call's word
+    if (gid == 0u) {
+        f.state->deferred_hint[f.hint_slot ^ 1u] = 0u;  // the next call's word
+        const uint32_t call = f.state->call_no[f.hint_slot] + 1u;  // (FrameState::call_no: this launch's number, and the next launch's word)
+        f.state->call_no[f.hint_slot ^ 1u] = call;
+        if (f.strays_record) __hip_atomic_store(&f.strays_record->started, call, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------
@@ -413,12 +457,14 @@ static hipError_t launch_fast_ppt(const LightingArgs& a, const CsmArgs& csm, con
     auto launch = [&](auto ppt_c) {
         constexpr int P = decltype(ppt_c)::value;
         // (f.sky_first sky workgroups lead the grid: api.cpp)
-        if (sky.enabled) hipLaunchKernelGGL((k_lighting_fast<SUN, GI, P, true>), dim3(f.sky_first + blocks), block, 0, st, a, csm, lpv, sky, f);
+        if (sky.enabled && f.strays_inline) hipLaunchKernelGGL((k_lighting_fast<SUN, GI, P, true, true>), dim3(f.sky_first + blocks), block, 0, st, a, csm, lpv, sky, f);
+        else if (sky.enabled) hipLaunchKernelGGL((k_lighting_fast<SUN, GI, P, true>), dim3(f.sky_first + blocks), block, 0, st, a, csm, lpv, sky, f);
         else hipLaunchKernelGGL((k_lighting_fast<SUN, GI, P, false>), dim3(blocks), block, 0, st, a, csm, lpv, sky, f);
     };
     if (ppt == 4) launch(std::integral_constant<int, 4>{});
     else if (ppt == 2) launch(std::integral_constant<int, 2>{});
     else launch(std::integral_constant<int, 1>{});
+    if (f.strays_inline && strays_inline_body(sky.enabled != 0u)) return hipGetLastError();  // the fast kernel has finished its own strays (api.cpp: lighting_strays)
     // (a grid-stride loop over the groups of segments)
     const uint32_t fgroups = (f.num_segments + kFixupSegs - 1) / kFixupSegs;
     const dim3 fgrid(fgroups < kFixupMaxWorkgroups ? fgroups : kFixupMaxWorkgroups);
@@ -439,6 +485,8 @@ static hipError_t launch_gi(const LightingArgs& a, const CsmArgs& csm, const Lpv
         default: return hipErrorNotSupported;
     }
 }
+
+bool lighting_fast_finishes_strays(bool sky_bound) { return strays_inline_body(sky_bound); }
 
 hipError_t launch_colx_table(const LightingArgs& a, const FastArgs& f, float* out, uint32_t stride, uint32_t row_stride, hipStream_t st) {
     const hipError_t me = hipMemsetAsync(&f.state->colx_neg_zero, 0, sizeof(uint32_t), st);  // the new table's verdict starts at "no -0"

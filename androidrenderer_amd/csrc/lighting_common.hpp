@@ -565,7 +565,8 @@ SAH_DEV uint2 pack_lit(const Hn (&lit)[4]) {
 }
 
 // ---- a0: per-pixel composition, general restatement ---------------------------------------------------------
-template <int SUN, int GI>
+// (SKY_FILL false: the caller knows that no pixel it brings is sky under a bound sky — the fast kernel finishing its own strays, lighting.hip)
+template <int SUN, int GI, bool SKY_FILL = true>
 SAH_DEV uint2 shade_pixel_general(const LightingArgs& a, const CsmArgs& csm, const LpvArgs& lpv, const SkyArgs& sky, uint32_t x, uint32_t y,
                                   const Px& p, const float* lut) {
     Hn lit[4] = {Hn::lit(0.f), Hn::lit(0.f), Hn::lit(0.f), Hn::lit(0.f)};
@@ -602,7 +603,7 @@ SAH_DEV uint2 shade_pixel_general(const LightingArgs& a, const CsmArgs& csm, con
         lit[2] = Hn(tof(lit[2]) + (Fn(lut[(p.emission >> 16) & 0xffu]) * e).v);
         lit[3] = Hn(tof(lit[3]) + 1.0f);
     }
-    if (sky.enabled && !surface) sky_frag(a, sky, x, y, lit);
+    if (SKY_FILL && sky.enabled && !surface) sky_frag(a, sky, x, y, lit);
     if constexpr (SUN == SAH_SHADOW_MODE_RT) {
         if (surface) {
             float add[3];

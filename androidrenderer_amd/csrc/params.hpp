@@ -95,6 +95,20 @@ struct FrameState {
     // memset) and raised where the table is rebuilt, read by the Lighting kernels that may share one reciprocal among the position divides
     // (FastArgs::pos_div_shared); a table that is kept over several Lighting calls keeps its verdict.
     uint32_t colx_neg_zero;
+    // How many fast Lighting launches the context has run, for StraysRecord below.  Two words, taken in turn like deferred_hint (and by the same
+    // FastArgs::hint_slot): word s holds the number of launches before the one that uses s; that launch's number is the word + 1, the same for every
+    // wave of it, since nobody writes its word while it runs — one of its threads stores that number into the OTHER word, for the next launch.  In
+    // memory, not in a kernel argument, for the reason given at `nonfinite`.  A captured launch replayed by itself keeps its slot and its number.
+    uint32_t call_no[2];
+};
+
+// What the fast kernel tells the host about its strays (ctx_cache.hpp: SahStraysRecord): host memory the device writes with plain system-scope
+// stores, which the launcher reads without waiting for anything.  `started`: the number (FrameState::call_no) of the newest launch that has begun;
+// `listed`: the number of the newest launch in which a wave listed a pixel — stored by one thread of the fix-up launch that found the hint word
+// raised, or, where no fix-up launch follows, by the listing waves themselves.  Never a condition of correctness — a prediction of what the next
+// launch will list — so a value that is a launch late does no harm.
+struct StraysRecord {
+    uint32_t started, listed;
 };
 
 // What the fast kernel may assume, established by the host (api.cpp: detect_fast_path):
@@ -124,6 +138,10 @@ struct FastArgs {
     uint16_t* seg_count;
     uint32_t num_segments, seg_stride;
     uint32_t hint_slot;  // which word of FrameState::deferred_hint this call uses (0 / 1, alternating per Lighting call of the context)
+    // 1: no fix-up launch follows — a wave of the fast kernel that lists pixels shades them itself, with the general restatement, before it ends
+    // (lighting.hip; the launcher's rule: ctx_cache.hpp, SahStraysRecord).  The image is the same bytes either way.
+    uint32_t strays_inline;
+    StraysRecord* strays_record;  // host memory (or null: the context has none): see StraysRecord
     // the shared-reciprocal divide with zeros of EITHER sign in inverse_projection[10], [12], [13]: holds where pos_div_nr's bounds do, the numerators
     // come from the table (colx_tab, state valid) and FrameState::colx_neg_zero is clear (DESIGN.md "Fast path proofs")
     uint32_t pos_div_shared;

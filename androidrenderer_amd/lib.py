@@ -203,7 +203,7 @@ def load():
     lib.sah_chain_destroy.argtypes = [C.c_void_p]
     lib.sah_debug_chain_graphs.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.sah_chain_destroy.restype = None
-    lib.sah_debug_set.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.sah_debug_set.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     lib.sah_lpv_inject_rsm_gv.argtypes = [C.c_void_p, C.POINTER(_abi.RsmTargets), C.POINTER(_abi.LpvCascadeMatrices), C.c_uint32, C.c_uint32, C.c_uint32,
                                           C.POINTER(_abi.Volume)]
     lib.sah_lpv_inject_scene_gv.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.POINTER(_abi.ViewData),
@@ -255,9 +255,15 @@ class Context:
     def set_stream(self, hip_stream_handle):
         self._check(self.lib.sah_set_stream(self.handle, C.c_void_p(hip_stream_handle)))
 
-    def debug_set(self, force_general=False, force_ppt=0):
-        """Testing hook: run the general kernel instead of the fast one / force pixels-per-thread."""
-        self._check(self.lib.sah_debug_set(self.handle, int(force_general), int(force_ppt)))
+    STRAYS_MODES = {"auto": _abi.DEBUG_STRAYS_AUTO, "launch": _abi.DEBUG_STRAYS_LAUNCH, "inline": _abi.DEBUG_STRAYS_INLINE}
+
+    def debug_set(self, force_general=False, force_ppt=0, strays="auto"):
+        """Testing hook: run the general kernel instead of the fast one / force pixels-per-thread / say how the fast kernel's strays (the
+        pixels it lists for the general restatement) are finished: "auto" by the context's record of recent calls, "launch" always by the
+        fix-up launch, "inline" always by the fast kernel itself where its body can (one with a sky bound)."""
+        if strays not in self.STRAYS_MODES:
+            raise ValueError(f"strays must be one of {tuple(self.STRAYS_MODES)}, not {strays!r}")
+        self._check(self.lib.sah_debug_set(self.handle, int(force_general), int(force_ppt), self.STRAYS_MODES[strays]))
 
     def deferred_pixels(self):
         """Analysis hook: pixels the last fast-path lighting call handed to the fix-up kernel (synchronises)."""
@@ -279,18 +285,21 @@ class Context:
         return int(e.value)
 
     DISPATCH_FIELDS = ("family", "ppt", "pos_div_nr", "ncasc_pow2", "row_magic", "sky_ratio", "sky_workgroups", "tiled_fast_geom", "tiled_fast_lpv",
-                       "repack", "table_rebuilt", "pos_div_shared")
+                       "repack", "table_rebuilt", "pos_div_shared", "strays")
 
     def lighting_dispatch(self):
         """Test hook: what the last lighting() call of this context decided, as a dict — family ('general' / 'fast' / 'tiled'), ppt, pos_div_nr,
         ncasc_pow2, row_magic (1: the multiply-high row split), sky_ratio, sky_workgroups (leading the grid), tiled_fast_geom, tiled_fast_lpv,
         repack, table_rebuilt, pos_div_shared (1: the position divides shared one reciprocal through the condition for zeros of either sign in the
         inverse projection; 0 where pos_div_nr is 1).  Recorded on the host: no device work, no synchronisation — except for pos_div_shared where
-        the host's half of its condition held: the kernel decides from a word the table's build leaves on the device, which is then fetched."""
+        the host's half of its condition held: the kernel decides from a word the table's build leaves on the device, which is then fetched.
+        strays: how the fast kernel's listed pixels were finished — 'launch' (the fix-up launch followed), 'inline' (the fast kernel shaded them
+        itself: one launch), None where the fast kernel did not run."""
         out = (C.c_uint32 * len(self.DISPATCH_FIELDS))()
         self._check(self.lib.sah_debug_lighting_dispatch(self.handle, out))
         rep = {k: int(v) for k, v in zip(self.DISPATCH_FIELDS, out)}
         rep["family"] = ("general", "fast", "tiled")[rep["family"]]
+        rep["strays"] = (None, "launch", "inline")[rep["strays"]]
         return rep
 
     def sync(self):
