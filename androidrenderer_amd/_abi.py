@@ -85,6 +85,19 @@ class ExposureState(C.Structure):  # sah_exposure_state: 16 bytes of device memo
     _fields_ = [("exposure", C.c_float), ("adapted", C.c_float), ("metered", C.c_uint32), ("window", C.c_uint32)]
 
 
+SHARPEN_DENOISE = 1  # SAH_SHARPEN_DENOISE (include/sah_sharpen.h)
+
+
+class SharpenParams(C.Structure):  # sah_sharpen_params (include/sah_sharpen.h): 12 bytes
+    _fields_ = [("sharpness", C.c_float), ("pre_scale", C.c_float), ("flags", C.c_uint32)]
+
+    @classmethod
+    def default(cls, **settings):
+        values = dict(sharpness=1.0, pre_scale=1.0, flags=0)
+        values.update(settings)
+        return cls(**values)
+
+
 RT_DENOISE_HISTORY_INVALID = 1  # SAH_RT_DENOISE_HISTORY_INVALID
 
 

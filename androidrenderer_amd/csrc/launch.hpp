@@ -9,6 +9,7 @@
 #include "../../include/sah_mip_chain.h"
 #include "../../include/sah_rt_denoise.h"
 #include "../../include/sah_rtgi_denoise.h"
+#include "../../include/sah_sharpen.h"
 #include "../../include/sah_ssao.h"
 #include "../../include/sah_taa.h"
 #include "../../include/sah_taa_upscale.h"
@@ -98,6 +99,17 @@ struct ExposureArgs {
 };
 hipError_t launch_exposure_meter(const ExposureArgs& a, bool apply, uint32_t max_workgroups, hipStream_t st);
 hipError_t launch_exposure_apply(const ExposureArgs& a, hipStream_t st);
+
+// --- sharpen.hip
+struct SharpenArgs {
+    PlaneArg scene, out;
+    uint32_t W, H;
+    uint32_t row_begin, row_end;         // rows of `out`
+    uint32_t tiles_x;                    // set by the launcher
+    const sah_exposure_state* exposure;  // device; null: k = pre_scale
+    float sharpness, pre_scale;
+};
+hipError_t launch_sharpen(const SharpenArgs& a, bool denoise, hipStream_t st);
 
 // --- rt_denoise.hip
 struct RtDenoiseArgs {

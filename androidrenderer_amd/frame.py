@@ -366,6 +366,28 @@ class AutoExposure:
         return self.exposed
 
 
+class Sharpener:
+    """Contrast-adaptive sharpening (include/sah_sharpen.h) behind the upscale: owns the sharpened plane, which is re-created when a scene of
+    another extent arrives.  `settings` are fields of _abi.SharpenParams."""
+
+    def __init__(self, ctx, width, height, device="cuda", **settings):
+        import torch
+        self.ctx, self.width, self.height = ctx, width, height
+        self.params = _abi.SharpenParams.default(**settings)
+        self.sharpened = torch.zeros((height, width, 4), dtype=torch.int16, device=device)
+
+    def sharpen(self, scene, exposure_state=None, rows=(0, 0)):
+        """scene (H, W, 4) int16 device array; exposure_state the data_ptr() of a 16-byte exposure state (AutoExposure's), or None.  Returns
+        the sharpened plane, (H, W, 4) int16: the same array every call while the extent stays."""
+        if tuple(scene.shape[:2]) != (self.height, self.width):
+            import torch
+            self.height, self.width = int(scene.shape[0]), int(scene.shape[1])
+            self.sharpened = torch.zeros((self.height, self.width, 4), dtype=torch.int16, device=self.sharpened.device)
+        self.ctx.sharpen(images.plane(scene, _abi.FORMAT_R16G16B16A16_SFLOAT), exposure_state, images.plane(self.sharpened, _abi.FORMAT_R16G16B16A16_SFLOAT),
+                         self.params, rows)
+        return self.sharpened
+
+
 class RayTracedDenoiser:
     """The temporal and edge-aware filter for a one-channel ray-traced plane (include/sah_rt_denoise.h) over successive frames of one
     extent: owns the two ping-ponged accumulation / sample-count pairs — this frame's accum_out and length_out are the next frame's history

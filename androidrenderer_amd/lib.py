@@ -61,6 +61,9 @@ EXPOSURE_EXPORTS = ["sah_exposure_meter", "sah_exposure_apply"]
 EXPOSURE_WORK_BYTES = 1040    # SAH_EXPOSURE_WORK_BYTES
 EXPOSURE_BINS = 256           # SAH_EXPOSURE_BINS
 
+# contrast-adaptive sharpening: exported, declared in include/sah_sharpen.h (not sah_hip.h)
+SHARPEN_EXPORTS = ["sah_sharpen"]
+
 # the mip-chain generator: exported, declared in include/sah_mip_chain.h (not sah_hip.h)
 MIP_CHAIN_EXPORTS = ["sah_mip_chain_generate"]
 MIP_CHAIN_MAX_LEVELS = 12     # SAH_MIP_CHAIN_MAX_LEVELS
@@ -225,6 +228,7 @@ def load():
     lib.sah_rtgi_denoise.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData), C.POINTER(_abi.RtgiDenoiseDesc), C.POINTER(_abi.RtgiDenoiseParams), C.c_uint32, C.c_uint32]
     lib.sah_exposure_meter.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.ExposureParams)]
     lib.sah_exposure_apply.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
+    lib.sah_sharpen.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.SharpenParams), C.c_uint32, C.c_uint32]
     lib.sah_mip_chain_generate.argtypes =[C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32]
     lib.sah_rt_refit.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.c_void_p]
     _lib = lib
@@ -468,6 +472,12 @@ class Context:
         """sah_exposure_apply: out.rgb = scene.rgb * state->exposure; state a device address; out may be the plane `scene` itself.  rows
         (begin, end) of `out`, (0, 0) = all."""
         self._check(self.lib.sah_exposure_apply(self.handle, C.byref(scene), C.c_void_p(state), C.byref(out), rows[0], rows[1]))
+
+    def sharpen(self, scene, exposure_state, out, params, rows=(0, 0)):
+        """sah_sharpen (include/sah_sharpen.h): scene and out R16G16B16A16_SFLOAT _abi.Plane of device memory, one extent, not overlapping;
+        exposure_state the device address of a 16-byte exposure state, or None; params an _abi.SharpenParams.  rows (begin, end) of `out`,
+        (0, 0) = all."""
+        self._check(self.lib.sah_sharpen(self.handle, C.byref(scene), C.c_void_p(exposure_state), C.byref(out), C.byref(params), rows[0], rows[1]))
 
     def vrsaa_shading_rate_image(self, contrast, sri, params):
         """sah_vrsaa_shading_rate_image: contrast R16G16_SFLOAT, sri R8_UINT (_abi.Plane of device memory), params an _abi.ShadingRateParams

@@ -37,6 +37,7 @@
 #include "sah_rt_denoise.h"
 #include "sah_rt_refit.h"
 #include "sah_rtgi_denoise.h"
+#include "sah_sharpen.h"
 #include "sah_ssao.h"
 #include "sah_taa.h"
 #include "sah_taa_upscale.h"
@@ -1572,6 +1573,50 @@ private:
     TextureHandle exposed = nullptr, buffers = nullptr;
     uint32_t current = 0;
     bool history_valid = false;
+};
+
+// ---- Sharpener (include/sah_sharpen.h; builder-owned: the sharpening half of the reference's vendor upscaler) -----------------------------
+// The settings of sah_sharpen_params with the header's defaults.  The vendor pass counts its strength in stops below full: from_stops(0)
+// is the full lobe, every stop halves it.
+struct SharpenSettings {
+    float sharpness = 1.0f, pre_scale = 1.0f;
+    bool denoise = false;
+    static float from_stops(float stops) {  // exp2(-stops), clamped into [0, 1]
+        const float s = std::exp2(-stops);
+        return s > 0.0f ? (s < 1.0f ? s : 1.0f) : 0.0f;
+    }
+};
+// Contrast-adaptive sharpening behind the upscaler (or TAA), ahead of AutoExposure and Bloomer::fill_bloom_tex.  Owns the sharpened texture,
+// (re-)created when the scene's extent changes.  sharpen records the pass ("Sharpen") and returns the sharpened texture; `exposure` is a
+// device state (AutoExposure::get_state(): what the LAST frame metered, when this is recorded ahead of AutoExposure::expose) or null.
+// Off unless a caller constructs one and calls it: no existing phase uses it.
+class Sharpener {
+public:
+    SharpenSettings settings;
+    explicit Sharpener(ResourceAllocator& allocator_in) : allocator(allocator_in) {}
+    TextureHandle get_sharpened() const { return sharpened; }
+    TextureHandle sharpen(RenderGraph& graph, TextureHandle scene, const sah_exposure_state* exposure = nullptr) {
+        if (!scene) {
+            graph.add_pass(hip_pass("Sharpen", [](sah_ctx*) { return (int)SAH_ERR_INVALID_ARGUMENT; }));
+            return nullptr;
+        }
+        const uint32_t w = scene->desc.width, h = scene->desc.height;
+        if (!sharpened || sharpened->desc.width != w || sharpened->desc.height != h)
+            sharpened = allocator.create_texture("Sharpened scene", SAH_FORMAT_R16G16B16A16_SFLOAT, w, h);
+        TextureHandle target = sharpened;
+        const SharpenSettings s = settings;
+        graph.add_pass(hip_pass("Sharpen", [=](sah_ctx* ctx) {
+                            sah_sharpen_params p{};
+                            p.sharpness = s.sharpness, p.pre_scale = s.pre_scale, p.flags = s.denoise ? SAH_SHARPEN_DENOISE : 0u;
+                            const sah_plane sc = scene->plane(), o = target->plane();
+                            return sah_sharpen(ctx, &sc, exposure, &o, &p, 0, 0);
+                        }));
+        return sharpened;
+    }
+
+private:
+    ResourceAllocator& allocator;
+    TextureHandle sharpened = nullptr;
 };
 
 // ---- LightingPhase (RenderCore/render/phase/lighting_phase.hpp:17-57, .cpp:34-134) -------------------------------------
