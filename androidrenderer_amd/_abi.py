@@ -300,6 +300,11 @@ class LightingDesc(C.Structure):
                 ("sky", C.POINTER(SkyLuts)), ("flags", C.c_uint32), ("row_begin", C.c_uint32), ("row_end", C.c_uint32)]
 
 
+class LightingVrsDesc(C.Structure):  # sah_lighting_vrs_desc (include/sah_vrs.h)
+    _fields_ = [("lighting", C.POINTER(LightingDesc)), ("shading_rate_image", C.POINTER(Plane)), ("texel_size", C.c_uint32 * 2),
+                ("depth_tolerance", C.c_float)]
+
+
 class ChainPlan(C.Structure):  # sah_chain_plan
     _fields_ = [("aa_rows", C.c_uint32 * 2), ("mip0_rows", C.c_uint32 * 2), ("mip1_rows", C.c_uint32 * 2), ("out_rows", C.c_uint32 * 2),
                 ("mip1_rows_per_rank", C.c_uint32), ("mip1_allocated_rows", C.c_uint32), ("rows_per_rank", C.c_uint32),

@@ -17,6 +17,7 @@
 #include "ctx.hpp"
 #include "fast_pixel_map.hpp"
 #include "launch.hpp"
+#include "lighting_stages.hpp"
 
 namespace {
 
@@ -64,12 +65,9 @@ enum DispatchField {
 };
 static_assert(kDispFields == sizeof(sah_ctx::last_dispatch) / sizeof(uint32_t), "sah_debug_lighting_dispatch reports uint32_t[13]");
 
-// What the stages of one call share about it
-struct LightingCall {
-    uint32_t W, H, r0, r1;  // extent of lit, output rows [r0, r1)
-    uint32_t sun_mode, gi_kind;
-    bool vec4ok;  // width, addresses and pitches of every plane allow 16-byte accesses (four pixels per thread)
-};
+}  // namespace
+
+// (LightingCall, and the declarations of the four stages that sah_lighting_vrs shares: lighting_stages.hpp)
 
 // Targets and G-buffer: validation, the row range, the planes, the view and the sun constants
 int lighting_targets(sah_ctx* ctx, const sah_lighting_desc* d, LightingCall& call, LightingArgs& a) {
@@ -199,6 +197,8 @@ int lighting_gi_lpv(sah_ctx* ctx, const sah_lighting_desc* d, const LightingCall
     return SAH_OK;
 }
 
+namespace {
+
 // The context's fp32 copy of the irradiance atlas, which the hot form of the cache gather reads: grown, rebuilt by k_probe_irr_unpack unless the
 // caller's change counter says the copy of an earlier call stands, and handed to the kernel.  Without room for it hot_ok is cleared.
 int lighting_irr32_copy(sah_ctx* ctx, const sah_gi& gi, CacheArgs& cache) {
@@ -289,6 +289,8 @@ int lighting_gi_rtgi(sah_ctx* ctx, const sah_lighting_desc* d, const LightingCal
     return SAH_OK;
 }
 
+}  // namespace
+
 int lighting_sky(sah_ctx* ctx, const sah_lighting_desc* d, SkyArgs& sky) {
     memset(&sky, 0, sizeof(sky));
     if (!d->sky) return SAH_OK;
@@ -300,6 +302,8 @@ int lighting_sky(sah_ctx* ctx, const sah_lighting_desc* d, SkyArgs& sky) {
     if (!fill_sky_args(*d->sky, sun_dir, &sky)) return fail(ctx, SAH_ERR_UNSUPPORTED_FORMAT, "sky LUTs must be RGBA16F");
     return SAH_OK;
 }
+
+namespace {
 
 int lighting_ppt(const sah_ctx* ctx, const LightingCall& call) {
     const uint32_t W = call.W;

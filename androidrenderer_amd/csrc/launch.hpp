@@ -13,6 +13,7 @@
 #include "../../include/sah_ssao.h"
 #include "../../include/sah_taa.h"
 #include "../../include/sah_taa_upscale.h"
+#include "../../include/sah_vrs.h"
 #include "../../include/sah_vrsaa.h"
 #include "params.hpp"
 #include "post_args.hpp"
@@ -54,6 +55,17 @@ hipError_t launch_vrsaa_contrast(const PlaneArg& color, const PlaneArg& depth, c
                                  uint32_t row_end, const float* luts, hipStream_t st);
 hipError_t launch_vrsaa_shading_rate(const PlaneArg& contrast, uint32_t cw, uint32_t ch, const PlaneArg& out, uint32_t sw, uint32_t sh, uint32_t d,
                                      const sah_shading_rate_params& params, hipStream_t st);
+
+// --- lighting_vrs.hip, vrs_resolve.hip
+struct VrsArgs {
+    PlaneArg rate;                      // R8_UINT shading-rate image
+    uint32_t texel_shift[2];            // log2 of the texel size, per axis
+    float depth_tolerance;
+    uint32_t vec4;                      // the depth and lit planes allow 16-byte accesses and the width is a multiple of 4
+};
+hipError_t launch_lighting_vrs(const LightingArgs& a, const CsmArgs& csm, const LpvArgs& lpv, const SkyArgs& sky, const VrsArgs& v, int sun_mode, int gi,
+                               hipStream_t st);
+hipError_t launch_vrsaa_resolve(const PlaneArg& lit, const PlaneArg& out, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_end, hipStream_t st);
 
 // --- taa.hip
 struct TaaArgs {

@@ -388,6 +388,30 @@ class Sharpener:
         return self.sharpened
 
 
+class VrsaaFrame:
+    """The lighting half of the reference's own anti-aliasing mode (AntiAliasingType::VRSAA) for an output of width x height
+    (include/sah_vrs.h): Lighting at 2W x 2H at the rate the shading-rate image of rasterised_frame(vrsaa=...) asks for, then the resolve to
+    W x H.  Owns the two planes.  Off by default: nothing creates one but the caller that selects the mode."""
+
+    def __init__(self, ctx, width, height, texel_size, depth_tolerance=0.01, device="cuda"):
+        import torch
+        self.ctx, self.width, self.height = ctx, width, height
+        self.texel_size, self.depth_tolerance = tuple(texel_size), depth_tolerance
+        self.lit = torch.zeros((2 * height, 2 * width, 4), dtype=torch.int16, device=device)
+        self.antialiased = torch.zeros((height, width, 4), dtype=torch.int16, device=device)
+
+    def render(self, inputs, arrays, shading_rate_image):
+        """inputs: the LightingInputs of the 2W x 2H frame; arrays: its device arrays (inputs.device_arrays(), or the G-buffer the rasteriser
+        has just written with the side planes); shading_rate_image: the uint8 device array rasterised_frame(vrsaa=...) returns.  Returns
+        antialiased, (H, W, 4) int16: the same array every call."""
+        if (inputs.width, inputs.height) != (2 * self.width, 2 * self.height):
+            raise ValueError(f"the frame is {inputs.width} x {inputs.height}, not twice {self.width} x {self.height}")
+        desc, keep = inputs.describe(arrays, self.lit)
+        self.ctx.lighting_vrs(desc, images.plane(shading_rate_image, _abi.FORMAT_R8_UINT), self.texel_size, self.depth_tolerance)
+        self.ctx.vrsaa_resolve(images.plane(self.lit, _abi.FORMAT_R16G16B16A16_SFLOAT), images.plane(self.antialiased, _abi.FORMAT_R16G16B16A16_SFLOAT))
+        return self.antialiased
+
+
 class RayTracedDenoiser:
     """The temporal and edge-aware filter for a one-channel ray-traced plane (include/sah_rt_denoise.h) over successive frames of one
     extent: owns the two ping-ponged accumulation / sample-count pairs — this frame's accum_out and length_out are the next frame's history

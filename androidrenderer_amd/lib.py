@@ -64,6 +64,9 @@ EXPOSURE_BINS = 256           # SAH_EXPOSURE_BINS
 # contrast-adaptive sharpening: exported, declared in include/sah_sharpen.h (not sah_hip.h)
 SHARPEN_EXPORTS = ["sah_sharpen"]
 
+# variable-rate lighting and the VRSAA resolve: exported, declared in include/sah_vrs.h (not sah_hip.h)
+VRS_EXPORTS = ["sah_lighting_vrs", "sah_vrsaa_resolve"]
+
 # the mip-chain generator: exported, declared in include/sah_mip_chain.h (not sah_hip.h)
 MIP_CHAIN_EXPORTS = ["sah_mip_chain_generate"]
 MIP_CHAIN_MAX_LEVELS = 12     # SAH_MIP_CHAIN_MAX_LEVELS
@@ -229,6 +232,8 @@ def load():
     lib.sah_exposure_meter.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.ExposureParams)]
     lib.sah_exposure_apply.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
     lib.sah_sharpen.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.SharpenParams), C.c_uint32, C.c_uint32]
+    lib.sah_lighting_vrs.argtypes = [C.c_void_p, C.POINTER(_abi.LightingVrsDesc)]
+    lib.sah_vrsaa_resolve.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
     lib.sah_mip_chain_generate.argtypes =[C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32]
     lib.sah_rt_refit.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.c_void_p]
     _lib = lib
@@ -478,6 +483,18 @@ class Context:
         exposure_state the device address of a 16-byte exposure state, or None; params an _abi.SharpenParams.  rows (begin, end) of `out`,
         (0, 0) = all."""
         self._check(self.lib.sah_sharpen(self.handle, C.byref(scene), C.c_void_p(exposure_state), C.byref(out), C.byref(params), rows[0], rows[1]))
+
+    def lighting_vrs(self, desc, sri, texel_size, depth_tolerance):
+        """sah_lighting_vrs (include/sah_vrs.h): desc the _abi.LightingDesc lighting() takes, sri the R8_UINT shading-rate image (_abi.Plane of
+        device memory), texel_size (x, y) pixels of `lit` per texel of it, depth_tolerance the relative depth difference up to which a pixel
+        takes its coarse pixel's representative.  Every pixel gets the bytes lighting(desc) writes at its source pixel."""
+        v = _abi.LightingVrsDesc(C.pointer(desc), C.pointer(sri), (C.c_uint32 * 2)(int(texel_size[0]), int(texel_size[1])), float(depth_tolerance))
+        self._check(self.lib.sah_lighting_vrs(self.handle, C.byref(v)))
+
+    def vrsaa_resolve(self, lit, out, rows=(0, 0)):
+        """sah_vrsaa_resolve (include/sah_vrs.h): lit 2W x 2H, out W x H, R16G16B16A16_SFLOAT _abi.Plane of device memory; rows (begin, end) of
+        `out`, (0, 0) = all."""
+        self._check(self.lib.sah_vrsaa_resolve(self.handle, C.byref(lit), C.byref(out), rows[0], rows[1]))
 
     def vrsaa_shading_rate_image(self, contrast, sri, params):
         """sah_vrsaa_shading_rate_image: contrast R16G16_SFLOAT, sri R8_UINT (_abi.Plane of device memory), params an _abi.ShadingRateParams

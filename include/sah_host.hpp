@@ -38,6 +38,7 @@
 #include "sah_rt_refit.h"
 #include "sah_rtgi_denoise.h"
 #include "sah_sharpen.h"
+#include "sah_vrs.h"
 #include "sah_ssao.h"
 #include "sah_taa.h"
 #include "sah_taa_upscale.h"
@@ -233,6 +234,11 @@ public:
         const sah_sun_light_constants* sun = nullptr;
         bool has_ao = false, has_mask = false, has_shadowmap = false, has_gi = false, has_sky = false;
         uint32_t flags = SAH_LIGHTING_DEFAULT_FLAGS;
+        // LightingPhase::set_variable_rate_shading with a shading-rate image passed to render(): the pass goes through sah_lighting_vrs
+        bool variable_rate = false;
+        sah_plane shading_rate_image{};
+        uint32_t shading_rate_texel_size[2] = {0, 0};
+        float depth_tolerance = 0.0f;
     } lighting;
     void submit_lighting() {
         if (!lighting.open) return;
@@ -247,7 +253,18 @@ public:
         if (lighting.has_gi) d.gi = &lighting.gi;
         if (lighting.has_sky) d.sky = &lighting.sky;
         d.flags = lighting.flags;
-        check(sah_lighting(ctx, &d), "Lighting");
+        // (what sah_lighting_vrs supports, include/sah_vrs.h: GI none or LPV — this recording never carries a light list; another kind is shaded at full rate)
+        const uint32_t gi_kind = lighting.has_gi ? lighting.gi.kind : (uint32_t)SAH_GI_NONE;
+        if (lighting.variable_rate && (gi_kind == SAH_GI_NONE || gi_kind == SAH_GI_LPV)) {
+            sah_lighting_vrs_desc v{};
+            v.lighting = &d;
+            v.shading_rate_image = &lighting.shading_rate_image;
+            v.texel_size[0] = lighting.shading_rate_texel_size[0], v.texel_size[1] = lighting.shading_rate_texel_size[1];
+            v.depth_tolerance = lighting.depth_tolerance;
+            check(sah_lighting_vrs(ctx, &v), "Lighting (variable rate)");
+        } else {
+            check(sah_lighting(ctx, &d), "Lighting");
+        }
         lighting = LightingRecording{};
     }
 
@@ -1689,8 +1706,9 @@ inline void GbufferPhase::render(RenderGraph& graph, const RenderScene& scene, c
 // RenderCore/render/phase/sampling_rate_calculator.hpp / .cpp:11-175.  SceneRenderer makes one when AntiAliasingType::VRSAA is selected
 // (scene_renderer.cpp:142-154), calls generate_shading_rate_image before the G-buffer pass (:357-361: it reads the LAST frame's contrast
 // image) and measure_aliasing after lighting (:476-481).  Not instantiated by the default frame (AA = None).  The two backend queries of the
-// reference — get_max_shading_rate_texel_size() and get_shading_rates() — have setters here; set them before init().  Nothing in this
-// library consumes the shading-rate image (hardware VRS; LightingPhase::render ignores it as the reference's TODO does).
+// reference — get_max_shading_rate_texel_size() and get_shading_rates() — have setters here; set them before init().  The
+// shading-rate image is consumed by LightingPhase::render once set_variable_rate_shading() has been called (sah_lighting_vrs), and resolve()
+// is the step from the 2W x 2H frame to antialiased_scene that the reference leaves as a TODO (include/sah_vrs.h).
 class VRSAA {
 public:
     explicit VRSAA(ResourceAllocator& allocator_in) : allocator(allocator_in) {}
@@ -1730,8 +1748,17 @@ public:
                             return sah_vrsaa_measure_aliasing(ctx, &c, &d, &o, 0, 0);
                         }));
     }
+    // the "proper VRS resolve" (scene_renderer.cpp:479): lit 2W x 2H -> antialiased W x H, the mean of each 2 x 2 block (sah_vrsaa_resolve)
+    void resolve(RenderGraph& graph, TextureHandle lit_scene, TextureHandle antialiased_scene) const {
+        graph.add_pass(hip_pass("VRSAA resolve", [lit_scene, antialiased_scene](sah_ctx* ctx) {
+                            if (!lit_scene || !antialiased_scene) return (int)SAH_ERR_INVALID_ARGUMENT;
+                            const sah_plane l = lit_scene->plane(), a = antialiased_scene->plane();
+                            return sah_vrsaa_resolve(ctx, &l, &a, 0, 0);
+                        }));
+    }
     TextureHandle get_shading_rate_image() const { return shading_rate_image; }
     TextureHandle get_contrast_image() const { return contrast_image; }
+    std::array<uint32_t, 2> get_max_shading_rate_texel_size() const { return texel_size; }
 
 private:
     ResourceAllocator& allocator;
@@ -1787,13 +1814,24 @@ private:
 class LightingPhase {
 public:
     void set_scene(RenderScene& scene_in) { scene = &scene_in; }
+    // Off by default.  Once called, a render() that is passed a shading-rate image shades at the rate the image asks for (sah_lighting_vrs,
+    // include/sah_vrs.h: texel size in pixels of lit_scene per texel of the image, depth_tolerance the relative depth difference up to which a
+    // pixel takes its coarse pixel's value) wherever that entry supports the frame's GI; in every other case the pass is the full-rate one.
+    void set_variable_rate_shading(uint32_t texel_x, uint32_t texel_y, float depth_tolerance) {
+        variable_rate = true;
+        vrs_texel_size = {texel_x, texel_y};
+        vrs_depth_tolerance = depth_tolerance;
+    }
     // lighting_phase.hpp:33-43 / lighting_phase.cpp:34-134, same parameters.  The "Lighting" render pass clears lit_scene and runs, in
     // this order, the CSM-mode sun, the GI overlay, the emissive pass and the sky; the RT-mode sun follows as its own dispatch.  Each of
     // them records into the command buffer; the fused sah_lighting call (which keeps that order and its fp16 blend roundings) is
     // submitted at the end.
     void render(RenderGraph& render_graph, const SceneView& view, const GBuffer& gbuffer, TextureHandle lit_scene_texture, TextureHandle ao_texture,
                 const IGlobalIlluminator* gi, std::optional<TextureHandle> vrsaa_shading_rate_image, const NoiseTexture& noise, TextureHandle noise_2d) {
-        (void)vrsaa_shading_rate_image;  // VRSAA (sampling_rate_calculator.cpp) is AA plumbing outside the path: full rate
+        // (the reference's TODO, scene_renderer.cpp:479: without set_variable_rate_shading() the image is ignored — full rate)
+        const TextureHandle rate_image = (variable_rate && vrsaa_shading_rate_image.has_value()) ? *vrsaa_shading_rate_image : nullptr;
+        const std::array<uint32_t, 2> rate_texel = vrs_texel_size;
+        const float rate_tolerance = vrs_depth_tolerance;
         if (scene == nullptr) return;     // silent no-op, lighting_phase.cpp:47-49
         auto& sun = scene->get_sun_light();
         TextureUsageList texture_usages;
@@ -1806,10 +1844,16 @@ public:
         pass.textures = texture_usages;
         pass.buffers = buffer_usages;
         pass.color_attachments = {RenderingAttachmentInfo{lit_scene_texture, /*VK_ATTACHMENT_LOAD_OP_CLEAR*/ 1}};
-        pass.execute = [&, lit_scene_texture, ao_texture, gi, noise_2d](CommandBuffer& commands) {
+        pass.execute = [&, lit_scene_texture, ao_texture, gi, noise_2d, rate_image, rate_texel, rate_tolerance](CommandBuffer& commands) {
             auto& rec = commands.lighting;
             rec = CommandBuffer::LightingRecording{};
             rec.open = true;
+            if (rate_image) {
+                rec.variable_rate = true;
+                rec.shading_rate_image = rate_image->plane();
+                rec.shading_rate_texel_size[0] = rate_texel[0], rec.shading_rate_texel_size[1] = rate_texel[1];
+                rec.depth_tolerance = rate_tolerance;
+            }
             rec.gbuffer = sah_gbuffer{gbuffer.color->plane(), gbuffer.normals->plane(), gbuffer.data->plane(), gbuffer.emission->plane(), gbuffer.depth->plane()};
             rec.lit = lit_scene_texture->plane();
             rec.view = static_cast<const sah_view_data*>(view.get_buffer()->data);
@@ -1830,6 +1874,9 @@ public:
 private:
     void add_emissive_lighting(CommandBuffer&) const {}  // lighting_phase.cpp:176-186: the emission plane is part of the bound G-buffer; nothing else to bind
     RenderScene* scene = nullptr;
+    bool variable_rate = false;
+    std::array<uint32_t, 2> vrs_texel_size = {0, 0};
+    float vrs_depth_tolerance = 0.0f;
 };
 
 // ---- Bloomer (RenderCore/render/bloomer.hpp:15-17, .cpp:38-285) -----------------------------------------------------------

@@ -1,0 +1,257 @@
+"""CPU: the numpy restatement of include/sah_vrs.h (tests/lighting_vrs_ref.py) on hand-made cases, the header facts, the committed fixture,
+the refusals on a context without a device, and that the inputs of the GPU parity cases (tests/test_lighting_vrs_gpu.py) are not vacuous."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from androidrenderer_amd import _abi, lib
+from tests import lighting_vrs_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import gen_golden_vrs as gen  # noqa: E402
+
+f32 = np.float32
+
+
+def _identity(h, w):
+    return tuple(np.mgrid[0:h, 0:w])
+
+
+def _same(a, b):
+    return all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+# ---- the header ---------------------------------------------------------------------------------------------------------------------------
+def test_entries_are_declared_in_their_own_header_and_the_abi_version_stands():
+    L = lib.load()
+    assert all(hasattr(L, s) for s in lib.VRS_EXPORTS)
+    header = open(os.path.join(ROOT, "include", "sah_vrs.h")).read()
+    assert sorted(re.findall(r"^int (sah_\w+)\(", header, re.M)) == sorted(lib.VRS_EXPORTS) == ["sah_lighting_vrs", "sah_vrsaa_resolve"]
+    assert not set(lib.VRS_EXPORTS) & set(lib.EXPORTS)
+    main = open(os.path.join(ROOT, "include", "sah_hip.h")).read()
+    assert "sah_lighting_vrs" not in main and "sah_vrsaa_resolve" not in main and "sah_vrs.h" not in main
+    assert re.search(r"#define\s+SAH_ABI_VERSION\s+6\b", main) and L.sah_abi_version() == 6
+    assert header.count("ABI-defined") >= 8  # every rule the reference leaves open is marked
+
+
+@pytest.mark.parametrize("language", ["c", "c++"])
+def test_header_compiles_and_the_structure_matches(tmp_path, language):
+    src = tmp_path / ("use.c" if language == "c" else "use.cpp")
+    check = "_Static_assert" if language == "c" else "static_assert"
+    src.write_text('#include <stddef.h>\n#include "sah_vrs.h"\n'
+                   f'{check}(sizeof(sah_lighting_vrs_desc) == 32, "size");\n'
+                   f'{check}(offsetof(sah_lighting_vrs_desc, shading_rate_image) == 8, "sri");\n'
+                   f'{check}(offsetof(sah_lighting_vrs_desc, texel_size) == 16, "texel");\n'
+                   f'{check}(offsetof(sah_lighting_vrs_desc, depth_tolerance) == 24, "tol");\n'
+                   "int use(sah_ctx* c, const sah_lighting_vrs_desc* d, const sah_plane* p) {\n"
+                   "    return sah_lighting_vrs(c, d) + sah_vrsaa_resolve(c, p, p, 0, 0) + (int)SAH_FORMAT_R8_UINT; }\n")
+    clang = "/opt/rocm/llvm/bin/clang" if os.path.exists("/opt/rocm/llvm/bin/clang") else "cc"
+    subprocess.check_call([clang, "-x", language, "-std=c11" if language == "c" else "-std=c++17", "-Wall", "-Werror", "-fsyntax-only",
+                           "-I", os.path.join(ROOT, "include"), str(src)], timeout=120)
+    assert C.sizeof(_abi.LightingVrsDesc) == 32
+    assert [(n, getattr(_abi.LightingVrsDesc, n).offset) for n, _ in _abi.LightingVrsDesc._fields_] == [
+        ("lighting", 0), ("shading_rate_image", 8), ("texel_size", 16), ("depth_tolerance", 24)]
+
+
+# ---- the source map -----------------------------------------------------------------------------------------------------------------------
+def test_every_rate_code_on_a_small_plane():
+    """13 x 10 (cut on both edges), uniform depth, tol 0: every surface pixel takes the origin of its coarse pixel, whose extent follows from
+    the two fields alone"""
+    h, w = 10, 13
+    depth = np.full((h, w), 0.5, f32)
+    yy, xx = _identity(h, w)
+    seen = set()
+    for code in range(256):
+        lw, lh = min((code >> 2) & 3, 2), min(code & 3, 2)
+        assert ref.rate_of(code) == (lw, lh)
+        seen.add((lw, lh))
+        sy, sx = ref.source_map(depth, np.full((3, 4), code, np.uint8), (4, 4), 0.0)
+        assert np.array_equal(sy, yy & ~((1 << lh) - 1)) and np.array_equal(sx, xx & ~((1 << lw) - 1)), code
+    assert len(seen) == 9
+    assert {ref.rate_of(c) for c in ref.RATE_CODES.values()} == {(0, 0), (0, 1), (1, 0), (1, 1), (1, 2), (2, 1), (2, 2)}
+
+
+def test_rate_1x1_is_the_identity():
+    depth, _ = ref.parity_inputs(0)
+    for code in (0, 0xf0, 0x30):
+        assert _same(ref.source_map(depth, np.full((6, 10), code, np.uint8), (8, 8), float("inf")), _identity(*depth.shape))
+
+
+def test_the_rate_comes_from_the_pixels_texel():
+    depth = np.full((8, 16), 0.25, f32)
+    rates = np.array([[0, 10, 5, 0]], np.uint8)  # texels of 4 x 8
+    sy, sx = ref.source_map(depth, rates, (4, 8), 0.0)
+    yy, xx = _identity(8, 16)
+    assert np.array_equal(sx[:, 0:4], xx[:, 0:4]) and np.array_equal(sx[:, 12:], xx[:, 12:])
+    assert (sx[:, 4:8] == 4).all() and np.array_equal(sy[:, 4:8], yy[:, 4:8] & ~3)
+    assert np.array_equal(sx[:, 8:12], xx[:, 8:12] & ~1) and np.array_equal(sy[:, 8:12], yy[:, 8:12] & ~1)
+
+
+def test_tolerance_infinite_and_zero():
+    depth = np.array([[0.5, 0.5000001, 0.75, 0.5], [0.0, 0.5, 1e30, 1e-30], [0.5, 0.5, 0.5, 0.5], [0.5, 0.5, 0.5, 0.5]], f32)
+    rates = np.full((1, 1), 10, np.uint8)
+    sy, sx = ref.source_map(depth, rates, (4, 4), float("inf"))
+    surface = depth != 0
+    assert (sy[surface] == 0).all() and (sx[surface] == 0).all()  # every finite surface pixel shares
+    assert (sy[1, 0], sx[1, 0]) == (1, 0)                         # the sky pixel shades itself
+    sy, sx = ref.source_map(depth, rates, (4, 4), 0.0)
+    equal = depth == f32(0.5)
+    assert (sy[equal] == 0).all() and (sx[equal] == 0).all()      # |d - d| <= 0 * |d| holds for the equal ones
+    yy, xx = _identity(4, 4)
+    assert np.array_equal(sy[~equal], yy[~equal]) and np.array_equal(sx[~equal], xx[~equal])
+    sy, sx = ref.source_map(depth, rates, (4, 4), 0.5)            # 0.75 is exactly at the bound: |0.75 - 0.5| <= 0.5 * 0.5
+    assert (sy[0, 2], sx[0, 2]) == (0, 0) and (sy[1, 2], sx[1, 2]) == (1, 2)
+
+
+def test_nan_negative_zero_and_infinite_depths():
+    nan, inf = f32("nan"), f32("inf")
+    rates = np.full((1, 2), 5, np.uint8)
+    # NaN is a surface: it is the representative, nothing compares with it, every pixel shades itself
+    depth = np.array([[nan, 0.5], [0.5, nan]], f32)
+    assert _same(ref.source_map(depth, rates, (4, 4), inf), _identity(2, 2))
+    # -0 is not a surface: the representative is the pixel behind it
+    depth = np.array([[-0.0, 0.5], [0.5, 0.5]], f32)
+    sy, sx = ref.source_map(depth, rates, (4, 4), 0.0)
+    assert (sy.tolist(), sx.tolist()) == ([[0, 0], [0, 0]], [[0, 1], [1, 1]])
+    # an infinite representative: the bound is tol * inf — infinite, and every difference but inf - inf (NaN) is within it; NaN at tol 0
+    depth = np.array([[inf, inf], [0.5, -inf]], f32)
+    sy, sx = ref.source_map(depth, rates, (4, 4), inf)
+    assert (sy.tolist(), sx.tolist()) == ([[0, 0], [0, 0]], [[0, 1], [0, 0]])
+    assert _same(ref.source_map(depth, rates, (4, 4), 1.0), (sy, sx))
+    assert _same(ref.source_map(depth, rates, (4, 4), 0.0), _identity(2, 2))
+    # infinite pixels under a finite representative share at tol inf only
+    depth = np.array([[0.5, inf], [-inf, 0.5]], f32)
+    sy, sx = ref.source_map(depth, rates, (4, 4), inf)
+    assert (sy == 0).all() and (sx == 0).all()
+    sy, sx = ref.source_map(depth, rates, (4, 4), 1e30)
+    assert (sy.tolist(), sx.tolist()) == ([[0, 0], [1, 0]], [[0, 1], [0, 0]])
+
+
+def test_images_cut_mid_texel_and_mid_coarse_pixel():
+    """7 x 6 under one 8 x 8 texel of 4 x 4: the right boxes are 3 wide, the lower ones 2 high; a representative is never outside"""
+    depth = np.full((6, 7), 0.5, f32)
+    depth[4, 4] = 0.0  # the cut corner box: its first pixel is sky
+    sy, sx = ref.source_map(depth, np.full((1, 1), 10, np.uint8), (8, 8), 0.0)
+    assert sy.max() < 6 and sx.max() < 7
+    assert (sy[:4, :4] == 0).all() and (sx[:4, 4:] == 4).all() and (sy[4:, :4] == 4).all()
+    assert (sy[4, 5], sx[4, 5]) == (4, 5) and (sy[5, 6], sx[5, 6]) == (4, 5) and (sy[4, 4], sx[4, 4]) == (4, 4)
+
+
+# ---- the resolve --------------------------------------------------------------------------------------------------------------------------
+def _halfs(values):
+    return np.array(values, np.float16).view(np.uint16)
+
+
+def test_resolve_special_values():
+    def one(a, b, c, d):
+        lit = np.zeros((2, 2, 4), np.uint16)
+        lit[0, 0], lit[0, 1], lit[1, 0], lit[1, 1] = a, b, c, d
+        return int(ref.resolve(lit)[0, 0, 0])
+    assert one(0x7bff, 0x7bff, 0x7bff, 0x7bff) == 0x7bff           # 65504 + 65504 does not overflow in fp32
+    assert one(0x0001, 0x0001, 0x0001, 0x0001) == 0x0001           # subnormals are values
+    assert one(0x0001, 0, 0, 0) == 0 and one(0x0001, 0x0001, 0, 0) == 0 and one(0x0003, 0, 0, 0) == 0x0001  # 0.25 -> 0, 0.5 -> even, 0.75 -> 1
+    assert one(0x0003, 0x0001, 0x0001, 0x0001) == 0x0002           # 1.5: the tie goes to even
+    assert one(0x7c00, 0x3c00, 0, 0) == 0x7c00 and one(0xfc00, 0x7bff, 0, 0) == 0xfc00
+    assert one(0x7c00, 0xfc00, 0, 0) == 0x7e00                     # inf - inf: the canonical NaN
+    assert one(0xfe01, 0x3c00, 0x3c00, 0x3c00) == 0x7e00 and one(0x3c00, 0x3c00, 0x3c00, 0x7d55) == 0x7e00
+    assert one(0x7bff, 0xfbff, 0x3c00, 0x3c00) == 0x3800           # (a + b) + (c + d): 0 + 2
+    # the order of the sum shows in fp32: 2^10 + 2^-14 is a tie that goes to 2^10, 2^-14 - 2^10 is exact — (a + b) + (c + d) = 2^-14, a quarter
+    # of it 2^-16; ((a + b) + c) + d would be 0
+    assert _halfs([1024.0, 2.0 ** -14, -1024.0]).tolist() == [0x6400, 0x0400, 0xe400]
+    assert one(0x6400, 0x0400, 0x0400, 0xe400) == 0x0100
+
+
+def test_resolve_rows_and_channels():
+    lit = gen.resolve_input(5, 4, 3)
+    full = ref.resolve(lit)
+    assert full.shape == (4, 5, 4) and np.array_equal(ref.resolve(lit, (1, 3)), full[1:3])
+    swapped = lit[..., ::-1]
+    assert np.array_equal(ref.resolve(swapped), full[..., ::-1])  # per channel
+
+
+# ---- the fixture --------------------------------------------------------------------------------------------------------------------------
+def test_fixture_is_what_the_generator_makes():
+    fx = np.load(gen.FIXTURE)
+    data = gen.generate()
+    assert sorted(fx.files) == sorted(data)
+    for k in data:
+        assert np.asarray(data[k]).tobytes() == fx[k].tobytes(), k
+    assert fx["resolve_out"].shape == (gen.RESOLVE_EXTENT[1], gen.RESOLVE_EXTENT[0], 4)
+    out = fx["resolve_out"]
+    assert (out == 0x7e00).any() and (out == 0x7c00).any() and (out == 0x7bff).any() and ((out & 0x7c00) == 0).any()
+    assert os.path.getsize(gen.FIXTURE) < 1 << 20
+
+
+# ---- the GPU parity cases are not vacuous -------------------------------------------------------------------------------------------------
+def _classes(depth, rates, texel, tol):
+    """what the source map of a case exercises, from the restatement alone"""
+    h, w = depth.shape
+    sy, sx = ref.source_map(depth, rates, texel, tol)
+    yy, xx = _identity(h, w)
+    moved = (sy != yy) | (sx != xx)
+    surface = depth != 0
+    found = {"share": float(moved.mean()), "rates": set(), "field3": False, "high_bits": False}
+    keys = ("rep_not_first", "rejected", "sky_beside_rep", "no_surface", "cut_right", "cut_bottom")
+    found.update({k: 0 for k in keys})
+    for ty in range(-(-h // texel[1])):
+        for tx in range(-(-w // texel[0])):
+            code = int(rates[ty, tx])
+            lw, lh = ref.rate_of(code)
+            found["rates"].add((1 << lw, 1 << lh))
+            found["field3"] |= (code & 3) == 3 or ((code >> 2) & 3) == 3
+            found["high_bits"] |= code >= 16
+            for oy in range(ty * texel[1], min((ty + 1) * texel[1], h), 1 << lh):
+                for ox in range(tx * texel[0], min((tx + 1) * texel[0], w), 1 << lw):
+                    box = surface[oy:oy + (1 << lh), ox:ox + (1 << lw)]
+                    if lw and ox + (1 << lw) > w:
+                        found["cut_right"] += 1
+                    if lh and oy + (1 << lh) > h:
+                        found["cut_bottom"] += 1
+                    if not box.any():
+                        found["no_surface"] += box.size > 1
+                        continue
+                    first = int(np.argmax(box.reshape(-1)))
+                    ry, rx = oy + first // box.shape[1], ox + first % box.shape[1]
+                    found["rep_not_first"] += first != 0
+                    found["sky_beside_rep"] += int((~box).sum()) > 0
+                    bs, by, bx = (a[oy:oy + (1 << lh), ox:ox + (1 << lw)] for a in (surface, sy, sx))
+                    found["rejected"] += int((bs & ((by != ry) | (bx != rx))).sum())
+    return found
+
+
+def test_parity_cases_exercise_the_map():
+    total = None
+    for case, (w, h, texel) in enumerate(ref.PARITY_CASES):
+        depth, rates = ref.parity_inputs(case)
+        assert depth.shape == (h, w) and rates.shape == (-(-h // texel[1]), -(-w // texel[0]))
+        found = _classes(depth, rates, texel, ref.TOLERANCE)
+        assert found["share"] >= 0.30, (case, found["share"])
+        if total is None:
+            total = found
+        else:
+            for k, v in found.items():
+                total[k] = (total[k] | v) if isinstance(v, (set, bool)) else total[k] + v
+    assert ref.PARITY_CASES[:2] == [(75, 45, (8, 8)), (64, 36, (16, 16))] and ref.PARITY_CASES[2][2] == (4, 64)
+    for k in ("rep_not_first", "rejected", "sky_beside_rep", "no_surface", "cut_right", "cut_bottom"):
+        assert total[k] > 0, k
+    assert total["rates"] == {(1, 1), (1, 2), (2, 1), (2, 2), (2, 4), (4, 2), (4, 4)}
+    assert total["field3"] and total["high_bits"]
+
+
+# ---- refusals on a context without a device -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", [1, 2])
+def test_argument_fuzz_on_a_detached_context(seed):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "vrs_fuzz_child.py"), str(seed), "2000"], stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True, timeout=600)
+    tail = "\n".join(r.stdout.splitlines()[-10:])
+    if "SKIP:" in r.stdout:
+        pytest.skip(r.stdout.strip().splitlines()[-1])
+    assert r.returncode == 0, f"the fuzz child ended with code {r.returncode}:\n{tail}"
+    assert "OK: 2000 iterations" in r.stdout, tail
+    assert "SAH_OK" not in r.stdout  # (a detached context never launches)
