@@ -98,6 +98,21 @@ class SharpenParams(C.Structure):  # sah_sharpen_params (include/sah_sharpen.h):
         return cls(**values)
 
 
+SSR_JITTER, SSR_REFLECTION_ONLY = 1, 2  # SAH_SSR_* (include/sah_ssr.h)
+
+
+class SsrParams(C.Structure):  # sah_ssr_params (include/sah_ssr.h): 36 bytes; default() = the header's defaults
+    _fields_ = [("max_distance", C.c_float), ("thickness", C.c_float), ("stride_pixels", C.c_float), ("max_steps", C.c_uint32), ("refine_steps", C.c_uint32),
+                ("max_roughness", C.c_float), ("edge_fade", C.c_float), ("intensity", C.c_float), ("flags", C.c_uint32)]
+
+    @classmethod
+    def default(cls, **changes):
+        values = dict(max_distance=50.0, thickness=0.5, stride_pixels=4.0, max_steps=64, refine_steps=4, max_roughness=0.6, edge_fade=0.1, intensity=1.0,
+                      flags=0)
+        values.update(changes)
+        return cls(**values)
+
+
 RT_DENOISE_HISTORY_INVALID = 1  # SAH_RT_DENOISE_HISTORY_INVALID
 
 

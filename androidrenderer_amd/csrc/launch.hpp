@@ -11,6 +11,7 @@
 #include "../../include/sah_rtgi_denoise.h"
 #include "../../include/sah_sharpen.h"
 #include "../../include/sah_ssao.h"
+#include "../../include/sah_ssr.h"
 #include "../../include/sah_taa.h"
 #include "../../include/sah_taa_upscale.h"
 #include "../../include/sah_vrs.h"
@@ -96,6 +97,21 @@ struct SsaoArgs {
     float max_radius_pixels, threshold, shadow_multiplier, shadow_clamp, fade_to, fade_span, edge_sharpness;
 };
 hipError_t launch_ssao(const SsaoArgs& a, uint32_t blur_passes, hipStream_t st);
+
+// --- ssr.hip
+struct SsrArgs {
+    PlaneArg color, normals, data, depth, source, lit, out;
+    uint32_t W, H;
+    uint32_t row_begin, row_end;        // rows of `out`
+    uint32_t tiles_x;                   // set by the launcher
+    float m[9];                         // the 3 x 3 of view, column major: m[3 * column + row]
+    float p00, p11, p20, p21, ipx, ipy, tx, ty, hw, hh;  // 1 / P00, 1 / P11, 2 / W, 2 / H, 0.5 W, 0.5 H
+    float z_near;
+    float max_distance, thickness, stride, max_roughness, edge_fade, intensity;
+    uint32_t max_steps, refine_steps, flags;
+    const float* luts;                  // the context's 512 floats: sRGB -> linear, UNORM8 -> float
+};
+hipError_t launch_ssr(const SsrArgs& a, hipStream_t st);
 
 // --- exposure.hip
 struct ExposureArgs {

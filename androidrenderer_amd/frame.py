@@ -388,6 +388,38 @@ class Sharpener:
         return self.sharpened
 
 
+class ScreenSpaceReflections:
+    """Screen-space reflections (include/sah_ssr.h) between Lighting and the anti-aliasing: owns the plane with the reflections added and the
+    scratch plane of one float per 8 x 8 block (reserved by the header, not touched yet), both re-created when a frame of another extent arrives.  `settings` are fields of _abi.SsrParams.  Off
+    by default: nothing creates one but the caller that wants reflections."""
+
+    def __init__(self, ctx, width, height, device="cuda", **settings):
+        self.ctx, self.device = ctx, device
+        self.params = _abi.SsrParams.default(**settings)
+        self._allocate(width, height)
+
+    def _allocate(self, width, height):
+        import torch
+        self.width, self.height = width, height
+        self.out = torch.zeros((height, width, 4), dtype=torch.int16, device=self.device)
+        self.scratch = torch.zeros(((height + 7) // 8, (width + 7) // 8), dtype=torch.float32, device=self.device)
+
+    def __call__(self, view_data, gbuffer, lit, source=None, rows=(0, 0)):
+        """gbuffer a dict of device arrays with "color", "normals", "data" and "depth" (the G-buffer's); lit (H, W, 4) int16, the image the
+        reflections are added to; source the image they are taken from — lit itself unless given (last frame's output, say: not this
+        object's `out`, which the call writes).  Returns the plane with the reflections added, (H, W, 4) int16: the same array every call
+        while the extent stays."""
+        if tuple(lit.shape[:2]) != (self.height, self.width):
+            self._allocate(int(lit.shape[1]), int(lit.shape[0]))
+        rgba16 = _abi.FORMAT_R16G16B16A16_SFLOAT
+        lit_p = images.plane(lit, rgba16)
+        self.ctx.ssr(view_data, images.plane(gbuffer["color"], _abi.FORMAT_R8G8B8A8_SRGB), images.plane(gbuffer["normals"], rgba16),
+                     images.plane(gbuffer["data"], _abi.FORMAT_R8G8B8A8_UNORM), images.plane(gbuffer["depth"], _abi.FORMAT_D32_SFLOAT),
+                     lit_p if source is None else images.plane(source, rgba16), lit_p, images.plane(self.scratch, _abi.FORMAT_R32_SFLOAT),
+                     images.plane(self.out, rgba16), self.params, rows)
+        return self.out
+
+
 class VrsaaFrame:
     """The lighting half of the reference's own anti-aliasing mode (AntiAliasingType::VRSAA) for an output of width x height
     (include/sah_vrs.h): Lighting at 2W x 2H at the rate the shading-rate image of rasterised_frame(vrsaa=...) asks for, then the resolve to

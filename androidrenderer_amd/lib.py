@@ -64,6 +64,9 @@ EXPOSURE_BINS = 256           # SAH_EXPOSURE_BINS
 # contrast-adaptive sharpening: exported, declared in include/sah_sharpen.h (not sah_hip.h)
 SHARPEN_EXPORTS = ["sah_sharpen"]
 
+# screen-space reflections: exported, declared in include/sah_ssr.h (not sah_hip.h)
+SSR_EXPORTS = ["sah_ssr"]
+
 # variable-rate lighting and the VRSAA resolve: exported, declared in include/sah_vrs.h (not sah_hip.h)
 VRS_EXPORTS = ["sah_lighting_vrs", "sah_vrsaa_resolve"]
 
@@ -232,6 +235,7 @@ def load():
     lib.sah_exposure_meter.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.ExposureParams)]
     lib.sah_exposure_apply.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
     lib.sah_sharpen.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.SharpenParams), C.c_uint32, C.c_uint32]
+    lib.sah_ssr.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData)] + [C.POINTER(_abi.Plane)] * 8 + [C.POINTER(_abi.SsrParams), C.c_uint32, C.c_uint32]
     lib.sah_lighting_vrs.argtypes = [C.c_void_p, C.POINTER(_abi.LightingVrsDesc)]
     lib.sah_vrsaa_resolve.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
     lib.sah_mip_chain_generate.argtypes =[C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32]
@@ -483,6 +487,13 @@ class Context:
         exposure_state the device address of a 16-byte exposure state, or None; params an _abi.SharpenParams.  rows (begin, end) of `out`,
         (0, 0) = all."""
         self._check(self.lib.sah_sharpen(self.handle, C.byref(scene), C.c_void_p(exposure_state), C.byref(out), C.byref(params), rows[0], rows[1]))
+
+    def ssr(self, view_data, color, normals, data, depth, source, lit, scratch, out, params, rows=(0, 0)):
+        """sah_ssr (include/sah_ssr.h): color R8G8B8A8_SRGB, normals R16G16B16A16_SFLOAT, data R8G8B8A8_UNORM, depth D32_SFLOAT (the G-buffer's),
+        source, lit and out R16G16B16A16_SFLOAT, one extent W x H; scratch R32_SFLOAT, ceil(W / 8) x ceil(H / 8); _abi.Plane of device memory.
+        lit may be the plane `source`; out overlaps nothing.  params an _abi.SsrParams.  rows (begin, end) of `out`, (0, 0) = all."""
+        self._check(self.lib.sah_ssr(self.handle, C.byref(view_data), C.byref(color), C.byref(normals), C.byref(data), C.byref(depth), C.byref(source),
+                                     C.byref(lit), C.byref(scratch), C.byref(out), C.byref(params), rows[0], rows[1]))
 
     def lighting_vrs(self, desc, sri, texel_size, depth_tolerance):
         """sah_lighting_vrs (include/sah_vrs.h): desc the _abi.LightingDesc lighting() takes, sri the R8_UINT shading-rate image (_abi.Plane of

@@ -40,6 +40,7 @@
 #include "sah_sharpen.h"
 #include "sah_vrs.h"
 #include "sah_ssao.h"
+#include "sah_ssr.h"
 #include "sah_taa.h"
 #include "sah_taa_upscale.h"
 #include "sah_vrsaa.h"
@@ -1877,6 +1878,53 @@ private:
     bool variable_rate = false;
     std::array<uint32_t, 2> vrs_texel_size = {0, 0};
     float vrs_depth_tolerance = 0.0f;
+};
+
+// ---- ScreenSpaceReflections (include/sah_ssr.h; builder-owned: the reference has "Other postprocessing // TODO" here) ---------------------
+// The settings of sah_ssr_params with the header's defaults.
+struct SsrSettings {
+    float max_distance = SAH_SSR_DEFAULT_MAX_DISTANCE, thickness = SAH_SSR_DEFAULT_THICKNESS, stride_pixels = SAH_SSR_DEFAULT_STRIDE_PIXELS;
+    uint32_t max_steps = SAH_SSR_DEFAULT_MAX_STEPS, refine_steps = SAH_SSR_DEFAULT_REFINE_STEPS;
+    float max_roughness = SAH_SSR_DEFAULT_MAX_ROUGHNESS, edge_fade = SAH_SSR_DEFAULT_EDGE_FADE, intensity = SAH_SSR_DEFAULT_INTENSITY;
+    bool jitter = false, reflection_only = false;
+};
+// Screen-space reflections between LightingPhase::render and the anti-aliasing (TemporalAntiAliasing / TemporalUpscaling / VRSAA::resolve).
+// Owns the reflected texture and the scratch texture of one float per 8 x 8 block (reserved by the header), (re-)created when the lit scene's extent changes.  render records
+// the pass ("Screen-space reflections") and returns the reflected texture; `source` is the image the reflections are taken from — the lit
+// scene itself when null, or last frame's output.  Off unless a caller constructs one and calls it: no existing phase uses it.
+class ScreenSpaceReflections {
+public:
+    SsrSettings settings;
+    explicit ScreenSpaceReflections(ResourceAllocator& allocator_in) : allocator(allocator_in) {}
+    TextureHandle get_reflected() const { return reflected; }
+    TextureHandle render(RenderGraph& graph, const SceneView& view, const GBuffer& gbuffer, TextureHandle lit_scene, TextureHandle source = nullptr) {
+        if (!lit_scene || !gbuffer.color || !gbuffer.normals || !gbuffer.data || !gbuffer.depth) {
+            graph.add_pass(hip_pass("Screen-space reflections", [](sah_ctx*) { return (int)SAH_ERR_INVALID_ARGUMENT; }));
+            return nullptr;
+        }
+        const uint32_t w = lit_scene->desc.width, h = lit_scene->desc.height;
+        if (!reflected || reflected->desc.width != w || reflected->desc.height != h) {
+            reflected = allocator.create_texture("Reflected scene", SAH_FORMAT_R16G16B16A16_SFLOAT, w, h);
+            blocks = allocator.create_texture("SSR blocks", SAH_FORMAT_R32_SFLOAT, (w + 7) / 8, (h + 7) / 8);
+        }
+        TextureHandle target = reflected, scratch = blocks, from = source ? source : lit_scene;
+        const SsrSettings s = settings;
+        const GBuffer g = gbuffer;
+        graph.add_pass(hip_pass("Screen-space reflections", [=, &view](sah_ctx* ctx) {
+                            sah_ssr_params p{};
+                            p.max_distance = s.max_distance, p.thickness = s.thickness, p.stride_pixels = s.stride_pixels, p.max_steps = s.max_steps;
+                            p.refine_steps = s.refine_steps, p.max_roughness = s.max_roughness, p.edge_fade = s.edge_fade, p.intensity = s.intensity;
+                            p.flags = (s.jitter ? SAH_SSR_JITTER : 0u) | (s.reflection_only ? SAH_SSR_REFLECTION_ONLY : 0u);
+                            const sah_plane c = g.color->plane(), n = g.normals->plane(), d = g.data->plane(), z = g.depth->plane();
+                            const sah_plane src = from->plane(), l = lit_scene->plane(), sc = scratch->plane(), o = target->plane();
+                            return sah_ssr(ctx, &view.get_gpu_data(), &c, &n, &d, &z, &src, &l, &sc, &o, &p, 0, 0);
+                        }));
+        return reflected;
+    }
+
+private:
+    ResourceAllocator& allocator;
+    TextureHandle reflected = nullptr, blocks = nullptr;
 };
 
 // ---- Bloomer (RenderCore/render/bloomer.hpp:15-17, .cpp:38-285) -----------------------------------------------------------
