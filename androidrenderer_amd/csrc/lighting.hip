@@ -215,11 +215,51 @@ __global__ void __launch_bounds__(256) k_colx_table(const LightingArgs a, const 
 // Which bodies of the fast kernel have a twin that finishes its own strays (FINISH; FastArgs::strays_inline): the ones with a sky bound.  The
 // general restatement wants 135-207 VGPRs (k_lighting_fixup), and a kernel has one register count.  A SKY body is held at 128 by its launch
 // bound, so the finish — a region at the kernel's end, behind a wave-uniform vote, where nothing of the hot path is live — spills what it must,
-// where only a wave with strays goes, and the hot path keeps its registers and its occupancy.  A body without a sky has no bound: with the
+// where only a wave with strays goes, and the hot path keeps its registers and its occupancy; its uniforms it reads there too (FinishArgs below),
+// so that no FINISH body has a private segment or an SGPR spill (profiles/finish_late_kernel_resources.txt).  A body without a sky has no bound: with the
 // finish it would take the restatement's count and lose one to five waves per SIMD for every wave of every frame.  Those keep the fix-up launch.
 // A twin, not a branch of the one body: compiled into the body that runs in front of a fix-up launch, the finish moved that body's SGPR spills
 // and cost it 1.1-1.8 % in every launch, strays or none (profiles/strays_inline_ab.txt).  The body in front of a fix-up launch is the kernel it was.
 constexpr bool strays_inline_body(bool sky) { return sky; }
+
+// The finish's view of the fast kernel's five argument blocks.  The general restatement wants nearly every uniform of them (the general matrices
+// of the sun and the LPV among them); as kernel arguments they are loaded in the kernel's prologue, for every wave, and kept — spilled to lanes of a
+// VGPR — across the hot path that never uses them: 49 SGPR spills in the headline's FINISH body against its twin's 17, and stack slots that left
+// the kernel a private segment (36 bytes no instruction touched).  So the finish reads them where it uses them: from the kernarg segment, where
+// they lie anyway — no copy, nothing per launch on the host —, through a pointer the optimiser cannot identify with the arguments it has loaded (an
+// empty asm statement it cannot see through).  The loads stay scalar loads of the constant address space, and sit behind the listing vote.
+// The offsets are the kernel ABI's: explicit arguments in order, each at its natural alignment, from offset 0.
+struct FinishArgs {
+    const LightingArgs* a;
+    const CsmArgs* csm;
+    const LpvArgs* lpv;
+    const SkyArgs* sky;
+    const FastArgs* f;
+};
+constexpr uint32_t kernarg_align(uint32_t off, uint32_t align) { return (off + align - 1u) / align * align; }
+SAH_DEV FinishArgs finish_args_of_fast_kernel() {
+    constexpr uint32_t at_a = 0u;
+    constexpr uint32_t at_csm = kernarg_align(at_a + (uint32_t)sizeof(LightingArgs), alignof(CsmArgs));
+    constexpr uint32_t at_lpv = kernarg_align(at_csm + (uint32_t)sizeof(CsmArgs), alignof(LpvArgs));
+    constexpr uint32_t at_sky = kernarg_align(at_lpv + (uint32_t)sizeof(LpvArgs), alignof(SkyArgs));
+    constexpr uint32_t at_f = kernarg_align(at_sky + (uint32_t)sizeof(SkyArgs), alignof(FastArgs));
+    typedef const __attribute__((address_space(4))) uint8_t* kernarg_ptr;
+    kernarg_ptr k = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    FinishArgs r;
+    r.a = (const LightingArgs*)(k + at_a);
+    r.csm = (const CsmArgs*)(k + at_csm);
+    r.lpv = (const LpvArgs*)(k + at_lpv);
+    r.sky = (const SkyArgs*)(k + at_sky);
+    r.f = (const FastArgs*)(k + at_f);
+    return r;
+}
+// (the argument itself in a body that is not a FINISH body: the same code as before there)
+template <bool LATE, class T>
+SAH_DEV const T& late_or(const T& arg, const T* late) {
+    if constexpr (LATE) return *late;
+    else return arg;
+}
 
 // ---- fast kernel (per-pixel body: lighting_fast.hpp) ----------------------------------------------------------------------
 template <int SUN, int GI, int PPT, bool SKY, bool FINISH = false>
@@ -241,22 +281,28 @@ __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const Lighti
     uint32_t block_id = blockIdx.x;
     if (SKY) {
         if (blockIdx.x < f.sky_first) {
-            const uint32_t ratio = f.sky_ratio;
-            const uint32_t groups_per_row = a.width / PPT, rows = a.row_end - a.row_begin, total = groups_per_row * rows;
+            // (a FINISH body's sky workgroup takes its uniforms — the sky block is its alone — where it uses them, like the finish: FinishArgs)
+            FinishArgs late = {nullptr, nullptr, nullptr, nullptr, nullptr};
+            if constexpr (FINISH) late = finish_args_of_fast_kernel();
+            const LightingArgs& wa = late_or<FINISH>(a, late.a);
+            const SkyArgs& wsky = late_or<FINISH>(sky, late.sky);
+            const FastArgs& wf = late_or<FINISH>(f, late.f);
+            const uint32_t ratio = wf.sky_ratio;
+            const uint32_t groups_per_row = wa.width / PPT, rows = wa.row_end - wa.row_begin, total = groups_per_row * rows;
 #pragma unroll 1
             for (uint32_t k = 0; k < ratio; k++) {
                 const uint32_t gid = (blockIdx.x * ratio + k) * 256u + threadIdx.x;
                 if (gid >= total) break;
-                const FastPixel at = fast_pixel_of(gid, groups_per_row, rows, PPT, f.tile_rows, f.row_magic);  // (the surface workgroups' map)
-                const uint32_t y = a.row_begin + at.row, x0 = at.x0;
+                const FastPixel at = fast_pixel_of(gid, groups_per_row, rows, PPT, wf.tile_rows, wf.row_magic);  // (the surface workgroups' map)
+                const uint32_t y = wa.row_begin + at.row, x0 = at.x0;
                 uint32_t wz[PPT];
-                load_words<PPT>(a.depth.ptr + (size_t)y * a.depth.pitch + (size_t)x0 * 4, wz);
+                load_words<PPT>(wa.depth.ptr + (size_t)y * wa.depth.pitch + (size_t)x0 * 4, wz);
 #pragma unroll 1
                 for (int i = 0; i < PPT; i++) {
                     if (__uint_as_float(wz[i]) != 0.f) continue;
                     Hn lit[4];
-                    sky_frag(a, sky, x0 + (uint32_t)i, y, lit);
-                    *reinterpret_cast<uint2*>(const_cast<uint8_t*>(a.lit.ptr) + (size_t)y * a.lit.pitch + (size_t)(x0 + i) * 8) = pack_lit(lit);
+                    sky_frag(wa, wsky, x0 + (uint32_t)i, y, lit);
+                    *reinterpret_cast<uint2*>(const_cast<uint8_t*>(wa.lit.ptr) + (size_t)y * wa.lit.pitch + (size_t)(x0 + i) * 8) = pack_lit(lit);
                 }
             }
             return;
@@ -276,6 +322,10 @@ __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const Lighti
     const bool lpv_bad = (GI == SAH_GI_LPV) ? (f.state->nonfinite != 0u) : false;
     const bool div_shared = (SUN == SAH_SHADOW_MODE_CSM || GI == SAH_GI_LPV) ? pos_div_shared_of(f) : false;
 
+    // The FINISH body of the traced sun under an LPV at 4 pixels per thread reads each pixel's AO texel where the pixel is shaded: eight planes' texels
+    // of four pixels do not fit beside the pixel loop, and its twin spills the AO plane's four words to scratch in the prologue and reloads them for
+    // every pixel (20 bytes of private segment, which a FINISH body does not have).  The same texel from the same plane: the same bytes.
+    constexpr bool ao_late = FINISH && SUN == SAH_SHADOW_MODE_RT && GI == SAH_GI_LPV && PPT == 4;
     uint32_t wc[PPT], wd[PPT], we[PPT], wz[PPT], wn[2 * PPT], wao[PPT], wm[PPT];
     float colx_g[PPT], colx_s[PPT];
     if (active) {
@@ -284,7 +334,7 @@ __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const Lighti
         load_words<PPT>(a.emission.ptr + (size_t)y * a.emission.pitch + (size_t)x0 * 4, we);
         load_words<PPT>(a.depth.ptr + (size_t)y * a.depth.pitch + (size_t)x0 * 4, wz);
         load_words<2 * PPT>(a.normals.ptr + (size_t)y * a.normals.pitch + (size_t)x0 * 8, wn);
-        if (GI == SAH_GI_LPV && a.has_ao) load_words<PPT>(a.ao.ptr + (size_t)y * a.ao.pitch + (size_t)x0 * 4, wao);
+        if (GI == SAH_GI_LPV && a.has_ao && !ao_late) load_words<PPT>(a.ao.ptr + (size_t)y * a.ao.pitch + (size_t)x0 * 4, wao);
         if (SUN == SAH_SHADOW_MODE_RT && a.has_mask) load_words<PPT>(a.shadow_mask.ptr + (size_t)y * a.shadow_mask.pitch + (size_t)x0 * 4, wm);
         if (f.colx_tab) {  // (uniform) the per-column numerators of the view-space x: one load instead of PPT IEEE divides
             uint32_t t[PPT];
@@ -343,6 +393,7 @@ __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const Lighti
         p.n23 = wn[2 * i + 1];
         p.depth = __uint_as_float(wz[i]);
         p.ao = (GI == SAH_GI_LPV && a.has_ao) ? __uint_as_float(wao[i]) : 1.0f;
+        if constexpr (ao_late) p.ao = a.has_ao ? *reinterpret_cast<const float*>(a.ao.ptr + (size_t)y * a.ao.pitch + (size_t)(x0 + i) * 4) : 1.0f;
         p.mask = (SUN == SAH_SHADOW_MODE_RT && a.has_mask) ? __uint_as_float(wm[i]) : 1.0f;
         const uint32_t x = x0 + i;
         float colx_glsl = 0.f, colx_slang = 0.f;
@@ -402,10 +453,12 @@ __global__ void __launch_bounds__(256, SKY ? 4 : 1) k_lighting_fast(const Lighti
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             // (the host's record, StraysRecord: nobody else tells it here.  One store per listing wave of a launch that was predicted to have none)
-            if (lane == 0u && f.strays_record)
-                __hip_atomic_store(&f.strays_record->listed, f.state->call_no[f.hint_slot] + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            const FinishArgs late = finish_args_of_fast_kernel();  // (every uniform of the finish: read here, not in the prologue)
+            if (lane == 0u && late.f->strays_record)
+                __hip_atomic_store(&late.f->strays_record->listed, late.f->state->call_no[late.f->hint_slot] + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 #pragma unroll 1
-            for (uint32_t i = lane; i < front; i += 64u) shade_listed_pixel<SUN, GI, PPT, false>(a, csm, lpv, sky, f, seg, seg_codes[i], s_lut);
+            for (uint32_t i = lane; i < front; i += 64u)
+                shade_listed_pixel<SUN, GI, PPT, false>(*late.a, *late.csm, *late.lpv, *late.sky, *late.f, seg, seg_codes[i], s_lut);
         }
     }
     if (lane == 0 && seg < f.num_segments) {
