@@ -113,6 +113,23 @@ class SsrParams(C.Structure):  # sah_ssr_params (include/sah_ssr.h): 36 bytes; d
         return cls(**values)
 
 
+MOTION_BLUR_DITHER = 1  # SAH_MOTION_BLUR_DITHER (include/sah_motion_blur.h)
+
+
+class MotionBlurParams(C.Structure):  # sah_motion_blur_params (include/sah_motion_blur.h): 44 bytes; default() = the header's defaults
+    _fields_ = [("shutter", C.c_float), ("max_blur_pixels", C.c_float), ("min_velocity_pixels", C.c_float), ("sample_count", C.c_uint32),
+                ("depth_extent", C.c_float), ("z_near", C.c_float), ("jitter", C.c_float * 2), ("previous_jitter", C.c_float * 2), ("flags", C.c_uint32)]
+
+    @classmethod
+    def default(cls, **changes):
+        values = dict(shutter=0.5, max_blur_pixels=32.0, min_velocity_pixels=0.5, sample_count=12, depth_extent=1.0, z_near=0.1, jitter=(0.0, 0.0),
+                      previous_jitter=(0.0, 0.0), flags=0)
+        values.update(changes)
+        for k in ("jitter", "previous_jitter"):
+            values[k] = (C.c_float * 2)(*values[k])
+        return cls(**values)
+
+
 RT_DENOISE_HISTORY_INVALID = 1  # SAH_RT_DENOISE_HISTORY_INVALID
 
 

@@ -7,6 +7,7 @@
 #include "../../include/sah_exposure.h"
 #include "../../include/sah_hip.h"
 #include "../../include/sah_mip_chain.h"
+#include "../../include/sah_motion_blur.h"
 #include "../../include/sah_rt_denoise.h"
 #include "../../include/sah_rtgi_denoise.h"
 #include "../../include/sah_sharpen.h"
@@ -112,6 +113,21 @@ struct SsrArgs {
     const float* luts;                  // the context's 512 floats: sRGB -> linear, UNORM8 -> float
 };
 hipError_t launch_ssr(const SsrArgs& a, hipStream_t st);
+
+// --- motion_blur.hip
+struct MotionBlurArgs {
+    PlaneArg scene, depth, mv, tiles, out;  // scene, out: W x H; depth, mv: w x h; tiles: tiles_x x tiles_y
+    uint32_t w, h, W, H;
+    uint32_t row_begin, row_end;            // rows of `out`
+    uint32_t tiles_x, tiles_y;              // ceil(w / 16), ceil(h / 16)
+    uint32_t tile_row_begin, tile_row_end;  // rows of `tiles` the band needs: its own tile rows and one on either side
+    uint32_t groups_x;                      // set by the launcher
+    float sx, sy, rx, ry;                   // fl(w / W), fl(h / H), fl(W / w), fl(H / h)
+    float jx, jy, djx, djy;                 // j = jitter, dj = previous_jitter - jitter
+    float shutter, max_blur, min_velocity, depth_extent, z_near, nf;  // nf = float(sample_count)
+    uint32_t sample_count, flags;
+};
+hipError_t launch_motion_blur(const MotionBlurArgs& a, hipStream_t st);
 
 // --- exposure.hip
 struct ExposureArgs {

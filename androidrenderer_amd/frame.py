@@ -420,6 +420,49 @@ class ScreenSpaceReflections:
         return self.out
 
 
+class MotionBlur:
+    """Camera motion blur (include/sah_motion_blur.h) behind the anti-aliasing and the sharpening and ahead of the exposure: owns the blurred
+    plane and the scratch plane of one vector per 16 x 16 tile of the render raster, both re-created when a frame of other extents arrives.
+    `settings` are fields of _abi.MotionBlurParams (the jitters are taken per frame).  Tracks the previous frame's jitter like
+    TemporalResolver; the first frame, and the first after reset() (a camera cut), takes the previous jitter to be this frame's.  Off by
+    default: nothing creates one but the caller that wants the blur."""
+
+    def __init__(self, ctx, width, height, render_width=None, render_height=None, device="cuda", **settings):
+        self.ctx, self.device = ctx, device
+        self.params = _abi.MotionBlurParams.default(**settings)
+        self.reset()
+        self._allocate(width, height, width if render_width is None else render_width, height if render_height is None else render_height)
+
+    def _allocate(self, width, height, render_width, render_height):
+        import torch
+        self.width, self.height, self.render_width, self.render_height = width, height, render_width, render_height
+        self.out = torch.zeros((height, width, 4), dtype=torch.int16, device=self.device)
+        self.tiles = torch.zeros(((render_height + 15) // 16, (render_width + 15) // 16, 2), dtype=torch.int16, device=self.device)
+
+    def reset(self):
+        self.history_valid = False
+        self.previous_jitter = (0.0, 0.0)
+
+    def __call__(self, scene, depth, motion_vectors, jitter=(0.0, 0.0), z_near=None, rows=(0, 0)):
+        """scene (H, W, 4) int16 of the output extent; depth (h, w) float32 and motion_vectors (h, w, 2) int16 of the render extent, device
+        arrays; `jitter` the (x, y) this frame was rendered with, z_near the view's (the parameters' unless given).  Returns the blurred
+        plane, (H, W, 4) int16: the same array every call while the extents stay."""
+        extents = (int(scene.shape[1]), int(scene.shape[0]), int(depth.shape[1]), int(depth.shape[0]))
+        if extents != (self.width, self.height, self.render_width, self.render_height):
+            self._allocate(*extents)
+        p = self.params
+        if z_near is not None:
+            p.z_near = float(z_near)
+        p.jitter[:] = [float(jitter[0]), float(jitter[1])]
+        p.previous_jitter[:] = self.previous_jitter if self.history_valid else p.jitter[:]
+        rgba16, rg16 = _abi.FORMAT_R16G16B16A16_SFLOAT, _abi.FORMAT_R16G16_SFLOAT
+        self.ctx.motion_blur(images.plane(scene, rgba16), images.plane(depth, _abi.FORMAT_D32_SFLOAT), images.plane(motion_vectors, rg16),
+                             images.plane(self.tiles, rg16), images.plane(self.out, rgba16), p, rows)
+        self.previous_jitter = (p.jitter[0], p.jitter[1])
+        self.history_valid = True
+        return self.out
+
+
 class VrsaaFrame:
     """The lighting half of the reference's own anti-aliasing mode (AntiAliasingType::VRSAA) for an output of width x height
     (include/sah_vrs.h): Lighting at 2W x 2H at the rate the shading-rate image of rasterised_frame(vrsaa=...) asks for, then the resolve to

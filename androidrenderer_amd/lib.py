@@ -67,6 +67,10 @@ SHARPEN_EXPORTS = ["sah_sharpen"]
 # screen-space reflections: exported, declared in include/sah_ssr.h (not sah_hip.h)
 SSR_EXPORTS = ["sah_ssr"]
 
+# camera motion blur: exported, declared in include/sah_motion_blur.h (not sah_hip.h)
+MOTION_BLUR_EXPORTS = ["sah_motion_blur"]
+MOTION_BLUR_TILE = 16         # SAH_MOTION_BLUR_TILE
+
 # variable-rate lighting and the VRSAA resolve: exported, declared in include/sah_vrs.h (not sah_hip.h)
 VRS_EXPORTS = ["sah_lighting_vrs", "sah_vrsaa_resolve"]
 
@@ -236,6 +240,7 @@ def load():
     lib.sah_exposure_apply.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
     lib.sah_sharpen.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.SharpenParams), C.c_uint32, C.c_uint32]
     lib.sah_ssr.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData)] + [C.POINTER(_abi.Plane)] * 8 + [C.POINTER(_abi.SsrParams), C.c_uint32, C.c_uint32]
+    lib.sah_motion_blur.argtypes = [C.c_void_p] + [C.POINTER(_abi.Plane)] * 5 + [C.POINTER(_abi.MotionBlurParams), C.c_uint32, C.c_uint32]
     lib.sah_lighting_vrs.argtypes = [C.c_void_p, C.POINTER(_abi.LightingVrsDesc)]
     lib.sah_vrsaa_resolve.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
     lib.sah_mip_chain_generate.argtypes =[C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32]
@@ -494,6 +499,13 @@ class Context:
         lit may be the plane `source`; out overlaps nothing.  params an _abi.SsrParams.  rows (begin, end) of `out`, (0, 0) = all."""
         self._check(self.lib.sah_ssr(self.handle, C.byref(view_data), C.byref(color), C.byref(normals), C.byref(data), C.byref(depth), C.byref(source),
                                      C.byref(lit), C.byref(scratch), C.byref(out), C.byref(params), rows[0], rows[1]))
+
+    def motion_blur(self, scene, depth, motion_vectors, tiles, out, params, rows=(0, 0)):
+        """sah_motion_blur (include/sah_motion_blur.h): scene and out R16G16B16A16_SFLOAT, W x H; depth D32_SFLOAT and motion_vectors
+        R16G16_SFLOAT, w x h <= W x H; tiles R16G16_SFLOAT scratch, ceil(w / 16) x ceil(h / 16), written by the call; _abi.Plane of device
+        memory.  out overlaps nothing, tiles no input.  params an _abi.MotionBlurParams.  rows (begin, end) of `out`, (0, 0) = all."""
+        self._check(self.lib.sah_motion_blur(self.handle, C.byref(scene), C.byref(depth), C.byref(motion_vectors), C.byref(tiles), C.byref(out),
+                                             C.byref(params), rows[0], rows[1]))
 
     def lighting_vrs(self, desc, sri, texel_size, depth_tolerance):
         """sah_lighting_vrs (include/sah_vrs.h): desc the _abi.LightingDesc lighting() takes, sri the R8_UINT shading-rate image (_abi.Plane of

@@ -40,6 +40,7 @@
 #include "sah_sharpen.h"
 #include "sah_vrs.h"
 #include "sah_ssao.h"
+#include "sah_motion_blur.h"
 #include "sah_ssr.h"
 #include "sah_taa.h"
 #include "sah_taa_upscale.h"
@@ -1635,6 +1636,55 @@ public:
 private:
     ResourceAllocator& allocator;
     TextureHandle sharpened = nullptr;
+};
+
+// The settings of sah_motion_blur_params with the header's defaults (z_near and the jitters come from the view).
+struct MotionBlurSettings {
+    float shutter = SAH_MOTION_BLUR_DEFAULT_SHUTTER, max_blur_pixels = SAH_MOTION_BLUR_DEFAULT_MAX_BLUR_PIXELS;
+    float min_velocity_pixels = SAH_MOTION_BLUR_DEFAULT_MIN_VELOCITY_PIXELS;
+    uint32_t sample_count = SAH_MOTION_BLUR_DEFAULT_SAMPLE_COUNT;
+    float depth_extent = SAH_MOTION_BLUR_DEFAULT_DEPTH_EXTENT;
+    bool dither = false;
+};
+// Camera motion blur (include/sah_motion_blur.h; builder-owned: the reference has "Other postprocessing // TODO" here) behind the upscaler
+// (or TAA) and the Sharpener, ahead of AutoExposure and Bloomer::fill_bloom_tex.  Owns the blurred texture and the scratch texture of one
+// vector per 16 x 16 tile of the render raster, (re-)created when the scene's or the vectors' extent changes.  render records the pass
+// ("Motion blur") and returns the blurred texture; `scene` has the output extent, `depth` and `motion_vectors` the render extent; z_near and
+// the two jitters are the view's.  Off unless a caller constructs one and calls it: no existing phase uses it.
+class MotionBlurPhase {
+public:
+    MotionBlurSettings settings;
+    explicit MotionBlurPhase(ResourceAllocator& allocator_in) : allocator(allocator_in) {}
+    TextureHandle get_blurred() const { return blurred; }
+    TextureHandle render(RenderGraph& graph, const SceneView& view, TextureHandle scene, TextureHandle depth, TextureHandle motion_vectors) {
+        if (!scene || !depth || !motion_vectors) {
+            graph.add_pass(hip_pass("Motion blur", [](sah_ctx*) { return (int)SAH_ERR_INVALID_ARGUMENT; }));
+            return nullptr;
+        }
+        const uint32_t W = scene->desc.width, H = scene->desc.height;
+        const uint32_t tw = (depth->desc.width + SAH_MOTION_BLUR_TILE - 1) / SAH_MOTION_BLUR_TILE, th = (depth->desc.height + SAH_MOTION_BLUR_TILE - 1) / SAH_MOTION_BLUR_TILE;
+        if (!blurred || blurred->desc.width != W || blurred->desc.height != H)
+            blurred = allocator.create_texture("Motion-blurred scene", SAH_FORMAT_R16G16B16A16_SFLOAT, W, H);
+        if (!tiles || tiles->desc.width != tw || tiles->desc.height != th) tiles = allocator.create_texture("Motion blur tiles", SAH_FORMAT_R16G16_SFLOAT, tw, th);
+        TextureHandle target = blurred, scratch = tiles;
+        const MotionBlurSettings s = settings;
+        graph.add_pass(hip_pass("Motion blur", [=, &view](sah_ctx* ctx) {
+                            const sah_view_data& v = view.get_gpu_data();
+                            sah_motion_blur_params p{};
+                            p.shutter = s.shutter, p.max_blur_pixels = s.max_blur_pixels, p.min_velocity_pixels = s.min_velocity_pixels;
+                            p.sample_count = s.sample_count, p.depth_extent = s.depth_extent, p.z_near = v.z_near;
+                            p.jitter[0] = v.jitter[0], p.jitter[1] = v.jitter[1];
+                            p.previous_jitter[0] = v.previous_jitter[0], p.previous_jitter[1] = v.previous_jitter[1];
+                            p.flags = s.dither ? SAH_MOTION_BLUR_DITHER : 0u;
+                            const sah_plane sc = scene->plane(), z = depth->plane(), mv = motion_vectors->plane(), t = scratch->plane(), o = target->plane();
+                            return sah_motion_blur(ctx, &sc, &z, &mv, &t, &o, &p, 0, 0);
+                        }));
+        return blurred;
+    }
+
+private:
+    ResourceAllocator& allocator;
+    TextureHandle blurred = nullptr, tiles = nullptr;
 };
 
 // ---- LightingPhase (RenderCore/render/phase/lighting_phase.hpp:17-57, .cpp:34-134) -------------------------------------

@@ -1,0 +1,345 @@
+"""Camera motion blur (include/sah_motion_blur.h) without a GPU: the export and the header, the 44-byte structure and its defaults, every
+refusal the header lists on a context without a device, an argument fuzz in a child process, and the numpy restatement
+(tests/motion_blur_ref.py) — the properties the design rests on and its committed fixture."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from androidrenderer_amd import _abi, lib
+from tests import motion_blur_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import gen_golden_motion_blur as gen  # noqa: E402
+
+f32 = np.float32
+HEADER = os.path.join(ROOT, "include", "sah_motion_blur.h")
+PARAM_OFFSETS = [("shutter", 0), ("max_blur_pixels", 4), ("min_velocity_pixels", 8), ("sample_count", 12), ("depth_extent", 16), ("z_near", 20),
+                 ("jitter", 24), ("previous_jitter", 32), ("flags", 40)]
+RGBA16, RG16, D32 = _abi.FORMAT_R16G16B16A16_SFLOAT, _abi.FORMAT_R16G16_SFLOAT, _abi.FORMAT_D32_SFLOAT
+FORMATS = dict(scene=RGBA16, depth=D32, motion_vectors=RG16, tiles=RG16, out=RGBA16)
+ORDER = ("scene", "depth", "motion_vectors", "tiles", "out")
+
+
+# ---- exports, header, structure -----------------------------------------------------------------------------------------------------------
+def test_library_exports_the_entry_its_header_declares():
+    L = lib.load()
+    assert all(hasattr(L, s) for s in lib.MOTION_BLUR_EXPORTS)
+    header = open(HEADER).read()
+    assert sorted(re.findall(r"^int (sah_\w+)\(", header, re.M)) == sorted(lib.MOTION_BLUR_EXPORTS) == ["sah_motion_blur"]
+    assert not set(lib.MOTION_BLUR_EXPORTS) & set(lib.EXPORTS)
+    hip_h = open(os.path.join(ROOT, "include", "sah_hip.h")).read()
+    assert "sah_motion_blur" not in hip_h and re.search(r"#define\s+SAH_ABI_VERSION\s+6\b", hip_h)  # sah_hip.h's declarations and ABI version stay
+    assert "ABI-defined" in header and "Parity unpinned" in header and "Off by default" in header
+    assert re.search(r"#define\s+SAH_MOTION_BLUR_DITHER\s+1u\b", header) and re.search(r"#define\s+SAH_MOTION_BLUR_TILE\s+16u\b", header)
+    assert _abi.MOTION_BLUR_DITHER == ref.DITHER == 1 and lib.MOTION_BLUR_TILE == ref.TILE == 16
+
+
+@pytest.mark.parametrize("language", ["c", "c++"])
+def test_header_compiles_and_the_structure_is_44_bytes(tmp_path, language):
+    src = tmp_path / ("use.c" if language == "c" else "use.cpp")
+    check = "_Static_assert" if language == "c" else "static_assert"
+    offsets = "".join(f'{check}(offsetof(sah_motion_blur_params, {n}) == {o}, "{n}");\n' for n, o in PARAM_OFFSETS)
+    src.write_text('#include <stddef.h>\n#include "sah_motion_blur.h"\n'
+                   f'{check}(sizeof(sah_motion_blur_params) == 44, "sah_motion_blur_params");\n' + offsets +
+                   "int use(sah_ctx* c, const sah_plane* p, const sah_motion_blur_params* q) {\n"
+                   "    return sah_motion_blur(c, p, p, p, p, p, q, 0, 0) + (int)SAH_MOTION_BLUR_DITHER; }\n")
+    clang = "/opt/rocm/llvm/bin/clang" if os.path.exists("/opt/rocm/llvm/bin/clang") else "cc"
+    subprocess.check_call([clang, "-x", language, "-std=c11" if language == "c" else "-std=c++17", "-Wall", "-Werror", "-fsyntax-only",
+                           "-I", os.path.join(ROOT, "include"), str(src)], timeout=120)
+    assert C.sizeof(_abi.MotionBlurParams) == 44
+    assert [(n, getattr(_abi.MotionBlurParams, n).offset) for n, _ in _abi.MotionBlurParams._fields_] == PARAM_OFFSETS
+
+
+def test_the_headers_defaults_are_the_python_defaults():
+    header = open(HEADER).read()
+    d = _abi.MotionBlurParams.default()
+    for name in ("shutter", "max_blur_pixels", "min_velocity_pixels", "sample_count", "depth_extent", "z_near"):
+        m = re.search(rf"#define\s+SAH_MOTION_BLUR_DEFAULT_{name.upper()}\s+([0-9.]+)[fu]\b", header)
+        assert m, name
+        assert f32(float(m.group(1))) == f32(getattr(d, name)) == f32(ref.DEFAULTS[name]), name
+        assert re.search(rf"{name};[^\n]*default {re.escape(m.group(1).rstrip('0').rstrip('.'))}\b", header), name  # the field's comment says the same
+    assert re.search(r"#define\s+SAH_MOTION_BLUR_DEFAULT_JITTER\s+0\.0f", header) and re.search(r"#define\s+SAH_MOTION_BLUR_DEFAULT_FLAGS\s+0u", header)
+    assert tuple(d.jitter) == tuple(d.previous_jitter) == (0.0, 0.0) and d.flags == 0 == ref.DEFAULTS["flags"]
+    changed = _abi.MotionBlurParams.default(sample_count=32, jitter=(0.25, -0.5), flags=1)
+    assert (changed.sample_count, tuple(changed.jitter), changed.flags, changed.shutter) == (32, (0.25, -0.5), 1, 0.5)
+
+
+# ---- refusals ---------------------------------------------------------------------------------------------------------------------------------
+OK, INVALID, FORMAT = "well-formed", _abi.SAH_ERR_INVALID_ARGUMENT, _abi.SAH_ERR_UNSUPPORTED_FORMAT
+W, H = 40, 24        # the output extent of the well-formed call
+LW, LH = 24, 18      # a lower render extent
+EXTENT = dict(scene=(W, H), out=(W, H), depth=(W, H), motion_vectors=(W, H), tiles=(3, 2))
+
+
+def _plane(name, base, w=None, h=None, pitch=None, ptr=True, offset=0, fmt=None):
+    bpp = _abi.FORMAT_BPP[FORMATS[name]]
+    w = EXTENT[name][0] if w is None else w
+    h = EXTENT[name][1] if h is None else h
+    return _abi.Plane((base + offset) if ptr else None, w, h, w * bpp if pitch is None else pitch, FORMATS[name] if fmt is None else fmt)
+
+
+def _cases(base):
+    """(name, (planes by name, params, row_begin, row_end), expected)"""
+    at = {n: base + (i << 16) for i, n in enumerate(ORDER)}
+    P = _abi.MotionBlurParams.default
+    size8 = (H - 1) * W * 8 + W * 8
+
+    def call(rows=(0, 0), params="default", **kw):
+        planes = {n: _plane(n, at[n]) for n in ORDER}
+        planes.update(kw)
+        return (planes, P() if params == "default" else params) + tuple(rows)
+
+    def low(**kw):
+        planes = dict(depth=_plane("depth", at["depth"], w=LW, h=LH), motion_vectors=_plane("motion_vectors", at["motion_vectors"], w=LW, h=LH),
+                      tiles=_plane("tiles", at["tiles"], w=2, h=2))
+        planes.update(kw)
+        return planes
+    yield "whole", call(), OK
+    yield "band", call((3, 9)), OK
+    yield "empty band", call((5, 5)), OK
+    yield "last row", call((H - 1, H)), OK
+    yield "a lower render extent", call(**low()), OK
+    yield "unequal ratios", call(**low(depth=_plane("depth", at["depth"], w=W, h=LH), motion_vectors=_plane("motion_vectors", at["motion_vectors"], w=W, h=LH),
+                                       tiles=_plane("tiles", at["tiles"], w=3, h=2))), OK
+    yield "padded pitches", call(scene=_plane("scene", at["scene"], pitch=W * 8 + 12), out=_plane("out", at["out"], pitch=W * 8 + 4),
+                                 tiles=_plane("tiles", at["tiles"], pitch=3 * 4 + 8)), OK
+    yield "limits of the ranges", call(params=P(shutter=1.0, max_blur_pixels=32.0, min_velocity_pixels=0.0, sample_count=2, depth_extent=1e-30, z_near=1e-30, flags=1)), OK
+    yield "other limits", call(params=P(shutter=1e-30, max_blur_pixels=1e-30, min_velocity_pixels=3e38, sample_count=32, depth_extent=3e38, z_near=3e38,
+                                        jitter=(-3e38, 3e38), previous_jitter=(3e38, -3e38))), OK
+    yield "out ends where scene begins", call(out=_plane("out", at["scene"] - size8)), OK
+    for name in ORDER:
+        yield f"{name} NULL", call(**{name: None}), INVALID
+        yield f"{name}: null pointer", call(**{name: _plane(name, at[name], ptr=False)}), INVALID
+        other = _abi.FORMAT_R32_SFLOAT
+        yield f"{name}: wrong format", call(**{name: _plane(name, at[name], fmt=other)}), FORMAT
+        bpp = _abi.FORMAT_BPP[FORMATS[name]]
+        w, h = EXTENT[name]
+        yield f"{name}: short pitch", call(**{name: _plane(name, at[name], pitch=w * bpp - 4)}), INVALID
+        yield f"{name}: misaligned pointer", call(**{name: _plane(name, at[name], offset=2)}), INVALID
+        yield f"{name}: pitch not a multiple of 4", call(**{name: _plane(name, at[name], pitch=w * bpp + 2)}), INVALID
+        yield f"{name}: zero width", call(**{name: _plane(name, at[name], w=0)}), INVALID
+        yield f"{name}: zero height", call(**{name: _plane(name, at[name], h=0)}), INVALID
+        yield f"{name}: other width", call(**{name: _plane(name, at[name], w=w + 1, pitch=(w + 1) * bpp)}), INVALID  # (depth, mv: 41 > 40 is also downscaling)
+        yield f"{name}: other height", call(**{name: _plane(name, at[name], h=h - 1)}), INVALID
+    yield "tiles of the frame's extent", call(tiles=_plane("tiles", at["tiles"], w=W, h=H)), INVALID
+    yield "tiles of the output's grid under a lower render extent", call(**low(tiles=_plane("tiles", at["tiles"]))), INVALID
+    yield "downscaling in x", call(scene=_plane("scene", at["scene"], w=LW), out=_plane("out", at["out"], w=LW), tiles=_plane("tiles", at["tiles"])), INVALID
+    yield "downscaling in y", call(scene=_plane("scene", at["scene"], h=LH), out=_plane("out", at["out"], h=LH), tiles=_plane("tiles", at["tiles"])), INVALID
+    yield "params NULL", call(params=None), INVALID
+    yield "row_begin > row_end", call((9, 3)), INVALID
+    yield "row_end > H", call((0, H + 1)), INVALID
+    nan, inf = float("nan"), float("inf")
+    bad = dict(shutter=(0.0, -0.5, 1.001, inf, nan), max_blur_pixels=(0.0, -1.0, 32.5, inf, nan), min_velocity_pixels=(-0.001, inf, -inf, nan),
+               sample_count=(0, 1, 3, 13, 31, 33, 34, 0xFFFFFFFF), depth_extent=(0.0, -1.0, inf, nan), z_near=(0.0, -0.05, inf, nan),
+               flags=(2, 3, 0x80000000))
+    for field, values in bad.items():
+        for v in values:
+            yield f"{field} {v}", call(params=P(**{field: v})), INVALID
+    for field in ("jitter", "previous_jitter"):
+        for v in ((nan, 0.0), (0.0, nan), (inf, 0.0), (0.0, -inf)):
+            yield f"{field} {v}", call(params=P(**{field: v})), INVALID
+    # overlaps
+    for name in ORDER[:-1]:
+        yield f"out is {name}'s memory", call(out=_plane("out", at[name])), INVALID
+    yield "out ends inside scene", call(out=_plane("out", at["scene"] - size8 + 4)), INVALID
+    yield "out begins inside scene", call(out=_plane("out", at["scene"] + size8 - 4)), INVALID
+    for name in ORDER[:3]:
+        yield f"tiles is {name}'s memory", call(tiles=_plane("tiles", at[name])), INVALID
+
+
+def _invoke(L, h, args):
+    planes, params, r0, r1 = args
+    ref_of = lambda a: None if a is None else C.byref(a)  # noqa: E731
+    return L.sah_motion_blur(h, *[ref_of(planes[n]) for n in ORDER], ref_of(params), r0, r1)
+
+
+def test_every_refusal_of_the_header_on_a_context_without_a_device():
+    """A malformed call answers its status; a well-formed one gets as far as selecting the device, which a detached context does not have
+    (SAH_ERR_HIP) — so nothing is launched and the made-up addresses are never used."""
+    L = lib.load()
+    L.sah_debug_create_detached.argtypes = [C.POINTER(C.c_void_p)]
+    h = C.c_void_p()
+    rc = L.sah_debug_create_detached(C.byref(h))
+    if rc == _abi.SAH_ERR_UNSUPPORTED:
+        pytest.skip("a HIP device is present (made-up addresses must not reach a GPU); tests/test_motion_blur_gpu.py checks the refusals there")
+    assert rc == 0 and h.value
+    n = 0
+    try:
+        for name, args, want in _cases(0x10000000):
+            got = _invoke(L, h, args)
+            assert got == (_abi.SAH_ERR_HIP if want == OK else want), f"{name}: status {got}"
+            n += 1
+        assert _invoke(L, None, next(_cases(0x10000000))[1]) == INVALID
+    finally:
+        L.sah_destroy(h)
+    assert n > 100
+
+
+@pytest.mark.parametrize("seed", [47])
+def test_no_argument_combination_crashes_the_entry(seed):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "motion_blur_fuzz_child.py"), str(seed), "2000"], stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, text=True, timeout=600)
+    tail = "\n".join(r.stdout.splitlines()[-10:])
+    if "SKIP:" in r.stdout:
+        pytest.skip(r.stdout.strip().splitlines()[-1])
+    assert r.returncode == 0, f"the fuzz child ended with code {r.returncode}:\n{tail}"
+    assert "OK: 2000 iterations" in r.stdout, tail
+    assert not re.search(r"\bok: \d", r.stdout)  # (a detached context never launches)
+
+
+# ---- properties of the restatement ------------------------------------------------------------------------------------------------------------
+SW, SH = 48, 40  # three tiles by two and a half
+
+
+def _mover(w, h, at, vector):
+    """vectors that are zero but for one texel"""
+    mv = np.zeros((h, w, 2), f32)
+    mv[at[1], at[0]] = vector
+    return ref.to_half_bits(mv)
+
+
+def test_a_zero_vectors_and_equal_jitters_copy_the_scene():
+    scene = ref.textured_scene(SW, SH, 1)
+    depth = ref.box_depth(SW, SH)
+    for jitter in ((0.0, 0.0), (0.25, -0.375)):
+        out, info = ref.motion_blur_ex(scene, depth, np.zeros((SH, SW, 2), np.uint16), jitter=jitter, previous_jitter=jitter, min_velocity_pixels=0.0)
+        assert out.tobytes() == scene.tobytes() and info["passed"].all() and not info["tiles"].any()
+
+
+@pytest.mark.parametrize("low", [False, True])
+def test_b_a_static_camera_with_a_jitter_pair_copies_the_scene(low):
+    scene = ref.textured_scene(SW, SH, 2)
+    w, h = (32, 27) if low else (SW, SH)
+    for jitter, previous in (((0.25, -0.375), (-0.125, 0.3125)), ((0.5, 0.5), (-0.5, -0.5)), ((0.3, -0.1), (-0.47, 0.21))):
+        mv = ref.static_vectors(w, h, jitter, previous)
+        out, info = ref.motion_blur_ex(scene, ref.box_depth(w, h), mv, jitter=jitter, previous_jitter=previous)
+        assert out.tobytes() == scene.tobytes() and info["passed"].all()
+        assert (info["speed"] < 1e-3).all()  # the jitter is taken out: what is left is the vectors' rounding to halfs
+        # and the reason a tile of zero velocities stores its selected pair and not (0, 0): the Velocity of (0, 0) is dj * shutter
+        assert (ref.velocity(np.zeros(1, np.uint32), ref.Params(jitter=jitter, previous_jitter=previous))[2] > 0.18).all()
+
+
+def test_c_a_constant_scene_is_a_fixed_point_whatever_the_vectors():
+    g = np.random.default_rng(3)
+    depth = (g.random((SH, SW)) * 0.5).astype(f32)
+    mv = ref.to_half_bits(g.normal(0.0, 20.0, (SH, SW, 2)))
+    for texel in ((0.75, 2.5, 0.125, 1.0), (0.0, 0.0, 0.0, 0.0), (-0.0, 6.1e-5, 65504.0, -3.0), (1.0 / 3.0, 5.96e-8, 1000.0, 0.5)):
+        scene = np.broadcast_to(ref.to_half_bits(np.array(texel, f32)), (SH, SW, 4)).copy()
+        out, info = ref.motion_blur_ex(scene, depth, mv, flags=ref.DITHER, sample_count=32)
+        assert out.tobytes() == scene.tobytes()
+        assert not info["passed"].all()  # ... and not because nothing ran
+
+
+def test_d_a_static_foreground_in_front_of_a_moving_background_keeps_its_bytes():
+    scene = ref.textured_scene(gen.WIDTH, gen.HEIGHT, 4)
+    depth, box = ref.box_depth(gen.WIDTH, gen.HEIGHT), ref.box_mask(gen.WIDTH, gen.HEIGHT)
+    mv = ref.to_half_bits(np.where(box[..., None], 0.0, np.array([18.0, 10.0])))
+    out, info = ref.motion_blur_ex(scene, depth, mv, depth_extent=1.0)
+    assert (ref.Z_WALL - ref.Z_BOX) > 1.0 and info["moving"].all()  # every tile blurs, the box's own included
+    assert (out[box] == scene[box]).all() and info["passed"][box].all()
+    assert (out[~box] != scene[~box]).any(-1).mean() > 0.9
+
+
+def test_e_a_moving_foreground_spreads_onto_the_static_background_within_its_reach():
+    scene = ref.textured_scene(gen.WIDTH, gen.HEIGHT, 5)
+    depth, box = ref.box_depth(gen.WIDTH, gen.HEIGHT), ref.box_mask(gen.WIDTH, gen.HEIGHT)
+    mv = ref.to_half_bits(np.where(box[..., None], np.array([24.0, 0.0]), 0.0))  # scaled by the shutter: 12 pixels, 6 to either side
+    out, _ = ref.motion_blur_ex(scene, depth, mv)
+    changed = (out != scene).any(-1)
+    xs = np.where(box.any(0))[0]
+    x0, x1 = xs[0], xs[-1]
+    rows = box.any(1)
+    assert changed[rows][:, x0 - 5:x0].all() and changed[rows][:, x1 + 1:x1 + 6].all()  # background pixels within reach take the box's colour
+    assert not changed[:, :x0 - 6].any() and not changed[:, x1 + 7:].any() and not changed[~rows].any()  # and none beyond it
+    assert changed[box].mean() > 0.9
+
+
+def test_f_a_mover_in_the_diagonal_tile_reaches_a_pixel_that_its_own_tile_would_not_blur():
+    """The reach is 16 pixels along the vector, so of the diagonal neighbour tile it is the near corner a pixel's taps can land on: the
+    mover is texel (16, 16), the pixel (5, 5) of tile (0, 0), whose outermost tap of 32 lies 15.5 pixels away, on the mover."""
+    scene = ref.textured_scene(SW, SH, 6)
+    depth = np.full((SH, SW), 0.01, f32)
+    mv = _mover(SW, SH, (16, 16), (-64.0, -64.0))  # scaled by the shutter and clamped to 32 pixels: 16 to either side, 11.3 per axis
+    pixel = (5, 5)
+    out, info = ref.motion_blur_ex(scene, depth, mv, sample_count=32)
+    alone, _ = ref.motion_blur_ex(scene, depth, mv, sample_count=32, reach=0)
+    assert (info["tiles"][1, 1] == ref.to_half_bits(np.array([-64.0, -64.0], f32))).all() and not info["tiles"][0, 0].any()
+    assert (alone[pixel[1], pixel[0]] == scene[pixel[1], pixel[0]]).all()
+    assert (out[pixel[1], pixel[0]] != scene[pixel[1], pixel[0]]).any()
+    assert not info["passed"][pixel[1], pixel[0]]
+    assert (info["speed"] == 32.0).all()  # every tile of the 3 x 3 grid is tile (1, 1) or a neighbour of it
+
+
+def test_g_equal_speeds_the_greater_bit_pattern_wins_in_any_order():
+    p = ref.Params()
+    a, b = np.array([3.0, 4.0], f32), np.array([-4.0, 3.0], f32)  # one squared length, exactly
+    for first, second in ((a, b), (b, a)):
+        mv = np.zeros((16, 16, 2), f32)
+        mv[2, 3], mv[11, 9] = first, second
+        tiles = ref.tile_vectors(ref.to_half_bits(mv), p)
+        bits = [int(ref.pair_bits(ref.to_half_bits(v))) for v in (a, b)]
+        assert ref.key(np.uint32(bits[0]), p) >> np.uint64(32) == ref.key(np.uint32(bits[1]), p) >> np.uint64(32)
+        assert int(ref.pair_bits(tiles)[0, 0]) == max(bits)
+    g = np.random.default_rng(7)
+    mv = ref.to_half_bits(np.round(g.normal(0.0, 3.0, (32, 48, 2))))  # small integers: many exact ties
+    want = ref.tile_vectors(mv, p)
+    for flip in (lambda v: v[::-1], lambda v: v[:, ::-1]):
+        assert (flip(ref.tile_vectors(flip(mv), p)) == want).all()
+
+
+def test_h_non_finite_vectors_and_unclean_texels_neither_fault_nor_spread():
+    scene = ref.textured_scene(SW, SH, 8)
+    depth = ref.box_depth(SW, SH)
+    mv = ref.to_half_bits(np.broadcast_to(np.array([14.0, 6.0], f32), (SH, SW, 2))).copy()
+    for k, bits in enumerate((0x7E00, 0x7C00, 0xFC00, 0xFE00)):  # NaN, +inf, -inf, -NaN vectors
+        mv[5 + k, 7, k & 1] = bits
+    dirty = {(20, 12): (0, 0x7E00), (21, 30): (1, 0x7C00), (33, 17): (2, 0xBC00), (40, 25): (0, 0xFC00)}  # NaN, +inf, -1, -inf
+    for (x, y), (c, bits) in dirty.items():
+        scene[y, x, c] = bits
+    out, info = ref.motion_blur_ex(scene, depth, mv)
+    clean = ref.clean(ref.h2f(out[..., :3]))
+    assert (~clean).sum() == len(dirty)
+    for (x, y) in dirty:
+        assert (out[y, x] == scene[y, x]).all() and info["passed"][y, x]
+    assert not info["passed"][clean].all() and (out[..., 3] == scene[..., 3]).all()
+    # a field of nothing but non-finite vectors counts as still
+    for bits in (0x7E00, 0x7C00, 0xFC00):
+        out, info = ref.motion_blur_ex(scene, depth, np.full((SH, SW, 2), bits, np.uint16))
+        assert out.tobytes() == scene.tobytes() and (info["speed"] == 0).all()
+    # depths without a surface, NaN and infinite ones
+    odd = depth.copy()
+    odd[::3, ::2], odd[1::3, 1::2], odd[2::5, ::3], odd[::7, 1::3] = 0.0, np.nan, np.inf, -1.0
+    out, info = ref.motion_blur_ex(scene, odd, mv)
+    assert ref.clean(ref.h2f(out[..., :3])).sum() == clean.sum() and np.isfinite(info["sw"]).all()
+
+
+# ---- the fixture ------------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def fixture():
+    return np.load(gen.FIXTURE)
+
+
+def test_i_generator_reproduces_the_committed_fixture(fixture):
+    got = gen.generate(int(fixture["seed"]))
+    assert sorted(got) == sorted(fixture.files)
+    for k in fixture.files:
+        assert np.asarray(got[k]).dtype == fixture[k].dtype and np.asarray(got[k]).tobytes() == fixture[k].tobytes(), k
+    assert (gen.WIDTH, gen.HEIGHT) == (96, 54) and fixture["out"].shape == (len(gen.CASES), gen.HEIGHT, gen.WIDTH, 4)
+    assert fixture["low_mv"].shape == (36, 64, 2)
+    assert os.path.getsize(gen.FIXTURE) < 1024 * 1024
+
+
+def test_the_fixture_blurs_and_passes_through_in_every_case(fixture):
+    for n, (field, params) in enumerate(gen.CASES):
+        passed = np.unpackbits(fixture["passed"][n], axis=-1)[:, :gen.WIDTH].astype(bool)
+        changed = (fixture["out"][n] != fixture["scene"]).any(-1)
+        assert 0.1 < changed.mean() and not (changed & passed).any(), (field, params)
+        assert (fixture["out"][n][..., 3] == fixture["scene"][..., 3]).all()
+    counts = {params.get("sample_count", 12) for _, params in gen.CASES}
+    assert {2, 12, 32} <= counts and any(p.get("flags") for _, p in gen.CASES) and any("jitter" in p for _, p in gen.CASES)
