@@ -130,6 +130,25 @@ class MotionBlurParams(C.Structure):  # sah_motion_blur_params (include/sah_moti
         return cls(**values)
 
 
+SUN_SHAFTS_DITHER, SUN_SHAFTS_TERM_ONLY = 1, 2  # SAH_SUN_SHAFTS_* (include/sah_sun_shafts.h)
+LIGHTING_EXPOSURE = 0.00031415927  # the constant sah_lighting scales the sun's colour by (directional_light.frag)
+
+
+class SunShaftsParams(C.Structure):  # sah_sun_shafts_params (include/sah_sun_shafts.h): 60 bytes; default() = the header's defaults
+    _fields_ = [("step_length", C.c_float), ("num_steps", C.c_uint32), ("step_transmittance", C.c_float), ("albedo", C.c_float * 3),
+                ("ambient", C.c_float * 3), ("anisotropy", C.c_float), ("depth_bias", C.c_float), ("depth_sharpness", C.c_float),
+                ("downscale", C.c_uint32), ("dither_offset", C.c_uint32), ("flags", C.c_uint32)]
+
+    @classmethod
+    def default(cls, **changes):
+        values = dict(step_length=0.5, num_steps=32, step_transmittance=0.98, albedo=(1.0, 1.0, 1.0), ambient=(0.0, 0.0, 0.0), anisotropy=0.6,
+                      depth_bias=0.0005, depth_sharpness=50.0, downscale=1, dither_offset=0, flags=0)
+        values.update(changes)
+        for k in ("albedo", "ambient"):
+            values[k] = (C.c_float * 3)(*values[k])
+        return cls(**values)
+
+
 RT_DENOISE_HISTORY_INVALID = 1  # SAH_RT_DENOISE_HISTORY_INVALID
 
 

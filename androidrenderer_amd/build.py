@@ -20,7 +20,7 @@ OUT = os.environ.get("SAH_HIP_LIBRARY") or os.path.join(HERE, "libsah_hip.so")
 OBJDIR = os.path.join(HERE, "_build", os.path.splitext(os.path.basename(OUT))[0])  # one object directory per output (A/B builds)
 SOURCES = ["api.cpp", "api_post.cpp", "api_lpv.cpp", "api_probes.cpp", "api_comm.cpp", "api_raster.cpp", "api_rt.cpp", "rt.hip", "rt_refit.hip", "api_ipc.cpp", "api_chain.cpp", "ipc.hip", "lighting.hip", "lighting_tiled.hip", "post.hip", "tonemap.hip", "tonemap_tol.hip", "lpv.hip",
            "probes.hip", "sky_luts.hip", "raster_setup.hip", "raster_tiles.hip", "vpl.hip", "lpv_gv.hip", "lpv_mesh_lights.hip", "api_vrsaa.cpp", "vrsaa.hip", "api_mip_chain.cpp", "mip_chain.hip", "api_taa.cpp", "taa.hip",
-           "api_taa_upscale.cpp", "taa_upscale.hip", "api_ssao.cpp", "ssao.hip", "api_rt_denoise.cpp", "rt_denoise.hip", "api_exposure.cpp", "exposure.hip", "api_sharpen.cpp", "sharpen.hip", "api_ssr.cpp", "ssr.hip", "api_motion_blur.cpp", "motion_blur.hip",
+           "api_taa_upscale.cpp", "taa_upscale.hip", "api_ssao.cpp", "ssao.hip", "api_rt_denoise.cpp", "rt_denoise.hip", "api_exposure.cpp", "exposure.hip", "api_sharpen.cpp", "sharpen.hip", "api_ssr.cpp", "ssr.hip", "api_motion_blur.cpp", "motion_blur.hip", "api_sun_shafts.cpp", "sun_shafts.hip",
            "api_rtgi_denoise.cpp", "rtgi_denoise.hip", "api_vrs.cpp", "lighting_vrs.hip", "vrs_resolve.hip"]
 # -fno-slp-vectorize: on MI355X v_pk_{mul,add,fma}_f32 issue in 4 cycles against 2 for the scalar forms (profiles/r1_valu_issue_cost.txt),
 # so the SLP vectoriser's packed pairs gain nothing and cost the register shuffles that feed them.

@@ -136,6 +136,38 @@ int lighting_targets(sah_ctx* ctx, const sah_lighting_desc* d, LightingCall& cal
     return SAH_OK;
 }
 
+// The constants of shadow_pcf()'s D16 conversion (lighting_common.hpp)
+void csm_d16_conversion(CsmArgs& csm) {
+    csm.d16_recip = 1.0f / 65535.0f;
+    static const bool recip_ok = [] {  // exhaustive check of the reciprocal sequence used by shadow_pcf()
+        const float y = 1.0f / 65535.0f;
+        for (uint32_t i = 0; i < 65536; i++) {
+            const float v = (float)i;
+            const float q = v * y;
+            const float q2 = std::fmaf(std::fmaf(-q, 65535.0f, v), y, q);
+            if (q2 != v / 65535.0f) return false;
+        }
+        return true;
+    }();
+    csm.d16_recip_ok = recip_ok;
+}
+
+// What the sun's constants alone decide of CsmArgs: the split depths and biasMat * cascade_matrices[c]
+void csm_sun_tables(const sah_sun_light_constants& sun, CsmArgs& csm) {
+    for (int c = 0; c < 4; c++) {
+        csm.splits[c] = sun.data[c][0];
+        // biasMat * cascade_matrices[c] (directional_light.frag:55-65), evaluated as the matrix product it is
+        const float* M = sun.cascade_matrices[c];
+        for (int col = 0; col < 4; col++) {
+            const float* m = M + col * 4;
+            csm.biased[c][col * 4 + 0] = ((0.5f * m[0] + 0.0f * m[1]) + 0.0f * m[2]) + 0.5f * m[3];
+            csm.biased[c][col * 4 + 1] = ((0.0f * m[0] + 0.5f * m[1]) + 0.0f * m[2]) + 0.5f * m[3];
+            csm.biased[c][col * 4 + 2] = ((0.0f * m[0] + 0.0f * m[1]) + 1.0f * m[2]) + 0.0f * m[3];
+            csm.biased[c][col * 4 + 3] = ((0.0f * m[0] + 0.0f * m[1]) + 0.0f * m[2]) + 1.0f * m[3];
+        }
+    }
+}
+
 // The sun's cascaded shadow map (all zero for another shadow mode)
 int lighting_csm(sah_ctx* ctx, const sah_lighting_desc* d, const LightingCall& call, CsmArgs& csm) {
     memset(&csm, 0, sizeof(csm));
@@ -146,31 +178,9 @@ int lighting_csm(sah_ctx* ctx, const sah_lighting_desc* d, const LightingCall& c
         if (d->shadowmap->depth < 4) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "shadowmap needs 4 layers");
         csm.shadowmap = varg(*d->shadowmap);
         csm.is_d16 = d->shadowmap->format == SAH_FORMAT_D16_UNORM;
-        csm.d16_recip = 1.0f / 65535.0f;
-        static const bool recip_ok = [] {  // exhaustive check of the reciprocal sequence used by shadow_pcf()
-            const float y = 1.0f / 65535.0f;
-            for (uint32_t i = 0; i < 65536; i++) {
-                const float v = (float)i;
-                const float q = v * y;
-                const float q2 = std::fmaf(std::fmaf(-q, 65535.0f, v), y, q);
-                if (q2 != v / 65535.0f) return false;
-            }
-            return true;
-        }();
-        csm.d16_recip_ok = recip_ok;
+        csm_d16_conversion(csm);
     }
-    for (int c = 0; c < 4; c++) {
-        csm.splits[c] = d->sun->data[c][0];
-        // biasMat * cascade_matrices[c] (directional_light.frag:55-65), evaluated as the matrix product it is
-        const float* M = d->sun->cascade_matrices[c];
-        for (int col = 0; col < 4; col++) {
-            const float* m = M + col * 4;
-            csm.biased[c][col * 4 + 0] = ((0.5f * m[0] + 0.0f * m[1]) + 0.0f * m[2]) + 0.5f * m[3];
-            csm.biased[c][col * 4 + 1] = ((0.0f * m[0] + 0.5f * m[1]) + 0.0f * m[2]) + 0.5f * m[3];
-            csm.biased[c][col * 4 + 2] = ((0.0f * m[0] + 0.0f * m[1]) + 1.0f * m[2]) + 0.0f * m[3];
-            csm.biased[c][col * 4 + 3] = ((0.0f * m[0] + 0.0f * m[1]) + 0.0f * m[2]) + 1.0f * m[3];
-        }
-    }
+    csm_sun_tables(*d->sun, csm);
     return SAH_OK;
 }
 

@@ -13,6 +13,7 @@
 #include "../../include/sah_sharpen.h"
 #include "../../include/sah_ssao.h"
 #include "../../include/sah_ssr.h"
+#include "../../include/sah_sun_shafts.h"
 #include "../../include/sah_taa.h"
 #include "../../include/sah_taa_upscale.h"
 #include "../../include/sah_vrs.h"
@@ -128,6 +129,25 @@ struct MotionBlurArgs {
     uint32_t sample_count, flags;
 };
 hipError_t launch_motion_blur(const MotionBlurArgs& a, hipStream_t st);
+
+// --- sun_shafts.hip
+struct SunShaftsArgs {
+    PlaneArg depth, lit, march, out;        // depth, lit, out: w x h; march: mw x mh
+    CsmArgs csm;                            // Lighting's block: the map, the splits and the biased matrices (shadowmap.ptr null: all lit)
+    uint32_t w, h, mw, mh;
+    uint32_t row_begin, row_end;            // rows of `out`
+    uint32_t march_row_begin, march_row_end;  // rows of `march` the band writes
+    uint32_t groups_x;                      // set by the launcher
+    uint32_t downscale, num_steps, num_cascades, dither_offset, flags;
+    float wf, hf;                           // float(w), float(h)
+    float inv_proj[16], inv_view[16];
+    float a[4][3];                          // a_c: the camera in cascade c's divided coordinates
+    float lv[3], sun_color[3], albedo[3], ambient[3];
+    float step_length, d_min, z_near, depth_bias, depth_sharpness;
+    float g1, g2, g3;                       // 1 + g g, 1 - g g, 2 g
+    float D[SAH_SUN_SHAFTS_MAX_STEPS];      // the energy a step removes
+};
+hipError_t launch_sun_shafts(const SunShaftsArgs& a, hipStream_t st);
 
 // --- exposure.hip
 struct ExposureArgs {

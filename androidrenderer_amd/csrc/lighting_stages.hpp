@@ -22,6 +22,10 @@ struct LightingCall {
 int lighting_targets(sah_ctx* ctx, const sah_lighting_desc* d, LightingCall& call, LightingArgs& a);
 // The sun's cascaded shadow map (all zero for another shadow mode)
 int lighting_csm(sah_ctx* ctx, const sah_lighting_desc* d, const LightingCall& call, CsmArgs& csm);
+// Its two parts that another pass sampling the cascades with shadow_pcf() shares (sah_sun_shafts): the constants of the D16 conversion, and
+// what the sun's constants alone decide, the split depths and biasMat * cascade_matrices[c]
+void csm_d16_conversion(CsmArgs& csm);
+void csm_sun_tables(const sah_sun_light_constants& sun, CsmArgs& csm);
 // The LPV overlay (all zero for another GI kind)
 int lighting_gi_lpv(sah_ctx* ctx, const sah_lighting_desc* d, const LightingCall& call, LpvArgs& lpv);
 // The sky fill (all zero without a sky)

@@ -16,6 +16,7 @@
 // access and the copy branch moves 16 bytes; otherwise every access is a dword.
 #include <hip/hip_runtime.h>
 
+#include "dither.hpp"
 #include "launch.hpp"
 #include "numerics.hpp"
 
@@ -23,8 +24,6 @@ namespace sah {
 
 constexpr int kMbT = (int)SAH_MOTION_BLUR_TILE;
 constexpr float kMbInf = __builtin_inff(), kMbFar = 0x1p100f;
-
-__constant__ float kMbBayer[16] = {0.f, 8.f, 2.f, 10.f, 12.f, 4.f, 14.f, 6.f, 3.f, 11.f, 1.f, 9.f, 15.f, 7.f, 13.f, 5.f};
 
 namespace {
 SAH_DEV float mb_clamp01(float a) { return a > 0.0f ? (a < 1.0f ? a : 1.0f) : 0.0f; }
@@ -163,7 +162,7 @@ template <bool kVec> __global__ void __launch_bounds__(256) k_mb_gather(MotionBl
     if (moving && mb_clean(c[0], c[1], c[2])) {
         const MbVelocity vp = mb_velocity(a, mb_load_dword(a.mv, i, j));
         const float zp = mb_surface(a, __builtin_bit_cast(float, mb_load_dword(a.depth, i, j)));
-        const float dith = (a.flags & SAH_MOTION_BLUR_DITHER) ? (kMbBayer[(X & 3) + 4 * (Y & 3)] - 7.5f) * 0.0625f : 0.0f;
+        const float dith = (a.flags & SAH_MOTION_BLUR_DITHER) ? (bayer4x4((uint32_t)X, (uint32_t)Y) - 7.5f) * 0.0625f : 0.0f;
         const float wf = (float)a.w, hf = (float)a.h, Wf = (float)a.W, Hf = (float)a.H;
         float sw = 0.0f, acc[3] = {0.0f, 0.0f, 0.0f};
         const int taps = (int)a.sample_count;

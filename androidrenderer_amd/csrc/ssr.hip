@@ -8,6 +8,7 @@
 // kVec: normals, lit and out are 8-byte aligned with pitches that are multiples of 8 — a texel is one 8-byte access, otherwise two dwords.
 #include <hip/hip_runtime.h>
 
+#include "dither.hpp"
 #include "launch.hpp"
 #include "numerics.hpp"
 
@@ -16,7 +17,6 @@ namespace sah {
 constexpr int kSsW = 32, kSsH = 8;  // the trace kernel's tile: four waves of 8 x 8
 constexpr float kSrInf = __builtin_inff();
 
-__constant__ float kSsrBayer[16] = {0.f, 8.f, 2.f, 10.f, 12.f, 4.f, 14.f, 6.f, 3.f, 11.f, 1.f, 9.f, 15.f, 7.f, 13.f, 5.f};
 
 namespace {
 SAH_DEV float ssr_clamp01(float a) { return a > 0.0f ? (a < 1.0f ? a : 1.0f) : 0.0f; }
@@ -100,7 +100,7 @@ template <bool kVec> __global__ void __launch_bounds__(256) k_ssr_trace(SsrArgs 
             r.dsx = s1x - r.s0x, r.dsy = s1y - r.s0y, r.dk = k1 - r.k0;
             const float ax = __builtin_fabsf(r.dsx), ay = __builtin_fabsf(r.dsy);
             r.L = ax > ay ? ax : ay;
-            r.jit = (a.flags & SAH_SSR_JITTER) ? kSsrBayer[(x & 3) + 4 * (y & 3)] * 0.0625f : 0.0f;
+            r.jit = (a.flags & SAH_SSR_JITTER) ? bayer4x4((uint32_t)x, (uint32_t)y) * 0.0625f : 0.0f;
             r.stride = a.stride, r.wf = (float)a.W, r.hf = (float)a.H;
             if ((ax < kSrInf) & (ay < kSrInf) & (r.L >= 1.0f) & (r.k0 < kSrInf)) {
                 const int steps = (int)a.max_steps;

@@ -179,7 +179,7 @@ class LightingInputs:
         return from_torch(lit, np.uint16)
 
 
-def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, stats_ptr=None, vrsaa=None, fused_motion=False):
+def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, stats_ptr=None, vrsaa=None, fused_motion=False, sun_shafts=None):
     """The rasterised part of a frame: sah_gbuffer_render into `gbuffer` (dict of device arrays: color, normals, data, emission, depth)
     and — only when a `motion_vectors` target (H, W, 2) int16 device array is given — sah_motion_vectors_render against the depth the
     G-buffer pass has just written, as the reference runs its motion-vectors phase after its depth pass (scene_renderer.cpp:308-316).
@@ -190,7 +190,13 @@ def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, sta
     (H, W, 2) int16 — the LAST frame's contrast image — and "shading_rate_image" (uint8, the extent of
     scene.shading_rate_image_extent); missing arrays are created, zeroed.  In the reference's order (scene_renderer.cpp:357-361, 476-481):
     the shading-rate image is made from the previous contrast image before the G-buffer pass, and this frame's contrast is measured into the
-    same array at the end, from the G-buffer's colour and depth.  Returns (contrast, shading_rate_image) then, None otherwise."""
+    same array at the end, from the G-buffer's colour and depth.  Returns (contrast, shading_rate_image) then, None otherwise.
+
+    `sun_shafts` (off by default): a dict with "pass" (a SunShafts), "sun" (the sah_sun_light_constants) and "shadowmap" (the cascades' device
+    array, or None), and optionally "lit", the (H, W, 4) int16 image Lighting made of an earlier G-buffer of this extent.  The volumetric sun
+    light is marched against the depth the G-buffer pass has just written — its place between Lighting and the anti-aliasing — and the
+    plane it returns is stored under "out".  Without "lit" the pass must carry SUN_SHAFTS_TERM_ONLY: "out" is then the term (S, T) for the
+    caller to apply once Lighting has run."""
     sri = contrast = None
     if vrsaa is not None:
         import torch
@@ -211,6 +217,8 @@ def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, sta
     if motion_vectors is not None and not fused_motion:
         ctx.motion_vectors_render(geometry, view_data, images.plane(gbuffer["depth"], _abi.FORMAT_D32_SFLOAT),
                                   images.plane(motion_vectors, _abi.FORMAT_R16G16_SFLOAT))
+    if sun_shafts is not None:
+        sun_shafts["out"] = sun_shafts["pass"](view_data, sun_shafts["sun"], sun_shafts.get("shadowmap"), gbuffer["depth"], sun_shafts.get("lit"))
     if vrsaa is not None:
         ctx.vrsaa_measure_aliasing(images.plane(gbuffer["color"], _abi.FORMAT_R8G8B8A8_SRGB), images.plane(gbuffer["depth"], _abi.FORMAT_D32_SFLOAT), contrast_p)
         return contrast, sri
@@ -460,6 +468,56 @@ class MotionBlur:
                              images.plane(self.tiles, rg16), images.plane(self.out, rgba16), p, rows)
         self.previous_jitter = (p.jitter[0], p.jitter[1])
         self.history_valid = True
+        return self.out
+
+
+class SunShafts:
+    """Volumetric sun light (include/sah_sun_shafts.h) between Lighting and the anti-aliasing: owns the plane with the shafts added and the
+    march plane, both re-created when a frame of another extent arrives or params.downscale was changed, and forms step_transmittance = exp(-extinction * step_length) —
+    the library itself never evaluates an exponential.  `settings` are fields of _abi.SunShaftsParams; unless given, the albedo is
+    Lighting's exposure constant (a white medium in lit's units).  Under SUN_SHAFTS_DITHER the dither offset steps by one every call, so
+    that a temporal resolve behind the pass averages the sixteen offsets.  Off by default: nothing creates one but the caller that wants
+    the shafts."""
+
+    def __init__(self, ctx, width, height, extinction=0.04, device="cuda", **settings):
+        self.ctx, self.device = ctx, device
+        settings.setdefault("albedo", (_abi.LIGHTING_EXPOSURE,) * 3)
+        given = "step_transmittance" in settings
+        self.params = _abi.SunShaftsParams.default(**settings)
+        self.extinction = None if given else extinction
+        if not given:
+            self.set_extinction(extinction)
+        self.calls = 0
+        self._allocate(width, height)
+
+    def set_extinction(self, extinction):
+        """extinction coefficient of the medium per view-space unit, >= 0"""
+        self.extinction = float(extinction)
+        self.params.step_transmittance = math.exp(-self.extinction * self.params.step_length)
+
+    def _allocate(self, width, height):
+        import torch
+        s = self.downscale = int(self.params.downscale)
+        self.width, self.height = width, height
+        self.out = torch.zeros((height, width, 4), dtype=torch.int16, device=self.device)
+        self.march = torch.zeros(((height + s - 1) // s, (width + s - 1) // s, 4), dtype=torch.int16, device=self.device)
+
+    def __call__(self, view_data, sun, shadowmap, depth, lit=None, rows=(0, 0)):
+        """depth (h, w) float32 and lit (h, w, 4) int16 (None under SUN_SHAFTS_TERM_ONLY) device arrays; shadowmap the cascades as a
+        (layers, H, W) device array, int16 for D16_UNORM or float32 for D32_SFLOAT, or None (every sample lit).  Returns the plane with the
+        shafts added, (h, w, 4) int16: the same array every call while the extent stays."""
+        import torch
+        p = self.params
+        if (int(depth.shape[1]), int(depth.shape[0]), int(p.downscale)) != (self.width, self.height, self.downscale):  # (params may be changed between calls)
+            self._allocate(int(depth.shape[1]), int(depth.shape[0]))
+        p.dither_offset = self.calls & 15 if p.flags & _abi.SUN_SHAFTS_DITHER else p.dither_offset
+        self.calls += 1
+        rgba16 = _abi.FORMAT_R16G16B16A16_SFLOAT
+        volume = None
+        if shadowmap is not None:
+            volume = images.volume(shadowmap, _abi.FORMAT_D32_SFLOAT if shadowmap.dtype == torch.float32 else _abi.FORMAT_D16_UNORM)
+        self.ctx.sun_shafts(view_data, sun, volume, images.plane(depth, _abi.FORMAT_D32_SFLOAT), None if lit is None else images.plane(lit, rgba16),
+                            images.plane(self.march, rgba16), images.plane(self.out, rgba16), p, rows)
         return self.out
 
 

@@ -71,6 +71,10 @@ SSR_EXPORTS = ["sah_ssr"]
 MOTION_BLUR_EXPORTS = ["sah_motion_blur"]
 MOTION_BLUR_TILE = 16         # SAH_MOTION_BLUR_TILE
 
+# volumetric sun light: exported, declared in include/sah_sun_shafts.h (not sah_hip.h)
+SUN_SHAFTS_EXPORTS = ["sah_sun_shafts"]
+SUN_SHAFTS_MAX_STEPS = 64     # SAH_SUN_SHAFTS_MAX_STEPS
+
 # variable-rate lighting and the VRSAA resolve: exported, declared in include/sah_vrs.h (not sah_hip.h)
 VRS_EXPORTS = ["sah_lighting_vrs", "sah_vrsaa_resolve"]
 
@@ -241,6 +245,8 @@ def load():
     lib.sah_sharpen.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.SharpenParams), C.c_uint32, C.c_uint32]
     lib.sah_ssr.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData)] + [C.POINTER(_abi.Plane)] * 8 + [C.POINTER(_abi.SsrParams), C.c_uint32, C.c_uint32]
     lib.sah_motion_blur.argtypes = [C.c_void_p] + [C.POINTER(_abi.Plane)] * 5 + [C.POINTER(_abi.MotionBlurParams), C.c_uint32, C.c_uint32]
+    lib.sah_sun_shafts.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData), C.POINTER(_abi.SunLightConstants), C.POINTER(_abi.Volume)] + [C.POINTER(_abi.Plane)] * 4 + \
+                                  [C.POINTER(_abi.SunShaftsParams), C.c_uint32, C.c_uint32]
     lib.sah_lighting_vrs.argtypes = [C.c_void_p, C.POINTER(_abi.LightingVrsDesc)]
     lib.sah_vrsaa_resolve.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
     lib.sah_mip_chain_generate.argtypes =[C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32]
@@ -506,6 +512,16 @@ class Context:
         memory.  out overlaps nothing, tiles no input.  params an _abi.MotionBlurParams.  rows (begin, end) of `out`, (0, 0) = all."""
         self._check(self.lib.sah_motion_blur(self.handle, C.byref(scene), C.byref(depth), C.byref(motion_vectors), C.byref(tiles), C.byref(out),
                                              C.byref(params), rows[0], rows[1]))
+
+    def sun_shafts(self, view_data, sun, shadowmap, depth, lit, march, out, params, rows=(0, 0)):
+        """sah_sun_shafts (include/sah_sun_shafts.h): view_data an _abi.ViewData, sun an _abi.SunLightConstants, shadowmap the _abi.Volume
+        lighting() takes in CSM mode or None (every sample lit); depth D32_SFLOAT, lit and out R16G16B16A16_SFLOAT, w x h; march
+        R16G16B16A16_SFLOAT scratch, ceil(w / s) x ceil(h / s), written by the call; _abi.Plane of device memory.  lit may be None under
+        SUN_SHAFTS_TERM_ONLY.  params an _abi.SunShaftsParams.  rows (begin, end) of `out`, (0, 0) = all."""
+        def ref(o):
+            return None if o is None else C.byref(o)
+        self._check(self.lib.sah_sun_shafts(self.handle, ref(view_data), ref(sun), ref(shadowmap), ref(depth), ref(lit), ref(march), ref(out),
+                                            ref(params), rows[0], rows[1]))
 
     def lighting_vrs(self, desc, sri, texel_size, depth_tolerance):
         """sah_lighting_vrs (include/sah_vrs.h): desc the _abi.LightingDesc lighting() takes, sri the R8_UINT shading-rate image (_abi.Plane of

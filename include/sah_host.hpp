@@ -42,6 +42,7 @@
 #include "sah_ssao.h"
 #include "sah_motion_blur.h"
 #include "sah_ssr.h"
+#include "sah_sun_shafts.h"
 #include "sah_taa.h"
 #include "sah_taa_upscale.h"
 #include "sah_vrsaa.h"
@@ -1685,6 +1686,65 @@ public:
 private:
     ResourceAllocator& allocator;
     TextureHandle blurred = nullptr, tiles = nullptr;
+};
+
+// The settings of SunShafts below; the defaults are the header's (include/sah_sun_shafts.h), with the medium given as an extinction
+// coefficient — the library takes the share of light one step lets through and never evaluates an exponential — and the albedo in
+// Lighting's units (a white medium: Lighting's exposure constant).
+struct SunShaftsSettings {
+    float extinction = 0.04f;  // per view-space unit
+    float step_length = SAH_SUN_SHAFTS_DEFAULT_STEP_LENGTH;
+    uint32_t num_steps = SAH_SUN_SHAFTS_DEFAULT_NUM_STEPS;
+    float albedo[3] = {0.00031415927f, 0.00031415927f, 0.00031415927f};
+    float ambient[3] = {SAH_SUN_SHAFTS_DEFAULT_AMBIENT, SAH_SUN_SHAFTS_DEFAULT_AMBIENT, SAH_SUN_SHAFTS_DEFAULT_AMBIENT};
+    float anisotropy = SAH_SUN_SHAFTS_DEFAULT_ANISOTROPY;
+    float depth_bias = SAH_SUN_SHAFTS_DEFAULT_DEPTH_BIAS;
+    float depth_sharpness = SAH_SUN_SHAFTS_DEFAULT_DEPTH_SHARPNESS;
+    uint32_t downscale = SAH_SUN_SHAFTS_DEFAULT_DOWNSCALE;
+    bool dither = false;  // SAH_SUN_SHAFTS_DITHER, the offset stepping by one every frame
+    float step_transmittance() const { return std::exp(-extinction * step_length); }
+};
+
+// Volumetric sun light (include/sah_sun_shafts.h; builder-owned: the reference leaves the medium between camera and geometry out) between
+// the Lighting pass and the anti-aliasing.  Owns the texture with the shafts added and the march plane of ceil(w / s) x ceil(h / s),
+// (re-)created when the frame's extent or the downscale changes.  render records the pass ("Sun shafts") and returns the texture; the
+// cascades are the sun's own shadow map (none: every sample is lit).  Off unless a caller constructs one and calls it: no existing phase
+// uses it.
+class SunShafts {
+public:
+    SunShaftsSettings settings;
+    explicit SunShafts(ResourceAllocator& allocator_in) : allocator(allocator_in) {}
+    TextureHandle get_output() const { return output; }
+    TextureHandle get_march() const { return march; }
+    TextureHandle render(RenderGraph& graph, const SceneView& view, const DirectionalLight& sun, TextureHandle depth, TextureHandle lit_scene) {
+        if (!depth || !lit_scene || (settings.downscale != 1 && settings.downscale != 2)) {
+            graph.add_pass(hip_pass("Sun shafts", [](sah_ctx*) { return (int)SAH_ERR_INVALID_ARGUMENT; }));
+            return nullptr;
+        }
+        const uint32_t w = depth->desc.width, h = depth->desc.height, s = settings.downscale;
+        const uint32_t mw = (w + s - 1) / s, mh = (h + s - 1) / s;
+        if (!output || output->desc.width != w || output->desc.height != h) output = allocator.create_texture("Lit scene with sun shafts", SAH_FORMAT_R16G16B16A16_SFLOAT, w, h);
+        if (!march || march->desc.width != mw || march->desc.height != mh) march = allocator.create_texture("Sun shafts march", SAH_FORMAT_R16G16B16A16_SFLOAT, mw, mh);
+        TextureHandle target = output, scratch = march;
+        const SunShaftsSettings st = settings;
+        const uint32_t offset = frame_index++ & 15u;
+        graph.add_pass(hip_pass("Sun shafts", [=, &view, &sun](sah_ctx* ctx) {
+                            sah_sun_shafts_params p{};
+                            p.step_length = st.step_length, p.num_steps = st.num_steps, p.step_transmittance = st.step_transmittance();
+                            for (int i = 0; i < 3; i++) p.albedo[i] = st.albedo[i], p.ambient[i] = st.ambient[i];
+                            p.anisotropy = st.anisotropy, p.depth_bias = st.depth_bias, p.depth_sharpness = st.depth_sharpness, p.downscale = st.downscale;
+                            p.dither_offset = st.dither ? offset : 0u, p.flags = st.dither ? SAH_SUN_SHAFTS_DITHER : 0u;
+                            const sah_plane z = depth->plane(), l = lit_scene->plane(), m = scratch->plane(), o = target->plane();
+                            return sah_sun_shafts(ctx, &view.get_gpu_data(), &sun.get_constants(), sun.shadowmap_handle ? &sun.shadowmap_handle->desc : nullptr, &z, &l, &m,
+                                                  &o, &p, 0, 0);
+                        }));
+        return output;
+    }
+
+private:
+    ResourceAllocator& allocator;
+    TextureHandle output = nullptr, march = nullptr;
+    uint32_t frame_index = 0;
 };
 
 // ---- LightingPhase (RenderCore/render/phase/lighting_phase.hpp:17-57, .cpp:34-134) -------------------------------------
