@@ -238,6 +238,7 @@ class ProbeAtlases(C.Structure):  # sah_probe_atlases
 
 
 PRIMITIVE_TYPE_SOLID, PRIMITIVE_TYPE_CUTOUT = 0, 1
+PRIMITIVE_TYPE_TRANSLUCENT = 2  # SAH_PRIMITIVE_TYPE_TRANSLUCENT (include/sah_translucent.h): drawn by sah_translucent_render only
 RASTER_STATS_WORDS = 8
 RT_STATS_WORDS = 4
 IPC_HANDLE_BYTES = 128
@@ -354,6 +355,10 @@ class LightingDesc(C.Structure):
 class LightingVrsDesc(C.Structure):  # sah_lighting_vrs_desc (include/sah_vrs.h)
     _fields_ = [("lighting", C.POINTER(LightingDesc)), ("shading_rate_image", C.POINTER(Plane)), ("texel_size", C.c_uint32 * 2),
                 ("depth_tolerance", C.c_float)]
+
+
+class TranslucentDesc(C.Structure):  # sah_translucent_desc (include/sah_translucent.h)
+    _fields_ = [("lighting", C.POINTER(LightingDesc)), ("scene", C.POINTER(SceneGeometry)), ("stats", C.c_void_p)]
 
 
 class ChainPlan(C.Structure):  # sah_chain_plan

@@ -8,8 +8,10 @@
 #include "../../include/sah_hip.h"
 #include "../../include/sah_gbuffer_motion.h"
 #include "../../include/sah_motion_vectors.h"
+#include "../../include/sah_translucent.h"
 #include "ctx.hpp"
 #include "launch.hpp"
+#include "lighting_stages.hpp"
 
 namespace {
 constexpr uint32_t kTile = sah::kRasterTile;
@@ -84,12 +86,14 @@ PassScratch scratch_of(sah::RasterPass pass, const sah_scene_geometry* scene) {
         // the fused pass owns both attribute buffers, and a merge cell and a ticket per tile stage
         case sah::RasterPass::GBufferMotion:
             return {{{S_ATTRS, sizeof(sah::RasterAttr)}, {S_MOTION, sizeof(sah::MotionAttr)}}, {sizeof(unsigned long long), sizeof(uint32_t)}, true};
+        // the translucent pass peels its lists whole: no merge cells
+        case sah::RasterPass::Translucent: return {{{S_ATTRS, sizeof(sah::RasterAttr)}, {S_MOTION, 0}}, {0, 0}, true};
     }
     return {};
 }
 
 // Runs both stages; grows the scratch buffers and repeats the pass when a guess was too small.
-int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, sah::RasterPass pass, uint32_t* stats) {
+int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, sah::RasterPass pass, uint32_t* stats, const sah::TranslucentShade* translucent = nullptr) {
     using namespace sah;  // Counter
     auto& r = ctx->raster;
     a.pass = pass;
@@ -155,7 +159,10 @@ int run(sah_ctx* ctx, sah::RasterArgs& a, const sah_scene_geometry* scene, sah::
         a.merge_seq = motion_cells ? (uint32_t*)((uint8_t*)r.buf[S_MERGE].ptr + (stages == 2 ? slot_cells * ps.cell_bytes[0] : 0)) : nullptr;
         a.motion_tickets = stages == 2 ? a.tickets + a.merge_capacity : nullptr;
         HIP_TRY(ctx, launch_raster_setup(a, ctx->stream));
-        HIP_TRY(ctx, launch_raster_tiles(a, ctx->stream));
+        // (the translucent tile stage blends, so it must not run twice: its workgroups look at the counts themselves and leave the lit image
+        //  alone in an attempt that the code below will repeat or fail — raster_tiles.hip: translucent_attempt_counts)
+        if (translucent) HIP_TRY(ctx, launch_translucent_tiles(a, *translucent, ctx->stream));
+        else HIP_TRY(ctx, launch_raster_tiles(a, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(r.host_counters, a.counters, C_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         const uint32_t report[4] = {(uint32_t)attempt + 1u, a.record_capacity, a.clip_capacity, a.pairs_capacity};
@@ -375,6 +382,60 @@ int sah_motion_vectors_render(sah_ctx* ctx, const sah_scene_geometry* scene, con
     fill_extent(a, W, H);
     fill_motion(a, view, depth, motion_vectors);
     return run(ctx, a, scene, sah::RasterPass::Motion, stats);
+}
+
+// sah_translucent.h: the primitives of type TRANSLUCENT, set up as the G-buffer pass sets them up, peeled per tile in draw order, every fragment
+// lit by the restatement of sah_lighting and blended into the lit image
+int sah_translucent_render(sah_ctx* ctx, const sah_translucent_desc* desc) {
+    SAH_RANGE();
+    using namespace sah;
+    if (!ctx) return SAH_ERR_INVALID_ARGUMENT;
+    if (!desc || !desc->lighting || !desc->scene) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "translucent_render: desc, its lighting desc and its scene are required");
+    const sah_lighting_desc* d = desc->lighting;
+    const sah_scene_geometry* scene = desc->scene;
+    TranslucentShade t{};
+    LightingCall call;
+    SkyArgs sky;
+    if (const int rc = lighting_targets(ctx, d, call, t.lighting); rc != SAH_OK) return rc;
+    if (call.sun_mode == SAH_SHADOW_MODE_RT) return fail(ctx, SAH_ERR_UNSUPPORTED, "translucent_render: the ray-traced sun has no shadow mask for a translucent fragment (off and CSM are supported)");
+    if (call.gi_kind == SAH_GI_CACHE || call.gi_kind == SAH_GI_RTGI)
+        return fail(ctx, SAH_ERR_UNSUPPORTED, "translucent_render: GI kind %u does not light translucent fragments (none and LPV do)", call.gi_kind);
+    if (d->lights && d->lights->count) return fail(ctx, SAH_ERR_UNSUPPORTED, "translucent_render: a light list does not light translucent fragments");
+    if (const int rc = lighting_csm(ctx, d, call, t.csm); rc != SAH_OK) return rc;
+    if (const int rc = lighting_gi_lpv(ctx, d, call, t.lpv); rc != SAH_OK) return rc;
+    if (const int rc = lighting_sky(ctx, d, sky); rc != SAH_OK) return rc;  // (validated as sah_lighting validates it; a fragment is never sky)
+    t.sun_mode = call.sun_mode;
+    t.gi_kind = call.gi_kind;
+    if (!geometry_ok(scene, true)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "translucent_render: bad scene");
+    if (call.W > kMaxExtent || call.H > kMaxExtent) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "translucent_render: extent must be 1..%u", kMaxExtent);
+    const sah_gbuffer& g = *d->gbuffer;
+    if (((uintptr_t)g.depth.ptr % 4) || (g.depth.row_pitch_bytes % 4) || ((uintptr_t)d->lit->ptr % 8) || (d->lit->row_pitch_bytes % 8))
+        return fail(ctx, SAH_ERR_UNSUPPORTED_FORMAT, "translucent_render: the depth plane must be 4-byte aligned and lit 8-byte aligned, pitches included");
+    // lit is read and written in place: it must not share memory with a plane the call reads
+    const auto span = [](const sah_plane& p, uint32_t bpp, uintptr_t& b, uintptr_t& e) {
+        b = (uintptr_t)p.ptr;
+        e = b + (uint64_t)(p.height - 1) * p.row_pitch_bytes + (uint64_t)p.width * bpp;
+    };
+    uintptr_t lb, le;
+    span(*d->lit, 8, lb, le);
+    const struct { const sah_plane* p; uint32_t bpp; } inputs[5] = {{&g.color, 4}, {&g.normals, 8}, {&g.data, 4}, {&g.emission, 4}, {&g.depth, 4}};
+    for (const auto& in : inputs) {
+        uintptr_t b, e;
+        span(*in.p, in.bpp, b, e);
+        if (lb < e && b < le) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "translucent_render: lit overlaps a plane of the G-buffer");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, sah_guard_touch(ctx, ctx->guard_raster));
+    if (int rc = ensure_srgb_table(ctx); rc != SAH_OK) return rc;
+    RasterArgs a{};
+    fill_scene(ctx, a, scene);
+    a.num_views = 1;
+    a.shader_mip_bias = d->view->material_texture_mip_bias;
+    std::memcpy(a.view_matrix, d->view->view, 64);
+    std::memcpy(a.clip_matrix[0], d->view->projection, 64);
+    fill_extent(a, call.W, call.H);
+    a.half_to_srgb8 = ctx->raster.half_to_srgb8;
+    return run(ctx, a, scene, RasterPass::Translucent, desc->stats, &t);
 }
 
 // Debug / test hook: how the last rasteriser call of the context (shadow, G-buffer, RSM, motion vectors or the fused pass) went through run() — recorded

@@ -242,6 +242,15 @@ hipError_t launch_probe_update(const ProbeAtlasArgs& atl, const VolumeArg& trace
 hipError_t launch_raster_setup(const RasterArgs& a, hipStream_t st);
 void launch_raster_fill_bins(const RasterArgs& a, hipStream_t st);  // raster_setup.hip's k_bin<fill>, first kernel of launch_raster_tiles
 hipError_t launch_raster_tiles(const RasterArgs& a, hipStream_t st);
+// the tile stage of RasterPass::Translucent (sah_translucent.h): what sah_lighting's stages made of the frame's Lighting descriptor, which
+// lights every fragment; `lighting` also names the lit image, the depth plane tested against and the row range
+struct TranslucentShade {
+    LightingArgs lighting;
+    CsmArgs csm;
+    LpvArgs lpv;
+    uint32_t sun_mode, gi_kind;  // off or CSM; none or LPV
+};
+hipError_t launch_translucent_tiles(const RasterArgs& a, const TranslucentShade& t, hipStream_t st);
 
 // --- rt.hip
 hipError_t launch_rt_scan(const sah_primitive* prims, uint32_t n, uint32_t* tri_base, RtBuildState* st, hipStream_t s);

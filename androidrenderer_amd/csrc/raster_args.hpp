@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/sah_hip.h"
+#include "../../include/sah_translucent.h"
 #include "params.hpp"
 
 #ifndef SAH_RASTER_TILE
@@ -29,6 +30,10 @@ enum class RasterPass : uint32_t {
     // then a second tile stage with the motion target over the same bin lists (mv_depth = out_depth), with tickets and a merge buffer of
     // its own (motion_tickets, merge_seq)
     GBufferMotion,
+    // sah_translucent_render (sah_translucent.h): the primitives of type SAH_PRIMITIVE_TYPE_TRANSLUCENT only — the scan counts no triangle of
+    // another type, so `seq` numbers the translucent triangles alone —, RasterAttr as the G-buffer pass writes it, no face culling; the tile
+    // stage peels every list by `seq` and blends into the lit image (raster_tiles.hip: k_translucent_tiles), lists never split
+    Translucent,
 };
 
 // RasterArgs::counters.  C_STATS .. C_STATS + 7 mirror SAH_RASTER_STATS_WORDS (C_EXTRA and C_HEAVY are statistics words 5 and 6).

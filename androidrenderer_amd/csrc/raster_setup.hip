@@ -108,6 +108,12 @@ __global__ __launch_bounds__(1024) void k_exclusive_scan(const sah_primitive* pr
     block_exclusive_scan<8>(n, [=](uint32_t i) { return prims ? prims[i].index_count / 3u : values[i]; }, out, total);
 }
 
+// the scan of the translucent pass: a primitive of another type contributes no triangle, so it owns no work item, no record and no
+// sequence number (find_primitive never lands on a primitive without triangles)
+__global__ __launch_bounds__(1024) void k_exclusive_scan_of_type(const sah_primitive* prims, uint32_t type, uint32_t n, uint32_t* out, uint32_t* total) {
+    block_exclusive_scan<8>(n, [=](uint32_t i) { return prims[i].type == type ? prims[i].index_count / 3u : 0u; }, out, total);
+}
+
 // ---- K1: vertex stage, clipping, fan, snapping, culling -> records ----------------------------------------------------------------
 // the half-precision varyings of one vertex (gltf_basic_pbr.slang:134-143): colour, normalize(model3x3 * normal), tangent
 SAH_DEV void rotate_normalize(const float* m, const float v[3], uint16_t out[3]) {
@@ -439,11 +445,16 @@ hipError_t launch_raster_setup(const RasterArgs& a, hipStream_t st) {
     if (e != hipSuccess) return e;
     if (a.num_primitives == 0) return hipSuccess;
     if (a.textures) hipLaunchKernelGGL(k_check_textures, dim3((a.num_textures + a.num_materials + 255u) / 256u), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, st, a.primitives, (const uint32_t*)nullptr, a.num_primitives, a.tri_base, &a.counters[C_TRIS]);
+    if (a.pass == RasterPass::Translucent)
+        hipLaunchKernelGGL(k_exclusive_scan_of_type, dim3(1), dim3(1024), 0, st, a.primitives, (uint32_t)SAH_PRIMITIVE_TYPE_TRANSLUCENT, a.num_primitives, a.tri_base,
+                           &a.counters[C_TRIS]);
+    else
+        hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, st, a.primitives, (const uint32_t*)nullptr, a.num_primitives, a.tri_base, &a.counters[C_TRIS]);
     switch (a.pass) {
         case RasterPass::Shadow: launch_setup_kernels<ShadowAttr>(a, st); break;
         case RasterPass::GBuffer:
-        case RasterPass::Rsm: launch_setup_kernels<RasterAttr>(a, st); break;
+        case RasterPass::Rsm:
+        case RasterPass::Translucent: launch_setup_kernels<RasterAttr>(a, st); break;
         case RasterPass::Motion: launch_setup_kernels<MotionAttr>(a, st); break;
         case RasterPass::GBufferMotion: launch_setup_kernels<RasterAttr, true>(a, st); break;
     }

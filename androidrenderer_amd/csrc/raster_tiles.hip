@@ -2,7 +2,9 @@
 // of a long bin list, resolves visibility in LDS — sweeping 8x8 pixel blocks with exact fp64 edge functions (raster_common.hpp) — then
 // shades and writes its tile once, coalesced.  ONE tile kernel serves the four passes: what a pass does with a covered pixel, what
 // it keeps per pixel and how it turns that into images is its *target* (ShadowTarget, GBufferTarget — RSM included —, MotionTarget);
-// the walk over the bin list, the split-list merge and the look-up from a sequence number to its record are written once.
+// the walk over the bin list, the split-list merge and the look-up from a sequence number to its record are written once.  The translucent
+// pass (sah_translucent.h) has a tile kernel of its own at the end of the file, which keeps every fragment of a pixel where the targets
+// keep one: it reuses the walk, the look-up and the G-buffer's fragment stage as they are.
 //   reference for the fragment stages: RenderCore/shaders/materials/gltf_basic_pbr.slang:169-253, RenderCore/render/material_pipelines.cpp:13-140,
 //              RenderCore/render/phase/motion_vectors_phase.cpp:55-103
 #include <hip/hip_runtime.h>
@@ -11,6 +13,7 @@
 #include <type_traits>
 
 #include "launch.hpp"
+#include "lighting_common.hpp"
 #include "numerics.hpp"
 #include "raster_args.hpp"
 #include "raster_common.hpp"
@@ -99,10 +102,11 @@ SAH_DEV void material_texel(const RasterArgs& a, uint32_t index, const float (&c
     for (int c = 0; c < 4; c++) out[c] = Hn(texel[c]);
 }
 
-// fragment stage of the winning triangle (gltf_basic_pbr.slang:169-253, SAH_MAIN_VIEW, constant textures)
-template <bool TEX>
-SAH_DEV void shade_and_store(const RasterArgs& a, const EdgeSetup& e, const RasterAttr& at, const sah_material& m, const sah_material_textures& mt, int32_t px,
-                             int32_t py, float z) {
+// fragment stage of one triangle at one pixel (gltf_basic_pbr.slang:169-253, SAH_MAIN_VIEW, constant textures): what it writes to the four
+// colour targets, in their formats, goes to sink(colour, normals, data, emission)
+template <bool TEX, class Sink>
+SAH_DEV void fragment_stage(const RasterArgs& a, const EdgeSetup& e, const RasterAttr& at, const sah_material& m, const sah_material_textures& mt, int32_t px,
+                            int32_t py, Sink&& sink) {
     double v[3];
     float b[3], lambda[3];
     cover(e, px, py, v);
@@ -147,11 +151,19 @@ SAH_DEV void shade_and_store(const RasterArgs& a, const EdgeSetup& e, const Rast
     uint2 nbits;
     nbits.x = (uint32_t)__builtin_bit_cast(uint16_t, n_out[0].v) | ((uint32_t)__builtin_bit_cast(uint16_t, n_out[1].v) << 16);
     nbits.y = (uint32_t)__builtin_bit_cast(uint16_t, n_out[2].v);
-    *(uint32_t*)(a.out_color.ptr + (size_t)py * a.out_color.pitch + (size_t)px * 4) = color_bits;
-    *(uint2*)(a.out_normals.ptr + (size_t)py * a.out_normals.pitch + (size_t)px * 8) = nbits;
-    *(uint32_t*)(a.out_data.ptr + (size_t)py * a.out_data.pitch + (size_t)px * 4) = data_bits;
-    *(uint32_t*)(a.out_emission.ptr + (size_t)py * a.out_emission.pitch + (size_t)px * 4) = emission_bits;
-    *(float*)(a.out_depth.ptr + (size_t)py * a.out_depth.pitch + (size_t)px * 4) = z;
+    sink(color_bits, nbits, data_bits, emission_bits);
+}
+// ... of the winning triangle of the G-buffer pass, stored with its depth
+template <bool TEX>
+SAH_DEV void shade_and_store(const RasterArgs& a, const EdgeSetup& e, const RasterAttr& at, const sah_material& m, const sah_material_textures& mt, int32_t px,
+                             int32_t py, float z) {
+    fragment_stage<TEX>(a, e, at, m, mt, px, py, [&](uint32_t color_bits, uint2 nbits, uint32_t data_bits, uint32_t emission_bits) {
+        *(uint32_t*)(a.out_color.ptr + (size_t)py * a.out_color.pitch + (size_t)px * 4) = color_bits;
+        *(uint2*)(a.out_normals.ptr + (size_t)py * a.out_normals.pitch + (size_t)px * 8) = nbits;
+        *(uint32_t*)(a.out_data.ptr + (size_t)py * a.out_data.pitch + (size_t)px * 4) = data_bits;
+        *(uint32_t*)(a.out_emission.ptr + (size_t)py * a.out_emission.pitch + (size_t)px * 4) = emission_bits;
+        *(float*)(a.out_depth.ptr + (size_t)py * a.out_depth.pitch + (size_t)px * 4) = z;
+    });
 }
 
 // RSM fragment stage of the winning triangle (gltf_basic_pbr.slang:169-253, SAH_RSM): flux = Fd(surface, -sun direction, normal) with
@@ -683,7 +695,151 @@ void launch_shared_motion_tiles(const RasterArgs& a, uint32_t ntiles, hipStream_
     hipLaunchKernelGGL(k_raster_tiles<SharedMotionTarget>, dim3(ntiles + a.extra_capacity), dim3(kTileThreads), 0, st, m);
 }
 
+// ---- translucent geometry over the lit scene (sah_translucent.h) ------------------------------------------------------------------------
+// Blending needs every fragment of a pixel, in draw order, where the cells above keep one winner.  One workgroup per tile peels its bin
+// list by sequence number: round k walks the WHOLE list (walk_list and sweep as they are) and keeps, per pixel, the smallest seq + 1 above
+// the one blended in round k - 1 among the fragments that pass the depth test — ds_min_u32, so the order of the list does not show —; the
+// resolve of the round rebuilds that fragment's texel (fragment_stage, the G-buffer's own), lights it with the general
+// restatement of sah_lighting (shade_pixel_general: no new shading arithmetic) and blends it into `lit`.  The workgroup owns its tile's
+// pixels: no global atomics.  Rounds end when no pixel of the tile found a fragment; a tile costs (list length) x (deepest pixel).
+// Lists are never split: a peel cannot be merged across workgroups without a barrier per layer.
+struct TranslucentTarget {
+    struct Cells {
+        uint32_t depth[kTile * kTile];   // the opaque depth texel's bits; a NaN for the pixels this call does not write
+        uint32_t done[kTile * kTile];    // seq + 1 of the fragment taken in the last round (0: none yet)
+        uint32_t merged[kTile * kTile];  // this round's: the smallest seq + 1 above `done` (~0: none)
+        uint16_t blended[kTile * kTile]; // fragments blended so far (statistics word 7), saturating
+    };
+    static SAH_DEV void fragment(const RasterArgs&, Cells& s, const EdgeSetup& e, uint32_t, int32_t, int32_t, const double*, uint32_t cell, float z) {
+        // reverse-Z GREATER, strict, no depth write; a NaN on either side compares false
+        if (z > __uint_as_float(s.depth[cell]) && e.seq + 1u > s.done[cell]) atomicMin(&s.merged[cell], e.seq + 1u);
+    }
+};
+
+// Blending is not idempotent, and the host repeats a pass whose scratch buffers were too small or fails one with a bad texture table
+// (api_raster.cpp: run): the tile stage of such an attempt must leave `lit` alone.  Every count the host will look at is final before this
+// stage starts, so the workgroups decide as the host will.
+SAH_DEV bool translucent_attempt_counts(const RasterArgs& a) {
+    const uint64_t tris = a.counters[C_TRIS];
+    return tris < (1u << 28) && a.counters[C_BAD_TEXTURE] == 0u && tris + a.counters[C_RECORDS] <= a.record_capacity &&
+           a.counters[C_CLIPPED] <= a.clip_capacity && a.counters[C_PAIRS] <= a.pairs_capacity && tris * 8u + 1u <= a.seq_capacity;
+}
+
+template <int SUN, int GI, bool TEX>
+__global__ __launch_bounds__(kTileThreads) void k_translucent_tiles(const RasterArgs a, const LightingArgs la, const CsmArgs csm, const LpvArgs lpv) {
+    __shared__ TranslucentTarget::Cells s;
+    __shared__ float s_lut[512];
+    __shared__ uint32_t s_deepest;
+    if (!translucent_attempt_counts(a)) return;
+    TileWork w;
+    w.tile = blockIdx.x;
+    w.part = 0;
+    w.parts = 1;
+    w.slot = ~0u;
+    w.view = 0;
+    w.tile_x = (int32_t)(w.tile % a.tiles_x) * kTile;
+    w.tile_y = (int32_t)(w.tile / a.tiles_x) * kTile;
+    w.begin = a.tile_offset[w.tile];
+    w.count = a.tile_count[w.tile];
+    // nothing to draw in this tile, or none of its rows in the range: no plane is read or written
+    if (w.count == 0u || (uint32_t)w.tile_y >= la.row_end || (uint32_t)w.tile_y + kTile <= la.row_begin) return;
+    for (uint32_t i = threadIdx.x; i < kTile * kTile; i += kTileThreads) {
+        const uint32_t px = (uint32_t)w.tile_x + i % kTile, py = (uint32_t)w.tile_y + i / kTile;
+        const bool mine = px < a.width && py >= la.row_begin && py < la.row_end;  // (row_end <= height)
+        s.depth[i] = mine ? *(const uint32_t*)(la.depth.ptr + (size_t)py * la.depth.pitch + (size_t)px * 4) : 0xffffffffu;
+        s.done[i] = 0u;
+        s.merged[i] = ~0u;
+        s.blended[i] = 0;
+    }
+    for (uint32_t i = threadIdx.x; i < 512u; i += kTileThreads) s_lut[i] = la.luts[i];
+    if (threadIdx.x == 0) s_deepest = 0u;
+    __syncthreads();
+    const SkyArgs sky{};  // (a fragment is a surface: the sky fill is compiled out)
+    uint32_t deepest = 0u;
+    for (;;) {
+        walk_list<TranslucentTarget>(a, w, s);  // (ends with a barrier)
+        bool found = false;
+        uint32_t cached = ~0u;
+        EdgeSetup e_c{};
+        RasterAttr at_c{};
+        sah_material m_c{};
+        sah_material_textures mt_c{};
+#pragma unroll 1
+        for (uint32_t i = threadIdx.x; i < kTile * kTile; i += kTileThreads) {
+            const uint32_t taken = s.merged[i];
+            if (taken == ~0u) continue;
+            found = true;
+            s.done[i] = taken;
+            s.merged[i] = ~0u;
+            const int32_t px = w.tile_x + (int32_t)(i % kTile), py = w.tile_y + (int32_t)(i / kTile);
+            const uint32_t r = record_of_seq(a, 0u, taken - 1u);
+            if (r != cached) {
+                cached = r;
+                e_c = edge_setup(a.records[r]);
+                at_c = a.attrs[r];
+                m_c = a.materials[min(at_c.material, a.num_materials - 1u)];
+                if (TEX) mt_c = textures_of(a, at_c.material);
+            }
+            Px p;  // the fragment's texel as the G-buffer would hold it
+            fragment_stage<TEX>(a, e_c, at_c, m_c, mt_c, px, py, [&](uint32_t color_bits, uint2 nbits, uint32_t data_bits, uint32_t emission_bits) {
+                p.color = color_bits;
+                p.data = data_bits;
+                p.emission = emission_bits;
+                p.n01 = nbits.x;
+                p.n23 = nbits.y;
+            });
+            const uint32_t code = p.color >> 24;
+            if (code == 0u) continue;  // alpha 0: skipped, not blended
+            p.depth = fragment_depth(e_c, px, py);
+            p.ao = 1.0f;
+            p.mask = 1.0f;
+            const uint2 src = shade_pixel_general<SUN, GI, false>(la, csm, lpv, sky, (uint32_t)px, (uint32_t)py, p, s_lut);
+            uint2* at = (uint2*)(const_cast<uint8_t*>(la.lit.ptr) + (size_t)py * la.lit.pitch + (size_t)px * 8);
+            const uint2 dst = *at;
+            // SRC_ALPHA / ONE_MINUS_SRC_ALPHA on colour and alpha alike, every operator rounded in fp32, stored as Lighting stores
+            const float alpha = s_lut[256u + code], rest = 1.0f - alpha;
+            const uint32_t sw[2] = {src.x, src.y}, dw[2] = {dst.x, dst.y};
+            uint32_t ow[2];
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const float lo = h2f((uint16_t)sw[k]) * alpha + h2f((uint16_t)dw[k]) * rest;
+                const float hi = h2f((uint16_t)(sw[k] >> 16)) * alpha + h2f((uint16_t)(dw[k] >> 16)) * rest;
+                ow[k] = (uint32_t)f2h(lo) | ((uint32_t)f2h(hi) << 16);
+            }
+            *at = make_uint2(ow[0], ow[1]);
+            const uint32_t n = min((uint32_t)s.blended[i] + 1u, 0xffffu);
+            s.blended[i] = (uint16_t)n;
+            deepest = max(deepest, n);
+        }
+        if (!__syncthreads_or(found)) break;
+    }
+    if (deepest) atomicMax(&s_deepest, deepest);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_deepest) atomicMax(&a.counters[C_STATS + 7], s_deepest);
+}
+
+template <int SUN, int GI>
+void launch_translucent(const RasterArgs& a, const TranslucentShade& t, uint32_t ntiles, hipStream_t st) {
+    if (a.textures) hipLaunchKernelGGL((k_translucent_tiles<SUN, GI, true>), dim3(ntiles), dim3(kTileThreads), 0, st, a, t.lighting, t.csm, t.lpv);
+    else hipLaunchKernelGGL((k_translucent_tiles<SUN, GI, false>), dim3(ntiles), dim3(kTileThreads), 0, st, a, t.lighting, t.csm, t.lpv);
+}
+
 }  // namespace
+
+// Stage 2 of the translucent pass: the bins, the sequence table, then the peel.  The list of every tile is walked whole (no k_split).
+hipError_t launch_translucent_tiles(const RasterArgs& a, const TranslucentShade& t, hipStream_t st) {
+    const uint32_t ntiles = a.tiles_x * a.tiles_y;
+    if (a.num_primitives == 0) return hipSuccess;
+    launch_raster_fill_bins(a, st);
+    hipLaunchKernelGGL(k_seq_table, dim3(64), dim3(256), 0, st, a);
+    const bool csm = t.sun_mode == SAH_SHADOW_MODE_CSM, lpv = t.gi_kind == SAH_GI_LPV;
+    if (csm && lpv) launch_translucent<SAH_SHADOW_MODE_CSM, SAH_GI_LPV>(a, t, ntiles, st);
+    else if (csm) launch_translucent<SAH_SHADOW_MODE_CSM, SAH_GI_NONE>(a, t, ntiles, st);
+    else if (lpv) launch_translucent<SAH_SHADOW_MODE_OFF, SAH_GI_LPV>(a, t, ntiles, st);
+    else launch_translucent<SAH_SHADOW_MODE_OFF, SAH_GI_NONE>(a, t, ntiles, st);
+    return hipGetLastError();
+}
+
 
 // Stage 2: fill the bins, rasterise and write the images.
 hipError_t launch_raster_tiles(const RasterArgs& a, hipStream_t st) {
@@ -708,6 +864,7 @@ hipError_t launch_raster_tiles(const RasterArgs& a, hipStream_t st) {
             else launch_tile_kernels<GBufferTarget<false>, KeyAndSeqCell>(a, ntiles, st);
             launch_shared_motion_tiles(a, ntiles, st);
             break;
+        case RasterPass::Translucent: break;  // (its tile stage needs the Lighting blocks: launch_translucent_tiles)
     }
     return hipGetLastError();
 }

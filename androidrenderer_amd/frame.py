@@ -179,7 +179,8 @@ class LightingInputs:
         return from_torch(lit, np.uint16)
 
 
-def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, stats_ptr=None, vrsaa=None, fused_motion=False, sun_shafts=None):
+def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, stats_ptr=None, vrsaa=None, fused_motion=False, sun_shafts=None,
+                     translucent=None):
     """The rasterised part of a frame: sah_gbuffer_render into `gbuffer` (dict of device arrays: color, normals, data, emission, depth)
     and — only when a `motion_vectors` target (H, W, 2) int16 device array is given — sah_motion_vectors_render against the depth the
     G-buffer pass has just written, as the reference runs its motion-vectors phase after its depth pass (scene_renderer.cpp:308-316).
@@ -196,7 +197,14 @@ def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, sta
     array, or None), and optionally "lit", the (H, W, 4) int16 image Lighting made of an earlier G-buffer of this extent.  The volumetric sun
     light is marched against the depth the G-buffer pass has just written — its place between Lighting and the anti-aliasing — and the
     plane it returns is stored under "out".  Without "lit" the pass must carry SUN_SHAFTS_TERM_ONLY: "out" is then the term (S, T) for the
-    caller to apply once Lighting has run."""
+    caller to apply once Lighting has run.
+
+    `translucent` (off by default): a dict with "pass" (a Translucency), "geometry" (the sah_scene_geometry of the translucent primitives,
+    back to front) and "lighting" (a callable taking the G-buffer dict this function has just filled and returning the frame's
+    sah_lighting_desc — or (desc, keepalive) — over it, its `lit` plane being the image to end up in).  `geometry`, the positional argument,
+    is then the scene WITHOUT its type-2 primitives (mesh.split_translucent): the G-buffer and motion-vectors passes see the opaque half
+    only, as sah_rt_build must.  After the raster passes the frame's Lighting pass runs — sah_lighting with that descriptor — and the
+    translucent primitives are blended into its `lit` (include/sah_translucent.h), before the sun shafts."""
     sri = contrast = None
     if vrsaa is not None:
         import torch
@@ -217,6 +225,11 @@ def rasterised_frame(ctx, geometry, view_data, gbuffer, motion_vectors=None, sta
     if motion_vectors is not None and not fused_motion:
         ctx.motion_vectors_render(geometry, view_data, images.plane(gbuffer["depth"], _abi.FORMAT_D32_SFLOAT),
                                   images.plane(motion_vectors, _abi.FORMAT_R16G16_SFLOAT))
+    if translucent is not None:
+        made = translucent["lighting"](gbuffer)
+        desc, translucent["keep"] = made if isinstance(made, tuple) else (made, None)
+        ctx.lighting(desc)
+        translucent["pass"](desc, translucent["geometry"])
     if sun_shafts is not None:
         sun_shafts["out"] = sun_shafts["pass"](view_data, sun_shafts["sun"], sun_shafts.get("shadowmap"), gbuffer["depth"], sun_shafts.get("lit"))
     if vrsaa is not None:
@@ -519,6 +532,34 @@ class SunShafts:
         self.ctx.sun_shafts(view_data, sun, volume, images.plane(depth, _abi.FORMAT_D32_SFLOAT), None if lit is None else images.plane(lit, rgba16),
                             images.plane(self.march, rgba16), images.plane(self.out, rgba16), p, rows)
         return self.out
+
+
+class Translucency:
+    """Alpha-blended geometry over the lit scene (include/sah_translucent.h), after Lighting (and after the screen-space reflections, where
+    they write into lit's place) and before the sun shafts and the anti-aliasing.  Owns the statistics words of the last call.  Calling it
+    blends the primitives of type PRIMITIVE_TYPE_TRANSLUCENT of `geometry` — the translucent half of mesh.split_translucent, ordered by
+    mesh.sort_back_to_front — into the `lit` plane of `lighting_desc`, the frame's own _abi.LightingDesc, each fragment lit by that
+    descriptor.  Off by default: nothing creates one but the caller that wants translucent geometry drawn."""
+
+    def __init__(self, ctx, device="cuda"):
+        import torch
+        self.ctx = ctx
+        self.stats = torch.zeros(_abi.RASTER_STATS_WORDS, dtype=torch.int32, device=device)
+
+    def __call__(self, lighting_desc, geometry, rows=None):
+        """rows: (begin, end) to blend a band of the frame only (None: the descriptor's own range)"""
+        if rows is not None:
+            saved = lighting_desc.row_begin, lighting_desc.row_end
+            lighting_desc.row_begin, lighting_desc.row_end = rows
+        try:
+            self.ctx.translucent_render(lighting_desc, geometry, self.stats.data_ptr())
+        finally:
+            if rows is not None:
+                lighting_desc.row_begin, lighting_desc.row_end = saved
+
+    def deepest_pixel(self):
+        """the most fragments the last call blended at one pixel (a read-back: synchronises)"""
+        return int(self.stats[7].item())
 
 
 class VrsaaFrame:

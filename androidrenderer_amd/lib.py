@@ -78,6 +78,9 @@ SUN_SHAFTS_MAX_STEPS = 64     # SAH_SUN_SHAFTS_MAX_STEPS
 # variable-rate lighting and the VRSAA resolve: exported, declared in include/sah_vrs.h (not sah_hip.h)
 VRS_EXPORTS = ["sah_lighting_vrs", "sah_vrsaa_resolve"]
 
+# alpha-blended geometry over the lit scene: exported, declared in include/sah_translucent.h (not sah_hip.h)
+TRANSLUCENT_EXPORTS = ["sah_translucent_render"]
+
 # the mip-chain generator: exported, declared in include/sah_mip_chain.h (not sah_hip.h)
 MIP_CHAIN_EXPORTS = ["sah_mip_chain_generate"]
 MIP_CHAIN_MAX_LEVELS = 12     # SAH_MIP_CHAIN_MAX_LEVELS
@@ -248,6 +251,7 @@ def load():
     lib.sah_sun_shafts.argtypes = [C.c_void_p, C.POINTER(_abi.ViewData), C.POINTER(_abi.SunLightConstants), C.POINTER(_abi.Volume)] + [C.POINTER(_abi.Plane)] * 4 + \
                                   [C.POINTER(_abi.SunShaftsParams), C.c_uint32, C.c_uint32]
     lib.sah_lighting_vrs.argtypes = [C.c_void_p, C.POINTER(_abi.LightingVrsDesc)]
+    lib.sah_translucent_render.argtypes = [C.c_void_p, C.POINTER(_abi.TranslucentDesc)]
     lib.sah_vrsaa_resolve.argtypes = [C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32, C.c_uint32]
     lib.sah_mip_chain_generate.argtypes =[C.c_void_p, C.POINTER(_abi.Plane), C.POINTER(_abi.Plane), C.c_uint32]
     lib.sah_rt_refit.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.c_void_p]
@@ -522,6 +526,13 @@ class Context:
             return None if o is None else C.byref(o)
         self._check(self.lib.sah_sun_shafts(self.handle, ref(view_data), ref(sun), ref(shadowmap), ref(depth), ref(lit), ref(march), ref(out),
                                             ref(params), rows[0], rows[1]))
+
+    def translucent_render(self, desc, scene, stats_ptr=None):
+        """sah_translucent_render (include/sah_translucent.h): desc the _abi.LightingDesc of the frame (its lit plane is blended into, its depth
+        plane tested against), scene the _abi.SceneGeometry whose primitives of type PRIMITIVE_TYPE_TRANSLUCENT are drawn, back to front;
+        stats_ptr: device pointer to SAH_RASTER_STATS_WORDS words, or None."""
+        t = _abi.TranslucentDesc(C.pointer(desc), C.pointer(scene), C.c_void_p(stats_ptr))
+        self._check(self.lib.sah_translucent_render(self.handle, C.byref(t)))
 
     def lighting_vrs(self, desc, sri, texel_size, depth_tolerance):
         """sah_lighting_vrs (include/sah_vrs.h): desc the _abi.LightingDesc lighting() takes, sri the R8_UINT shading-rate image (_abi.Plane of

@@ -221,6 +221,42 @@ def to_device(arrays, device="cuda"):
     return out
 
 
+def split_translucent(arrays):
+    """(opaque, translucent): two scenes over the vertex, index, material and texture arrays of `arrays`, the first with the primitives of
+    type SOLID and CUTOUT — what the opaque passes and sah_rt_build are given, which do not look at a type-2 primitive's type and would draw
+    it as an opaque wall — and the second with those of type PRIMITIVE_TYPE_TRANSLUCENT, for sah_translucent_render
+    (include/sah_translucent.h).  Both keep the order of the list.  Without a translucent primitive the first holds the bytes of `arrays`."""
+    prims = arrays["primitives"]
+    is_t = prims["type"] == _abi.PRIMITIVE_TYPE_TRANSLUCENT
+    opaque, translucent = dict(arrays), dict(arrays)
+    opaque["primitives"] = np.ascontiguousarray(prims[~is_t])
+    translucent["primitives"] = np.ascontiguousarray(prims[is_t])
+    for part in (opaque, translucent):
+        part.pop("counts", None)
+    return opaque, translucent
+
+
+def sort_back_to_front(arrays, view):
+    """`arrays` with its primitives ordered for blending, farthest first: by the view-space depth of the centre of each primitive's
+    bounding box (of the vertices its index range names, in model space, carried through its model matrix and `view`, the column-major
+    world-to-view matrix of sah_view_data; the camera looks down -z, so the most negative z comes first).  Stable: primitives at one depth
+    keep their order.  On the host, in fp64, as the reference feeds draw_transparent()."""
+    view = np.asarray(view, dtype=np.float64).reshape(4, 4).T
+    prims = arrays["primitives"]
+    z = np.zeros(len(prims), np.float64)
+    for i, p in enumerate(prims):
+        idx = arrays["indices"][int(p["first_index"]):int(p["first_index"]) + int(p["index_count"])].astype(np.int64) + int(p["vertex_offset"])
+        if idx.size == 0:
+            continue
+        pos = arrays["positions"][idx].astype(np.float64)
+        centre = np.append((pos.min(axis=0) + pos.max(axis=0)) * 0.5, 1.0)
+        model = p["model"].astype(np.float64).reshape(4, 4).T
+        z[i] = (view @ (model @ centre))[2]
+    out = dict(arrays)
+    out["primitives"] = np.ascontiguousarray(prims[np.argsort(z, kind="stable")])
+    return out
+
+
 def emissive_primitives(arrays):
     """[(primitive index, ordinal of its index range)] of every primitive whose material is emissive — length(emission_factor.rgb) > 0
     in fp32 or an emission texture (gltf_model.cpp:210-213, 264-276) — in primitive order.  Primitives drawing the same index range
@@ -273,14 +309,20 @@ _ATRIUM_ROUGH = [0.65, 0.8, 0.7, 0.5, 0.4, 0.3]
 _ATRIUM_METAL = [0.0, 0.0, 0.0, 0.1, 0.0, 0.9]
 
 
-def atrium(subdiv=1):
-    """The procedural atrium as a mesh: one primitive per box (12 * subdiv^2 triangles each), six materials, emissive lamps."""
+def atrium(subdiv=1, translucent_fraction=0.0):
+    """The procedural atrium as a mesh: one primitive per box (12 * subdiv^2 triangles each), six materials, emissive lamps.
+    translucent_fraction (default 0: the mesh is what it always was): that share of the boxes, evenly spread over the list, becomes glass
+    — type PRIMITIVE_TYPE_TRANSLUCENT with a seventh, half-transparent material."""
     m = Mesh()
     for i in range(6):
         emission = (1.0, 0.67, 0.4, 0.0) if i == 5 else (0, 0, 0, 0)
         m.add_material(material(base=_ATRIUM_BASE[i] + (1.0,), rough=_ATRIUM_ROUGH[i], metal=_ATRIUM_METAL[i], emission=emission))
-    for bmin, bmax, mat in synth._atrium_boxes():
-        m.add_box(bmin, bmax, mat, subdiv=subdiv)
+    glass = m.add_material(material(base=(0.55, 0.75, 0.8, 0.5), rough=0.1)) if translucent_fraction > 0 else None
+    for k, (bmin, bmax, mat) in enumerate(synth._atrium_boxes()):
+        if glass is not None and int((k + 1) * translucent_fraction) > int(k * translucent_fraction):
+            m.add_box(bmin, bmax, glass, subdiv=subdiv, ptype=_abi.PRIMITIVE_TYPE_TRANSLUCENT)
+        else:
+            m.add_box(bmin, bmax, mat, subdiv=subdiv)
     return m
 
 

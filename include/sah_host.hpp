@@ -45,6 +45,7 @@
 #include "sah_sun_shafts.h"
 #include "sah_taa.h"
 #include "sah_taa_upscale.h"
+#include "sah_translucent.h"
 #include "sah_vrsaa.h"
 
 namespace sah {
@@ -243,19 +244,27 @@ public:
         uint32_t shading_rate_texel_size[2] = {0, 0};
         float depth_tolerance = 0.0f;
     } lighting;
+    // the descriptor a recording amounts to (it points into the recording)
+    static sah_lighting_desc lighting_desc_of(const LightingRecording& r) {
+        sah_lighting_desc d{};
+        d.gbuffer = &r.gbuffer;
+        d.lit = &r.lit;
+        d.view = r.view;
+        d.sun = r.sun;
+        if (r.has_ao) d.ao = &r.ao;
+        if (r.has_mask) d.shadow_mask = &r.shadow_mask;
+        if (r.has_shadowmap) d.shadowmap = &r.shadowmap;
+        if (r.has_gi) d.gi = &r.gi;
+        if (r.has_sky) d.sky = &r.sky;
+        d.flags = r.flags;
+        return d;
+    }
+    // the Lighting pass submitted last in this frame, kept for the pass that blends into its lit image with its descriptor
+    // (TranslucencyPhase); `open` is false until a Lighting pass has been submitted
+    LightingRecording submitted_lighting;
     void submit_lighting() {
         if (!lighting.open) return;
-        sah_lighting_desc d{};
-        d.gbuffer = &lighting.gbuffer;
-        d.lit = &lighting.lit;
-        d.view = lighting.view;
-        d.sun = lighting.sun;
-        if (lighting.has_ao) d.ao = &lighting.ao;
-        if (lighting.has_mask) d.shadow_mask = &lighting.shadow_mask;
-        if (lighting.has_shadowmap) d.shadowmap = &lighting.shadowmap;
-        if (lighting.has_gi) d.gi = &lighting.gi;
-        if (lighting.has_sky) d.sky = &lighting.sky;
-        d.flags = lighting.flags;
+        const sah_lighting_desc d = lighting_desc_of(lighting);
         // (what sah_lighting_vrs supports, include/sah_vrs.h: GI none or LPV — this recording never carries a light list; another kind is shaded at full rate)
         const uint32_t gi_kind = lighting.has_gi ? lighting.gi.kind : (uint32_t)SAH_GI_NONE;
         if (lighting.variable_rate && (gi_kind == SAH_GI_NONE || gi_kind == SAH_GI_LPV)) {
@@ -268,6 +277,7 @@ public:
         } else {
             check(sah_lighting(ctx, &d), "Lighting");
         }
+        submitted_lighting = lighting;
         lighting = LightingRecording{};
     }
 
@@ -1988,6 +1998,36 @@ private:
     bool variable_rate = false;
     std::array<uint32_t, 2> vrs_texel_size = {0, 0};
     float vrs_depth_tolerance = 0.0f;
+};
+
+// ---- TranslucencyPhase (include/sah_translucent.h) --------------------------------------------------------------------------
+// The reference's frame is commented "Gbuffers, lighting, and translucency" (scene_renderer.cpp:363) and its scene keeps
+// `translucent_primitives` with a draw_transparent() (render_scene.cpp:66-67, 234-236); the phase itself was never written there.  Here:
+// recorded after LightingPhase::render (and after ScreenSpaceReflections, where used, when that wrote into lit_scene's place), before
+// SunShafts and the anti-aliasing, it blends the primitives of type SAH_PRIMITIVE_TYPE_TRANSLUCENT of `translucent` — sorted back to front by
+// the caller, as draw_transparent() would be fed — into the lit image of the Lighting pass submitted last, lit by that pass's own
+// descriptor.  RenderScene::geometry, which the opaque phases and RaytracingScene draw, holds the scene WITHOUT those primitives.  Off
+// unless a caller constructs one and calls it: no existing phase uses it.
+class TranslucencyPhase {
+public:
+    // `translucent` must stay alive until the graph has finished; stats: device, SAH_RASTER_STATS_WORDS words, or null
+    void render(RenderGraph& graph, const sah_scene_geometry& translucent, uint32_t* stats = nullptr) {
+        ComputePass pass;
+        pass.name = "Translucency";
+        pass.execute = [&translucent, stats](CommandBuffer& commands) {
+            if (!commands.submitted_lighting.open) {  // no Lighting pass in this frame: nothing to blend into
+                commands.check(SAH_ERR_INVALID_ARGUMENT, "Translucency");
+                return;
+            }
+            const sah_lighting_desc d = CommandBuffer::lighting_desc_of(commands.submitted_lighting);
+            sah_translucent_desc t{};
+            t.lighting = &d;
+            t.scene = &translucent;
+            t.stats = stats;
+            commands.check(sah_translucent_render(commands.get_context(), &t), "Translucency");
+        };
+        graph.add_pass(std::move(pass));
+    }
 };
 
 // ---- ScreenSpaceReflections (include/sah_ssr.h; builder-owned: the reference has "Other postprocessing // TODO" here) ---------------------

@@ -1,0 +1,393 @@
+"""GPU: sah_translucent_render (include/sah_translucent.h) against the composition of tests/translucent_ref.py run on sah_gbuffer_render +
+sah_lighting (HipBackend), which the rest of the suite pins to the CPU oracle, and against the committed fixture, which the composition made
+on the CPU oracle.  Every comparison is of all bytes of `lit`, bit for bit: no tolerance, no pixel left out.  96 x 54 is two 64 x 64 tiles,
+both partial; 130 x 70 is 3 x 2 tiles, where the large panes span four and more.  Each scene asserts its own precondition on the reference
+side (pixels changed, deepest pixel, non-commutativity), so that a degenerate input cannot pass quietly."""
+import ctypes as C
+import faulthandler
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from androidrenderer_amd import _abi, images, lib, mesh
+from tests import layouts
+from tests import translucent_ref as ref
+from tests import util
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import gen_golden_translucent as gen  # noqa: E402
+
+OFF, CSM, RT = _abi.SHADOW_MODE_OFF, _abi.SHADOW_MODE_CSM, _abi.SHADOW_MODE_RT
+NONE, LPV = _abi.GI_NONE, _abi.GI_LPV
+BLEND = _abi.LIGHTING_QUIRK_SUN_BLEND
+SMALL, WIDE = (96, 54), (130, 70)
+
+
+@pytest.fixture(autouse=True)
+def _time_limit():
+    faulthandler.dump_traceback_later(120, exit=True)  # each test under a limit of its own: an overrun ends the process
+    yield
+    faulthandler.cancel_dump_traceback_later()
+
+
+def _differs(got, want):
+    bad = (got != want).reshape(got.shape[0], got.shape[1], -1).any(-1)
+    return f"{int(bad.sum())} of {bad.size} pixels differ, first at {np.argwhere(bad)[:4].tolist()}"
+
+
+def device_geometry(arrays):
+    keep = []
+    return mesh.geometry(mesh.to_device(arrays), keep), keep
+
+
+class Case:
+    """one scene under one sun mode and GI kind: the reference frame on the GPU backend (computed once), the device scene and the call"""
+
+    def __init__(self, ctx, m, extent, sun=CSM, gi=LPV, flags=BLEND, compose=True):
+        self.fr = ref.Frame(ref.HipBackend(ctx), m, extent[0], extent[1], sun, gi, flags)
+        self.w, self.h = extent
+        self.geo, self.keep = device_geometry(self.fr.translucent)
+        self.dev = self.fr.f.device_arrays()
+        if compose:
+            self.want, self.blended = self.fr.compose()
+            self.want.setflags(write=False)
+
+    def run(self, ctx, rows=(0, 0), geo=None, lit0=None, edit=None):
+        """the call over tight device arrays, starting from lit0 (default: the frame's own Lighting output): (lit, statistics words)"""
+        import torch
+        lit = util.to_torch(np.array(self.fr.lit0 if lit0 is None else lit0))
+        stats = torch.full((_abi.RASTER_STATS_WORDS,), -1, dtype=torch.int32, device="cuda")
+        f = self.fr.f
+        f.row_begin, f.row_end = rows
+        try:
+            d, keep = f.describe(self.dev, lit)
+        finally:
+            f.row_begin = f.row_end = 0
+        if edit:
+            keep.append(edit(d))
+        ctx.translucent_render(d, self.geo if geo is None else geo, stats.data_ptr())
+        torch.cuda.synchronize()
+        return util.from_torch(lit, np.uint16), util.from_torch(stats, np.uint32)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(ctx, scene, extent, sun=CSM, gi=LPV, flags=BLEND):
+    makers = {"panes": ref.scene_panes, "plain": lambda: ref.scene_panes(textured=False), "stack": ref.scene_stack, "stack3": lambda: ref.scene_stack(3),
+              "stack3r": lambda: ref.scene_stack(3, reverse=True), "near": ref.scene_near, "alpha": ref.scene_alpha_codes, "long": ref.scene_long_list}
+    return Case(ctx, makers[scene](), extent, sun, gi, flags)
+
+
+def _check(ctx, c, min_changed=0.2, min_depth=1):
+    ref.assert_preconditions(c.fr, c.want, c.blended, min_changed, min_depth)
+    got, stats = c.run(ctx)
+    print(f"{_differs(got, c.want)}; statistics {stats.tolist()}; the reference's deepest pixel blends {int(c.blended.max())}")
+    assert got.tobytes() == c.want.tobytes(), _differs(got, c.want)
+    assert stats[7] == c.blended.max() and stats[5] == 0 and stats[6] == 0
+    return got, stats
+
+
+# ---- parity -------------------------------------------------------------------------------------------------------------------------------
+def test_the_fixture(hip_ctx):
+    """the image the composition made on the CPU oracle, from the lit image the CPU oracle made"""
+    fx = np.load(gen.FIXTURE)
+    c = Case(hip_ctx, ref.scene_panes(), (gen.WIDTH, gen.HEIGHT), gen.SUN, gen.GI, compose=False)
+    assert c.fr.depth.view(np.uint32).tobytes() == fx["depth"].view(np.uint32).tobytes(), "sah_gbuffer_render's depth is not the oracle's"
+    got, stats = c.run(hip_ctx, lit0=fx["lit0"])
+    print(f"{_differs(got, fx['lit'])}; statistics {stats.tolist()}")
+    assert got.tobytes() == fx["lit"].tobytes(), _differs(got, fx["lit"])
+    assert stats[7] == fx["blended"].max() >= 3
+
+
+@pytest.mark.parametrize("flags", [BLEND, 0])
+@pytest.mark.parametrize("gi", [NONE, LPV])
+@pytest.mark.parametrize("sun", [OFF, CSM])
+def test_sun_and_gi_modes(hip_ctx, sun, gi, flags):
+    """textured and constant materials, over the sky, behind opaque geometry, a back-facing triangle; four and more tiles per pane"""
+    c = _case(hip_ctx, "panes", WIDE, sun, gi, flags)
+    _check(hip_ctx, c, min_depth=3)
+    sky = c.fr.depth == 0
+    assert (c.blended[sky] > 0).any() and (c.blended[~sky] > 0).any(), "fragments over the sky and over geometry"
+
+
+def test_over_the_sky_behind_geometry_and_back_facing(hip_ctx):
+    """the panes one by one: the one behind the end wall changes nothing, the back-facing triangle is kept"""
+    c = _case(hip_ctx, "panes", SMALL)
+    prims = c.fr.translucent["primitives"]
+    assert len(prims) == 7
+
+    def alone(k):
+        geo, keep = device_geometry(dict(c.fr.translucent, primitives=prims[k:k + 1]))
+        got, stats = c.run(hip_ctx, geo=geo)
+        want, blended = c.fr.compose(dict(c.fr.translucent, primitives=prims[k:k + 1]))
+        assert got.tobytes() == want.tobytes(), (k, _differs(got, want))
+        return got, stats, blended
+    got, stats, blended = alone(0)  # behind the end wall
+    assert got.tobytes() == c.fr.lit0.tobytes() and stats[3] == 2 and stats[7] == 0 and blended.max() == 0
+    got, stats, blended = alone(6)  # the back-facing triangle
+    assert stats[0] == 1 and stats[1] == 0 and stats[3] == 1 and stats[7] == 1 and (got != c.fr.lit0).any()
+
+
+def test_constant_materials(hip_ctx):
+    _check(hip_ctx, _case(hip_ctx, "plain", SMALL), min_depth=3)
+
+
+def test_textured_materials_two_partial_tiles(hip_ctx):
+    _check(hip_ctx, _case(hip_ctx, "panes", SMALL), min_depth=3)
+
+
+@pytest.mark.parametrize("extent", [SMALL, WIDE])
+def test_a_triangle_crossing_the_near_plane(hip_ctx, extent):
+    """fan pieces keep their order"""
+    c = _case(hip_ctx, "near", extent)
+    got, stats = _check(hip_ctx, c, min_depth=3)
+    assert stats[3] > stats[0] == 6, "the sheet's two triangles are clipped and fanned"
+
+
+def test_a_stack_at_least_five_fragments_deep(hip_ctx):
+    c = _case(hip_ctx, "stack", WIDE)
+    got, stats = _check(hip_ctx, c, min_depth=5)
+    assert stats[7] == c.blended.max() == 6
+
+
+def test_a_tile_list_longer_than_one_round(hip_ctx):
+    """300 small triangles inside the first tile: the walk takes two rounds of 256 entries per layer"""
+    c = _case(hip_ctx, "long", SMALL)
+    got, stats = _check(hip_ctx, c, min_changed=0.2, min_depth=4)
+    assert stats[4] == stats[3] > 256, "every triangle is in one tile, and the tile's list is longer than a round"
+
+
+def test_alpha_codes_0_1_128_255(hip_ctx):
+    c = _case(hip_ctx, "alpha", SMALL)
+    got, stats = _check(hip_ctx, c)
+    assert stats[7] == 1
+
+
+def test_swapped_primitive_order(hip_ctx):
+    a, b = _case(hip_ctx, "stack3", SMALL), _case(hip_ctx, "stack3r", SMALL)
+    ga, _ = _check(hip_ctx, a, min_depth=3)
+    gb, _ = _check(hip_ctx, b, min_depth=3)
+    assert a.fr.lit0.tobytes() == b.fr.lit0.tobytes() and (ga != gb).any(), "blending does not commute"
+
+
+def test_the_whole_scene_gives_what_its_translucent_half_gives(hip_ctx):
+    """only the type-2 primitives of the scene are drawn, numbered among themselves"""
+    c = _case(hip_ctx, "panes", SMALL)
+    geo, keep = device_geometry(c.fr.arrays)
+    got, stats = c.run(hip_ctx, geo=geo)
+    assert got.tobytes() == c.want.tobytes(), _differs(got, c.want)
+    assert stats[0] == 13
+
+
+def test_ten_calls_give_identical_bytes(hip_ctx):
+    c = _case(hip_ctx, "panes", WIDE)
+    first, stats = c.run(hip_ctx)
+    assert first.tobytes() == c.want.tobytes()
+    for _ in range(9):
+        got, again = c.run(hip_ctx)
+        assert got.tobytes() == first.tobytes() and again.tolist() == stats.tolist()
+
+
+# ---- layouts and rows -----------------------------------------------------------------------------------------------------------------------
+FORMATS = {"color": (layouts.SRGBA8, 2), "normals": (layouts.RGBA16F, 2), "data": (layouts.RGBA8, 2), "emission": (layouts.SRGBA8, 2), "depth": (layouts.D32F, 2),
+           "lit": (layouts.RGBA16F, 2)}
+SPEC_A = {"depth": dict(row_pad=4, offset=4), "lit": dict(row_pad=8, offset=8), "color": dict(row_pad=4, offset=4)}
+SPEC_B = {"depth": dict(row_pad=20, offset=36), "lit": dict(row_pad=40, offset=24), "normals": dict(row_pad=24, offset=8), "data": dict(row_pad=12),
+          "emission": dict(offset=12)}
+
+
+def _pitched_call(ctx, c, spec, rows=(0, 0)):
+    import torch
+    arrays = {k: c.dev[k] for k in ref.GBUFFER_KEYS}
+    arrays["lit"] = util.to_torch(np.array(c.fr.lit0))
+    wrapped = layouts.wrap(arrays, FORMATS, spec)
+    d, keep = c.fr.f.describe(c.dev, torch.zeros((1, 1, 4), dtype=torch.int16, device="cuda"))  # (every plane is replaced below)
+    gb = _abi.GBuffer(*(wrapped[k].plane() for k in ref.GBUFFER_KEYS))
+    lit_p = wrapped["lit"].plane()
+    d.gbuffer, d.lit = C.pointer(gb), C.pointer(lit_p)
+    d.row_begin, d.row_end = rows
+    ctx.translucent_render(d, c.geo)
+    torch.cuda.synchronize()
+    got = wrapped["lit"].read(np.uint16)
+    layouts.assert_padding_intact(wrapped, what=f"translucent_render {spec}")
+    layouts.assert_inputs_unchanged({k: wrapped[k] for k in ref.GBUFFER_KEYS}, what=f"translucent_render {spec}")
+    return got
+
+
+@pytest.mark.parametrize("spec", [SPEC_A, SPEC_B], ids=["smallest", "odd"])
+def test_pitched_and_offset_planes(hip_ctx, spec):
+    c = _case(hip_ctx, "panes", SMALL)
+    got = _pitched_call(hip_ctx, c, spec)
+    assert got.tobytes() == c.want.tobytes(), _differs(got, c.want)
+
+
+@pytest.mark.parametrize("rows", [(10, 30), (0, 1), (53, 54), (64, 70), (63, 65), (20, 20)])
+def test_a_row_range_equals_the_same_rows_of_the_whole_frame(hip_ctx, rows):
+    c = _case(hip_ctx, "panes", WIDE)
+    assert c.h == 70
+    want = np.array(c.fr.lit0)
+    want[rows[0]:rows[1]] = c.want[rows[0]:rows[1]]
+    got, _ = c.run(hip_ctx, rows=rows)
+    assert got.tobytes() == want.tobytes(), f"rows {rows}: " + _differs(got, want)
+    layouts.assert_rows_untouched(c.fr.lit0, got, rows[0], rows[1], what=f"rows {rows}")
+    if rows == (10, 30):
+        assert c.fr.compose(rows=rows)[0].tobytes() == want.tobytes()
+        small = _case(hip_ctx, "panes", SMALL)
+        assert _pitched_call(hip_ctx, small, SPEC_B, rows).tobytes() == np.concatenate([small.fr.lit0[:10], small.want[10:30], small.fr.lit0[30:]]).tobytes()
+
+
+def test_no_translucent_primitive_leaves_lit_alone(hip_ctx):
+    c = _case(hip_ctx, "panes", SMALL)
+    poison = np.random.default_rng(5).integers(0, 1 << 16, c.fr.lit0.shape, dtype=np.uint16)  # NaNs and infinities too: nothing is read or written
+    for arrays in (c.fr.opaque, dict(c.fr.opaque, primitives=c.fr.opaque["primitives"][:0])):
+        geo, keep = device_geometry(arrays)
+        got, stats = c.run(hip_ctx, geo=geo, lit0=poison)
+        assert got.tobytes() == poison.tobytes()
+        assert stats.tolist() == [0] * 8, "no triangle set up, no bin entry: every tile's workgroup returns at once"
+    # translucent primitives, none on screen
+    m = mesh.Mesh()
+    ref.pane(m, -20.0, (0.0, 2.0), (-1.0, 1.0), ref.glass(m, (1, 1, 1, 0.5)))           # behind the camera
+    ref.pane(m, 3.0, (0.0, 2.0), (40.0, 42.0), ref.glass(m, (1, 1, 1, 0.5)))            # far to the right
+    geo, keep = device_geometry(m.arrays())
+    got, stats = c.run(hip_ctx, geo=geo, lit0=poison)
+    assert got.tobytes() == poison.tobytes() and stats[0] == 4 and stats[3] == 0 and stats[4] == 0 and stats[7] == 0
+
+
+# ---- the opaque passes ------------------------------------------------------------------------------------------------------------------------
+def test_gbuffer_render_of_the_opaque_half_equals_the_unsplit_scene(hip_ctx):
+    b = ref.HipBackend(hip_ctx)
+    view = _case(hip_ctx, "panes", SMALL).fr.f.view
+    plain = mesh.atrium(2).arrays()
+    opaque, translucent = mesh.split_translucent(plain)
+    whole, half = b.gbuffer(plain, view, *SMALL), b.gbuffer(opaque, view, *SMALL)
+    assert all(whole[k].tobytes() == half[k].tobytes() for k in ref.GBUFFER_KEYS) and (whole["depth"] > 0).mean() > 0.5
+    # and the opaque half of a scene with glass in it is the scene with the glass taken out
+    glassy = mesh.atrium(2, translucent_fraction=0.1).arrays()
+    kept = glassy["primitives"]["type"] != ref.T
+    without = dict(plain, primitives=np.ascontiguousarray(plain["primitives"][kept]))
+    a, w = b.gbuffer(mesh.split_translucent(glassy)[0], view, *SMALL), b.gbuffer(without, view, *SMALL)
+    assert all(a[k].tobytes() == w[k].tobytes() for k in ref.GBUFFER_KEYS)
+    assert any(a[k].tobytes() != whole[k].tobytes() for k in ref.GBUFFER_KEYS), "some of the glass boxes were visible"
+
+
+# ---- a repeated attempt ---------------------------------------------------------------------------------------------------------------------
+def test_a_repeated_attempt_blends_once(hip_ctx):
+    """Blending is not idempotent.  On a fresh context the record buffer is guessed at (index triples) + 1024 = 1042 entries (1304 after
+    ensure()'s margin); 700 further draws of the first pane's two triangles, all off screen, make 1406: the first attempt comes up short and
+    the pass is rendered again, and the visible panes — whose records did fit — must have been left alone by the first.  The reference was
+    made on the session's context, so that this one's scratch is untouched."""
+    import torch
+    m = ref.scene_stack(3)
+    aside = np.eye(4, dtype=np.float32)
+    aside[2, 3] = 60.0
+    glass_first = next(i for i, p in enumerate(m.primitives) if p["type"] == ref.T)
+    c = _case(hip_ctx, "stack3", SMALL)
+    for _ in range(700):
+        m.add_instance(glass_first, aside.T.reshape(16))
+    geo, keep = device_geometry(mesh.split_translucent(m.arrays())[1])
+    fresh = lib.Context(device=0)
+    try:
+        fresh.set_stream(torch.cuda.current_stream().cuda_stream)
+        got, stats = c.run(fresh, geo=geo)
+        one = fresh.raster_last_pass()
+        again, _ = c.run(fresh, geo=geo)
+        two = fresh.raster_last_pass()
+        print(f"first call {one}, second call {two}; statistics {stats.tolist()}")
+        assert one["attempts"] >= 2 and two["attempts"] == 1
+        assert got.tobytes() == c.want.tobytes(), _differs(got, c.want)
+        assert again.tobytes() == c.want.tobytes() and stats[0] == 1406 and stats[3] == 6 and stats[7] == 3
+    finally:
+        torch.cuda.synchronize()
+        fresh.close()
+
+
+# ---- refusals -----------------------------------------------------------------------------------------------------------------------------
+def test_refusals_leave_lit_untouched(hip_ctx):
+    import torch
+    c = _case(hip_ctx, "panes", SMALL)
+    INV, FMT, UNS = _abi.SAH_ERR_INVALID_ARGUMENT, _abi.SAH_ERR_UNSUPPORTED_FORMAT, _abi.SAH_ERR_UNSUPPORTED
+    lit = util.to_torch(np.array(c.fr.lit0))
+
+    def call(status, edit=None, rows=(0, 0), geo=None):
+        d, keep = c.fr.f.describe(c.dev, lit)
+        d.row_begin, d.row_end = rows
+        if edit:
+            keep.append(edit(d))
+        with pytest.raises(lib.SahError) as e:
+            hip_ctx.translucent_render(d, c.geo if geo is None else geo)
+        assert e.value.status == status, (e.value, status)
+
+    def sun_mode(mode):
+        def edit(d):
+            s = _abi.SunLightConstants.from_buffer_copy(bytes(d.sun.contents))
+            s.shadow_mode = mode
+            d.sun = C.pointer(s)
+            return s
+        return edit
+
+    def gi_kind(kind):
+        def edit(d):
+            g = _abi.GI.from_buffer_copy(bytes(d.gi.contents))
+            g.kind = kind
+            d.gi = C.pointer(g)
+            return g
+        return edit
+
+    def lights(d):
+        ll = _abi.LightList(c.dev["depth"].data_ptr(), 1)
+        d.lights = C.pointer(ll)
+        return ll
+
+    def no_lit(d):
+        d.lit = None
+
+    def lit_format(d):
+        q = _abi.Plane(lit.data_ptr(), c.w, c.h, c.w * 8, _abi.FORMAT_R32_SFLOAT)
+        d.lit = C.pointer(q)
+        return q
+
+    def lit_extent(d):
+        q = _abi.Plane(lit.data_ptr(), c.w - 1, c.h, c.w * 8, _abi.FORMAT_R16G16B16A16_SFLOAT)
+        d.lit = C.pointer(q)
+        return q
+
+    def lit_on_normals(d):
+        n = d.gbuffer.contents.normals
+        q = _abi.Plane(n.ptr + 8 * c.w * (c.h - 1), c.w, c.h, c.w * 8, _abi.FORMAT_R16G16B16A16_SFLOAT)  # its first row is the normals' last
+        d.lit = C.pointer(q)
+        return q
+
+    def lit_misaligned(d):
+        q = _abi.Plane(lit.data_ptr() + 4, c.w, c.h, c.w * 8, _abi.FORMAT_R16G16B16A16_SFLOAT)
+        d.lit = C.pointer(q)
+        return q
+
+    call(UNS, sun_mode(RT))                 # no shadow mask for a fragment
+    call(UNS, gi_kind(_abi.GI_CACHE))
+    call(UNS, gi_kind(_abi.GI_RTGI))
+    call(UNS, lights)
+    call(INV, gi_kind(7))                   # what sah_lighting refuses, with its codes
+    call(INV, sun_mode(3))
+    call(INV, no_lit)
+    call(FMT, lit_format)
+    call(FMT, lit_extent)                   # another extent than the depth plane's
+    call(FMT, lit_misaligned)
+    call(INV, rows=(8, 4))
+    call(INV, rows=(0, c.h + 1))
+    call(INV, lit_on_normals)               # lit overlaps an input
+    bad = _abi.SceneGeometry.from_buffer_copy(bytes(c.geo))
+    bad.indices = None
+    call(INV, geo=bad)                      # what sah_gbuffer_render refuses
+    t = _abi.TranslucentDesc(None, C.pointer(c.geo), None)
+    assert hip_ctx.lib.sah_translucent_render(hip_ctx.handle, C.byref(t)) == INV and hip_ctx.lib.sah_translucent_render(hip_ctx.handle, None) == INV
+    d, keep = c.fr.f.describe(c.dev, lit)
+    t = _abi.TranslucentDesc(C.pointer(d), None, None)
+    assert hip_ctx.lib.sah_translucent_render(hip_ctx.handle, C.byref(t)) == INV and hip_ctx.lib.sah_translucent_render(None, C.byref(t)) == INV
+    torch.cuda.synchronize()
+    assert util.from_torch(lit, np.uint16).tobytes() == c.fr.lit0.tobytes()
+    got, _ = c.run(hip_ctx)  # and the call goes on as before
+    assert got.tobytes() == c.want.tobytes()
