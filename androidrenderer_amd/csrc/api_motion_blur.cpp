@@ -8,20 +8,6 @@
 #include "launch.hpp"
 
 namespace {
-// 0, or the status a plane of `format` with `bpp`-byte texels earns (the alignment rules of sah_taa_resolve)
-int plane_status(const sah_plane* p, uint32_t format, uint32_t bpp) {
-    if (!p || !p->ptr) return SAH_ERR_INVALID_ARGUMENT;
-    if (p->format != format) return SAH_ERR_UNSUPPORTED_FORMAT;
-    if (!p->width || !p->height || (uint64_t)p->row_pitch_bytes < (uint64_t)p->width * bpp || ((uintptr_t)p->ptr % 4) || (p->row_pitch_bytes % 4))
-        return SAH_ERR_INVALID_ARGUMENT;
-    return SAH_OK;
-}
-bool overlap(const sah_plane* a, uint32_t a_bpp, const sah_plane* b, uint32_t b_bpp) {
-    const uintptr_t a0 = (uintptr_t)a->ptr, a1 = a0 + (uint64_t)(a->height - 1) * a->row_pitch_bytes + (uint64_t)a->width * a_bpp;
-    const uintptr_t b0 = (uintptr_t)b->ptr, b1 = b0 + (uint64_t)(b->height - 1) * b->row_pitch_bytes + (uint64_t)b->width * b_bpp;
-    return a0 < b1 && b0 < a1;
-}
-bool too_large(uint32_t w, uint32_t h) { return ((w | h) >> 31) || (uint64_t)w * h >= (1ull << 32); }
 // Nearest of the header for a row: the render row that output row Y sits on (the device's expression, operator by operator)
 uint32_t nearest_row(uint32_t Y, float sy, float jy, uint32_t h) {
     volatile float centre = (float)Y + 0.5f;  // (volatile: each product and difference is rounded to fp32 on its own, whatever the host's flags)
@@ -41,30 +27,23 @@ extern "C" int sah_motion_blur(sah_ctx* ctx, const sah_plane* scene, const sah_p
     if (!params) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: params is null");
     const sah_motion_blur_params& s = *params;
     if (s.flags & ~SAH_MOTION_BLUR_DITHER) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: an undefined flag bit is set");
-    const struct {
-        const sah_plane* p;
-        uint32_t format, bpp;
-        const char* what;
-    } planes[5] = {{out, SAH_FORMAT_R16G16B16A16_SFLOAT, 8, "out must be an R16G16B16A16_SFLOAT plane"},
-                   {scene, SAH_FORMAT_R16G16B16A16_SFLOAT, 8, "scene must be an R16G16B16A16_SFLOAT plane"},
-                   {depth, SAH_FORMAT_D32_SFLOAT, 4, "depth must be a D32_SFLOAT plane"},
-                   {motion_vectors, SAH_FORMAT_R16G16_SFLOAT, 4, "motion_vectors must be an R16G16_SFLOAT plane"},
-                   {tiles, SAH_FORMAT_R16G16_SFLOAT, 4, "tiles must be an R16G16_SFLOAT plane"}};
-    for (const auto& pl : planes)
-        if (const int rc = plane_status(pl.p, pl.format, pl.bpp); rc != SAH_OK)
-            return fail(ctx, rc, "motion_blur: %s, 4-byte aligned, with a pitch of at least a row", pl.what);
+    const PlaneSpec planes[5] = {{out, SAH_FORMAT_R16G16B16A16_SFLOAT, "out (R16G16B16A16_SFLOAT)"},
+                                 {scene, SAH_FORMAT_R16G16B16A16_SFLOAT, "scene (R16G16B16A16_SFLOAT)"},
+                                 {depth, SAH_FORMAT_D32_SFLOAT, "depth (D32_SFLOAT)"},
+                                 {motion_vectors, SAH_FORMAT_R16G16_SFLOAT, "motion_vectors (R16G16_SFLOAT)"},
+                                 {tiles, SAH_FORMAT_R16G16_SFLOAT, "tiles (R16G16_SFLOAT)"}};
+    if (const int rc = check_planes(ctx, "motion_blur", planes, 5); rc != SAH_OK) return rc;
     const uint32_t W = out->width, H = out->height, w = depth->width, h = depth->height;
     if (scene->width != W || scene->height != H)
         return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: scene and out must have one extent (the output resolution)");
     if (motion_vectors->width != w || motion_vectors->height != h)
         return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: depth and motion_vectors must have one extent (the render resolution)");
     if (w > W || h > H) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: %u x %u to %u x %u is downscaling", w, h, W, H);
-    if (too_large(w, h) || too_large(W, H)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: 2^32 texels or more");
+    if (texel_count_too_large(w, h) || texel_count_too_large(W, H)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: 2^32 texels or more");
     const uint32_t tiles_x = (w + SAH_MOTION_BLUR_TILE - 1) / SAH_MOTION_BLUR_TILE, tiles_y = (h + SAH_MOTION_BLUR_TILE - 1) / SAH_MOTION_BLUR_TILE;
     if (tiles->width != tiles_x || tiles->height != tiles_y)
         return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: tiles must be ceil(w / 16) x ceil(h / 16) = %u x %u", tiles_x, tiles_y);
-    if (row_begin == 0 && row_end == 0) row_end = H;
-    if (row_end > H || row_begin > row_end) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: bad row range");
+    if (!resolve_rows(&row_begin, &row_end, H)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: bad row range");
     for (const float v : {s.shutter, s.max_blur_pixels, s.min_velocity_pixels, s.depth_extent, s.z_near, s.jitter[0], s.jitter[1], s.previous_jitter[0],
                           s.previous_jitter[1]})
         if (std::isnan(v)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: a parameter is NaN");
@@ -78,10 +57,10 @@ extern "C" int sah_motion_blur(sah_ctx* ctx, const sah_plane* scene, const sah_p
     for (const float j : {s.jitter[0], s.jitter[1], s.previous_jitter[0], s.previous_jitter[1]})
         if (!std::isfinite(j)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: a jitter is not finite");
     for (int i = 1; i < 5; i++)
-        if (overlap(out, 8, planes[i].p, planes[i].bpp))
+        if (overlaps(byte_range(out), byte_range(planes[i].p)))
             return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: out overlaps an input or tiles (the pass gathers along the motion: not in place)");
     for (int i = 1; i < 4; i++)
-        if (overlap(tiles, 4, planes[i].p, planes[i].bpp)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: tiles overlaps an input");
+        if (overlaps(byte_range(tiles), byte_range(planes[i].p))) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "motion_blur: tiles overlaps an input");
     sah::MotionBlurArgs a{};
     a.scene = parg(scene), a.depth = parg(depth), a.mv = parg(motion_vectors), a.tiles = parg(tiles), a.out = parg(out);
     a.w = w, a.h = h, a.W = W, a.H = H, a.row_begin = row_begin, a.row_end = row_end;

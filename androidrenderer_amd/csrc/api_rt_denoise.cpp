@@ -9,25 +9,10 @@
 #include "launch.hpp"
 
 namespace {
-// 0, or the status a plane of `format` with `bpp`-byte texels earns (the alignment rules of sah_taa_resolve)
-int plane_status(const sah_plane* p, uint32_t format, uint32_t bpp) {
-    if (!p || !p->ptr) return SAH_ERR_INVALID_ARGUMENT;
-    if (p->format != format) return SAH_ERR_UNSUPPORTED_FORMAT;
-    if (!p->width || !p->height || (uint64_t)p->row_pitch_bytes < (uint64_t)p->width * bpp || ((uintptr_t)p->ptr % 4) || (p->row_pitch_bytes % 4))
-        return SAH_ERR_INVALID_ARGUMENT;
-    return SAH_OK;
-}
 struct Checked {
-    const sah_plane* p;
-    uint32_t format, bpp;
+    PlaneSpec spec;
     bool output, previous;  // previous: one of the three planes SAH_RT_DENOISE_HISTORY_INVALID excuses
-    const char* what;
 };
-bool overlap(const Checked& a, const Checked& b) {
-    const uintptr_t a0 = (uintptr_t)a.p->ptr, a1 = a0 + (uint64_t)(a.p->height - 1) * a.p->row_pitch_bytes + (uint64_t)a.p->width * a.bpp;
-    const uintptr_t b0 = (uintptr_t)b.p->ptr, b1 = b0 + (uint64_t)(b.p->height - 1) * b.p->row_pitch_bytes + (uint64_t)b.p->width * b.bpp;
-    return a0 < b1 && b0 < a1;
-}
 }  // namespace
 
 extern "C" int sah_rt_denoise(sah_ctx* ctx, const sah_view_data* view, const sah_rt_denoise_desc* desc, const sah_rt_denoise_params* params,
@@ -40,27 +25,25 @@ extern "C" int sah_rt_denoise(sah_ctx* ctx, const sah_view_data* view, const sah
     if (s.flags & ~SAH_RT_DENOISE_HISTORY_INVALID) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rt_denoise: unknown flag bits");
     const bool history = !(s.flags & SAH_RT_DENOISE_HISTORY_INVALID);
     if (s.passes > 3 || s.normal_squarings > 7) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rt_denoise: passes must be 0..3 and normal_squarings 0..7");
-    const Checked planes[10] = {{desc->noisy, SAH_FORMAT_R32_SFLOAT, 4, false, false, "noisy must be an R32_SFLOAT plane"},
-                                {desc->depth, SAH_FORMAT_D32_SFLOAT, 4, false, false, "depth must be a D32_SFLOAT plane"},
-                                {desc->normals, SAH_FORMAT_R16G16B16A16_SFLOAT, 8, false, false, "normals must be an R16G16B16A16_SFLOAT plane"},
-                                {desc->motion_vectors, SAH_FORMAT_R16G16_SFLOAT, 4, false, false, "motion_vectors must be an R16G16_SFLOAT plane"},
-                                {desc->previous_depth, SAH_FORMAT_D32_SFLOAT, 4, false, true, "previous_depth must be a D32_SFLOAT plane"},
-                                {desc->history, SAH_FORMAT_R32_SFLOAT, 4, false, true, "history must be an R32_SFLOAT plane"},
-                                {desc->history_length, SAH_FORMAT_R16_SFLOAT, 2, false, true, "history_length must be an R16_SFLOAT plane"},
-                                {desc->accum_out, SAH_FORMAT_R32_SFLOAT, 4, true, false, "accum_out must be an R32_SFLOAT plane"},
-                                {desc->length_out, SAH_FORMAT_R16_SFLOAT, 2, true, false, "length_out must be an R16_SFLOAT plane"},
-                                {desc->denoised, SAH_FORMAT_R32_SFLOAT, 4, true, false, "denoised must be an R32_SFLOAT plane"}};
+    const Checked planes[10] = {{{desc->noisy, SAH_FORMAT_R32_SFLOAT, "noisy (R32_SFLOAT)"}, false, false},
+                                {{desc->depth, SAH_FORMAT_D32_SFLOAT, "depth (D32_SFLOAT)"}, false, false},
+                                {{desc->normals, SAH_FORMAT_R16G16B16A16_SFLOAT, "normals (R16G16B16A16_SFLOAT)"}, false, false},
+                                {{desc->motion_vectors, SAH_FORMAT_R16G16_SFLOAT, "motion_vectors (R16G16_SFLOAT)"}, false, false},
+                                {{desc->previous_depth, SAH_FORMAT_D32_SFLOAT, "previous_depth (D32_SFLOAT)"}, false, true},
+                                {{desc->history, SAH_FORMAT_R32_SFLOAT, "history (R32_SFLOAT)"}, false, true},
+                                {{desc->history_length, SAH_FORMAT_R16_SFLOAT, "history_length (R16_SFLOAT)"}, false, true},
+                                {{desc->accum_out, SAH_FORMAT_R32_SFLOAT, "accum_out (R32_SFLOAT)"}, true, false},
+                                {{desc->length_out, SAH_FORMAT_R16_SFLOAT, "length_out (R16_SFLOAT)"}, true, false},
+                                {{desc->denoised, SAH_FORMAT_R32_SFLOAT, "denoised (R32_SFLOAT)"}, true, false}};
     const auto used = [history](const Checked& c) { return history || !c.previous; };  // (a previous-frame plane that is not used is not looked at)
     for (const Checked& c : planes)
         if (used(c))
-            if (const int rc = plane_status(c.p, c.format, c.bpp); rc != SAH_OK)
-                return fail(ctx, rc, "rt_denoise: %s, 4-byte aligned, with a pitch of at least a row that is a multiple of 4", c.what);
+            if (const int rc = check_planes(ctx, "rt_denoise", &c.spec, 1); rc != SAH_OK) return rc;
     const uint32_t w = desc->denoised->width, h = desc->denoised->height;
     for (const Checked& c : planes)
-        if (used(c) && (c.p->width != w || c.p->height != h)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rt_denoise: the planes must have one extent");
-    if (((w | h) >> 31) || (uint64_t)w * h >= (1ull << 32)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rt_denoise: 2^32 texels or more");
-    if (row_begin == 0 && row_end == 0) row_end = h;
-    if (row_end > h || row_begin > row_end) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rt_denoise: bad row range");
+        if (used(c) && (c.spec.p->width != w || c.spec.p->height != h)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rt_denoise: the planes must have one extent");
+    if (texel_count_too_large(w, h)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rt_denoise: 2^32 texels or more");
+    if (!resolve_rows(&row_begin, &row_end, h)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rt_denoise: bad row range");
     if (!(s.max_history >= 1.0f && s.max_history <= 256.0f)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rt_denoise: max_history must be in [1, 256]");
     if (!(std::isfinite(s.depth_tolerance) && s.depth_tolerance > 0.0f)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rt_denoise: depth_tolerance must be finite and positive");
     if (!(std::isfinite(s.depth_sharpness) && s.depth_sharpness >= 0.0f)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rt_denoise: depth_sharpness must be finite and not negative");
@@ -74,7 +57,7 @@ extern "C" int sah_rt_denoise(sah_ctx* ctx, const sah_view_data* view, const sah
     if (!(std::isfinite(view->z_near) && view->z_near > 0.0f)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rt_denoise: z_near must be finite and positive");
     for (int o = 0; o < 10; o++)
         for (int i = 0; planes[o].output && i < 10; i++)
-            if (i != o && used(planes[i]) && overlap(planes[o], planes[i])) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rt_denoise: an output overlaps an input or another output");
+            if (i != o && used(planes[i]) && overlaps(byte_range(planes[o].spec.p), byte_range(planes[i].spec.p))) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "rt_denoise: an output overlaps an input or another output");
     sah::RtDenoiseArgs a{};
     a.noisy = parg(desc->noisy), a.depth = parg(desc->depth), a.normals = parg(desc->normals), a.mv = parg(desc->motion_vectors);
     if (history) a.prev_depth = parg(desc->previous_depth), a.history = parg(desc->history), a.hist_len = parg(desc->history_length);

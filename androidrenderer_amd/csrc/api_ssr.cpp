@@ -7,22 +7,6 @@
 #include "ctx.hpp"
 #include "launch.hpp"
 
-namespace {
-// 0, or the status a plane of `format` with `bpp`-byte texels earns (the alignment rules of sah_taa_resolve)
-int plane_status(const sah_plane* p, uint32_t format, uint32_t bpp) {
-    if (!p || !p->ptr) return SAH_ERR_INVALID_ARGUMENT;
-    if (p->format != format) return SAH_ERR_UNSUPPORTED_FORMAT;
-    if (!p->width || !p->height || (uint64_t)p->row_pitch_bytes < (uint64_t)p->width * bpp || ((uintptr_t)p->ptr % 4) || (p->row_pitch_bytes % 4))
-        return SAH_ERR_INVALID_ARGUMENT;
-    return SAH_OK;
-}
-bool overlap(const sah_plane* a, uint32_t a_bpp, const sah_plane* b, uint32_t b_bpp) {
-    const uintptr_t a0 = (uintptr_t)a->ptr, a1 = a0 + (uint64_t)(a->height - 1) * a->row_pitch_bytes + (uint64_t)a->width * a_bpp;
-    const uintptr_t b0 = (uintptr_t)b->ptr, b1 = b0 + (uint64_t)(b->height - 1) * b->row_pitch_bytes + (uint64_t)b->width * b_bpp;
-    return a0 < b1 && b0 < a1;
-}
-}  // namespace
-
 extern "C" int sah_ssr(sah_ctx* ctx, const sah_view_data* view, const sah_plane* color, const sah_plane* normals, const sah_plane* data,
                        const sah_plane* depth, const sah_plane* source, const sah_plane* lit, const sah_plane* scratch, const sah_plane* out,
                        const sah_ssr_params* params, uint32_t row_begin, uint32_t row_end) {
@@ -32,29 +16,22 @@ extern "C" int sah_ssr(sah_ctx* ctx, const sah_view_data* view, const sah_plane*
     if (!view || !params) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: view or params is null");
     const sah_ssr_params& s = *params;
     if (s.flags & ~(SAH_SSR_JITTER | SAH_SSR_REFLECTION_ONLY)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: an undefined flag bit is set");
-    const struct {
-        const sah_plane* p;
-        uint32_t format, bpp;
-        const char* what;
-    } planes[8] = {{out, SAH_FORMAT_R16G16B16A16_SFLOAT, 8, "out must be an R16G16B16A16_SFLOAT plane"},
-                   {color, SAH_FORMAT_R8G8B8A8_SRGB, 4, "color must be an R8G8B8A8_SRGB plane"},
-                   {normals, SAH_FORMAT_R16G16B16A16_SFLOAT, 8, "normals must be an R16G16B16A16_SFLOAT plane"},
-                   {data, SAH_FORMAT_R8G8B8A8_UNORM, 4, "data must be an R8G8B8A8_UNORM plane"},
-                   {depth, SAH_FORMAT_D32_SFLOAT, 4, "depth must be a D32_SFLOAT plane"},
-                   {source, SAH_FORMAT_R16G16B16A16_SFLOAT, 8, "source must be an R16G16B16A16_SFLOAT plane"},
-                   {lit, SAH_FORMAT_R16G16B16A16_SFLOAT, 8, "lit must be an R16G16B16A16_SFLOAT plane"},
-                   {scratch, SAH_FORMAT_R32_SFLOAT, 4, "scratch must be an R32_SFLOAT plane"}};
-    for (const auto& pl : planes)
-        if (const int rc = plane_status(pl.p, pl.format, pl.bpp); rc != SAH_OK)
-            return fail(ctx, rc, "ssr: %s, 4-byte aligned, with a pitch of at least a row", pl.what);
+    const PlaneSpec planes[8] = {{out, SAH_FORMAT_R16G16B16A16_SFLOAT, "out (R16G16B16A16_SFLOAT)"},
+                                 {color, SAH_FORMAT_R8G8B8A8_SRGB, "color (R8G8B8A8_SRGB)"},
+                                 {normals, SAH_FORMAT_R16G16B16A16_SFLOAT, "normals (R16G16B16A16_SFLOAT)"},
+                                 {data, SAH_FORMAT_R8G8B8A8_UNORM, "data (R8G8B8A8_UNORM)"},
+                                 {depth, SAH_FORMAT_D32_SFLOAT, "depth (D32_SFLOAT)"},
+                                 {source, SAH_FORMAT_R16G16B16A16_SFLOAT, "source (R16G16B16A16_SFLOAT)"},
+                                 {lit, SAH_FORMAT_R16G16B16A16_SFLOAT, "lit (R16G16B16A16_SFLOAT)"},
+                                 {scratch, SAH_FORMAT_R32_SFLOAT, "scratch (R32_SFLOAT)"}};
+    if (const int rc = check_planes(ctx, "ssr", planes, 8); rc != SAH_OK) return rc;
     const uint32_t w = out->width, h = out->height;
     for (int i = 0; i < 7; i++)
         if (planes[i].p->width != w || planes[i].p->height != h) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: the planes must have one extent");
-    if (((w | h) >> 31) || (uint64_t)w * h >= (1ull << 32)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: 2^32 texels or more");
+    if (texel_count_too_large(w, h)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: 2^32 texels or more");
     if (scratch->width != (w + 7) / 8 || scratch->height != (h + 7) / 8)
         return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: scratch must be ceil(W / 8) x ceil(H / 8)");
-    if (row_begin == 0 && row_end == 0) row_end = h;
-    if (row_end > h || row_begin > row_end) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: bad row range");
+    if (!resolve_rows(&row_begin, &row_end, h)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: bad row range");
     for (const float v : {s.max_distance, s.thickness, s.stride_pixels, s.max_roughness, s.edge_fade, s.intensity})
         if (std::isnan(v)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: a parameter is NaN");
     if (!(std::isfinite(s.max_distance) && s.max_distance > 0.0f)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: max_distance must be finite and positive");
@@ -71,10 +48,10 @@ extern "C" int sah_ssr(sah_ctx* ctx, const sah_view_data* view, const sah_plane*
         if (std::isnan(v)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: a field of the view that the pass reads is NaN");
     if (!(std::isfinite(view->z_near) && view->z_near > 0.0f)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: z_near must be finite and positive");
     for (int i = 1; i < 8; i++)
-        if (overlap(out, 8, planes[i].p, planes[i].bpp))
+        if (overlaps(byte_range(out), byte_range(planes[i].p)))
             return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: out overlaps an input or scratch (the rays read any texel of source)");
     for (int i = 1; i < 7; i++)
-        if (overlap(scratch, 4, planes[i].p, planes[i].bpp)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: scratch overlaps an input");
+        if (overlaps(byte_range(scratch), byte_range(planes[i].p))) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "ssr: scratch overlaps an input");
     sah::SsrArgs a{};
     a.color = parg(color), a.normals = parg(normals), a.data = parg(data), a.depth = parg(depth), a.source = parg(source), a.lit = parg(lit);
     a.out = parg(out);  // (scratch is reserved: checked above, neither read nor written)

@@ -10,19 +10,6 @@
 #include "lighting_stages.hpp"
 
 namespace {
-// 0, or the status a plane of `format` with `bpp`-byte texels earns (the alignment rules of sah_taa_resolve)
-int plane_status(const sah_plane* p, uint32_t format, uint32_t bpp) {
-    if (!p || !p->ptr) return SAH_ERR_INVALID_ARGUMENT;
-    if (p->format != format) return SAH_ERR_UNSUPPORTED_FORMAT;
-    if (!p->width || !p->height || (uint64_t)p->row_pitch_bytes < (uint64_t)p->width * bpp || ((uintptr_t)p->ptr % 4) || (p->row_pitch_bytes % 4))
-        return SAH_ERR_INVALID_ARGUMENT;
-    return SAH_OK;
-}
-bool overlap(const sah_plane* a, uint32_t a_bpp, const sah_plane* b, uint32_t b_bpp) {
-    const uintptr_t a0 = (uintptr_t)a->ptr, a1 = a0 + (uint64_t)(a->height - 1) * a->row_pitch_bytes + (uint64_t)a->width * a_bpp;
-    const uintptr_t b0 = (uintptr_t)b->ptr, b1 = b0 + (uint64_t)(b->height - 1) * b->row_pitch_bytes + (uint64_t)b->width * b_bpp;
-    return a0 < b1 && b0 < a1;
-}
 // M * v of the header (numerics.hpp's mul44, on the host: the library is compiled without contraction)
 void mul44(const float* m, const float v[4], float r[4]) {
     for (int i = 0; i < 4; i++) r[i] = ((m[i] * v[0] + m[4 + i] * v[1]) + m[8 + i] * v[2]) + m[12 + i] * v[3];
@@ -41,28 +28,21 @@ extern "C" int sah_sun_shafts(sah_ctx* ctx, const sah_view_data* view, const sah
     if (s.flags & ~(SAH_SUN_SHAFTS_DITHER | SAH_SUN_SHAFTS_TERM_ONLY)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: an undefined flag bit is set");
     const bool term_only = (s.flags & SAH_SUN_SHAFTS_TERM_ONLY) != 0;
     if (term_only) lit = nullptr;  // not read
-    const struct {
-        const sah_plane* p;
-        uint32_t format, bpp;
-        const char* what;
-    } planes[4] = {{out, SAH_FORMAT_R16G16B16A16_SFLOAT, 8, "out must be an R16G16B16A16_SFLOAT plane"},
-                   {march, SAH_FORMAT_R16G16B16A16_SFLOAT, 8, "march must be an R16G16B16A16_SFLOAT plane"},
-                   {depth, SAH_FORMAT_D32_SFLOAT, 4, "depth must be a D32_SFLOAT plane"},
-                   {lit, SAH_FORMAT_R16G16B16A16_SFLOAT, 8, "lit must be an R16G16B16A16_SFLOAT plane"}};
+    const PlaneSpec planes[4] = {{out, SAH_FORMAT_R16G16B16A16_SFLOAT, "out (R16G16B16A16_SFLOAT)"},
+                                 {march, SAH_FORMAT_R16G16B16A16_SFLOAT, "march (R16G16B16A16_SFLOAT)"},
+                                 {depth, SAH_FORMAT_D32_SFLOAT, "depth (D32_SFLOAT)"},
+                                 {lit, SAH_FORMAT_R16G16B16A16_SFLOAT, "lit (R16G16B16A16_SFLOAT; not looked at with SAH_SUN_SHAFTS_TERM_ONLY)"}};
     const int num_planes = term_only ? 3 : 4;
-    for (int i = 0; i < num_planes; i++)
-        if (const int rc = plane_status(planes[i].p, planes[i].format, planes[i].bpp); rc != SAH_OK)
-            return fail(ctx, rc, "sun_shafts: %s, 4-byte aligned, with a pitch of at least a row", planes[i].what);
+    if (const int rc = check_planes(ctx, "sun_shafts", planes, num_planes); rc != SAH_OK) return rc;
     const uint32_t w = out->width, h = out->height;
     if (depth->width != w || depth->height != h || (lit && (lit->width != w || lit->height != h)))
         return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: depth, lit and out must have one extent (the render resolution)");
-    if (((w | h) >> 31) || (uint64_t)w * h >= (1ull << 32)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: 2^32 texels or more");
+    if (texel_count_too_large(w, h)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: 2^32 texels or more");
     if (s.downscale != 1 && s.downscale != 2) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: downscale must be 1 or 2");
     const uint32_t mw = (w + s.downscale - 1) / s.downscale, mh = (h + s.downscale - 1) / s.downscale;
     if (march->width != mw || march->height != mh)
         return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: march must be ceil(w / s) x ceil(h / s) = %u x %u", mw, mh);
-    if (row_begin == 0 && row_end == 0) row_end = h;
-    if (row_end > h || row_begin > row_end) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: bad row range");
+    if (!resolve_rows(&row_begin, &row_end, h)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: bad row range");
     for (const float v : {s.step_length, s.step_transmittance, s.albedo[0], s.albedo[1], s.albedo[2], s.ambient[0], s.ambient[1], s.ambient[2], s.anisotropy,
                           s.depth_bias, s.depth_sharpness, view->z_near})
         if (std::isnan(v)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: a parameter is NaN");
@@ -76,9 +56,9 @@ extern "C" int sah_sun_shafts(sah_ctx* ctx, const sah_view_data* view, const sah
     if (!(std::isfinite(s.depth_sharpness) && s.depth_sharpness >= 0.0f)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: depth_sharpness must be finite and not negative");
     if (s.dither_offset > 15) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: dither_offset must be 0..15");
     for (int i = 1; i < num_planes; i++)
-        if (overlap(out, 8, planes[i].p, planes[i].bpp)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: out overlaps depth, lit or march");
+        if (overlaps(byte_range(out), byte_range(planes[i].p))) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: out overlaps depth, lit or march");
     for (int i = 2; i < num_planes; i++)
-        if (overlap(march, 8, planes[i].p, planes[i].bpp)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: march overlaps depth or lit");
+        if (overlaps(byte_range(march), byte_range(planes[i].p))) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "sun_shafts: march overlaps depth or lit");
 
     sah::SunShaftsArgs a;
     memset(&a, 0, sizeof(a));

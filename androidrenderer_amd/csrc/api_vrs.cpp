@@ -17,14 +17,6 @@ int texel_shift(uint32_t t) {
         if (t == (1u << s)) return s;
     return -1;
 }
-struct Range {
-    uintptr_t begin, end;
-};
-Range range_of(const sah_plane* p) {
-    const uintptr_t b = (uintptr_t)p->ptr;
-    return {b, b + (uint64_t)(p->height - 1) * p->row_pitch_bytes + (uint64_t)p->width * 8};
-}
-bool overlap(const Range& a, const Range& b) { return a.begin < b.end && b.begin < a.end; }
 }  // namespace
 
 extern "C" {
@@ -90,7 +82,7 @@ int sah_vrsaa_resolve(sah_ctx* ctx, const sah_plane* lit, const sah_plane* antia
         return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "vrsaa_resolve: lit is %u x %u, not twice the %u x %u of antialiased", lit->width, lit->height, w, h);
     if (row_begin == 0 && row_end == 0) row_end = h;
     if (row_end > h || row_begin > row_end) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "vrsaa_resolve: bad row range");
-    if (overlap(range_of(lit), range_of(antialiased))) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "vrsaa_resolve: the planes overlap");
+    if (overlaps(byte_range(lit), byte_range(antialiased))) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "vrsaa_resolve: the planes overlap");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, sah::launch_vrsaa_resolve(parg(lit), parg(antialiased), w, h, row_begin, row_end, ctx->stream));
     return SAH_OK;

@@ -7,38 +7,22 @@
 #include "ctx.hpp"
 #include "launch.hpp"
 
-namespace {
-// 0, or the status a plane of `format` with 4-byte texels earns
-int plane4_status(const sah_plane* p, uint32_t format) {
-    if (!p || !p->ptr) return SAH_ERR_INVALID_ARGUMENT;
-    if (p->format != format) return SAH_ERR_UNSUPPORTED_FORMAT;
-    if (!p->width || !p->height || (uint64_t)p->row_pitch_bytes < (uint64_t)p->width * 4 || ((uintptr_t)p->ptr % 4) || (p->row_pitch_bytes % 4))
-        return SAH_ERR_INVALID_ARGUMENT;
-    return SAH_OK;
-}
-}  // namespace
-
 extern "C" {
 
 int sah_vrsaa_measure_aliasing(sah_ctx* ctx, const sah_plane* scene_color, const sah_plane* depth, const sah_plane* contrast, uint32_t row_begin,
                                uint32_t row_end) {
     SAH_RANGE();
     if (!ctx) return SAH_ERR_INVALID_ARGUMENT;
-    const struct {
-        const sah_plane* p;
-        uint32_t format;
-        const char* what;
-    } planes[3] = {{scene_color, SAH_FORMAT_R8G8B8A8_SRGB, "scene_color must be an R8G8B8A8_SRGB plane"},
-                   {depth, SAH_FORMAT_D32_SFLOAT, "depth must be a D32_SFLOAT plane"},
-                   {contrast, SAH_FORMAT_R16G16_SFLOAT, "contrast must be an R16G16_SFLOAT plane"}};
-    for (const auto& e : planes)
-        if (const int rc = plane4_status(e.p, e.format); rc != SAH_OK) return fail(ctx, rc, "measure_aliasing: %s, 4-byte aligned, with a pitch of at least a row", e.what);
+    const PlaneSpec planes[3] = {{scene_color, SAH_FORMAT_R8G8B8A8_SRGB, "scene_color (R8G8B8A8_SRGB)"},
+                                 {depth, SAH_FORMAT_D32_SFLOAT, "depth (D32_SFLOAT)"},
+                                 {contrast, SAH_FORMAT_R16G16_SFLOAT, "contrast (R16G16_SFLOAT)"}};
+    if (const int rc = check_planes(ctx, "measure_aliasing", planes, 3); rc != SAH_OK) return rc;
     const uint32_t w = contrast->width, h = contrast->height;
     if (scene_color->width != w || scene_color->height != h || depth->width != w || depth->height != h)
         return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "measure_aliasing: the three planes must have one extent");
+    // (not texel_count_too_large: this entry has always taken an extent of 2^31 and more as long as the product fits)
     if ((uint64_t)w * h >= (1ull << 32)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "measure_aliasing: 2^32 texels or more");
-    if (row_begin == 0 && row_end == 0) row_end = h;
-    if (row_end > h || row_begin > row_end) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "bad row range");
+    if (!resolve_rows(&row_begin, &row_end, h)) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "measure_aliasing: bad row range");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, sah::launch_vrsaa_contrast(parg(scene_color), parg(depth), parg(contrast), w, h, row_begin, row_end, ctx->luts, ctx->stream));
     return SAH_OK;
@@ -49,7 +33,7 @@ int sah_vrsaa_shading_rate_image(sah_ctx* ctx, const sah_plane* contrast, const 
     static_assert(sizeof(sah_shading_rate_params) == 92, "ShadingRateParams is 92 bytes (sampling_rate_calculator.cpp:126-132)");
     if (!ctx) return SAH_ERR_INVALID_ARGUMENT;
     if (!params) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "shading_rate_image: params is null");
-    if (const int rc = plane4_status(contrast, SAH_FORMAT_R16G16_SFLOAT); rc != SAH_OK)
+    if (const int rc = plane_status(contrast, SAH_FORMAT_R16G16_SFLOAT); rc != SAH_OK)
         return fail(ctx, rc, "shading_rate_image: contrast must be an R16G16_SFLOAT plane, 4-byte aligned, with a pitch of at least a row");
     const sah_plane* s = shading_rate_image;
     if (!s || !s->ptr) return fail(ctx, SAH_ERR_INVALID_ARGUMENT, "shading_rate_image: no target");

@@ -10,6 +10,7 @@
 #include "../../include/sah_hip.h"
 #include "ctx_cache.hpp"
 #include "params.hpp"
+#include "plane_check.hpp"
 #include "rt_args.hpp"
 
 // Context-wide device state that entry points build once and re-use (gather copies, tables, scratch) is written and read on whatever
@@ -208,27 +209,12 @@ inline bool fill_sky_args(const sah_sky_luts& s, const float sun_dir[3], sah::Sk
     return true;
 }
 
-inline uint32_t format_bpp(uint32_t f) {
-    switch (f) {
-        case SAH_FORMAT_R8_UNORM: return 1;
-        case SAH_FORMAT_R16_SFLOAT: case SAH_FORMAT_D16_UNORM: return 2;
-        case SAH_FORMAT_R8G8B8A8_UNORM: case SAH_FORMAT_R8G8B8A8_SRGB: case SAH_FORMAT_R16G16_SFLOAT: case SAH_FORMAT_R32_SFLOAT:
-        case SAH_FORMAT_B10G11R11_UFLOAT_PACK32: case SAH_FORMAT_D32_SFLOAT: return 4;
-        case SAH_FORMAT_R16G16B16A16_SFLOAT: return 8;
-    }
-    return 0;
-}
-
-inline bool plane_ok(const sah_plane* p, uint32_t fmt_a, uint32_t fmt_b, uint32_t w, uint32_t h) {
-    if (!p || !p->ptr) return false;
-    if (p->format != fmt_a && p->format != fmt_b) return false;
-    if (p->width != w || p->height != h) return false;
-    return (uint64_t)p->row_pitch_bytes >= (uint64_t)w * format_bpp(p->format);
-}
-
-inline bool rgba16f_ok(const sah_plane* p) {
-    return p && p->ptr && p->format == SAH_FORMAT_R16G16B16A16_SFLOAT && p->width && p->height &&
-           (uint64_t)p->row_pitch_bytes >= (uint64_t)p->width * 8 && ((uintptr_t)p->ptr % 8) == 0 && (p->row_pitch_bytes % 8) == 0;
+// plane_check.hpp's rule over `n` planes of the pass `pass`: SAH_OK, or the first offender's status with the message that names it
+inline int check_planes(sah_ctx* ctx, const char* pass, const PlaneSpec* specs, int n) {
+    int bad = 0;
+    const int rc = planes_status(specs, n, &bad);
+    if (rc == SAH_OK) return rc;
+    return fail(ctx, rc, "%s: %s must be a plane of that format, not empty, 4-byte aligned, with a pitch of at least a row that is a multiple of 4", pass, specs[bad].name);
 }
 
 inline sah::PlaneArg parg(const sah_plane* p) { return sah::PlaneArg{p ? (const uint8_t*)p->ptr : nullptr, p ? p->row_pitch_bytes : 0}; }
