@@ -19,7 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
-#include "numerics.hpp"
+#include "screen_common.hpp"
 
 namespace sah {
 
@@ -28,26 +28,23 @@ constexpr int kExW = 128, kExH = 4;                // the tile: a wave per row, 
 // atomics, a release and a ticket on one word, so more workgroups cost more than they hide: metering alone at 1280 x 720 / 3840 x 2160
 // took 0.0144 / 0.0459 ms under 256 workgroups, 0.0181 / 0.0372 under 512, 0.0300 / 0.0420 under 1,024 and 0.0484 / 0.0627 under 2,048.
 constexpr uint32_t kExSmallGrid = 256, kExLargeGrid = 512, kExSmallTiles = 4096;
-constexpr float kExInf = __builtin_inff();
 
 namespace {
 
 SAH_DEV uint32_t ex_f2u(float x) { return x >= 4294967296.0f ? 0xffffffffu : (x > 0.0f ? (uint32_t)x : 0u); }
-SAH_DEV float ex_min(float a, float b) { return a < b ? a : b; }
-SAH_DEV float ex_max(float a, float b) { return a > b ? a : b; }
 
 // the bin of the pixel (lo = r | g << 16, hi = b | a << 16), or -1 when it is not counted
 SAH_DEV int ex_bin(uint32_t lo, uint32_t hi) {
-    const float r = h2f((uint16_t)(lo & 0xffffu)), g = h2f((uint16_t)(lo >> 16)), b = h2f((uint16_t)(hi & 0xffffu));
+    const float r = half_lo(lo), g = half_hi(lo), b = half_lo(hi);
     const float L = (r * 0.2126f + g * 0.7152f) + b * 0.0722f;
-    if (!(L > 0.0f && L < kExInf)) return -1;
+    if (!(L > 0.0f && L < kScreenInf)) return -1;
     const int k = (int)(__builtin_bit_cast(uint32_t, L) >> 20) - 856;
     return k < 0 ? 0 : (k > 255 ? 255 : k);
 }
 
 SAH_DEV void ex_scale(uint32_t& lo, uint32_t& hi, float e) {
-    const float r = h2f((uint16_t)(lo & 0xffffu)), g = h2f((uint16_t)(lo >> 16)), b = h2f((uint16_t)(hi & 0xffffu));
-    lo = (uint32_t)f2h(r * e) | ((uint32_t)f2h(g * e) << 16);
+    const float r = half_lo(lo), g = half_hi(lo), b = half_lo(hi);
+    lo = (uint32_t)f2h(r * e) | ((uint32_t)f2h(g * e) << 16);  // (not pack_half2: each product is rounded before the next is formed)
     hi = (uint32_t)f2h(b * e) | (hi & 0xffff0000u);
 }
 
@@ -167,7 +164,7 @@ template <bool kApply, bool kWide> __global__ void __launch_bounds__(256) k_expo
     bool history = false;
     if (a.history) {
         m_p = a.state_in->adapted;
-        history = __builtin_fabsf(m_p) < kExInf;
+        history = __builtin_fabsf(m_p) < kScreenInf;
     }
     float m = 0.0f;
     if (metered) {
@@ -179,10 +176,10 @@ template <bool kApply, bool kWide> __global__ void __launch_bounds__(256) k_expo
     sah_exposure_state out;
     if (metered || history) {
         const float L_avg = __builtin_bit_cast(float, ex_f2u((m + 127.0f) * 8388608.0f));
-        out.exposure = ex_min(ex_max(a.key / L_avg, a.min_exposure), a.max_exposure);
+        out.exposure = sel_min(sel_max(a.key / L_avg, a.min_exposure), a.max_exposure);
         out.adapted = m;
     } else {
-        out.exposure = ex_min(ex_max(1.0f, a.min_exposure), a.max_exposure);
+        out.exposure = sel_min(sel_max(1.0f, a.min_exposure), a.max_exposure);
         out.adapted = __builtin_bit_cast(float, 0x7fc00000u);
     }
     out.metered = N, out.window = hi - lo;
@@ -202,9 +199,7 @@ template <bool kWide> __global__ void __launch_bounds__(256) k_exposure_apply(Ex
 }
 
 bool ex_wide(const ExposureArgs& a, bool with_out) {
-    bool wide = ((uintptr_t)a.scene.ptr % 16) == 0 && (a.scene.pitch % 16) == 0;
-    if (with_out) wide = wide && ((uintptr_t)a.out.ptr % 16) == 0 && (a.out.pitch % 16) == 0;
-    return wide;
+    return planes_aligned({&a.scene}, 16) && (!with_out || planes_aligned({&a.out}, 16));
 }
 
 }  // namespace

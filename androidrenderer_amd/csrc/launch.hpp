@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "../../include/sah_exposure.h"
 #include "../../include/sah_hip.h"
 #include "../../include/sah_mip_chain.h"
@@ -26,6 +28,13 @@
 struct sah_ctx;  // ctx.hpp
 
 namespace sah {
+
+// whether every plane's pointer and pitch are multiples of `align`: what lets a launcher pick its kernel's wide accesses
+inline bool planes_aligned(std::initializer_list<const PlaneArg*> planes, uint32_t align) {
+    bool ok = true;
+    for (const PlaneArg* p : planes) ok = ok && ((uintptr_t)p->ptr % align) == 0 && (p->pitch % align) == 0;
+    return ok;
+}
 
 // --- lighting.hip, lighting_tiled.hip
 hipError_t launch_lighting(const LightingArgs& a, const CsmArgs& csm, const LpvArgs& lpv, const CacheArgs& cache, const RtgiArgs& rtgi,

@@ -18,41 +18,20 @@
 
 #include "dither.hpp"
 #include "launch.hpp"
-#include "numerics.hpp"
+#include "screen_common.hpp"
 
 namespace sah {
 
 constexpr int kMbT = (int)SAH_MOTION_BLUR_TILE;
-constexpr float kMbInf = __builtin_inff(), kMbFar = 0x1p100f;
+constexpr float kMbFar = 0x1p100f;
 
 namespace {
-SAH_DEV float mb_clamp01(float a) { return a > 0.0f ? (a < 1.0f ? a : 1.0f) : 0.0f; }
-SAH_DEV int mb_clampi(int i, int n) { return min(max(i, 0), n - 1); }
-SAH_DEV int mb_floor_to_int(float v) { return (int)__builtin_fminf(__builtin_fmaxf(__builtin_floorf(v), -2147483648.0f), 2147483520.0f); }
-SAH_DEV float mb_sample_position(int X, float scale, float jitter) { return ((float)X + 0.5f) * scale - jitter; }
-
-template <bool kVec> SAH_DEV uint2 mb_load_texel8(const PlaneArg& p, int x, int y) {
-    const uint8_t* at = p.ptr + (size_t)y * p.pitch + (size_t)x * 8;
-    if (kVec) return *reinterpret_cast<const uint2*>(at);
-    return make_uint2(reinterpret_cast<const uint32_t*>(at)[0], reinterpret_cast<const uint32_t*>(at)[1]);
-}
-template <bool kVec> SAH_DEV void mb_store_texel8(const PlaneArg& p, int x, int y, uint2 v) {
-    uint8_t* at = const_cast<uint8_t*>(p.ptr) + (size_t)y * p.pitch + (size_t)x * 8;
-    if (kVec) {
-        *reinterpret_cast<uint2*>(at) = v;
-    } else {
-        reinterpret_cast<uint32_t*>(at)[0] = v.x;
-        reinterpret_cast<uint32_t*>(at)[1] = v.y;
-    }
-}
-SAH_DEV uint32_t mb_load_dword(const PlaneArg& p, int x, int y) { return *reinterpret_cast<const uint32_t*>(p.ptr + (size_t)y * p.pitch + (size_t)x * 4); }
-
 // Velocity up to the clamp: the scaled vector of a pair of halfs and its squared length, zero where that is not finite
 SAH_DEV float mb_scaled(const MotionBlurArgs& a, uint32_t m, float& ax, float& ay) {
-    ax = (h2f((uint16_t)(m & 0xffffu)) + a.djx) * a.shutter;
-    ay = (h2f((uint16_t)(m >> 16)) + a.djy) * a.shutter;
+    ax = (half_lo(m) + a.djx) * a.shutter;
+    ay = (half_hi(m) + a.djy) * a.shutter;
     float l2 = ax * ax + ay * ay;
-    if (!(l2 < kMbInf)) ax = 0.0f, ay = 0.0f, l2 = 0.0f;
+    if (!(l2 < kScreenInf)) ax = 0.0f, ay = 0.0f, l2 = 0.0f;
     return l2;
 }
 SAH_DEV uint64_t mb_key(const MotionBlurArgs& a, uint32_t m) {
@@ -73,17 +52,16 @@ SAH_DEV MbVelocity mb_velocity(const MotionBlurArgs& a, uint32_t m) {
     return {ax, ay, l};
 }
 // Surface: the linear depth of a texel, a large finite one without a surface
-SAH_DEV float mb_surface(const MotionBlurArgs& a, float d) {
+SAH_DEV float mb_linear_depth(const MotionBlurArgs& a, float d) {
     const float z = d > 0.0f ? a.z_near / d : kMbFar;
     return z < kMbFar ? z : kMbFar;
 }
-SAH_DEV float mb_cone(float d, float s) { return mb_clamp01(1.0f - d / s); }
+SAH_DEV float mb_cone(float d, float s) { return clamp01(1.0f - d / s); }
 SAH_DEV float mb_cyl(float d, float s) {
     const float e0 = 0.95f * s, e1 = 1.05f * s;
-    const float y = mb_clamp01((e1 - d) / (e1 - e0));
+    const float y = clamp01((e1 - d) / (e1 - e0));
     return (y * y) * (3.0f - 2.0f * y);
 }
-SAH_DEV bool mb_clean(float r, float g, float b) { return (r >= 0.0f) & (r < kMbInf) & (g >= 0.0f) & (g < kMbInf) & (b >= 0.0f) & (b < kMbInf); }
 }  // namespace
 
 __global__ void __launch_bounds__(256) k_mb_tiles(MotionBlurArgs a) {
@@ -92,7 +70,7 @@ __global__ void __launch_bounds__(256) k_mb_tiles(MotionBlurArgs a) {
     const uint32_t row = blockIdx.x / a.tiles_x, tile_x = blockIdx.x - row * a.tiles_x, tile_y = a.tile_row_begin + row;
     const int x = (int)tile_x * kMbT + (tid & 15), y = (int)tile_y * kMbT + (tid >> 4);
     uint64_t key = 0;  // a texel outside the image takes no part
-    if (x < (int)a.w && y < (int)a.h) key = mb_key(a, mb_load_dword(a.mv, x, y)) + 1;
+    if (x < (int)a.w && y < (int)a.h) key = mb_key(a, load_u32(a.mv, x, y)) + 1;
 #pragma unroll
     for (int off = 32; off; off >>= 1) {
         const uint64_t other = __shfl_xor(key, off);
@@ -115,11 +93,11 @@ template <bool kVec> __global__ void __launch_bounds__(256) k_mb_gather(MotionBl
     const uint32_t group_y = blockIdx.x / a.groups_x, group_x = blockIdx.x - group_y * a.groups_x;  // (rows folded into grid.x, as k_ssr_trace)
     const int X0 = (int)group_x * kMbT, Y0 = (int)(a.row_begin + group_y * kMbT);
     // the tile of the workgroup's first pixel; every pixel's tile is that one or the next, per axis
-    const int bx0 = mb_clampi(mb_floor_to_int(mb_sample_position(X0, a.sx, a.jx)), w) >> 4;
-    const int by0 = mb_clampi(mb_floor_to_int(mb_sample_position(Y0, a.sy, a.jy)), h) >> 4;
+    const int bx0 = clampi(floor_i32(sample_position(X0, a.sx, a.jx)), w) >> 4;
+    const int by0 = clampi(floor_i32(sample_position(Y0, a.sy, a.jy)), h) >> 4;
     if (tid < 16) {
-        const int tx = mb_clampi(bx0 - 1 + (tid & 3), (int)a.tiles_x), ty = mb_clampi(by0 - 1 + (tid >> 2), (int)a.tiles_y);
-        s_key[tid] = mb_key(a, mb_load_dword(a.tiles, tx, ty));
+        const int tx = clampi(bx0 - 1 + (tid & 3), (int)a.tiles_x), ty = clampi(by0 - 1 + (tid >> 2), (int)a.tiles_y);
+        s_key[tid] = mb_key(a, load_u32(a.tiles, tx, ty));
     }
     __syncthreads();
     if (tid < 4) {
@@ -137,8 +115,8 @@ template <bool kVec> __global__ void __launch_bounds__(256) k_mb_gather(MotionBl
     __syncthreads();
     const int X = X0 + (tid & 15), Y = Y0 + (tid >> 4);
     const bool inside = X < W && Y < row_end;
-    const float ux = mb_sample_position(min(X, W - 1), a.sx, a.jx), uy = mb_sample_position(min(Y, row_end - 1), a.sy, a.jy);
-    const int i = mb_clampi(mb_floor_to_int(ux), w), j = mb_clampi(mb_floor_to_int(uy), h);
+    const float ux = sample_position(min(X, W - 1), a.sx, a.jx), uy = sample_position(min(Y, row_end - 1), a.sy, a.jy);
+    const int i = clampi(floor_i32(ux), w), j = clampi(floor_i32(uy), h);
     const MbVelocity vn = mb_velocity(a, s_neighbour[min((i >> 4) - bx0, 1) + 2 * min((j >> 4) - by0, 1)]);
     const bool moving = inside && !(vn.speed < a.min_velocity);
     if (!wave_any(moving)) {  // nothing but a copy: the static-camera frame
@@ -151,17 +129,18 @@ template <bool kVec> __global__ void __launch_bounds__(256) k_mb_gather(MotionBl
                 else *reinterpret_cast<uint2*>(dst) = *reinterpret_cast<const uint2*>(src);
             }
         } else if (inside) {
-            mb_store_texel8<false>(a.out, X, Y, mb_load_texel8<false>(a.scene, X, Y));
+            store_texel8<false>(a.out, X, Y, load_texel8<false>(a.scene, X, Y));
         }
         return;
     }
     if (!inside) return;
-    const uint2 own = mb_load_texel8<kVec>(a.scene, X, Y);
+    const uint2 own = load_texel8<kVec>(a.scene, X, Y);
     uint2 res = own;
+    // (spelled out, not half_lo / half_hi: through the helpers this one line leaves the kernel another register assignment)
     const float c[3] = {h2f((uint16_t)(own.x & 0xffffu)), h2f((uint16_t)(own.x >> 16)), h2f((uint16_t)(own.y & 0xffffu))};
-    if (moving && mb_clean(c[0], c[1], c[2])) {
-        const MbVelocity vp = mb_velocity(a, mb_load_dword(a.mv, i, j));
-        const float zp = mb_surface(a, __builtin_bit_cast(float, mb_load_dword(a.depth, i, j)));
+    if (moving && all_nonneg_finite(c[0], c[1], c[2])) {
+        const MbVelocity vp = mb_velocity(a, load_u32(a.mv, i, j));
+        const float zp = mb_linear_depth(a, load_f32(a.depth, i, j));
         const float dith = (a.flags & SAH_MOTION_BLUR_DITHER) ? (bayer4x4((uint32_t)X, (uint32_t)Y) - 7.5f) * 0.0625f : 0.0f;
         const float wf = (float)a.w, hf = (float)a.h, Wf = (float)a.W, Hf = (float)a.H;
         float sw = 0.0f, acc[3] = {0.0f, 0.0f, 0.0f};
@@ -176,13 +155,13 @@ template <bool kVec> __global__ void __launch_bounds__(256) k_mb_gather(MotionBl
             // (the min: float(w) rounds up for some w > 2^24, and no address may follow it)
             const int ti = min((int)__builtin_floorf(px), w - 1), tj = min((int)__builtin_floorf(py), h - 1);
             const int si = min((int)__builtin_floorf(qx), W - 1), sj = min((int)__builtin_floorf(qy), (int)a.H - 1);
-            const uint2 st = mb_load_texel8<kVec>(a.scene, si, sj);
-            const float s[3] = {h2f((uint16_t)(st.x & 0xffffu)), h2f((uint16_t)(st.x >> 16)), h2f((uint16_t)(st.y & 0xffffu))};
-            if (!mb_clean(s[0], s[1], s[2])) continue;
-            const MbVelocity vs = mb_velocity(a, mb_load_dword(a.mv, ti, tj));
-            const float zs = mb_surface(a, __builtin_bit_cast(float, mb_load_dword(a.depth, ti, tj)));
+            const uint2 st = load_texel8<kVec>(a.scene, si, sj);
+            const float s[3] = {half_lo(st.x), half_hi(st.x), half_lo(st.y)};
+            if (!all_nonneg_finite(s[0], s[1], s[2])) continue;
+            const MbVelocity vs = mb_velocity(a, load_u32(a.mv, ti, tj));
+            const float zs = mb_linear_depth(a, load_f32(a.depth, ti, tj));
             const float d = __builtin_sqrtf(ex * ex + ey * ey);
-            const float f = mb_clamp01(1.0f - (zs - zp) / a.depth_extent), g = mb_clamp01(1.0f - (zp - zs) / a.depth_extent);
+            const float f = clamp01(1.0f - (zs - zp) / a.depth_extent), g = clamp01(1.0f - (zp - zs) / a.depth_extent);
             const float wk = (f * mb_cone(d, vs.speed) + g * mb_cone(d, vp.speed)) + (2.0f * mb_cyl(d, vs.speed)) * mb_cyl(d, vp.speed);
             if (wk != 0.0f) {
                 sw = sw + wk;
@@ -194,7 +173,7 @@ template <bool kVec> __global__ void __launch_bounds__(256) k_mb_gather(MotionBl
             float r[3], o[3];
 #pragma unroll
             for (int ch = 0; ch < 3; ch++) r[ch] = acc[ch] / sw, o[ch] = c[ch] + r[ch];
-            if ((__builtin_fabsf(o[0]) < kMbInf) & (__builtin_fabsf(o[1]) < kMbInf) & (__builtin_fabsf(o[2]) < kMbInf)) {
+            if (all_finite(o[0], o[1], o[2])) {
                 const uint32_t h0 = r[0] != 0.0f ? (uint32_t)f2h(o[0]) : own.x & 0xffffu;
                 const uint32_t h1 = r[1] != 0.0f ? (uint32_t)f2h(o[1]) : own.x >> 16;
                 const uint32_t h2 = r[2] != 0.0f ? (uint32_t)f2h(o[2]) : own.y & 0xffffu;
@@ -202,14 +181,13 @@ template <bool kVec> __global__ void __launch_bounds__(256) k_mb_gather(MotionBl
             }
         }
     }
-    mb_store_texel8<kVec>(a.out, X, Y, res);
+    store_texel8<kVec>(a.out, X, Y, res);
 }
 
 hipError_t launch_motion_blur(const MotionBlurArgs& args, hipStream_t st) {
     if (args.row_end <= args.row_begin) return hipSuccess;
     MotionBlurArgs a = args;
-    bool vec = true;
-    for (const PlaneArg* p : {&a.scene, &a.depth, &a.mv, &a.out}) vec = vec && ((uintptr_t)p->ptr % 16) == 0 && (p->pitch % 16) == 0;
+    const bool vec = planes_aligned({&a.scene, &a.depth, &a.mv, &a.out}, 16);
     // w, h, W, H < 2^31 and w * h, W * H < 2^32 (api_motion_blur.cpp): both tile counts stay below 2^31 however thin the frame
     a.groups_x = (a.W + kMbT - 1) / kMbT;
     const uint64_t groups = (uint64_t)a.groups_x * ((a.row_end - a.row_begin + kMbT - 1) / kMbT);

@@ -14,64 +14,37 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
-#include "numerics.hpp"
+#include "screen_common.hpp"
 
 namespace sah {
 
 constexpr int kRtW = 64, kRtH = 16;  // the temporal kernel's tile
 constexpr int kRfW = 32, kRfH = 16;  // the filter kernel's tile: 27.6 KB of LDS with three passes, five workgroups a CU (profiles/rt_denoise.txt has 64 x 16 measured against it)
-constexpr float kRdInf = __builtin_inff();
-
-SAH_DEV float rd_max0(float a) { return a > 0.0f ? a : 0.0f; }
-SAH_DEV bool rd_finite(float a) { return __builtin_fabsf(a) < kRdInf; }
-
-// "Surface" of the header: false when the pixel has none.  n01, n2: the bits of its normal (x | y << 16, z | w << 16).
-SAH_DEV bool rd_surface(const RtDenoiseArgs& a, int x, int y, float d, uint32_t n01, uint32_t n2, float& z, float P[3], float N[3]) {
-    if (!(d > 0.0f)) return false;
-    z = a.z_near / d;
-    const float cx = (float)x + 0.5f, cy = (float)y + 0.5f;
-    P[0] = (z * ((cx * a.tx - 1.0f) + a.p20)) * a.ipx, P[1] = (z * ((cy * a.ty - 1.0f) + a.p21)) * a.ipy, P[2] = -z;
-    const float nx = h2f((uint16_t)(n01 & 0xffffu)), ny = h2f((uint16_t)(n01 >> 16)), nz = h2f((uint16_t)(n2 & 0xffffu));
-    const float l = __builtin_sqrtf((nx * nx + ny * ny) + nz * nz);
-    N[0] = nx / l, N[1] = ny / l, N[2] = nz / l;
-    return rd_finite(P[0]) && rd_finite(P[1]) && rd_finite(P[2]) && rd_finite(N[0]) && rd_finite(N[1]) && rd_finite(N[2]);
-}
 
 // One pixel of the temporal pass: the bits of accum_out and of length_out.
 template <bool kHistory> SAH_DEV void rd_pixel(const RtDenoiseArgs& a, int x, int y, uint32_t noisy, float d, uint32_t n01, uint32_t n2, uint32_t mv, uint32_t& acc, uint16_t& len) {
     float z, P[3], N[3];
     acc = noisy, len = 0;
-    if (!rd_surface(a, x, y, d, n01, n2, z, P, N)) return;
+    if (!view_surface(a, x, y, d, n01, n2, z, P, N)) return;
     const float s = __builtin_bit_cast(float, noisy);
-    const float c = rd_finite(s) ? s : 1.0f;
+    const float c = finite_f32(s) ? s : 1.0f;
     acc = __builtin_bit_cast(uint32_t, c), len = 0x3c00u;  // a = c, n = 1
     if (!kHistory) return;
     const int W = (int)a.W, H = (int)a.H;
-    const float qx = (((float)x + 0.5f) + h2f((uint16_t)(mv & 0xffffu))) + a.djx, qy = (((float)y + 0.5f) + h2f((uint16_t)(mv >> 16))) + a.djy;
-    bool valid = (qx >= 0.0f) & (qx <= (float)a.W) & (qy >= 0.0f) & (qy <= (float)a.H);
-    const float wx = ((a.iv[0] * P[0] + a.iv[3] * P[1]) + a.iv[6] * P[2]) + a.iv[9];
-    const float wy = ((a.iv[1] * P[0] + a.iv[4] * P[1]) + a.iv[7] * P[2]) + a.iv[10];
-    const float wz = ((a.iv[2] * P[0] + a.iv[5] * P[1]) + a.iv[8] * P[2]) + a.iv[11];
-    const float z_prev = -(((a.l2[0] * wx + a.l2[1] * wy) + a.l2[2] * wz) + a.l2[3]);
-    valid = valid && rd_finite(z_prev) && z_prev > 0.0f;
-    const float tol = a.depth_tolerance * z_prev;
-    const float pxf = qx - 0.5f, pyf = qy - 0.5f;
-    const float fx0 = __builtin_floorf(pxf), fy0 = __builtin_floorf(pyf);
-    const float fx = pxf - fx0, fy = pyf - fy0;
-    const float gx = 1.0f - fx, gy = 1.0f - fy;
-    const int ix = (int)__builtin_fminf(__builtin_fmaxf(fx0, -1.0e9f), 1.0e9f), iy = (int)__builtin_fminf(__builtin_fmaxf(fy0, -1.0e9f), 1.0e9f);
-    const float w4[4] = {gx * gy, fx * gy, gx * fy, fx * fy};
+    const Reprojection rp = reproject(a, x, y, mv, P);
+    const bool valid = rp.valid;
+    const float z_prev = rp.z_prev, tol = rp.tol;
     float sw = 0.0f, sh = 0.0f, sn = 0.0f;
 #pragma unroll
     for (int t = 0; t < 4; t++) {
-        const int u = ix + (t & 1), v = iy + (t >> 1);
-        const float w = w4[t];
+        const int u = rp.ix + (t & 1), v = rp.iy + (t >> 1);
+        const float w = rp.w4[t];
         if (valid && w > 0.0f && u >= 0 && u < W && v >= 0 && v < H) {
             const float pd = *reinterpret_cast<const float*>(a.prev_depth.ptr + (size_t)v * a.prev_depth.pitch + (size_t)u * 4);
             const float hv = *reinterpret_cast<const float*>(a.history.ptr + (size_t)v * a.history.pitch + (size_t)u * 4);
             const float hl = h2f(*reinterpret_cast<const uint16_t*>(a.hist_len.ptr + (size_t)v * a.hist_len.pitch + (size_t)u * 2));
             const float zt = a.z_near / pd;
-            if (pd > 0.0f && __builtin_fabsf(zt - z_prev) <= tol && rd_finite(hv) && rd_finite(hl) && hl >= 1.0f) {
+            if (pd > 0.0f && __builtin_fabsf(zt - z_prev) <= tol && finite_f32(hv) && finite_f32(hl) && hl >= 1.0f) {
                 sw = sw + w;
                 sh = sh + w * hv;
                 sn = sn + w * hl;
@@ -134,7 +107,7 @@ template <int S> SAH_DEV float rd_filter_cell(const float* v, const float* zs, c
     if (zc != zc) return vc;
     const float gc = sharp / zc;
     const uint2 nc = ns[idx];
-    const float cx = h2f((uint16_t)(nc.x & 0xffffu)), cy = h2f((uint16_t)(nc.x >> 16)), cz = h2f((uint16_t)(nc.y & 0xffffu));
+    const float cx = half_lo(nc.x), cy = half_hi(nc.x), cz = half_lo(nc.y);
     float wsum = 0.0f, dsum = 0.0f;
 #pragma unroll
     for (int dy = -1; dy <= 1; dy++)
@@ -149,10 +122,10 @@ template <int S> SAH_DEV float rd_filter_cell(const float* v, const float* zs, c
             const float zt = zs[j];
             if (zt == zt) {
                 const float k = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);
-                const float dw = rd_max0(1.0f - __builtin_fabsf(zt - zc) * gc);
+                const float dw = max0(1.0f - __builtin_fabsf(zt - zc) * gc);
                 const uint2 nt = ns[j];
-                const float ex = h2f((uint16_t)(nt.x & 0xffffu)), ey = h2f((uint16_t)(nt.x >> 16)), ez = h2f((uint16_t)(nt.y & 0xffffu));
-                float e = rd_max0((cx * ex + cy * ey) + cz * ez);
+                const float ex = half_lo(nt.x), ey = half_hi(nt.x), ez = half_lo(nt.y);
+                float e = max0((cx * ex + cy * ey) + cz * ez);
                 for (uint32_t q = 0; q < squarings; q++) e = e * e;
                 const float w = (k * dw) * e;
                 wsum = wsum + w;
@@ -181,9 +154,9 @@ template <int kPasses, int kTW> __global__ void __launch_bounds__(256) k_rd_filt
             const uint32_t* np = reinterpret_cast<const uint32_t*>(a.normals.ptr + (size_t)gy * a.normals.pitch + (size_t)gx * 8);
             v = *reinterpret_cast<const float*>(a.accum.ptr + (size_t)gy * a.accum.pitch + (size_t)gx * 4);
             float zz, P[3], N[3];
-            if (rd_surface(a, gx, gy, d, np[0], np[1], zz, P, N)) {
+            if (view_surface(a, gx, gy, d, np[0], np[1], zz, P, N)) {
                 z = zz;
-                n = make_uint2((uint32_t)f2h(N[0]) | ((uint32_t)f2h(N[1]) << 16), (uint32_t)f2h(N[2]));
+                n = make_uint2(pack_half2(N[0], N[1]), (uint32_t)f2h(N[2]));
             }
         }
         s_z[i] = z, s_v0[i] = v, s_n[i] = n;
@@ -220,9 +193,8 @@ template <int kPasses, int kTW> __global__ void __launch_bounds__(256) k_rd_filt
 
 hipError_t launch_rt_denoise(const RtDenoiseArgs& a, uint32_t passes, bool history, hipStream_t st) {
     if (a.row_end <= a.row_begin || a.acc_end <= a.acc_begin) return hipSuccess;
-    bool vec = true;
-    for (const PlaneArg* p : {&a.noisy, &a.depth, &a.normals, &a.mv, &a.prev_depth, &a.history, &a.hist_len, &a.accum, &a.length, &a.out})
-        vec = vec && ((uintptr_t)p->ptr % 16) == 0 && (p->pitch % 16) == 0;  // (planes the flag excuses arrive as null, pitch 0)
+    // (planes the flag excuses arrive as null, pitch 0)
+    const bool vec = planes_aligned({&a.noisy, &a.depth, &a.normals, &a.mv, &a.prev_depth, &a.history, &a.hist_len, &a.accum, &a.length, &a.out}, 16);
     const bool out = passes == 0;
     void (*temporal)(RtDenoiseArgs);
     if (history) temporal = vec ? (out ? k_rd_temporal<true, true, true> : k_rd_temporal<true, true, false>) : (out ? k_rd_temporal<false, true, true> : k_rd_temporal<false, true, false>);

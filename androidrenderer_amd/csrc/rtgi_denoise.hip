@@ -1,6 +1,6 @@
 // Temporal accumulation and variance-guided filter for the RTGI ray planes, for gfx950 (include/sah_rtgi_denoise.h): builder-owned
-// arithmetic, restated by tests/rtgi_denoise_ref.py.  The device helpers for "Surface" and the reprojection are copies of rt_denoise.hip's
-// (that file stays as it is).
+// arithmetic, restated by tests/rtgi_denoise_ref.py.  "Surface" and the reprojection are rt_denoise.hip's, shared through
+// screen_common.hpp.
 //
 // k_gd_temporal: a 256-thread workgroup covers a 64 x 8 tile, two adjacent pixels of one row per thread.  kVec: every plane is 16-byte
 // aligned with a pitch that is a multiple of 16 — the thread's two rays, irradiances and normals are one 16-byte load each, its depths and
@@ -16,29 +16,14 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
-#include "numerics.hpp"
+#include "screen_common.hpp"
 
 namespace sah {
 
 constexpr int kGtW = 64, kGtH = 8;   // the temporal kernel's tile
 constexpr int kGfW = 16, kGfH = 16;  // the filter kernel's tile: 39.6 KB of LDS with three passes, four workgroups a CU (profiles/rtgi_denoise.txt has 32 x 16 and 32 x 8 measured against it)
-constexpr float kGdInf = __builtin_inff();
 
-SAH_DEV float gd_max0(float a) { return a > 0.0f ? a : 0.0f; }
-SAH_DEV bool gd_finite(float a) { return __builtin_fabsf(a) < kGdInf; }
 SAH_DEV float gd_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-
-// "Surface" of sah_rt_denoise.h: false when the pixel has none.  n01, n2: the bits of its normal (x | y << 16, z | w << 16).
-SAH_DEV bool gd_surface(const RtgiDenoiseArgs& a, int x, int y, float d, uint32_t n01, uint32_t n2, float& z, float P[3], float N[3]) {
-    if (!(d > 0.0f)) return false;
-    z = a.z_near / d;
-    const float cx = (float)x + 0.5f, cy = (float)y + 0.5f;
-    P[0] = (z * ((cx * a.tx - 1.0f) + a.p20)) * a.ipx, P[1] = (z * ((cy * a.ty - 1.0f) + a.p21)) * a.ipy, P[2] = -z;
-    const float nx = h2f((uint16_t)(n01 & 0xffffu)), ny = h2f((uint16_t)(n01 >> 16)), nz = h2f((uint16_t)(n2 & 0xffffu));
-    const float l = __builtin_sqrtf((nx * nx + ny * ny) + nz * nz);
-    N[0] = nx / l, N[1] = ny / l, N[2] = nz / l;
-    return gd_finite(P[0]) && gd_finite(P[1]) && gd_finite(P[2]) && gd_finite(N[0]) && gd_finite(N[1]) && gd_finite(N[2]);
-}
 
 // One pixel of the temporal pass.  rb, ri, nrm: the 64 bits of its ray, irradiance and normal.  acc: accum_out's texel, mom: moments_out's;
 // orb, oir: the texels of the two denoised planes when passes == 0.
@@ -47,38 +32,26 @@ SAH_DEV void gd_pixel(const RtgiDenoiseArgs& a, int x, int y, uint2 rb, uint2 ri
     float z, P[3], N[3];
     acc[0] = acc[1] = acc[2] = acc[3] = 0.0f, mom[0] = mom[1] = 0.0f;
     orb = rb, oir = ri;
-    if (!gd_surface(a, x, y, d, nrm.x, nrm.y, z, P, N)) return;
-    const float dx = h2f((uint16_t)(rb.x & 0xffffu)), dy = h2f((uint16_t)(rb.x >> 16)), dz = h2f((uint16_t)(rb.y & 0xffffu));
-    const float dt = (dx * N[0] + dy * N[1]) + dz * N[2];
-    const float cs = dt > 0.0f ? (dt < 1.0f ? dt : 1.0f) : 0.0f;
+    if (!view_surface(a, x, y, d, nrm.x, nrm.y, z, P, N)) return;
+    const float dx = half_lo(rb.x), dy = half_hi(rb.x), dz = half_lo(rb.y);
+    const float cs = clamp01((dx * N[0] + dy * N[1]) + dz * N[2]);
     float c[5];
-    c[0] = h2f((uint16_t)(ri.x & 0xffffu)) * cs, c[1] = h2f((uint16_t)(ri.x >> 16)) * cs, c[2] = h2f((uint16_t)(ri.y & 0xffffu)) * cs;
+    c[0] = half_lo(ri.x) * cs, c[1] = half_hi(ri.x) * cs, c[2] = half_lo(ri.y) * cs;
 #pragma unroll
-    for (int k = 0; k < 3; k++) c[k] = gd_finite(c[k]) ? c[k] : 0.0f;
+    for (int k = 0; k < 3; k++) c[k] = finite_f32(c[k]) ? c[k] : 0.0f;
     c[3] = gd_lum(c[0], c[1], c[2]);
     c[4] = c[3] * c[3];
     float n = 1.0f;
     if (kHistory) {
         const int W = (int)a.W, H = (int)a.H;
-        const float qx = (((float)x + 0.5f) + h2f((uint16_t)(mv & 0xffffu))) + a.djx, qy = (((float)y + 0.5f) + h2f((uint16_t)(mv >> 16))) + a.djy;
-        bool valid = (qx >= 0.0f) & (qx <= (float)a.W) & (qy >= 0.0f) & (qy <= (float)a.H);
-        const float wx = ((a.iv[0] * P[0] + a.iv[3] * P[1]) + a.iv[6] * P[2]) + a.iv[9];
-        const float wy = ((a.iv[1] * P[0] + a.iv[4] * P[1]) + a.iv[7] * P[2]) + a.iv[10];
-        const float wz = ((a.iv[2] * P[0] + a.iv[5] * P[1]) + a.iv[8] * P[2]) + a.iv[11];
-        const float z_prev = -(((a.l2[0] * wx + a.l2[1] * wy) + a.l2[2] * wz) + a.l2[3]);
-        valid = valid && gd_finite(z_prev) && z_prev > 0.0f;
-        const float tol = a.depth_tolerance * z_prev;
-        const float pxf = qx - 0.5f, pyf = qy - 0.5f;
-        const float fx0 = __builtin_floorf(pxf), fy0 = __builtin_floorf(pyf);
-        const float fx = pxf - fx0, fy = pyf - fy0;
-        const float gx = 1.0f - fx, gy = 1.0f - fy;
-        const int ix = (int)__builtin_fminf(__builtin_fmaxf(fx0, -1.0e9f), 1.0e9f), iy = (int)__builtin_fminf(__builtin_fmaxf(fy0, -1.0e9f), 1.0e9f);
-        const float w4[4] = {gx * gy, fx * gy, gx * fy, fx * fy};
+        const Reprojection rp = reproject(a, x, y, mv, P);
+        const bool valid = rp.valid;
+        const float z_prev = rp.z_prev, tol = rp.tol;
         float sw = 0.0f, sn = 0.0f, s[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int t = 0; t < 4; t++) {
-            const int u = ix + (t & 1), v = iy + (t >> 1);
-            const float w = w4[t];
+            const int u = rp.ix + (t & 1), v = rp.iy + (t >> 1);
+            const float w = rp.w4[t];
             if (valid && w > 0.0f && u >= 0 && u < W && v >= 0 && v < H) {
                 const float pd = *reinterpret_cast<const float*>(a.prev_depth.ptr + (size_t)v * a.prev_depth.pitch + (size_t)u * 4);
                 const uint8_t* hp = a.history.ptr + (size_t)v * a.history.pitch + (size_t)u * 16;
@@ -94,8 +67,8 @@ SAH_DEV void gd_pixel(const RtgiDenoiseArgs& a, int x, int y, uint2 rb, uint2 ri
                     h[0] = hf[0], h[1] = hf[1], h[2] = hf[2], hn = hf[3], h[3] = mf[0], h[4] = mf[1];
                 }
                 const float zt = a.z_near / pd;
-                if (pd > 0.0f && __builtin_fabsf(zt - z_prev) <= tol && gd_finite(hn) && hn >= 1.0f && gd_finite(h[0]) && gd_finite(h[1]) && gd_finite(h[2]) &&
-                    gd_finite(h[3]) && gd_finite(h[4])) {
+                if (pd > 0.0f && __builtin_fabsf(zt - z_prev) <= tol && finite_f32(hn) && hn >= 1.0f && finite_f32(h[0]) && finite_f32(h[1]) && finite_f32(h[2]) &&
+                    finite_f32(h[3]) && finite_f32(h[4])) {
                     sw = sw + w;
                     sn = sn + w * hn;
 #pragma unroll
@@ -112,8 +85,8 @@ SAH_DEV void gd_pixel(const RtgiDenoiseArgs& a, int x, int y, uint2 rb, uint2 ri
         }
     }
     acc[0] = c[0], acc[1] = c[1], acc[2] = c[2], acc[3] = n, mom[0] = c[3], mom[1] = c[4];
-    orb = make_uint2((uint32_t)f2h(N[0]) | ((uint32_t)f2h(N[1]) << 16), (uint32_t)f2h(N[2]) | (rb.y & 0xffff0000u));
-    oir = make_uint2((uint32_t)f2h(c[0]) | ((uint32_t)f2h(c[1]) << 16), (uint32_t)f2h(c[2]));
+    orb = make_uint2(pack_half2(N[0], N[1]), (uint32_t)f2h(N[2]) | (rb.y & 0xffff0000u));
+    oir = make_uint2(pack_half2(c[0], c[1]), (uint32_t)f2h(c[2]));
 }
 
 template <bool kVec, bool kHistory, bool kOut> __global__ void __launch_bounds__(256) k_gd_temporal(RtgiDenoiseArgs a) {
@@ -183,7 +156,7 @@ template <int S> SAH_DEV void gd_filter_cell(const RtgiDenoiseArgs& a, const GdC
     if (zc != zc) return;
     const float gc = a.depth_sharpness / zc;
     const uint2 nc = ns[idx];
-    const float cx = h2f((uint16_t)(nc.x & 0xffffu)), cy = h2f((uint16_t)(nc.x >> 16)), cz = h2f((uint16_t)(nc.y & 0xffffu));
+    const float cx = half_lo(nc.x), cy = half_hi(nc.x), cz = half_lo(nc.y);
     const bool use_lum = a.luminance_sigma != 0.0f && !(nc.y >> 16);
     const float lc = gd_lum(vc[0], vc[1], vc[2]);
     float den = 1.0f;
@@ -218,14 +191,14 @@ template <int S> SAH_DEV void gd_filter_cell(const RtgiDenoiseArgs& a, const GdC
             const float zt = zs[j];
             if (zt == zt) {
                 const float k = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);
-                const float dw = gd_max0(1.0f - __builtin_fabsf(zt - zc) * gc);
+                const float dw = max0(1.0f - __builtin_fabsf(zt - zc) * gc);
                 const uint2 nt = ns[j];
-                const float ex = h2f((uint16_t)(nt.x & 0xffffu)), ey = h2f((uint16_t)(nt.x >> 16)), ez = h2f((uint16_t)(nt.y & 0xffffu));
-                float e = gd_max0((cx * ex + cy * ey) + cz * ez);
+                const float ex = half_lo(nt.x), ey = half_hi(nt.x), ez = half_lo(nt.y);
+                float e = max0((cx * ex + cy * ey) + cz * ez);
                 for (uint32_t q = 0; q < a.normal_squarings; q++) e = e * e;
                 const float vt[3] = {v.r[j], v.g[j], v.b[j]};
                 float w = (k * dw) * e;
-                if (use_lum) w = w * gd_max0(1.0f - __builtin_fabsf(gd_lum(vt[0], vt[1], vt[2]) - lc) / den);
+                if (use_lum) w = w * max0(1.0f - __builtin_fabsf(gd_lum(vt[0], vt[1], vt[2]) - lc) / den);
                 wsum = wsum + w;
 #pragma unroll
                 for (int c = 0; c < 3; c++) dsum[c] = dsum[c] + w * (vt[c] - vc[c]);
@@ -259,7 +232,7 @@ template <int kPasses, int kTW, int kTH> __global__ void __launch_bounds__(256) 
             const float d = *reinterpret_cast<const float*>(a.depth.ptr + (size_t)gy * a.depth.pitch + (size_t)gx * 4);
             const uint32_t* np = reinterpret_cast<const uint32_t*>(a.normals.ptr + (size_t)gy * a.normals.pitch + (size_t)gx * 8);
             float zz, P[3], N[3];
-            if (gd_surface(a, gx, gy, d, np[0], np[1], zz, P, N)) {
+            if (view_surface(a, gx, gy, d, np[0], np[1], zz, P, N)) {
                 const uint8_t* ap = a.accum.ptr + (size_t)gy * a.accum.pitch + (size_t)gx * 16;
                 const uint8_t* mp = a.moments.ptr + (size_t)gy * a.moments.pitch + (size_t)gx * 8;
                 float4 ac;
@@ -270,8 +243,8 @@ template <int kPasses, int kTW, int kTH> __global__ void __launch_bounds__(256) 
                 else mo = make_float2(reinterpret_cast<const float*>(mp)[0], reinterpret_cast<const float*>(mp)[1]);
                 z = zz;
                 v[0] = ac.x, v[1] = ac.y, v[2] = ac.z;
-                q = gd_max0(mo.y - mo.x * mo.x);
-                n = make_uint2((uint32_t)f2h(N[0]) | ((uint32_t)f2h(N[1]) << 16), (uint32_t)f2h(N[2]) | (ac.w < a.min_history ? 0x10000u : 0u));
+                q = max0(mo.y - mo.x * mo.x);
+                n = make_uint2(pack_half2(N[0], N[1]), (uint32_t)f2h(N[2]) | (ac.w < a.min_history ? 0x10000u : 0u));
             }
         }
         s_z[i] = z, s_r0[i] = v[0], s_g0[i] = v[1], s_b0[i] = v[2], s_q0[i] = q, s_n[i] = n;
@@ -311,7 +284,7 @@ template <int kPasses, int kTW, int kTH> __global__ void __launch_bounds__(256) 
                 gd_filter_cell<1 << (kPasses - 1)>(a, last, s_z, s_n, idx, CW, o);
                 const uint2 n = s_n[idx];
                 ob = make_uint2(n.x, (n.y & 0xffffu) | (rp[1] & 0xffff0000u));
-                oi = make_uint2((uint32_t)f2h(o[0]) | ((uint32_t)f2h(o[1]) << 16), (uint32_t)f2h(o[2]));
+                oi = make_uint2(pack_half2(o[0], o[1]), (uint32_t)f2h(o[2]));
             } else {  // no surface: the 64 bits of both inputs
                 const uint32_t* ip = reinterpret_cast<const uint32_t*>(a.irr.ptr + (size_t)gy * a.irr.pitch + (size_t)gx * 8);
                 ob = make_uint2(rp[0], rp[1]), oi = make_uint2(ip[0], ip[1]);
@@ -330,9 +303,8 @@ template <int kPasses, int kTW, int kTH> __global__ void __launch_bounds__(256) 
 
 hipError_t launch_rtgi_denoise(const RtgiDenoiseArgs& a, uint32_t passes, bool history, hipStream_t st) {
     if (a.row_end <= a.row_begin || a.acc_end <= a.acc_begin) return hipSuccess;
-    bool vec = true;
-    for (const PlaneArg* p : {&a.rays, &a.irr, &a.depth, &a.normals, &a.mv, &a.prev_depth, &a.history, &a.hist_mom, &a.accum, &a.moments, &a.out_rays, &a.out_irr})
-        vec = vec && ((uintptr_t)p->ptr % 16) == 0 && (p->pitch % 16) == 0;  // (planes the flag excuses arrive as null, pitch 0)
+    // (planes the flag excuses arrive as null, pitch 0)
+    const bool vec = planes_aligned({&a.rays, &a.irr, &a.depth, &a.normals, &a.mv, &a.prev_depth, &a.history, &a.hist_mom, &a.accum, &a.moments, &a.out_rays, &a.out_irr}, 16);
     const bool out = passes == 0;
     void (*temporal)(RtgiDenoiseArgs);
     if (history) temporal = vec ? (out ? k_gd_temporal<true, true, true> : k_gd_temporal<true, true, false>) : (out ? k_gd_temporal<false, true, true> : k_gd_temporal<false, true, false>);

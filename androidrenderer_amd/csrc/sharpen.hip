@@ -13,31 +13,22 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
-#include "numerics.hpp"
+#include "screen_common.hpp"
 
 namespace sah {
 
 constexpr uint32_t kShW = 64, kShH = 16, kShCols = kShW + 2, kShRows = kShH + 2;
-constexpr float kShInf = __builtin_inff();
 
 namespace {
 
-SAH_DEV float sh_min(float a, float b) { return a < b ? a : b; }
-SAH_DEV float sh_max(float a, float b) { return a > b ? a : b; }
 SAH_DEV uint32_t sh_minu(uint32_t a, uint32_t b) { return a < b ? a : b; }
-
-template <bool kVec> SAH_DEV uint2 sh_load8(const uint8_t* p) {
-    if (kVec) return *reinterpret_cast<const uint2*>(p);
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-    return make_uint2(q[0], q[1]);
-}
 
 // Compress: the texel (x = r | g << 16, y = b | a << 16) as t.rgb and, in w, the bit pattern 1 where it is CLEAN and 0 where it is not
 SAH_DEV float4 sh_compress(uint2 raw, float k) {
-    const float r = h2f((uint16_t)(raw.x & 0xffffu)), g = h2f((uint16_t)(raw.x >> 16)), b = h2f((uint16_t)(raw.y & 0xffffu));
-    const bool clean = (__builtin_fabsf(r) < kShInf) & (__builtin_fabsf(g) < kShInf) & (__builtin_fabsf(b) < kShInf) & !(r < 0.0f) & !(g < 0.0f) & !(b < 0.0f);
+    const float r = half_lo(raw.x), g = half_hi(raw.x), b = half_lo(raw.y);
+    const bool clean = all_finite(r, g, b) & !(r < 0.0f) & !(g < 0.0f) & !(b < 0.0f);
     const float cr = r * k, cg = g * k, cb = b * k;
-    const float d = 1.0f + sh_max(sh_max(cr, cg), cb);
+    const float d = 1.0f + sel_max(sel_max(cr, cg), cb);
     return make_float4(cr / d, cg / d, cb / d, __builtin_bit_cast(float, clean ? 1u : 0u));
 }
 
@@ -67,7 +58,7 @@ template <bool kVec, bool kDenoise> __global__ void __launch_bounds__(256) k_sha
             centre[0] = make_uint2(v0.x, v0.y), centre[1] = make_uint2(v0.z, v0.w), centre[2] = make_uint2(v1.x, v1.y), centre[3] = make_uint2(v1.z, v1.w);
         } else {
 #pragma unroll
-            for (uint32_t j = 0; j < 4; j++) centre[j] = sh_load8<kVec>(row + (size_t)sh_minu(px + j, W - 1u) * 8);
+            for (uint32_t j = 0; j < 4; j++) centre[j] = load_texel8<kVec>(row + (size_t)sh_minu(px + j, W - 1u) * 8);
         }
 #pragma unroll
         for (uint32_t j = 0; j < 4; j++) s_t[(ty + 1u) * kShCols + 4u * tx + 1u + j] = sh_compress(centre[j], k);
@@ -81,7 +72,7 @@ template <bool kVec, bool kDenoise> __global__ void __launch_bounds__(256) k_sha
             r = 1u + (tid & 15u), c = tid < 144u ? 0u : kShCols - 1u;
         }
         const uint32_t gy = sh_minu((y0 + r ? y0 + r : 1u) - 1u, H - 1u), gx = sh_minu((x0 + c ? x0 + c : 1u) - 1u, W - 1u);
-        s_t[r * kShCols + c] = sh_compress(sh_load8<kVec>(a.scene.ptr + (size_t)gy * a.scene.pitch + (size_t)gx * 8), k);
+        s_t[r * kShCols + c] = sh_compress(load_texel8<kVec>(a.scene.ptr + (size_t)gy * a.scene.pitch + (size_t)gx * 8), k);
     }
     __syncthreads();
     if (px >= W || py >= a.row_end) return;
@@ -101,19 +92,19 @@ template <bool kVec, bool kDenoise> __global__ void __launch_bounds__(256) k_sha
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
             const float b = sh_channel(B, ch), d = sh_channel(D, ch), e = sh_channel(E, ch), f = sh_channel(F, ch), h = sh_channel(Hh, ch);
-            const float mn4 = sh_min(sh_min(sh_min(b, d), f), h), mx4 = sh_max(sh_max(sh_max(b, d), f), h);
-            const float hit_min = mx4 > 0.0f ? sh_min(mn4, e) / (4.0f * mx4) : 0.0f;
-            const float hit_max = (1.0f - sh_max(mx4, e)) / (4.0f * mn4 - 4.0f);
-            const float lobe_c = sh_max(-hit_min, hit_max);
-            lobe = ch == 0 ? lobe_c : sh_max(lobe, lobe_c);
+            const float mn4 = sel_min(sel_min(sel_min(b, d), f), h), mx4 = sel_max(sel_max(sel_max(b, d), f), h);
+            const float hit_min = mx4 > 0.0f ? sel_min(mn4, e) / (4.0f * mx4) : 0.0f;
+            const float hit_max = (1.0f - sel_max(mx4, e)) / (4.0f * mn4 - 4.0f);
+            const float lobe_c = sel_max(-hit_min, hit_max);
+            lobe = ch == 0 ? lobe_c : sel_max(lobe, lobe_c);
         }
-        lobe = sh_max(-0.1875f, sh_min(lobe, 0.0f)) * a.sharpness;
+        lobe = sel_max(-0.1875f, sel_min(lobe, 0.0f)) * a.sharpness;
         // Noise
         if (kDenoise) {
             const float lb = sh_luma(B), ld = sh_luma(D), le = sh_luma(E), lf = sh_luma(F), lh = sh_luma(Hh);
             const float nz = ((lb + ld) + (lf + lh)) * 0.25f - le;
-            const float range = sh_max(sh_max(sh_max(sh_max(lb, ld), le), lf), lh) - sh_min(sh_min(sh_min(sh_min(lb, ld), le), lf), lh);
-            const float q = range > 0.0f ? sh_min(__builtin_fabsf(nz) / range, 1.0f) : 0.0f;
+            const float range = sel_max(sel_max(sel_max(sel_max(lb, ld), le), lf), lh) - sel_min(sel_min(sel_min(sel_min(lb, ld), le), lf), lh);
+            const float q = range > 0.0f ? sel_min(__builtin_fabsf(nz) / range, 1.0f) : 0.0f;
             lobe = lobe * (1.0f - q * 0.5f);
         }
         // Resolve
@@ -122,17 +113,18 @@ template <bool kVec, bool kDenoise> __global__ void __launch_bounds__(256) k_sha
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
             const float b = sh_channel(B, ch), d = sh_channel(D, ch), e = sh_channel(E, ch), f = sh_channel(F, ch), h = sh_channel(Hh, ch);
-            s[ch] = sh_min(sh_max((lobe * ((b + d) + (f + h)) + e) / den, 0.0f), 1.0f);
+            s[ch] = sel_min(sel_max((lobe * ((b + d) + (f + h)) + e) / den, 0.0f), 1.0f);
         }
         // Expand, Store
-        const float rest = 1.0f - sh_min(sh_max(sh_max(s[0], s[1]), s[2]), 1.0f - 0x1p-17f);
-        const float o0 = sh_min((s[0] / rest) / k, 65504.0f), o1 = sh_min((s[1] / rest) / k, 65504.0f), o2 = sh_min((s[2] / rest) / k, 65504.0f);
+        const float rest = 1.0f - sel_min(sel_max(sel_max(s[0], s[1]), s[2]), 1.0f - 0x1p-17f);
+        const float o0 = sel_min((s[0] / rest) / k, 65504.0f), o1 = sel_min((s[1] / rest) / k, 65504.0f), o2 = sel_min((s[2] / rest) / k, 65504.0f);
         packed[j] = centre[j];
         if (eligible) {
-            packed[j].x = (uint32_t)f2h(o0) | ((uint32_t)f2h(o1) << 16);
+            packed[j].x = pack_half2(o0, o1);
             packed[j].y = (uint32_t)f2h(o2) | (centre[j].y & 0xffff0000u);
         }
     }
+    // (the same store ends taa.hip and taa_upscale.hip: as a shared function it leaves another block layout, see screen_common.hpp)
     uint8_t* row = const_cast<uint8_t*>(a.out.ptr) + (size_t)py * a.out.pitch + (size_t)px * 8;
     if (kVec && px + 3u < W) {
         reinterpret_cast<uint4*>(row)[0] = make_uint4(packed[0].x, packed[0].y, packed[1].x, packed[1].y);
@@ -154,8 +146,7 @@ hipError_t launch_sharpen(const SharpenArgs& in, bool denoise, hipStream_t st) {
     SharpenArgs a = in;
     a.tiles_x = (a.W + kShW - 1) / kShW;
     const dim3 grid(a.tiles_x * ((a.row_end - a.row_begin + kShH - 1) / kShH));  // one dimension: no limit of 65535 tile rows (W * H < 2^32: fits)
-    bool vec = true;
-    for (const PlaneArg* p : {&a.scene, &a.out}) vec = vec && ((uintptr_t)p->ptr % 16) == 0 && (p->pitch % 16) == 0;
+    const bool vec = planes_aligned({&a.scene, &a.out}, 16);
     void (*kernel)(SharpenArgs);
     if (denoise) kernel = vec ? k_sharpen<true, true> : k_sharpen<false, true>;
     else kernel = vec ? k_sharpen<true, false> : k_sharpen<false, false>;

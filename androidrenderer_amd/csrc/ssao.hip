@@ -14,20 +14,15 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
-#include "numerics.hpp"
+#include "screen_common.hpp"
 
 namespace sah {
 
 constexpr int kSrW = 64, kSrH = 16;  // the raw kernel's tile
 constexpr int kSbW = 32, kSbH = 16;  // the blur kernel's tile
-constexpr float kSsInf = __builtin_inff();
 
 __constant__ float kSsaoOffsets[SAH_SSAO_TAPS][2] = SAH_SSAO_OFFSETS;
 __constant__ float kSsaoRotations[16][2] = SAH_SSAO_ROTATIONS;
-
-SAH_DEV float clamp01(float a) { return a > 0.0f ? (a < 1.0f ? a : 1.0f) : 0.0f; }
-SAH_DEV float max0(float a) { return a > 0.0f ? a : 0.0f; }
-SAH_DEV bool finite_f(float a) { return __builtin_fabsf(a) < kSsInf; }
 
 // One pixel of the raw pass.  d: its depth; n01, n2: the bits of its normal (x | y << 16, z | w << 16); j4 = 4 * (y & 3), kx = x & 3.
 SAH_DEV float ssao_pixel(const SsaoArgs& a, const float2* s_e, int x, int y, float d, uint32_t n01, uint32_t n2) {
@@ -35,12 +30,10 @@ SAH_DEV float ssao_pixel(const SsaoArgs& a, const float2* s_e, int x, int y, flo
     const float wf = (float)a.W, hf = (float)a.H;
     const float z = a.z_near / d;
     const float cx = (float)x + 0.5f, cy = (float)y + 0.5f;
-    const float px = (z * ((cx * a.tx - 1.0f) + a.p20)) * a.ipx, py = (z * ((cy * a.ty - 1.0f) + a.p21)) * a.ipy, pz = -z;
-    const float nx = h2f((uint16_t)(n01 & 0xffffu)), ny = h2f((uint16_t)(n01 >> 16)), nz = h2f((uint16_t)(n2 & 0xffffu));
-    const float vx = (a.m[0] * nx + a.m[3] * ny) + a.m[6] * nz, vy = (a.m[1] * nx + a.m[4] * ny) + a.m[7] * nz, vz = (a.m[2] * nx + a.m[5] * ny) + a.m[8] * nz;
-    const float l = __builtin_sqrtf((vx * vx + vy * vy) + vz * vz);
-    const float Nx = vx / l, Ny = vy / l, Nz = vz / l;
-    if (!(finite_f(px) && finite_f(py) && finite_f(pz) && finite_f(Nx) && finite_f(Ny) && finite_f(Nz))) return 1.0f;
+    const float px = view_x(a, cx, z), py = view_y(a, cy, z), pz = -z;
+    float Nx, Ny, Nz;
+    view_normal(a, make_uint2(n01, n2), Nx, Ny, Nz);
+    if (!(finite_f32(px) && finite_f32(py) && finite_f32(pz) && finite_f32(Nx) && finite_f32(Ny) && finite_f32(Nz))) return 1.0f;
     const float t = a.rs / z;
     const float r_px = t > 1.0f ? (t < a.max_radius_pixels ? t : a.max_radius_pixels) : 1.0f;
     const float R = (r_px * z) / a.sx;
@@ -57,10 +50,10 @@ SAH_DEV float ssao_pixel(const SsaoArgs& a, const float2* s_e, int x, int y, flo
         const float dt = *reinterpret_cast<const float*>(a.depth.ptr + (size_t)iy * a.depth.pitch + (size_t)ix * 4);
         bool use = inside & !((ix == x) & (iy == y)) & (dt > 0.0f);
         const float zt = a.z_near / dt;
-        const float sx = (zt * ((((float)ix + 0.5f) * a.tx - 1.0f) + a.p20)) * a.ipx, sy = (zt * ((((float)iy + 0.5f) * a.ty - 1.0f) + a.p21)) * a.ipy;
+        const float sx = view_x(a, (float)ix + 0.5f, zt), sy = view_y(a, (float)iy + 0.5f, zt);
         const float dx = sx - px, dy = sy - py, dz = -zt - pz;
         const float vv = (dx * dx + dy * dy) + dz * dz;
-        use = use & (vv > 0.0f) & (vv < kSsInf);
+        use = use & (vv > 0.0f) & (vv < kScreenInf);
         const float ndotd = ((Nx * dx + Ny * dy) + Nz * dz) / __builtin_sqrtf(vv);
         const float o = max0(ndotd - a.threshold) * clamp01(1.0f - vv / RR);
         sum = use ? sum + o : sum;
@@ -170,8 +163,7 @@ template <int kPasses> __global__ void __launch_bounds__(256) k_ssao_blur(SsaoAr
 
 hipError_t launch_ssao(const SsaoArgs& a, uint32_t blur_passes, hipStream_t st) {
     if (a.row_end <= a.row_begin || a.raw_end <= a.raw_begin) return hipSuccess;
-    bool vec = true;
-    for (const PlaneArg* p : {&a.depth, &a.normals, &a.raw}) vec = vec && ((uintptr_t)p->ptr % 16) == 0 && (p->pitch % 16) == 0;
+    const bool vec = planes_aligned({&a.depth, &a.normals, &a.raw}, 16);
     const dim3 raw_grid((a.W + kSrW - 1) / kSrW, (a.raw_end - a.raw_begin + kSrH - 1) / kSrH);
     hipLaunchKernelGGL(vec ? k_ssao_raw<true> : k_ssao_raw<false>, raw_grid, dim3(256), 0, st, a);
     if (hipError_t e = hipGetLastError(); e != hipSuccess || blur_passes == 0) return e;

@@ -10,33 +10,13 @@
 
 #include "dither.hpp"
 #include "launch.hpp"
-#include "numerics.hpp"
+#include "screen_common.hpp"
 
 namespace sah {
 
 constexpr int kSsW = 32, kSsH = 8;  // the trace kernel's tile: four waves of 8 x 8
-constexpr float kSrInf = __builtin_inff();
-
 
 namespace {
-SAH_DEV float ssr_clamp01(float a) { return a > 0.0f ? (a < 1.0f ? a : 1.0f) : 0.0f; }
-SAH_DEV float ssr_min(float a, float b) { return a < b ? a : b; }
-SAH_DEV bool ssr_finite(float a) { return __builtin_fabsf(a) < kSrInf; }
-
-template <bool kVec> SAH_DEV uint2 load_texel8(const PlaneArg& p, int x, int y) {
-    const uint8_t* at = p.ptr + (size_t)y * p.pitch + (size_t)x * 8;
-    if (kVec) return *reinterpret_cast<const uint2*>(at);
-    return make_uint2(reinterpret_cast<const uint32_t*>(at)[0], reinterpret_cast<const uint32_t*>(at)[1]);
-}
-
-// the unit view-space normal of a texel from the bits of its halfs (Centre of sah_ssao.h)
-SAH_DEV void view_normal(const SsrArgs& a, uint2 n, float& Nx, float& Ny, float& Nz) {
-    const float nx = h2f((uint16_t)(n.x & 0xffffu)), ny = h2f((uint16_t)(n.x >> 16)), nz = h2f((uint16_t)(n.y & 0xffffu));
-    const float vx = (a.m[0] * nx + a.m[3] * ny) + a.m[6] * nz, vy = (a.m[1] * nx + a.m[4] * ny) + a.m[7] * nz, vz = (a.m[2] * nx + a.m[5] * ny) + a.m[8] * nz;
-    const float l = __builtin_sqrtf((vx * vx + vy * vy) + vz * vz);
-    Nx = vx / l, Ny = vy / l, Nz = vz / l;
-}
-
 struct Ray {
     float s0x, s0y, k0, dsx, dsy, dk, L, jit, stride, wf, hf;
     SAH_DEV float t_of(float i) const { return ((i + jit) * stride) / L; }
@@ -51,7 +31,6 @@ struct Ray {
     }
 };
 
-SAH_DEV float depth_at(const SsrArgs& a, int x, int y) { return *reinterpret_cast<const float*>(a.depth.ptr + (size_t)y * a.depth.pitch + (size_t)x * 4); }
 }  // namespace
 
 template <bool kVec> __global__ void __launch_bounds__(256) k_ssr_trace(SsrArgs a) {
@@ -67,17 +46,17 @@ template <bool kVec> __global__ void __launch_bounds__(256) k_ssr_trace(SsrArgs 
     float t_hit = 0.0f, nv = 0.0f, rough = 0.0f;
     int hx = 0, hy = 0;
     float Rx = 0.0f, Ry = 0.0f, Rz = 0.0f;
-    const float d = depth_at(a, x, y);
+    const float d = load_f32(a.depth, x, y);
     uint32_t dat = 0;
     if (d > 0.0f && a.intensity != 0.0f) {
         dat = *reinterpret_cast<const uint32_t*>(a.data.ptr + (size_t)y * a.data.pitch + (size_t)x * 4);
         rough = a.luts[256 + ((dat >> 8) & 0xffu)];
         const float z = a.z_near / d;
         const float cx = (float)x + 0.5f, cy = (float)y + 0.5f;
-        const float Px = (z * ((cx * a.tx - 1.0f) + a.p20)) * a.ipx, Py = (z * ((cy * a.ty - 1.0f) + a.p21)) * a.ipy, Pz = -z;
+        const float Px = view_x(a, cx, z), Py = view_y(a, cy, z), Pz = -z;
         float Nx, Ny, Nz;
         view_normal(a, load_texel8<kVec>(a.normals, x, y), Nx, Ny, Nz);
-        const bool finite = ssr_finite(Px) && ssr_finite(Py) && ssr_finite(Pz) && ssr_finite(Nx) && ssr_finite(Ny) && ssr_finite(Nz);
+        const bool finite = finite_f32(Px) && finite_f32(Py) && finite_f32(Pz) && finite_f32(Nx) && finite_f32(Ny) && finite_f32(Nz);
         if (finite && rough < a.max_roughness) {
             const float pl = __builtin_sqrtf((Px * Px + Py * Py) + Pz * Pz);
             const float Vx = Px / pl, Vy = Py / pl, Vz = Pz / pl;
@@ -102,7 +81,7 @@ template <bool kVec> __global__ void __launch_bounds__(256) k_ssr_trace(SsrArgs 
             r.L = ax > ay ? ax : ay;
             r.jit = (a.flags & SAH_SSR_JITTER) ? bayer4x4((uint32_t)x, (uint32_t)y) * 0.0625f : 0.0f;
             r.stride = a.stride, r.wf = (float)a.W, r.hf = (float)a.H;
-            if ((ax < kSrInf) & (ay < kSrInf) & (r.L >= 1.0f) & (r.k0 < kSrInf)) {
+            if ((ax < kScreenInf) & (ay < kScreenInf) & (r.L >= 1.0f) & (r.k0 < kScreenInf)) {
                 const int steps = (int)a.max_steps;
                 int hit_i = 0;
                 for (int i = 1; i <= steps; i++) {
@@ -111,7 +90,7 @@ template <bool kVec> __global__ void __launch_bounds__(256) k_ssr_trace(SsrArgs 
                     int ix, iy;
                     float zr;
                     if (!r.sample(t, ix, iy, zr)) break;
-                    const float dt = depth_at(a, ix, iy);
+                    const float dt = load_f32(a.depth, ix, iy);
                     if (dt > 0.0f) {
                         const float dz = zr - a.z_near / dt;
                         if ((dz >= 0.0f) & (dz <= a.thickness)) {
@@ -127,7 +106,7 @@ template <bool kVec> __global__ void __launch_bounds__(256) k_ssr_trace(SsrArgs 
                         int ix, iy;
                         float zr;
                         bool pass = r.sample(mid, ix, iy, zr);
-                        const float dt = depth_at(a, ix, iy);  // ((0, 0) outside the image: a texel of every image)
+                        const float dt = load_f32(a.depth, ix, iy);  // ((0, 0) outside the image: a texel of every image)
                         pass = pass && dt > 0.0f && zr >= a.z_near / dt;
                         hi = pass ? mid : hi, lo = pass ? lo : mid;
                     }
@@ -141,25 +120,25 @@ template <bool kVec> __global__ void __launch_bounds__(256) k_ssr_trace(SsrArgs 
     }
     if (found) {
         const uint2 src = load_texel8<false>(a.source, hx, hy);
-        const float sr = h2f((uint16_t)(src.x & 0xffffu)), sg = h2f((uint16_t)(src.x >> 16)), sb = h2f((uint16_t)(src.y & 0xffffu));
+        const float sr = half_lo(src.x), sg = half_hi(src.x), sb = half_lo(src.y);
         float Hx, Hy, Hz;
         view_normal(a, load_texel8<false>(a.normals, hx, hy), Hx, Hy, Hz);
-        const bool clean = (sr >= 0.0f) & (sr < kSrInf) & (sg >= 0.0f) & (sg < kSrInf) & (sb >= 0.0f) & (sb < kSrInf);
+        const bool clean = all_nonneg_finite(sr, sg, sb);
         const bool facing = ((Hx * Rx + Hy * Ry) + Hz * Rz) < 0.0f;
         if (clean && facing) {
             const uint32_t col = *reinterpret_cast<const uint32_t*>(a.color.ptr + (size_t)y * a.color.pitch + (size_t)x * 4);
             const float metal = a.luts[256 + ((dat >> 16) & 0xffu)];
-            const float m = 1.0f - ssr_clamp01(-nv);
+            const float m = 1.0f - clamp01(-nv);
             const float m2 = m * m;
             const float m5 = (m2 * m2) * m;
-            const float rf = ssr_clamp01(1.0f - rough / a.max_roughness);
+            const float rf = clamp01(1.0f - rough / a.max_roughness);
             const float u = ((float)hx + 0.5f) / (float)a.W, v = ((float)hy + 0.5f) / (float)a.H;
-            const float e = ssr_min(ssr_min(u, 1.0f - u), ssr_min(v, 1.0f - v));
-            const float ef = ssr_clamp01(e / a.edge_fade);
-            const float tf = ssr_clamp01(1.0f - t_hit);
+            const float e = sel_min(sel_min(u, 1.0f - u), sel_min(v, 1.0f - v));
+            const float ef = clamp01(e / a.edge_fade);
+            const float tf = clamp01(1.0f - t_hit);
             const float w = ((a.intensity * rf) * ef) * tf;
             const float s[3] = {sr, sg, sb};
-            const float l[3] = {h2f((uint16_t)(lit.x & 0xffffu)), h2f((uint16_t)(lit.x >> 16)), h2f((uint16_t)(lit.y & 0xffffu))};
+            const float l[3] = {half_lo(lit.x), half_hi(lit.x), half_lo(lit.y)};
             uint32_t o[3];
 #pragma unroll
             for (int c = 0; c < 3; c++) {
@@ -174,19 +153,13 @@ template <bool kVec> __global__ void __launch_bounds__(256) k_ssr_trace(SsrArgs 
             res = make_uint2(o[0] | (o[1] << 16), o[2] | (alpha << 16));
         }
     }
-    if (kVec) {
-        *reinterpret_cast<uint2*>(orow) = res;
-    } else {
-        reinterpret_cast<uint32_t*>(orow)[0] = res.x;
-        reinterpret_cast<uint32_t*>(orow)[1] = res.y;
-    }
+    store_texel8<kVec>(orow, res);
 }
 
 hipError_t launch_ssr(const SsrArgs& args, hipStream_t st) {
     if (args.row_end <= args.row_begin) return hipSuccess;
     SsrArgs a = args;
-    bool vec = true;
-    for (const PlaneArg* p : {&a.normals, &a.lit, &a.out}) vec = vec && ((uintptr_t)p->ptr % 8) == 0 && (p->pitch % 8) == 0;
+    const bool vec = planes_aligned({&a.normals, &a.lit, &a.out}, 8);
     // W, H < 2^31 and W * H < 2^32 (api_ssr.cpp): ceil(W / 32) * ceil(H / 8) stays below 2^29 however thin the frame, so grid.x holds every tile
     a.tiles_x = (a.W + kSsW - 1) / kSsW;
     const uint64_t tiles = (uint64_t)a.tiles_x * ((a.row_end - a.row_begin + kSsH - 1) / kSsH);

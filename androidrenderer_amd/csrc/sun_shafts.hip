@@ -15,34 +15,20 @@
 #include "dither.hpp"
 #include "launch.hpp"
 #include "lighting_common.hpp"
-#include "numerics.hpp"
+#include "screen_common.hpp"
 
 namespace sah {
 
-constexpr float kSsInf = __builtin_inff();
 constexpr float kSsInv4Pi = 0.07957747f;
 
 namespace {
-SAH_DEV float ss_clamp01(float a) { return a > 0.0f ? (a < 1.0f ? a : 1.0f) : 0.0f; }
 SAH_DEV uint32_t ss_half(float v) { return v != v ? 0x7E00u : (uint32_t)f2h(v); }
 SAH_DEV float ss_sel(uint32_t c, float v0, float v1, float v2, float v3) { return c == 0 ? v0 : (c == 1 ? v1 : (c == 2 ? v2 : v3)); }
 
-// an 8-byte texel of a plane that is 4-byte aligned: two dwords in the source, which the compiler joins into one 8-byte access
-SAH_DEV uint2 ss_get8(const PlaneArg& p, uint32_t x, uint32_t y) {
-    const uint32_t* at = reinterpret_cast<const uint32_t*>(p.ptr + (size_t)y * p.pitch + (size_t)x * 8);
-    return make_uint2(at[0], at[1]);
-}
-SAH_DEV void ss_put8(const PlaneArg& p, uint32_t x, uint32_t y, uint2 v) {
-    uint32_t* at = reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(p.ptr) + (size_t)y * p.pitch + (size_t)x * 8);
-    at[0] = v.x;
-    at[1] = v.y;
-}
+// (the planes are 4-byte aligned: texels move as load_texel8<false> / store_texel8<false>, two dwords the compiler joins into one access)
 SAH_DEV float ss_depth(const SunShaftsArgs& a, uint32_t x, uint32_t y) {
-    const float d = *reinterpret_cast<const float*>(a.depth.ptr + (size_t)y * a.depth.pitch + (size_t)x * 4);
+    const float d = load_f32(a.depth, x, y);
     return d > a.d_min ? d : a.d_min;
-}
-SAH_DEV void ss_unpack(uint2 t, float (&v)[4]) {
-    v[0] = h2f((uint16_t)(t.x & 0xffffu)), v[1] = h2f((uint16_t)(t.x >> 16)), v[2] = h2f((uint16_t)(t.y & 0xffffu)), v[3] = h2f((uint16_t)(t.y >> 16));
 }
 
 // Sums of the header: E and V of one ray.  kD16: the map's format, a constant inside shadow_pcf once it is inlined.
@@ -55,7 +41,7 @@ SAH_DEV void ss_sums(const SunShaftsArgs& a, float ez, float n, float r, float o
     E = 0.0f, V = 0.0f;
     for (int k = 0; k < steps; k++) {
         const float kf = (float)k;
-        const float frac = ss_clamp01(n - kf);
+        const float frac = clamp01(n - kf);
         if (!wave_any(frac > 0.0f)) break;
         const float t = (kf + o * frac) * r;
         const float zv = ez * t;
@@ -120,17 +106,17 @@ SAH_DEV void ss_write(const SunShaftsArgs& a, uint32_t x, uint32_t y, const floa
     if (a.flags & SAH_SUN_SHAFTS_TERM_ONLY) {
         res = own ? texel : make_uint2(ss_half(st[0]) | (ss_half(st[1]) << 16), ss_half(st[2]) | (ss_half(st[3]) << 16));
     } else {
-        const uint2 l = ss_get8(a.lit, x, y);
+        const uint2 l = load_texel8<false>(a.lit, x, y);
         res = l;
         float lf[4], o[3];
-        ss_unpack(l, lf);
+        unpack_halfs(l, lf);
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) o[ch] = lf[ch] * st[3] + st[ch];
         const bool identity = (st[3] == 1.0f) & (st[0] == 0.0f) & (st[1] == 0.0f) & (st[2] == 0.0f);
-        const bool finite = (__builtin_fabsf(o[0]) < kSsInf) & (__builtin_fabsf(o[1]) < kSsInf) & (__builtin_fabsf(o[2]) < kSsInf);
-        if (!identity && finite) res = make_uint2((uint32_t)f2h(o[0]) | ((uint32_t)f2h(o[1]) << 16), (uint32_t)f2h(o[2]) | (l.y & 0xffff0000u));
+        const bool finite = all_finite(o[0], o[1], o[2]);
+        if (!identity && finite) res = make_uint2(pack_half2(o[0], o[1]), (uint32_t)f2h(o[2]) | (l.y & 0xffff0000u));
     }
-    ss_put8(a.out, x, y, res);
+    store_texel8<false>(a.out, x, y, res);
 }
 }  // namespace
 
@@ -141,10 +127,10 @@ template <bool kFused> __global__ void __launch_bounds__(256) k_ss_march(SunShaf
     if (mx >= a.mw || my >= a.march_row_end) return;
     const uint32_t x = kFused ? mx : mx * a.downscale, y = kFused ? my : my * a.downscale;
     const uint2 texel = ss_texel(a, mx, my, x, y);
-    ss_put8(a.march, mx, my, texel);
+    store_texel8<false>(a.march, mx, my, texel);
     if (kFused) {
         float st[4];
-        ss_unpack(texel, st);
+        unpack_halfs(texel, st);
         ss_write(a, x, y, st, true, texel);
     }
 }
@@ -166,7 +152,7 @@ __global__ void __launch_bounds__(256) k_ss_composite(SunShaftsArgs a) {
         const uint32_t mx = X[j & 1], my = Y[j >> 1];
         const float zj = a.z_near / ss_depth(a, 2u * mx, 2u * my);
         W[j] = bw[j] * (1.0f / (1.0f + (a.depth_sharpness * __builtin_fabsf(z - zj)) / z));
-        ss_unpack(ss_get8(a.march, mx, my), t[j]);
+        unpack_halfs(load_texel8<false>(a.march, mx, my), t[j]);
     }
     const float sum = ((W[0] + W[1]) + W[2]) + W[3];
     float st[4];

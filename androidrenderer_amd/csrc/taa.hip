@@ -11,24 +11,12 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
-#include "numerics.hpp"
+#include "screen_common.hpp"
 
 namespace sah {
 
 constexpr int kTaW = 64, kTaH = 16, kTaCols = kTaW + 2, kTaRows = kTaH + 2, kTaPitch = 68;  // pitch: a thread's six cells are 16-byte aligned
 constexpr int kTaLitUnits = kTaW / 2 + 2, kTaDepthUnits = kTaW / 4 + 2;                     // per row: pairs / quads of interior cells + two halo cells
-constexpr float kTaInf = __builtin_inff();
-
-SAH_DEV int clampi(int i, int n) { return min(max(i, 0), n - 1); }
-
-template <bool kVec> SAH_DEV uint2 load_texel8(const uint8_t* p) {
-    if (kVec) return *reinterpret_cast<const uint2*>(p);
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-    return make_uint2(q[0], q[1]);
-}
-
-SAH_DEV bool finite3(float a, float b, float c) { return (__builtin_fabsf(a) < kTaInf) & (__builtin_fabsf(b) < kTaInf) & (__builtin_fabsf(c) < kTaInf); }
-SAH_DEV float taa_luma(float r, float g, float b) { return __builtin_fmaxf((r * 0.2126f + g * 0.7152f) + b * 0.0722f, 0.0f); }
 
 template <bool kVec, bool kHistory, bool kHdr> __global__ void __launch_bounds__(256) k_taa_resolve(TaaArgs a) {
     __shared__ __attribute__((aligned(16))) uint2 s_lit[kTaRows * kTaPitch];
@@ -98,7 +86,7 @@ template <bool kVec, bool kHistory, bool kHdr> __global__ void __launch_bounds__
             const uint32_t w[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
 #pragma unroll
             for (int c = 0; c < 6; c++) {
-                l[r][c][0] = h2f((uint16_t)(w[2 * c] & 0xffffu)), l[r][c][1] = h2f((uint16_t)(w[2 * c] >> 16)), l[r][c][2] = h2f((uint16_t)(w[2 * c + 1] & 0xffffu));
+                l[r][c][0] = half_lo(w[2 * c]), l[r][c][1] = half_hi(w[2 * c]), l[r][c][2] = half_lo(w[2 * c + 1]);
             }
             if (r == 1) {
 #pragma unroll
@@ -138,7 +126,7 @@ template <bool kVec, bool kHistory, bool kHdr> __global__ void __launch_bounds__
             }
         const uint32_t m = *reinterpret_cast<const uint32_t*>(a.mv.ptr + (size_t)clampi(py + bdy, H) * a.mv.pitch + (size_t)clampi(x + bdx, W) * 4);
         // Position, Validity
-        const float qx = (((float)x + 0.5f) + h2f((uint16_t)(m & 0xffffu))) + a.djx, qy = (((float)py + 0.5f) + h2f((uint16_t)(m >> 16))) + a.djy;
+        const float qx = (((float)x + 0.5f) + half_lo(m)) + a.djx, qy = (((float)py + 0.5f) + half_hi(m)) + a.djy;
         bool valid = (qx >= 0.0f) & (qx <= wf) & (qy >= 0.0f) & (qy <= hf);
         // History: bilinear<ADDR_CLAMP> of post_common.hpp at pixel coordinates, rgb only
         const float pxf = qx - 0.5f, pyf = qy - 0.5f;
@@ -154,20 +142,19 @@ template <bool kVec, bool kHistory, bool kHdr> __global__ void __launch_bounds__
         float h[3];
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
-            const auto tap = [ch](uint2 t) { return h2f((uint16_t)(ch == 0 ? t.x & 0xffffu : ch == 1 ? t.x >> 16 : t.y & 0xffffu)); };
-            float s = __builtin_fmaf(w00, tap(t00), 0.0f);
-            s = __builtin_fmaf(w10, tap(t10), s);
-            s = __builtin_fmaf(w01, tap(t01), s);
-            h[ch] = __builtin_fmaf(w11, tap(t11), s);
+            float s = __builtin_fmaf(w00, texel_channel(t00, ch), 0.0f);
+            s = __builtin_fmaf(w10, texel_channel(t10, ch), s);
+            s = __builtin_fmaf(w01, texel_channel(t01, ch), s);
+            h[ch] = __builtin_fmaf(w11, texel_channel(t11, ch), s);
         }
-        valid = valid & finite3(h[0], h[1], h[2]);
+        valid = valid & all_finite(h[0], h[1], h[2]);
         // Bounds, Clamp
-        const float c[3] = {h2f((uint16_t)(centre[k].x & 0xffffu)), h2f((uint16_t)(centre[k].x >> 16)), h2f((uint16_t)(centre[k].y & 0xffffu))};
+        const float c[3] = {half_lo(centre[k].x), half_hi(centre[k].x), half_lo(centre[k].y)};
         float hc[3];
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
-            const float lo = __builtin_fminf(__builtin_fminf(__builtin_fminf(kTaInf, cmin[k][ch]), cmin[k + 1][ch]), cmin[k + 2][ch]);
-            const float hi = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(-kTaInf, cmax[k][ch]), cmax[k + 1][ch]), cmax[k + 2][ch]);
+            const float lo = __builtin_fminf(__builtin_fminf(__builtin_fminf(kScreenInf, cmin[k][ch]), cmin[k + 1][ch]), cmin[k + 2][ch]);
+            const float hi = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(-kScreenInf, cmax[k][ch]), cmax[k + 1][ch]), cmax[k + 2][ch]);
             hc[ch] = __builtin_fminf(__builtin_fmaxf(h[ch], lo), hi);
         }
         // Weight, Blend
@@ -178,11 +165,12 @@ template <bool kVec, bool kHistory, bool kHdr> __global__ void __launch_bounds__
             wk = wc / (wc + wh);
         }
         const float o0 = hc[0] + (c[0] - hc[0]) * wk, o1 = hc[1] + (c[1] - hc[1]) * wk, o2 = hc[2] + (c[2] - hc[2]) * wk;
-        if (valid & finite3(o0, o1, o2)) {
-            packed[k].x = (uint32_t)f2h(o0) | ((uint32_t)f2h(o1) << 16);
+        if (valid & all_finite(o0, o1, o2)) {
+            packed[k].x = pack_half2(o0, o1);
             packed[k].y = (uint32_t)f2h(o2) | (centre[k].y & 0xffff0000u);
         }
     }
+    // (the same store ends taa_upscale.hip and sharpen.hip: as a shared function it leaves another block layout, see screen_common.hpp)
     uint8_t* row = const_cast<uint8_t*>(a.out.ptr) + (size_t)py * a.out.pitch + (size_t)px * 8;
     if (kVec && px + 3 < W) {
         reinterpret_cast<uint4*>(row)[0] = make_uint4(packed[0].x, packed[0].y, packed[1].x, packed[1].y);
@@ -200,8 +188,7 @@ template <bool kVec, bool kHistory, bool kHdr> __global__ void __launch_bounds__
 hipError_t launch_taa_resolve(const TaaArgs& a, bool history, bool hdr_weights, hipStream_t st) {
     if (a.row_end <= a.row_begin) return hipSuccess;
     const dim3 grid((a.W + kTaW - 1) / kTaW, (a.row_end - a.row_begin + kTaH - 1) / kTaH);
-    bool vec = true;
-    for (const PlaneArg* p : {&a.lit, &a.depth, &a.mv, &a.history, &a.out}) vec = vec && ((uintptr_t)p->ptr % 16) == 0 && (p->pitch % 16) == 0;
+    const bool vec = planes_aligned({&a.lit, &a.depth, &a.mv, &a.history, &a.out}, 16);
     void (*kernel)(TaaArgs);
     if (!history) kernel = vec ? k_taa_resolve<true, false, false> : k_taa_resolve<false, false, false>;
     else if (hdr_weights) kernel = vec ? k_taa_resolve<true, true, true> : k_taa_resolve<false, true, true>;

@@ -17,27 +17,11 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
-#include "numerics.hpp"
+#include "screen_common.hpp"
 
 namespace sah {
 
 constexpr int kTuW = 64, kTuH = 16, kTuCols = kTuW + 3, kTuRows = kTuH + 3, kTuPitch = 68;
-constexpr float kTuInf = __builtin_inff();
-
-SAH_DEV int clampi(int i, int n) { return min(max(i, 0), n - 1); }
-SAH_DEV int floor_to_int(float v) { return (int)__builtin_fminf(__builtin_fmaxf(__builtin_floorf(v), -2147483648.0f), 2147483520.0f); }
-// Sample: the centre of output pixel X in the jittered render raster
-SAH_DEV float sample_position(int X, float scale, float jitter) { return ((float)X + 0.5f) * scale - jitter; }
-
-template <bool kVec> SAH_DEV uint2 load_texel8(const uint8_t* p) {
-    if (kVec) return *reinterpret_cast<const uint2*>(p);
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-    return make_uint2(q[0], q[1]);
-}
-
-SAH_DEV bool finite3(float a, float b, float c) { return (__builtin_fabsf(a) < kTuInf) & (__builtin_fabsf(b) < kTuInf) & (__builtin_fabsf(c) < kTuInf); }
-SAH_DEV float taa_luma(float r, float g, float b) { return __builtin_fmaxf((r * 0.2126f + g * 0.7152f) + b * 0.0722f, 0.0f); }
-SAH_DEV float channel(uint2 t, int ch) { return h2f((uint16_t)(ch == 0 ? t.x & 0xffffu : ch == 1 ? t.x >> 16 : t.y & 0xffffu)); }
 
 // The library's bilinear rule at pixel coordinates (post_common.hpp's bilinear<ADDR_CLAMP>): indices and weights of one axis
 struct BilinearAxis {
@@ -46,7 +30,7 @@ struct BilinearAxis {
 };
 SAH_DEV BilinearAxis bilinear_axis(float q, int n) {
     const float p = q - 0.5f, p0 = __builtin_floorf(p), f = p - p0;
-    const int i = floor_to_int(p);
+    const int i = floor_i32(p);
     return {clampi(i, n), clampi(i + 1, n), 1.0f - f, f};
 }
 // rgb of the four taps (t00, t10, t01, t11: x first) under the weights of the two axes, one fma chain from +0 per channel
@@ -54,10 +38,10 @@ SAH_DEV void bilinear_rgb(const BilinearAxis& x, const BilinearAxis& y, uint2 t0
     const float w00 = x.w0 * y.w0, w10 = x.w1 * y.w0, w01 = x.w0 * y.w1, w11 = x.w1 * y.w1;
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) {
-        float s = __builtin_fmaf(w00, channel(t00, ch), 0.0f);
-        s = __builtin_fmaf(w10, channel(t10, ch), s);
-        s = __builtin_fmaf(w01, channel(t01, ch), s);
-        out[ch] = __builtin_fmaf(w11, channel(t11, ch), s);
+        float s = __builtin_fmaf(w00, texel_channel(t00, ch), 0.0f);
+        s = __builtin_fmaf(w10, texel_channel(t10, ch), s);
+        s = __builtin_fmaf(w01, texel_channel(t01, ch), s);
+        out[ch] = __builtin_fmaf(w11, texel_channel(t11, ch), s);
     }
 }
 
@@ -76,21 +60,21 @@ SAH_DEV void resolve_four(const TaaUpscaleArgs& a, const uint2* s_lit, const flo
     };
     const float wf = (float)a.W, hf = (float)a.H;
     const float uy = sample_position(py, a.sy, a.jy);
-    const int j = clampi(floor_to_int(uy), h);
+    const int j = clampi(floor_i32(uy), h);
     const float ey = (((float)j + 0.5f) - uy) * a.ry;
     uint2 packed[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int x = min(px + k, W - 1);  // (beyond the image for the last thread of a row: the last pixel again, nothing stored)
         const float ux = sample_position(x, a.sx, a.jx);
-        const int i = clampi(floor_to_int(ux), w);
+        const int i = clampi(floor_i32(ux), w);
         const uint2 centre = lit_at(j, i);
         packed[k] = centre;
         bool stored = false;
         if (kHistory) {
             // Bounds and Motion over the 3 x 3 neighbourhood of (i, j): the nearest tap, the first in tap order among equals, the centre
             // unless a tap is strictly nearer
-            float lo[3] = {kTuInf, kTuInf, kTuInf}, hi[3] = {-kTuInf, -kTuInf, -kTuInf};
+            float lo[3] = {kScreenInf, kScreenInf, kScreenInf}, hi[3] = {-kScreenInf, -kScreenInf, -kScreenInf};
             float best = depth_at(j, i);
             int bdx = 0, bdy = 0;
 #pragma unroll
@@ -100,7 +84,7 @@ SAH_DEV void resolve_four(const TaaUpscaleArgs& a, const uint2* s_lit, const flo
                     const uint2 t = (dx == 0 && dy == 0) ? centre : lit_at(j + dy, i + dx);
 #pragma unroll
                     for (int ch = 0; ch < 3; ch++) {
-                        const float v = channel(t, ch);
+                        const float v = texel_channel(t, ch);
                         lo[ch] = __builtin_fminf(lo[ch], v);
                         hi[ch] = __builtin_fmaxf(hi[ch], v);
                     }
@@ -112,8 +96,8 @@ SAH_DEV void resolve_four(const TaaUpscaleArgs& a, const uint2* s_lit, const flo
                 }
             const uint32_t m = *reinterpret_cast<const uint32_t*>(a.mv.ptr + (size_t)clampi(j + bdy, h) * a.mv.pitch + (size_t)clampi(i + bdx, w) * 4);
             // Position, Validity (output pixels)
-            const float qx = ((float)x + 0.5f) + (h2f((uint16_t)(m & 0xffffu)) + a.djx) * a.rx;
-            const float qy = ((float)py + 0.5f) + (h2f((uint16_t)(m >> 16)) + a.djy) * a.ry;
+            const float qx = ((float)x + 0.5f) + (half_lo(m) + a.djx) * a.rx;
+            const float qy = ((float)py + 0.5f) + (half_hi(m) + a.djy) * a.ry;
             bool valid = (qx >= 0.0f) & (qx <= wf) & (qy >= 0.0f) & (qy <= hf);
             // History
             const BilinearAxis bx = bilinear_axis(qx, W), by = bilinear_axis(qy, H);
@@ -122,9 +106,9 @@ SAH_DEV void resolve_four(const TaaUpscaleArgs& a, const uint2* s_lit, const flo
             float hv[3];
             bilinear_rgb(bx, by, load_texel8<kVec>(ra + (size_t)bx.a * 8), load_texel8<kVec>(ra + (size_t)bx.b * 8), load_texel8<kVec>(rb + (size_t)bx.a * 8),
                          load_texel8<kVec>(rb + (size_t)bx.b * 8), hv);
-            valid = valid & finite3(hv[0], hv[1], hv[2]);
+            valid = valid & all_finite(hv[0], hv[1], hv[2]);
             // Clamp
-            const float c[3] = {channel(centre, 0), channel(centre, 1), channel(centre, 2)};
+            const float c[3] = {texel_channel(centre, 0), texel_channel(centre, 1), texel_channel(centre, 2)};
             float hc[3];
 #pragma unroll
             for (int ch = 0; ch < 3; ch++) hc[ch] = __builtin_fminf(__builtin_fmaxf(hv[ch], lo[ch]), hi[ch]);
@@ -139,9 +123,9 @@ SAH_DEV void resolve_four(const TaaUpscaleArgs& a, const uint2* s_lit, const flo
                 wk = wc / (wc + wh);
             }
             const float o0 = hc[0] + (c[0] - hc[0]) * wk, o1 = hc[1] + (c[1] - hc[1]) * wk, o2 = hc[2] + (c[2] - hc[2]) * wk;
-            stored = valid & finite3(o0, o1, o2);
+            stored = valid & all_finite(o0, o1, o2);
             if (stored) {
-                packed[k].x = (uint32_t)f2h(o0) | ((uint32_t)f2h(o1) << 16);
+                packed[k].x = pack_half2(o0, o1);
                 packed[k].y = (uint32_t)f2h(o2) | (centre.y & 0xffff0000u);
             }
         }
@@ -149,12 +133,13 @@ SAH_DEV void resolve_four(const TaaUpscaleArgs& a, const uint2* s_lit, const flo
             const BilinearAxis bx = bilinear_axis(ux, w), by = bilinear_axis(uy, h);
             float b[3];
             bilinear_rgb(bx, by, lit_at(by.a, bx.a), lit_at(by.a, bx.b), lit_at(by.b, bx.a), lit_at(by.b, bx.b), b);
-            if (finite3(b[0], b[1], b[2])) {
-                packed[k].x = (uint32_t)f2h(b[0]) | ((uint32_t)f2h(b[1]) << 16);
+            if (all_finite(b[0], b[1], b[2])) {
+                packed[k].x = pack_half2(b[0], b[1]);
                 packed[k].y = (uint32_t)f2h(b[2]) | (centre.y & 0xffff0000u);
             }
         }
     }
+    // (the same store ends taa.hip and sharpen.hip: as a shared function it leaves another block layout, see screen_common.hpp)
     uint8_t* row = const_cast<uint8_t*>(a.out.ptr) + (size_t)py * a.out.pitch + (size_t)px * 8;
     if (kVec && px + 3 < W) {
         reinterpret_cast<uint4*>(row)[0] = make_uint4(packed[0].x, packed[0].y, packed[1].x, packed[1].y);
@@ -177,8 +162,8 @@ template <bool kVec, bool kHistory, bool kHdr> __global__ void __launch_bounds__
     const int x0 = (int)blockIdx.x * kTuW, y0 = (int)(a.row_begin + blockIdx.y * kTuH);
     const int x1 = min(x0 + kTuW, W) - 1, y1 = min(y0 + kTuH, (int)a.row_end) - 1;  // the tile's last pixel
     // the footprint: texels i0 - 1 .. i1 + 1 by j0 - 1 .. j1 + 1 (0 <= i0 <= i1 < 2^31: the differences do not overflow)
-    const int i0 = clampi(floor_to_int(sample_position(x0, a.sx, a.jx)), w), i1 = clampi(floor_to_int(sample_position(x1, a.sx, a.jx)), w);
-    const int j0 = clampi(floor_to_int(sample_position(y0, a.sy, a.jy)), h), j1 = clampi(floor_to_int(sample_position(y1, a.sy, a.jy)), h);
+    const int i0 = clampi(floor_i32(sample_position(x0, a.sx, a.jx)), w), i1 = clampi(floor_i32(sample_position(x1, a.sx, a.jx)), w);
+    const int j0 = clampi(floor_i32(sample_position(y0, a.sy, a.jy)), h), j1 = clampi(floor_i32(sample_position(y1, a.sy, a.jy)), h);
     const bool staged = (i1 - i0 <= kTuCols - 3) & (j1 - j0 <= kTuRows - 3);  // the same for the whole workgroup
     if (staged) {
         const int cols = i1 - i0 + 3, rows = j1 - j0 + 3;
@@ -203,8 +188,7 @@ template <bool kVec, bool kHistory, bool kHdr> __global__ void __launch_bounds__
 hipError_t launch_taa_upscale(const TaaUpscaleArgs& a, bool history, bool hdr_weights, hipStream_t st) {
     if (a.row_end <= a.row_begin) return hipSuccess;
     const dim3 grid((a.W + kTuW - 1) / kTuW, (a.row_end - a.row_begin + kTuH - 1) / kTuH);
-    bool vec = true;
-    for (const PlaneArg* p : {&a.lit, &a.depth, &a.mv, &a.history, &a.out}) vec = vec && ((uintptr_t)p->ptr % 16) == 0 && (p->pitch % 16) == 0;
+    const bool vec = planes_aligned({&a.lit, &a.depth, &a.mv, &a.history, &a.out}, 16);
     void (*kernel)(TaaUpscaleArgs);
     if (!history) kernel = vec ? k_taa_upscale<true, false, false> : k_taa_upscale<false, false, false>;
     else if (hdr_weights) kernel = vec ? k_taa_upscale<true, true, true> : k_taa_upscale<false, true, true>;

@@ -60,7 +60,7 @@ __global__ void __launch_bounds__(256) k_vrsaa_resolve(const PlaneArg lit, const
 hipError_t launch_vrsaa_resolve(const PlaneArg& lit, const PlaneArg& out, uint32_t w, uint32_t h, uint32_t row_begin, uint32_t row_end, hipStream_t st) {
     (void)h;
     if (row_end <= row_begin || w == 0u) return hipSuccess;
-    const bool vec4 = w % 4u == 0u && ((uintptr_t)lit.ptr % 16u) == 0u && lit.pitch % 16u == 0u && ((uintptr_t)out.ptr % 16u) == 0u && out.pitch % 16u == 0u;
+    const bool vec4 = w % 4u == 0u && planes_aligned({&lit, &out}, 16);
     const uint32_t rows = row_end - row_begin, groups = vec4 ? w / 4u : w;
     const dim3 grid((groups + 255u) / 256u, rows < 65535u ? rows : 65535u);
     if (vec4) hipLaunchKernelGGL(k_vrsaa_resolve<true>, grid, dim3(256), 0, st, lit, out, w, row_begin, row_end);

@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
-#include "numerics.hpp"
+#include "screen_common.hpp"
 
 namespace sah {
 
@@ -111,7 +111,7 @@ __global__ void __launch_bounds__(256) k_vrsaa_contrast(PlaneArg color, PlaneArg
         sobel<true>(tz, zx, zy);
         // :62-67: max(luma_gradient * 0.5, depth_gradient); max is maxNum (a NaN depth gradient leaves the luma term, which is never NaN)
         const float ox = __builtin_fmaxf(lx * 0.5f, zx), oy = __builtin_fmaxf(ly * 0.5f, zy);
-        packed[k] = (uint32_t)f2h(ox) | ((uint32_t)f2h(oy) << 16);
+        packed[k] = pack_half2(ox, oy);
     }
     uint8_t* row = const_cast<uint8_t*>(out.ptr) + (size_t)py * out.pitch + (size_t)px * 4;
     if (vec_store && px + 3 < W) {
@@ -127,7 +127,7 @@ hipError_t launch_vrsaa_contrast(const PlaneArg& color, const PlaneArg& depth, c
                                  uint32_t row_end, const float* luts, hipStream_t st) {
     if (row_end <= row_begin) return hipSuccess;
     const dim3 grid((w + kCtW - 1) / kCtW, (row_end - row_begin + kCtH - 1) / kCtH);
-    const int vec_store = ((uintptr_t)out.ptr % 16) == 0 && (out.pitch % 16) == 0;
+    const int vec_store = planes_aligned({&out}, 16);
     hipLaunchKernelGGL(k_vrsaa_contrast, grid, dim3(256), 0, st, color, depth, out, w, h, row_begin, row_end, luts, vec_store);
     return hipGetLastError();
 }
@@ -153,7 +153,7 @@ __global__ void __launch_bounds__(256) k_vrsaa_shading_rate(PlaneArg contrast, u
             uint32_t j = lane / ni, i = lane - j * ni;
             for (uint32_t e = lane; e < total; e += G) {
                 const uint32_t t = *reinterpret_cast<const uint32_t*>(contrast.ptr + (size_t)(by0 + j) * contrast.pitch + (size_t)(bx0 + i) * 4);
-                const float gx = h2f((uint16_t)(t & 0xffffu)), gy = h2f((uint16_t)(t >> 16));
+                const float gx = half_lo(t), gy = half_hi(t);
                 mx = __builtin_fmaxf(mx, __builtin_fabsf(gx * gx));
                 my = __builtin_fmaxf(my, __builtin_fabsf(gy * gy));
                 i += ri;
