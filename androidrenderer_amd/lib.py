@@ -154,6 +154,7 @@ def load():
     lib.sah_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.sah_destroy.argtypes = [C.c_void_p]
     lib.sah_destroy.restype = None
+    lib.sah_debug_create_detached.argtypes = [C.POINTER(C.c_void_p)]
     lib.sah_comm_unique_id.argtypes = [C.c_void_p]
     lib.sah_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     lib.sah_sync.argtypes = [C.c_void_p]
@@ -257,6 +258,19 @@ def load():
     lib.sah_rt_refit.argtypes = [C.c_void_p, C.POINTER(_abi.SceneGeometry), C.c_void_p]
     _lib = lib
     return lib
+
+
+def create_detached():
+    """Test hook (sah_debug_create_detached): the handle (c_void_p) of a context with no device behind it, for the caller to sah_destroy — or
+    None where a HIP device is present: there the library refuses, because what is thrown at such a context must never reach a GPU."""
+    lib = load()
+    h = C.c_void_p()
+    rc = lib.sah_debug_create_detached(C.byref(h))
+    if rc == _abi.SAH_ERR_UNSUPPORTED:
+        return None
+    if rc != _abi.SAH_OK or not h.value:
+        raise SahError(rc, f"sah_debug_create_detached: {lib.sah_status_string(rc).decode()}")
+    return h
 
 
 class Context:

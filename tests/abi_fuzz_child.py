@@ -7,6 +7,9 @@ are never dereferenced on the host by contract; host structures (uniform blocks,
 valid memory filled with random bits, because a caller's invalid HOST pointer is outside what a C ABI can check.
 
     python tests/abi_fuzz_child.py SEED ITERATIONS      (prints one line per entry point: calls and the status codes seen)
+
+The other fuzz children (tests/*_fuzz_child.py) take their generators (Fuzz) and their main from here: a child is a make_calls(L, h, f) that
+returns {entry point: a function making one call}, handed to child_main; run_calls is the loop, usable without the library.
 """
 import collections
 import ctypes as C
@@ -147,19 +150,45 @@ class Fuzz:
                                  self.volume(_abi.FORMAT_R8_UNORM, (32, 32, 32)))
 
 
-def main():
-    seed, iterations = int(sys.argv[1]), int(sys.argv[2])
+def run_calls(calls, seed, iterations, fuzz, width=26):
+    """The loop every fuzz child shares: `iterations` times, each entry of `calls` ({name: function of no argument that makes one call and
+    returns its status}) in sorted order; what an iteration kept alive (fuzz.keep) is dropped after it.  A return that is no sah_status
+    ends the run with a FAIL: line and 1; otherwise one line per entry (the statuses seen, names padded to `width`), the OK: line and 0."""
+    seen = collections.defaultdict(collections.Counter)
+    names = sorted(calls)
+    for i in range(iterations):
+        for name in names:
+            rc = calls[name]()
+            if rc not in STATUS:
+                print(f"FAIL: {name} returned {rc}, not a sah_status (iteration {i}, seed {seed})")
+                return 1
+            seen[name][rc] += 1
+        fuzz.keep.clear()
+    for name in names:
+        print(f"{name:{width}s} " + "  ".join(f"{_abi_name(rc)}: {n}" for rc, n in sorted(seen[name].items(), reverse=True)))
+    print(f"OK: {iterations} iterations x {len(names)} entry points, seed {seed}")
+    return 0
+
+
+def child_main(make_calls, exports, argv, exclude=(), width=26):
+    """A fuzz child's main(): argv = [program, SEED, ITERATIONS]; a context without a device (or the SKIP: line and 0 where a device is
+    present), Fuzz(seed), calls = make_calls(L, h, f), which must cover `exports` but for `exclude`; run_calls; the context destroyed."""
+    seed, iterations = int(argv[1]), int(argv[2])
     L = lib.load()
-    L.sah_debug_create_detached.argtypes = [C.POINTER(C.c_void_p)]
-    h = C.c_void_p()
-    rc = L.sah_debug_create_detached(C.byref(h))
-    if rc == _abi.SAH_ERR_UNSUPPORTED:
+    h = lib.create_detached()
+    if h is None:
         print("SKIP: a HIP device is present (the fuzz's made-up addresses must not reach a GPU)")
         return 0
-    assert rc == 0 and h.value, rc
     f = Fuzz(seed)
-    seen = collections.defaultdict(collections.Counter)
-    P, V = C.POINTER(_abi.Plane), C.POINTER(_abi.Volume)
+    calls = make_calls(L, h, f)
+    uncovered = sorted(set(exports) - set(calls) - set(exclude))
+    assert not uncovered, f"entry points without a fuzz case: {uncovered}"
+    rc = run_calls(calls, seed, iterations, f, width)
+    L.sah_destroy(h)
+    return rc
+
+
+def make_calls(L, h, f):
 
     def ctx():
         return None if f.g.random() < 0.03 else h
@@ -282,24 +311,15 @@ def main():
         "sah_chain_counts": lambda: L.sah_chain_counts(None, None, None),
         "sah_create": lambda: L.sah_create(None if f.g.random() < 0.3 else C.byref(C.c_void_p()), int(f.g.integers(-2, 20)), int(f.g.integers(-2, 20)), int(f.g.integers(-2, 20)), None),
     }
-    uncovered = sorted(set(lib.EXPORTS) - set(calls) - {"sah_abi_version", "sah_destroy", "sah_chain_destroy"})
-    assert not uncovered, f"entry points without a fuzz case: {uncovered}"
-    names = sorted(calls)
-    for i in range(iterations):
-        for name in names:
-            rc = calls[name]()
-            if rc not in STATUS:
-                print(f"FAIL: {name} returned {rc}, not a sah_status (iteration {i}, seed {seed})")
-                return 1
-            seen[name][rc] += 1
-        f.keep.clear()
-    L.sah_chain_destroy(None)
+    return calls
+
+
+def main():
+    rc = child_main(make_calls, lib.EXPORTS, sys.argv, exclude=("sah_abi_version", "sah_destroy", "sah_chain_destroy"), width=34)
+    L = lib.load()
+    L.sah_chain_destroy(None)  # the two destroy entries take NULL
     L.sah_destroy(None)
-    L.sah_destroy(h)
-    for name in names:
-        print(f"{name:34s} " + "  ".join(f"{_abi_name(rc)}: {n}" for rc, n in sorted(seen[name].items(), reverse=True)))
-    print(f"OK: {iterations} iterations x {len(names)} entry points, seed {seed}")
-    return 0
+    return rc
 
 
 def _abi_name(rc):

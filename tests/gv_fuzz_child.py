@@ -3,28 +3,15 @@ tests/test_lpv_gv_cpu.py): the generators of tests/abi_fuzz_child.py, every call
 
     python tests/gv_fuzz_child.py SEED ITERATIONS
 """
-import collections
-import ctypes as C
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from androidrenderer_amd import _abi, lib  # noqa: E402
-from tests.abi_fuzz_child import STATUS, Fuzz, _abi_name  # noqa: E402
+from tests.abi_fuzz_child import child_main  # noqa: E402
 
 
-def main():
-    seed, iterations = int(sys.argv[1]), int(sys.argv[2])
-    L = lib.load()
-    L.sah_debug_create_detached.argtypes = [C.POINTER(C.c_void_p)]
-    h = C.c_void_p()
-    rc = L.sah_debug_create_detached(C.byref(h))
-    if rc == _abi.SAH_ERR_UNSUPPORTED:
-        print("SKIP: a HIP device is present (the fuzz's made-up addresses must not reach a GPU)")
-        return 0
-    assert rc == 0 and h.value, rc
-    f = Fuzz(seed)
-    seen = collections.defaultdict(collections.Counter)
+def make_calls(L, h, f):
     rgba16 = _abi.FORMAT_R16G16B16A16_SFLOAT
 
     def ctx():
@@ -55,28 +42,17 @@ def main():
         return L.sah_lpv_inject_scene_gv(ctx(), opt(f.plane(_abi.FORMAT_D32_SFLOAT, s)), opt(f.plane(rgba16, s)), opt(f.random_bits(_abi.ViewData)),
                                          cascades(), ncasc(), opt(f.volume(rgba16, (128, 32, 32))))
 
-    calls = {
+    return {
         "sah_lpv_inject_rsm_gv": lambda: L.sah_lpv_inject_rsm_gv(ctx(), rsm(), cascades(), f.u32((0, 0, 1, 3, 4)), f.u32((0, 1, 4, 4, 5)), ncasc(),
                                                                  opt(f.volume(rgba16, (128, 32, 32)))),
         "sah_lpv_inject_scene_gv": scene_gv,
         "sah_lpv_propagate_gv": lambda: L.sah_lpv_propagate_gv(ctx(), vols3(), vols3(), opt(f.volume(rgba16, (128, 32, 32)), 0.3), ncasc(),
                                                                int(f.pick([0, 1, 2, 3, 32]))),
     }
-    uncovered = sorted(set(lib.GV_EXPORTS) - set(calls))
-    assert not uncovered, f"entry points without a fuzz case: {uncovered}"
-    for i in range(iterations):
-        for name in sorted(calls):
-            rc = calls[name]()
-            if rc not in STATUS:
-                print(f"FAIL: {name} returned {rc}, not a sah_status (iteration {i}, seed {seed})")
-                return 1
-            seen[name][rc] += 1
-        f.keep.clear()
-    L.sah_destroy(h)
-    for name in sorted(calls):
-        print(f"{name:26s} " + "  ".join(f"{_abi_name(rc)}: {n}" for rc, n in sorted(seen[name].items(), reverse=True)))
-    print(f"OK: {iterations} iterations x {len(calls)} entry points, seed {seed}")
-    return 0
+
+
+def main():
+    return child_main(make_calls, lib.GV_EXPORTS, sys.argv)
 
 
 if __name__ == "__main__":

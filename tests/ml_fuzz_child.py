@@ -23,12 +23,8 @@ def main():
     g = np.random.default_rng(seed)
     arrays = mesh.atrium().arrays()
     pos, vd, idx = arrays["positions"], arrays["vertex_data"], arrays["indices"]
-    L.sah_debug_create_detached.argtypes = [C.POINTER(C.c_void_p)]
-    h = C.c_void_p()
-    rc = L.sah_debug_create_detached(C.byref(h))
-    device_free = rc == 0 and h.value
-    if not device_free and rc != _abi.SAH_ERR_UNSUPPORTED:
-        raise SystemExit(f"detached context: {rc}")
+    h = lib.create_detached()
+    device_free = h is not None
     pick = lambda *xs: xs[int(g.integers(len(xs)))]
     counts = {}
     for it in range(iterations):

@@ -4,33 +4,21 @@ must come back with a sah_status code.
 
     python tests/rtgi_denoise_fuzz_child.py SEED ITERATIONS
 """
-import collections
 import ctypes as C
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from androidrenderer_amd import _abi, lib  # noqa: E402
-from tests.abi_fuzz_child import STATUS, Fuzz, _abi_name  # noqa: E402
+from tests.abi_fuzz_child import child_main  # noqa: E402
 
 FORMATS = dict(ray_buffer=97, ray_irradiance=97, depth=126, normals=97, motion_vectors=83, previous_depth=126, history=109, history_moments=103,
                accum_out=109, moments_out=103, denoised_ray_buffer=97, denoised_irradiance=97)
 
 
-def main():
-    seed, iterations = int(sys.argv[1]), int(sys.argv[2])
-    L = lib.load()
-    L.sah_debug_create_detached.argtypes = [C.POINTER(C.c_void_p)]
-    h = C.c_void_p()
-    rc = L.sah_debug_create_detached(C.byref(h))
-    if rc == _abi.SAH_ERR_UNSUPPORTED:
-        print("SKIP: a HIP device is present (the fuzz's made-up addresses must not reach a GPU)")
-        return 0
-    assert rc == 0 and h.value, rc
+def make_calls(L, h, f):
     assert list(FORMATS) == list(_abi.RtgiDenoiseDesc.PLANES)
-    f = Fuzz(seed)
     f.wild = 0.03  # twelve planes a call: with the generators' usual 0.1 no call would get past the plane checks
-    seen = collections.defaultdict(collections.Counter)
 
     def view():
         r = f.g.random()
@@ -83,22 +71,11 @@ def main():
     def denoise():
         return L.sah_rtgi_denoise(None if f.g.random() < 0.03 else h, view(), desc(), params(), f.u32((0, 0, 0, 3, 16)), f.u32((0, 0, 9, 16, 64)))
 
-    calls = {"sah_rtgi_denoise": denoise}
-    uncovered = sorted(set(lib.RTGI_DENOISE_EXPORTS) - set(calls))
-    assert not uncovered, f"entry points without a fuzz case: {uncovered}"
-    for i in range(iterations):
-        for name in sorted(calls):
-            rc = calls[name]()
-            if rc not in STATUS:
-                print(f"FAIL: {name} returned {rc}, not a sah_status (iteration {i}, seed {seed})")
-                return 1
-            seen[name][rc] += 1
-        f.keep.clear()
-    L.sah_destroy(h)
-    for name in sorted(calls):
-        print(f"{name:26s} " + "  ".join(f"{_abi_name(rc)}: {n}" for rc, n in sorted(seen[name].items(), reverse=True)))
-    print(f"OK: {iterations} iterations x {len(calls)} entry points, seed {seed}")
-    return 0
+    return {"sah_rtgi_denoise": denoise}
+
+
+def main():
+    return child_main(make_calls, lib.RTGI_DENOISE_EXPORTS, sys.argv)
 
 
 if __name__ == "__main__":

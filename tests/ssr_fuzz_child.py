@@ -3,28 +3,16 @@ generators of tests/abi_fuzz_child.py, NULLs, view and parameter blocks of rando
 
     python tests/ssr_fuzz_child.py SEED ITERATIONS
 """
-import collections
 import ctypes as C
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from androidrenderer_amd import _abi, lib  # noqa: E402
-from tests.abi_fuzz_child import STATUS, Fuzz, _abi_name  # noqa: E402
+from tests.abi_fuzz_child import child_main  # noqa: E402
 
 
-def main():
-    seed, iterations = int(sys.argv[1]), int(sys.argv[2])
-    L = lib.load()
-    L.sah_debug_create_detached.argtypes = [C.POINTER(C.c_void_p)]
-    h = C.c_void_p()
-    rc = L.sah_debug_create_detached(C.byref(h))
-    if rc == _abi.SAH_ERR_UNSUPPORTED:
-        print("SKIP: a HIP device is present (the fuzz's made-up addresses must not reach a GPU)")
-        return 0
-    assert rc == 0 and h.value, rc
-    f = Fuzz(seed)
-    seen = collections.defaultdict(collections.Counter)
+def make_calls(L, h, f):
     nan, inf = float("nan"), float("inf")
 
     def view():
@@ -64,22 +52,11 @@ def main():
         return L.sah_ssr(None if f.g.random() < 0.03 else h, view(), f.ptr(f.plane(43, size)), f.ptr(f.plane(97, size)), f.ptr(f.plane(37, size)),
                          f.ptr(f.plane(126, size)), f.ptr(source), f.ptr(lit), f.ptr(scratch), f.ptr(out), params(), f.u32((0, 0, 1, 16)), f.u32((0, 0, 16, 64)))
 
-    calls = {"sah_ssr": ssr}
-    uncovered = sorted(set(lib.SSR_EXPORTS) - set(calls))
-    assert not uncovered, f"entry points without a fuzz case: {uncovered}"
-    for i in range(iterations):
-        for name in sorted(calls):
-            rc = calls[name]()
-            if rc not in STATUS:
-                print(f"FAIL: {name} returned {rc}, not a sah_status (iteration {i}, seed {seed})")
-                return 1
-            seen[name][rc] += 1
-        f.keep.clear()
-    L.sah_destroy(h)
-    for name in sorted(calls):
-        print(f"{name:26s} " + "  ".join(f"{_abi_name(rc)}: {n}" for rc, n in sorted(seen[name].items(), reverse=True)))
-    print(f"OK: {iterations} iterations x {len(calls)} entry points, seed {seed}")
-    return 0
+    return {"sah_ssr": ssr}
+
+
+def main():
+    return child_main(make_calls, lib.SSR_EXPORTS, sys.argv)
 
 
 if __name__ == "__main__":

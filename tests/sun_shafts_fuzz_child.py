@@ -4,28 +4,16 @@ call must come back with a sah_status code.
 
     python tests/sun_shafts_fuzz_child.py SEED ITERATIONS
 """
-import collections
 import ctypes as C
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from androidrenderer_amd import _abi, lib  # noqa: E402
-from tests.abi_fuzz_child import STATUS, Fuzz, _abi_name  # noqa: E402
+from tests.abi_fuzz_child import child_main  # noqa: E402
 
 
-def main():
-    seed, iterations = int(sys.argv[1]), int(sys.argv[2])
-    L = lib.load()
-    L.sah_debug_create_detached.argtypes = [C.POINTER(C.c_void_p)]
-    h = C.c_void_p()
-    rc = L.sah_debug_create_detached(C.byref(h))
-    if rc == _abi.SAH_ERR_UNSUPPORTED:
-        print("SKIP: a HIP device is present (the fuzz's made-up addresses must not reach a GPU)")
-        return 0
-    assert rc == 0 and h.value, rc
-    f = Fuzz(seed)
-    seen = collections.defaultdict(collections.Counter)
+def make_calls(L, h, f):
     nan, inf = float("nan"), float("inf")
 
     def params():
@@ -56,22 +44,11 @@ def main():
         return L.sah_sun_shafts(None if f.g.random() < 0.03 else h, f.ptr(view), f.ptr(sun), f.ptr(shadowmap, 0.2), f.ptr(f.plane(126, size)), f.ptr(lit),
                                 f.ptr(march), f.ptr(out), params(), f.u32((0, 0, 1, 16)), f.u32((0, 0, 16, 64)))
 
-    calls = {"sah_sun_shafts": sun_shafts}
-    uncovered = sorted(set(lib.SUN_SHAFTS_EXPORTS) - set(calls))
-    assert not uncovered, f"entry points without a fuzz case: {uncovered}"
-    for i in range(iterations):
-        for name in sorted(calls):
-            rc = calls[name]()
-            if rc not in STATUS:
-                print(f"FAIL: {name} returned {rc}, not a sah_status (iteration {i}, seed {seed})")
-                return 1
-            seen[name][rc] += 1
-        f.keep.clear()
-    L.sah_destroy(h)
-    for name in sorted(calls):
-        print(f"{name:26s} " + "  ".join(f"{_abi_name(rc)}: {n}" for rc, n in sorted(seen[name].items(), reverse=True)))
-    print(f"OK: {iterations} iterations x {len(calls)} entry points, seed {seed}")
-    return 0
+    return {"sah_sun_shafts": sun_shafts}
+
+
+def main():
+    return child_main(make_calls, lib.SUN_SHAFTS_EXPORTS, sys.argv)
 
 
 if __name__ == "__main__":

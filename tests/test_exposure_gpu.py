@@ -15,7 +15,8 @@ import pytest
 from androidrenderer_amd import _abi, frame, images, lib, mesh, scene
 from tests import exposure_ref as ref
 from tests import util
-from tests.test_vrsaa_gpu import SENTINEL, Image
+from tests.host_programs import host_program
+from tests.support import context_state, differs, Image, retyped, same, SENTINEL, side_stream_context
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -94,19 +95,6 @@ def _texels(img):
     return img.texels(np.uint16).reshape(img.h, img.w, 4)
 
 
-def _differs(got, want):
-    bad = (got != want).reshape(got.shape[0], got.shape[1], -1).any(-1) if got.ndim == 3 else got != want
-    return f"{int(bad.sum())} of {bad.size} differ, first at {np.argwhere(bad)[:4].tolist()}"
-
-
-def _raw(a):
-    return a if isinstance(a, bytes) else np.asarray(a).tobytes()
-
-
-def _same(got, want):
-    return _raw(got) == _raw(want)
-
-
 def _meter(ctx, scene_img, buffers, state_in, state_out, out_img, params):
     import torch
     ctx.exposure_meter(scene_img.plane, buffers.state_ptr(state_in), buffers.state_ptr(state_out), buffers.work, None if out_img is None else out_img.plane, params)
@@ -123,13 +111,13 @@ def _check_meter(ctx, scene_np, settings, state_in=None, fused=True, pitches=(No
     _meter(ctx, scene_img, buffers, None if cut else 0, 1, out_img, _params(**settings))
     want_n, want_state = ref.meter(scene_np, state_in, settings)
     got_n, got_state = buffers.histogram(), buffers.state(1)
-    assert _same(got_n, want_n), "histogram: " + _differs(got_n, want_n)
-    assert _same(got_state, want_state), f"state {got_state} != {want_state}"
+    assert same(got_n, want_n), "histogram: " + differs(got_n, want_n)
+    assert same(got_state, want_state), f"state {got_state} != {want_state}"
     assert buffers.intact((1,)), "bytes around work or the states changed"
     exposed = None
     if fused:
         exposed, want = _texels(out_img), ref.apply(scene_np, state_in["exposure"])
-        assert _same(exposed, want), "exposed: " + _differs(exposed, want)
+        assert same(exposed, want), "exposed: " + differs(exposed, want)
         assert out_img.padding_intact()
     if not in_place:
         assert scene_img.unchanged()
@@ -162,11 +150,11 @@ def _fixture_sequence(ctx, fixture):
 def test_fixture_bit_for_bit_and_repeatable(hip_ctx, fixture):
     got = _fixture_sequence(hip_ctx, fixture)
     for i, (n, state, exposed) in enumerate(got):
-        assert _same(n, fixture["histograms"][i]), f"frame {i}, histogram: " + _differs(n, fixture["histograms"][i])
-        assert _same(state, fixture["states"][i]), f"frame {i}: state {state} != {fixture['states'][i]}"
-        assert _same(exposed, fixture["exposed"][i]), f"frame {i}, exposed: " + _differs(exposed, fixture["exposed"][i])
+        assert same(n, fixture["histograms"][i]), f"frame {i}, histogram: " + differs(n, fixture["histograms"][i])
+        assert same(state, fixture["states"][i]), f"frame {i}: state {state} != {fixture['states'][i]}"
+        assert same(exposed, fixture["exposed"][i]), f"frame {i}, exposed: " + differs(exposed, fixture["exposed"][i])
     again = _fixture_sequence(hip_ctx, fixture)
-    assert all(_same(a, b) for x, y in zip(got, again) for a, b in zip(x, y))
+    assert all(same(a, b) for x, y in zip(got, again) for a, b in zip(x, y))
 
 
 # ---- extents --------------------------------------------------------------------------------------------------------------------------------
@@ -192,10 +180,10 @@ def test_extents(hip_ctx, extent):
 @pytest.mark.parametrize("in_place", [False, True])
 def test_pitches_offsets_sentinels_and_inputs(hip_ctx, fixture, pitches, offsets, in_place):
     n, state, exposed = _check_meter(hip_ctx, fixture["scene"], dict(gen.PARAMS), PREVIOUS, pitches=pitches, offsets=offsets, in_place=in_place, work_offset=4)
-    assert _same(n, fixture["histograms"][0])
+    assert same(n, fixture["histograms"][0])
     # the metering alone on the same planes, and apply on them
     n2, state2, _ = _check_meter(hip_ctx, fixture["scene"], dict(gen.PARAMS), PREVIOUS, fused=False, pitches=pitches, offsets=offsets)
-    assert _same(n, n2) and _same(state, state2)
+    assert same(n, n2) and same(state, state2)
 
 
 # ---- the persistent loop and the ticket -------------------------------------------------------------------------------------------------------
@@ -204,7 +192,7 @@ def test_max_workgroups_never_changes_a_byte(hip_ctx):
     scene_np = ref.random_inputs(w, h, 4242)
     results = [_check_meter(hip_ctx, scene_np, dict(adaptation=0.25, max_workgroups=m), PREVIOUS) for m in (1, 2, 3, 0, 9, 1000)]
     for r in results[1:]:
-        assert all(_same(a, b) for a, b in zip(results[0], r))
+        assert all(same(a, b) for a, b in zip(results[0], r))
 
 
 # ---- inputs made to break it --------------------------------------------------------------------------------------------------------------------
@@ -275,7 +263,7 @@ def test_four_frames_ping_pong_and_in_place_then_a_cut(hip_ctx):
             hip_ctx.exposure_meter(_scene_image(sc).plane, None if first else buffers.state_ptr(at), buffers.state_ptr(new), buffers.work, None,
                                    _params(**dict(s, flags=CUT if first else 0)))
             torch.cuda.synchronize()
-            assert _same(buffers.state(new), want[i]), f"frame {i}, in place {in_place}: {buffers.state(new)} != {want[i]}"
+            assert same(buffers.state(new), want[i]), f"frame {i}, in place {in_place}: {buffers.state(new)} != {want[i]}"
             at = new
         assert buffers.intact((0,) if in_place else (0, 1))
     assert len({w.tobytes() for w in want}) == 5 and want[4]["adapted"] != want[3]["adapted"]
@@ -287,19 +275,19 @@ def test_fused_equals_meter_then_apply_and_row_bands(hip_ctx, fixture):
     p = _params(**gen.PARAMS)
     fused_n, fused_state, fused_out = _check_meter(hip_ctx, sc, dict(gen.PARAMS), PREVIOUS)
     in_place = _check_meter(hip_ctx, sc, dict(gen.PARAMS), PREVIOUS, in_place=True)
-    assert all(_same(a, b) for a, b in zip((fused_n, fused_state, fused_out), in_place))
+    assert all(same(a, b) for a, b in zip((fused_n, fused_state, fused_out), in_place))
     # meter, then apply with state_in
     buffers = Buffers(0, [PREVIOUS, None])
     scene_img, out_img = _scene_image(sc), Image(RGBA16F, W, H, 69 * 8 + 12)
     _meter(hip_ctx, scene_img, buffers, 0, 1, None, p)
     hip_ctx.exposure_apply(scene_img.plane, buffers.state_ptr(0), out_img.plane)
     torch.cuda.synchronize()
-    assert _same(buffers.histogram(), fused_n) and _same(buffers.state(1), fused_state) and _same(_texels(out_img), fused_out) and out_img.padding_intact()
+    assert same(buffers.histogram(), fused_n) and same(buffers.state(1), fused_state) and same(_texels(out_img), fused_out) and out_img.padding_intact()
     # apply in place
     own = _scene_image(sc, 69 * 8 + 4, 4)
     hip_ctx.exposure_apply(own.plane, buffers.state_ptr(0), own.plane)
     torch.cuda.synchronize()
-    assert _same(_texels(own), fused_out) and own.padding_intact()
+    assert same(_texels(own), fused_out) and own.padding_intact()
     # row bands write their rows and nothing else, and assemble to the whole
     assembled = np.full((H, W, 4), 0xA5A5, np.uint16)
     for rows in ((9, 10), (0, 9), (10, H), (5, 5), (0, 1), (H - 1, H)):
@@ -307,11 +295,11 @@ def test_fused_equals_meter_then_apply_and_row_bands(hip_ctx, fixture):
         hip_ctx.exposure_apply(scene_img.plane, buffers.state_ptr(0), band.plane, rows)
         torch.cuda.synchronize()
         got = _texels(band)
-        assert _same(got[rows[0]:rows[1]], fused_out[rows[0]:rows[1]]), f"{rows}: " + _differs(got[rows[0]:rows[1]], fused_out[rows[0]:rows[1]])
+        assert same(got[rows[0]:rows[1]], fused_out[rows[0]:rows[1]]), f"{rows}: " + differs(got[rows[0]:rows[1]], fused_out[rows[0]:rows[1]])
         assert band.padding_intact(ref.band_rows(rows, H)), f"{rows}: out changed outside the band"
-        assert _same(got, ref.apply(sc, PREVIOUS["exposure"], rows))
+        assert same(got, ref.apply(sc, PREVIOUS["exposure"], rows))
         assembled[rows[0]:rows[1]] = got[rows[0]:rows[1]]
-    assert _same(assembled, fused_out) and scene_img.unchanged() and buffers.intact((1,))
+    assert same(assembled, fused_out) and scene_img.unchanged() and buffers.intact((1,))
 
 
 # ---- the call contract ----------------------------------------------------------------------------------------------------------------------
@@ -323,8 +311,6 @@ def test_refusals_launch_nothing(hip_ctx, fixture):
     scene_img, out_img = _scene_image(fixture["scene"]), Image(RGBA16F, W, H)
     sc, out, work, s0, s1 = scene_img.plane, out_img.plane, buffers.work, buffers.state_ptr(0), buffers.state_ptr(1)
 
-    def retyped(plane, fmt):
-        return _abi.Plane(plane.ptr, plane.width, plane.height, plane.row_pitch_bytes, fmt)
     INVALID, FORMAT = _abi.SAH_ERR_INVALID_ARGUMENT, _abi.SAH_ERR_UNSUPPORTED_FORMAT
     ok, nan = _params(), float("nan")
     meter_cases = [((retyped(sc, _abi.FORMAT_R32_SFLOAT), s0, s1, work, out, ok), FORMAT),
@@ -367,22 +353,19 @@ def test_refusals_launch_nothing(hip_ctx, fixture):
 
 def test_side_stream_captured_graph_replayed_twice_and_no_side_effects(fixture):
     import torch
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
-    try:
-        ctx.set_stream(s.cuda_stream)
+    with side_stream_context() as (ctx, s):
         W, H = gen.WIDTH, gen.HEIGHT
         settings = dict(gen.PARAMS)
         params = _params(**settings)
         buffers = Buffers(0, [PREVIOUS, None])
         scene_img, out_img = _scene_image(fixture["scene"]), Image(RGBA16F, W, H)
-        state = (ctx.cache_epoch(), ctx.lighting_dispatch(), ctx.copy_rebuilds())
+        state = context_state(ctx)
         torch.cuda.synchronize()
         with torch.cuda.stream(s):
             ctx.exposure_meter(scene_img.plane, buffers.state_ptr(0), buffers.state_ptr(1), buffers.work, out_img.plane, params)
         s.synchronize()
-        assert _same(buffers.histogram(), fixture["histograms"][0]) and _same(buffers.state(1), ref.meter(fixture["scene"], PREVIOUS, settings)[1])
-        assert (ctx.cache_epoch(), ctx.lighting_dispatch(), ctx.copy_rebuilds()) == state
+        assert same(buffers.histogram(), fixture["histograms"][0]) and same(buffers.state(1), ref.meter(fixture["scene"], PREVIOUS, settings)[1])
+        assert context_state(ctx) == state
         # one captured graph (the kernel that zeroes work, then the metering kernel: a linear chain), replayed twice over other scene contents
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=s):
@@ -396,12 +379,9 @@ def test_side_stream_captured_graph_replayed_twice_and_no_side_effects(fixture):
             graph.replay()
             torch.cuda.synchronize()
             want_n, want_state = ref.meter(other, PREVIOUS, settings)
-            assert _same(buffers.histogram(), want_n), f"replay with seed {seed}: " + _differs(buffers.histogram(), want_n)
-            assert _same(buffers.state(1), want_state) and _same(_texels(out_img), ref.apply(other, PREVIOUS["exposure"]))
-        assert (ctx.cache_epoch(), ctx.lighting_dispatch(), ctx.copy_rebuilds()) == state
-    finally:
-        torch.cuda.synchronize()
-        ctx.close()
+            assert same(buffers.histogram(), want_n), f"replay with seed {seed}: " + differs(buffers.histogram(), want_n)
+            assert same(buffers.state(1), want_state) and same(_texels(out_img), ref.apply(other, PREVIOUS["exposure"]))
+        assert context_state(ctx) == state
 
 
 # ---- wrappers -----------------------------------------------------------------------------------------------------------------------------------
@@ -427,24 +407,13 @@ def test_three_frames_through_the_python_wrapper(hip_ctx):
         out = auto.expose(util.to_torch(sc))
         torch.cuda.synchronize()
         assert out is auto.exposed and tuple(out.shape) == sc.shape
-        assert _same(auto.histogram(), want_n) and _same(bytes(auto.state()), want_state), f"frame {i}"
+        assert same(auto.histogram(), want_n) and same(bytes(auto.state()), want_state), f"frame {i}"
         got = out.cpu().numpy().view(np.uint16)
-        assert _same(got, want_exposed), f"frame {i}: " + _differs(got, want_exposed)
+        assert same(got, want_exposed), f"frame {i}: " + differs(got, want_exposed)
     auto.reset()
     out = auto.expose(util.to_torch(frames[2]))  # after a cut: metered, then exposed by its own state
     torch.cuda.synchronize()
-    assert _same(out.cpu().numpy().view(np.uint16), want_exposed) and _same(bytes(auto.state()), want_state)
-
-
-def _host_program(tmp_path):
-    built = os.path.join(ROOT, "tests", "cpp", "host_exposure")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_exposure.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_exposure"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
+    assert same(out.cpu().numpy().view(np.uint16), want_exposed) and same(bytes(auto.state()), want_state)
 
 
 def test_three_frames_through_the_cpp_facade(tmp_path):
@@ -454,15 +423,15 @@ def test_three_frames_through_the_cpp_facade(tmp_path):
         f.write(np.array([len(frames)], np.uint32).tobytes() + f32(0.25).tobytes())
         for sc in frames:
             f.write(np.array([sc.shape[1], sc.shape[0]], np.uint32).tobytes() + sc.tobytes())
-    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    subprocess.check_call([host_program("host_exposure", tmp_path), str(inp), str(outp)], timeout=120)
     blob = open(outp, "rb").read()
     at = 0
     for i, (sc, (want_n, want_state, want_exposed)) in enumerate(zip(frames, _wrapper_sequence(frames, 0.25))):
         state, n = blob[at:at + 16], np.frombuffer(blob[at + 16:at + 16 + 1024], np.uint32)
         exposed = np.frombuffer(blob[at + 1040:at + 1040 + sc.nbytes], np.uint16).reshape(sc.shape)
         at += 1040 + sc.nbytes
-        assert _same(n, want_n) and state == want_state.tobytes(), f"frame {i}: {np.frombuffer(state, ref.STATE)} != {want_state}"
-        assert _same(exposed, want_exposed), f"frame {i}: " + _differs(exposed, want_exposed)
+        assert same(n, want_n) and state == want_state.tobytes(), f"frame {i}: {np.frombuffer(state, ref.STATE)} != {want_state}"
+        assert same(exposed, want_exposed), f"frame {i}: " + differs(exposed, want_exposed)
     assert at == len(blob)
 
 
@@ -503,7 +472,7 @@ def test_atrium_lit_with_the_sun_eight_times_brighter_is_exposed_alike(hip_ctx):
         torch.cuda.synchronize()
         exposed[gain], states[gain] = out.cpu().numpy().view(np.uint16), np.frombuffer(bytes(auto.state()), ref.STATE)[0]
         want_n, want_state = ref.meter(lit[gain], None, cut)
-        assert _same(auto.histogram(), want_n) and _same(states[gain], want_state) and _same(exposed[gain], ref.apply(lit[gain], want_state["exposure"]))
+        assert same(auto.histogram(), want_n) and same(states[gain], want_state) and same(exposed[gain], ref.apply(lit[gain], want_state["exposure"]))
         for name, plane_t in (("unexposed", lit_t), ("exposed", out)):
             mips = [torch.zeros((mh, mw, 4), dtype=torch.int16, device="cuda") for (mw, mh) in images.bloom_mip_sizes(W, H, 6)]
             ldr = torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda")

@@ -4,11 +4,11 @@ status codes of the two calls it replaces before anything is launched."""
 import os
 import re
 import subprocess
-import sys
 
 import pytest
 
 from androidrenderer_amd import lib
+from tests import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -38,10 +38,4 @@ def test_header_compiles_as_c_and_as_cpp(tmp_path, language):
 
 @pytest.mark.parametrize("seed", [41, 42])
 def test_malformed_calls_are_refused_and_launch_nothing(seed):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "gbuffer_motion_fuzz_child.py"), str(seed), "3000"], stdout=subprocess.PIPE,
-                       stderr=subprocess.STDOUT, text=True, timeout=600)
-    tail = "\n".join(r.stdout.splitlines()[-10:])
-    if "SKIP:" in r.stdout:
-        pytest.skip(r.stdout.strip().splitlines()[-1])
-    assert r.returncode == 0, f"the fuzz child ended with code {r.returncode}:\n{tail}"
-    assert "OK: 3000 iterations" in r.stdout, tail
+    support.run_fuzz_child("gbuffer_motion_fuzz_child.py", seed, 3000)

@@ -12,6 +12,7 @@ import pytest
 
 from androidrenderer_amd import _abi, frame, mesh
 from tests import util
+from tests.host_programs import host_program
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,17 +25,6 @@ def _time_limit():
     faulthandler.dump_traceback_later(300, exit=True)  # an overrun ends the process
     yield
     faulthandler.cancel_dump_traceback_later()
-
-
-def _host_program(tmp_path):
-    built = os.path.join(ROOT, "tests", "cpp", "host_gbuffer_motion")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_motion_vectors.h", "sah_gbuffer_motion.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_gbuffer_motion"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
 
 
 def _run_facade(exe, tmp_path, arrays, W, H, share):
@@ -57,7 +47,7 @@ def _run_facade(exe, tmp_path, arrays, W, H, share):
 
 def test_shared_setup_frame_equals_the_default_frame(tmp_path, hip_ctx):
     import torch
-    exe = _host_program(tmp_path)
+    exe = host_program("host_gbuffer_motion", tmp_path)
     W, H = 320, 180
     arrays = mesh.random_soup(43, triangles=600, extent=8.0).arrays()
     vd_on, on, passes_on = _run_facade(exe, tmp_path, arrays, W, H, 1)

@@ -3,7 +3,6 @@ lighting → copy scene → bloom → tonemap — compared with the oracle runni
 C++ program produced."""
 import ctypes as C
 import math
-import os
 import subprocess
 
 import numpy as np
@@ -11,25 +10,14 @@ import pytest
 
 from androidrenderer_amd import _abi, images, scene, synth
 from tests import util
+from tests.host_programs import host_program
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "host_frame")
-
-
-def _build():
-    src = os.path.join(ROOT, "tests", "cpp", "host_frame.cpp")
-    if os.path.exists(EXE) and os.path.getmtime(EXE) > max(os.path.getmtime(src), os.path.getmtime(os.path.join(ROOT, "include", "sah_host.hpp"))):
-        return
-    libdir = os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), src, "-o", EXE, "-L", libdir,
-                           "-lsah_hip", f"-Wl,-rpath,{libdir}"])
 
 
 @pytest.mark.parametrize("sun_mode", [_abi.SHADOW_MODE_RT])
 def test_frame_through_cpp_facade(tmp_path, sun_mode):
-    _build()
+    exe = host_program("host_frame")  # (in place, where build() leaves it)
     W, H, steps = 192, 108, 4
     view = scene.SceneView.default(W, H)
     g = synth.atrium_gbuffer(W, H, view, seed=2)
@@ -42,7 +30,7 @@ def test_frame_through_cpp_facade(tmp_path, sun_mode):
         f.write(np.array([W, H, sun_mode, steps], dtype=np.uint32).tobytes())
         for a in (g["color"], g["normals"], g["data"], g["emission"], g["depth"], ao, mask, luts["transmittance"], luts["sky_view"], *vols):
             f.write(np.ascontiguousarray(a).tobytes())
-    subprocess.check_call([EXE, str(inp), str(outp)])
+    subprocess.check_call([exe, str(inp), str(outp)])
     blob = open(outp, "rb").read()
     off = 0
 
@@ -98,23 +86,11 @@ def test_frame_through_cpp_facade(tmp_path, sun_mode):
     assert math.isclose(view_c.inverse_projection[0], view.gpu_data.inverse_projection[0], rel_tol=1e-5)
 
 
-RASTER_EXE = os.path.join(ROOT, "tests", "cpp", "host_raster")
-
-
-def _build_raster():
-    src = os.path.join(ROOT, "tests", "cpp", "host_raster.cpp")
-    if os.path.exists(RASTER_EXE) and os.path.getmtime(RASTER_EXE) > max(os.path.getmtime(src), os.path.getmtime(os.path.join(ROOT, "include", "sah_host.hpp"))):
-        return
-    libdir = os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), src, "-o", RASTER_EXE, "-L", libdir,
-                           "-lsah_hip", f"-Wl,-rpath,{libdir}"])
-
-
 def test_producer_passes_through_cpp_facade(tmp_path):
     """update_shadow_cascades + render_shadows + GbufferPhase::render in C++ against the oracle fed with the blocks C++ built, and
     the C++ cascade fitting against scene.py's."""
     from androidrenderer_amd import mesh
-    _build_raster()
+    exe = host_program("host_raster")
     W, H, R = 160, 90, 256
     m = mesh.atrium(2)
     # material textures through the facade's TextureDescriptorPool: base colour / normal / data on every material, emission on the lamps
@@ -139,7 +115,7 @@ def test_producer_passes_through_cpp_facade(tmp_path):
         noise = g.integers(0, 256, (128, 128, 4), dtype=np.uint8)
         f.write(noise.tobytes())  # (read before the material-texture table: see host_raster.cpp)
         f.write(np.ascontiguousarray(arrays["material_textures"], dtype=np.uint32).tobytes())
-    subprocess.check_call([RASTER_EXE, str(inp), str(outp)])
+    subprocess.check_call([exe, str(inp), str(outp)])
     blob = open(outp, "rb").read()
     off = 0
 

@@ -10,12 +10,9 @@ from androidrenderer_amd import _abi, lib
 def _context():
     """a Context without a device where there is none, on cuda:0 where there is one: the knob is host state either way"""
     L = lib.load()
-    L.sah_debug_create_detached.argtypes = [C.POINTER(C.c_void_p)]
-    h = C.c_void_p()
-    rc = L.sah_debug_create_detached(C.byref(h))
-    if rc == _abi.SAH_ERR_UNSUPPORTED:  # a HIP device is present
+    h = lib.create_detached()
+    if h is None:  # a HIP device is present
         return lib.Context(device=0)
-    assert rc == 0 and h.value
     ctx = lib.Context.__new__(lib.Context)
     ctx.lib, ctx.handle = L, h
     return ctx

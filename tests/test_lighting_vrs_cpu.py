@@ -11,6 +11,7 @@ import pytest
 
 from androidrenderer_amd import _abi, lib
 from tests import lighting_vrs_ref as ref
+from tests import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -247,11 +248,5 @@ def test_parity_cases_exercise_the_map():
 # ---- refusals on a context without a device -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("seed", [1, 2])
 def test_argument_fuzz_on_a_detached_context(seed):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "vrs_fuzz_child.py"), str(seed), "2000"], stdout=subprocess.PIPE,
-                       stderr=subprocess.STDOUT, text=True, timeout=600)
-    tail = "\n".join(r.stdout.splitlines()[-10:])
-    if "SKIP:" in r.stdout:
-        pytest.skip(r.stdout.strip().splitlines()[-1])
-    assert r.returncode == 0, f"the fuzz child ended with code {r.returncode}:\n{tail}"
-    assert "OK: 2000 iterations" in r.stdout, tail
-    assert "SAH_OK" not in r.stdout  # (a detached context never launches)
+    stdout = support.run_fuzz_child("vrs_fuzz_child.py", seed, 2000)
+    assert "SAH_OK" not in stdout  # (a detached context never launches)

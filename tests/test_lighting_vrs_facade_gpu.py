@@ -11,6 +11,7 @@ import pytest
 from androidrenderer_amd import _abi, frame, images, scene, synth
 from tests import lighting_vrs_ref as ref
 from tests import util
+from tests.host_programs import host_program
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,17 +23,6 @@ def _time_limit():
     faulthandler.dump_traceback_later(300, exit=True)  # an overrun ends the process
     yield
     faulthandler.cancel_dump_traceback_later()
-
-
-def _host_program(tmp_path):
-    built = os.path.join(ROOT, "tests", "cpp", "host_lighting_vrs")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_vrsaa.h", "sah_vrs.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_lighting_vrs"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
 
 
 def _direct(ctx, fr, dev, rates, texel, tol):
@@ -63,7 +53,7 @@ def test_variable_rate_lighting_and_resolve_through_cpp_facade(tmp_path, hip_ctx
         f.write(np.array([ref.TOLERANCE], np.float32).tobytes())
         for a in (g["color"], g["normals"], g["data"], g["emission"], g["depth"], ao, mask, luts["transmittance"], luts["sky_view"], *vols, rates):
             f.write(np.ascontiguousarray(a).tobytes())
-    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    subprocess.check_call([host_program("host_lighting_vrs", tmp_path), str(inp), str(outp)], timeout=120)
     blob = open(outp, "rb").read()
     off = 0
 

@@ -15,7 +15,7 @@ import pytest
 from androidrenderer_amd import _abi, images, lib
 from tests import lighting_vrs_ref as ref
 from tests import util
-from tests.test_vrsaa_gpu import SENTINEL, Image
+from tests.support import context_state, differs, Image, SENTINEL, side_stream_context
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -74,11 +74,6 @@ def _case(ctx, case, sun, gi):
     return Case(ctx, case, sun, gi)
 
 
-def _differs(got, want):
-    bad = (got != want).reshape(got.shape[0], got.shape[1], -1).any(-1)
-    return f"{int(bad.sum())} of {bad.size} pixels differ, first at {np.argwhere(bad)[:4].tolist()}"
-
-
 # ---- parity -------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("gi", GIS)
 @pytest.mark.parametrize("sun", SUNS)
@@ -87,7 +82,7 @@ def test_parity_with_the_gather_of_sah_lighting(hip_ctx, case, sun, gi):
     c = _case(hip_ctx, case, sun, gi)
     got = c.run(hip_ctx)
     want = c.want()
-    assert got.tobytes() == want.tobytes(), f"case {ref.PARITY_CASES[case]}, sun {sun}, gi {gi}: " + _differs(got, want)
+    assert got.tobytes() == want.tobytes(), f"case {ref.PARITY_CASES[case]}, sun {sun}, gi {gi}: " + differs(got, want)
     assert (got != c.full).any(), "the gather is not the identity: the variable-rate frame differs from the full-rate one"
     assert c.run(hip_ctx).tobytes() == got.tobytes()  # repeatable
 
@@ -106,7 +101,7 @@ def test_uniform_1x1_is_sah_lighting(hip_ctx, sun, gi):
         c = _case(hip_ctx, case, sun, gi)
         for code in (0, 0xf0):
             got = c.run(hip_ctx, np.full_like(c.rates, code), float("inf"))
-            assert got.tobytes() == c.full.tobytes(), _differs(got, c.full)
+            assert got.tobytes() == c.full.tobytes(), differs(got, c.full)
 
 
 def test_tolerances_zero_and_infinite(hip_ctx):
@@ -116,7 +111,7 @@ def test_tolerances_zero_and_infinite(hip_ctx):
     for tol, (sy, sx) in zip(fx["tolerances"], fx["source_map"]):
         got = c.run(hip_ctx, tol=float(tol))
         want = c.full[sy.astype(np.int64), sx.astype(np.int64)]
-        assert got.tobytes() == want.tobytes(), f"tolerance {tol}: " + _differs(got, want)
+        assert got.tobytes() == want.tobytes(), f"tolerance {tol}: " + differs(got, want)
 
 
 def test_uniform_coarse_rates(hip_ctx):
@@ -126,7 +121,7 @@ def test_uniform_coarse_rates(hip_ctx):
         rates = np.full_like(c.rates, code)
         got = c.run(hip_ctx, rates, float("inf"))
         want = c.want(rates, float("inf"))
-        assert got.tobytes() == want.tobytes(), f"code {code}: " + _differs(got, want)
+        assert got.tobytes() == want.tobytes(), f"code {code}: " + differs(got, want)
 
 
 def test_force_general_gives_the_same_bytes(hip_ctx):
@@ -182,7 +177,7 @@ def test_pitched_offset_planes_sentinels_and_inputs(hip_ctx, case, pad, offset, 
     hip_ctx.lighting_vrs(d, p.rate.plane, c.texel, ref.TOLERANCE)
     torch.cuda.synchronize()
     got, want = p.texels(), c.want()
-    assert got.tobytes() == want.tobytes(), _differs(got, want)
+    assert got.tobytes() == want.tobytes(), differs(got, want)
     assert p.lit.padding_intact(), "bytes outside the texels of lit changed"
     assert p.inputs_unchanged()
 
@@ -198,7 +193,7 @@ def test_row_bands(hip_ctx, rows):
     torch.cuda.synchronize()
     got, want = p.texels(), np.full((c.h, c.w, 4), PATTERN, np.uint16)
     want[rows[0]:rows[1]] = c.want()[rows[0]:rows[1]]  # the whole-frame call on the band's rows, the sentinel elsewhere
-    assert got.tobytes() == want.tobytes(), f"rows {rows}: " + _differs(got, want)
+    assert got.tobytes() == want.tobytes(), f"rows {rows}: " + differs(got, want)
     assert p.lit.padding_intact(rows) and p.inputs_unchanged()
     assert c.run(hip_ctx, rows=rows).tobytes() == want.tobytes()
 
@@ -208,7 +203,7 @@ def test_no_side_effects_on_the_context(hip_ctx):
     c.f.run_hip(hip_ctx, c.dev)
 
     def state():
-        return hip_ctx.cache_epoch(), hip_ctx.lighting_dispatch(), hip_ctx.copy_rebuilds()
+        return context_state(hip_ctx)
     before = state()
     got = c.run(hip_ctx)
     assert state() == before
@@ -219,10 +214,7 @@ def test_no_side_effects_on_the_context(hip_ctx):
 def test_recorded_under_stream_capture_and_replayed(hip_ctx):
     import torch
     c = _case(hip_ctx, 0, _abi.SHADOW_MODE_CSM, _abi.GI_LPV)
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
-    try:
-        ctx.set_stream(s.cuda_stream)
+    with side_stream_context() as (ctx, s):
         lit = torch.full((c.h, c.w, 4), PATTERN - 0x10000, dtype=torch.int16, device="cuda")
         sri = util.to_torch(c.rates)
         d, keep = c.f.describe(c.dev, lit)
@@ -239,11 +231,8 @@ def test_recorded_under_stream_capture_and_replayed(hip_ctx):
         graph.replay()
         torch.cuda.synchronize()
         got, want = util.from_torch(lit, np.uint16), c.want(rates2)
-        assert got.tobytes() == want.tobytes(), _differs(got, want)
+        assert got.tobytes() == want.tobytes(), differs(got, want)
         assert want.tobytes() != c.want().tobytes()
-    finally:
-        torch.cuda.synchronize()
-        ctx.close()
 
 
 # ---- the resolve --------------------------------------------------------------------------------------------------------------------------
@@ -259,7 +248,7 @@ def _resolve(ctx, lit_np, pitches=(None, None), offsets=(0, 0), rows=(0, 0)):
     r0, r1 = (0, h) if tuple(rows) == (0, 0) else rows
     want = np.full((h, w, 4), PATTERN, np.uint16)
     want[r0:r1] = ref.resolve(lit_np, rows)
-    assert got.tobytes() == want.tobytes(), f"{w} x {h}, pitches {pitches}, offsets {offsets}, rows {rows}: " + _differs(got, want)
+    assert got.tobytes() == want.tobytes(), f"{w} x {h}, pitches {pitches}, offsets {offsets}, rows {rows}: " + differs(got, want)
     assert out.padding_intact((r0, r1)) and lit.unchanged()
     return got
 

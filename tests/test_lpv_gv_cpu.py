@@ -4,13 +4,13 @@ answers for one GV sample, one face factor and one point through each injection.
 import ctypes as C
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 from androidrenderer_amd import _abi, lib
+from tests import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -30,20 +30,13 @@ def test_library_exports_the_gv_entries_its_header_declares():
 
 @pytest.mark.parametrize("seed", [21, 22])
 def test_no_argument_combination_crashes_a_gv_entry(seed):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "gv_fuzz_child.py"), str(seed), "2000"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       text=True, timeout=600)
-    tail = "\n".join(r.stdout.splitlines()[-10:])
-    if "SKIP:" in r.stdout:
-        pytest.skip(r.stdout.strip().splitlines()[-1])
-    assert r.returncode == 0, f"the fuzz child ended with code {r.returncode}:\n{tail}"
-    assert "OK: 2000 iterations" in r.stdout, tail
+    support.run_fuzz_child("gv_fuzz_child.py", seed, 2000)
 
 
 def test_gv_entries_check_their_arguments():
     L = lib.load()
-    L.sah_debug_create_detached.argtypes = [C.POINTER(C.c_void_p)]
-    h = C.c_void_p()
-    if L.sah_debug_create_detached(C.byref(h)) == _abi.SAH_ERR_UNSUPPORTED:
+    h = lib.create_detached()
+    if h is None:
         pytest.skip("a HIP device is present")
     rgba16 = _abi.FORMAT_R16G16B16A16_SFLOAT
     vol = lambda w=128, fmt=rgba16, bpp=8: _abi.Volume(0x7F0000000000, w, 32, 32, w * bpp, w * bpp * 32, fmt)

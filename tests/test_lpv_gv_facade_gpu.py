@@ -10,6 +10,7 @@ import pytest
 
 from androidrenderer_amd import _abi, images, mesh, scene
 from tests import util
+from tests.host_programs import host_program
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,10 +20,7 @@ import gen_golden_gv as ggv  # noqa: E402
 
 def test_lpv_frame_with_gv_through_cpp_facade(tmp_path, hip_ctx):
     import torch
-    exe = str(tmp_path / "host_lpv_gv")
-    libdir = os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "host_lpv_gv.cpp"),
-                           "-o", exe, "-L", libdir, "-lsah_hip", f"-Wl,-rpath,{libdir}"], timeout=600)
+    exe = host_program("host_lpv_gv", tmp_path)  # (not among those build() leaves: compiled here)
     W, H, steps = 192, 108, 2
     view = scene.SceneView.default(W, H)
     keep = []

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from androidrenderer_amd import _abi, lib, mesh, scene
+from tests import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -175,11 +176,7 @@ def test_point_cloud_refuses_bad_ranges_and_capacities():
 
 @pytest.mark.parametrize("seed", [31, 32])
 def test_no_argument_combination_crashes_a_mesh_light_entry(seed):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ml_fuzz_child.py"), str(seed), "1500"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       text=True, timeout=600)
-    tail = "\n".join(r.stdout.splitlines()[-10:])
-    assert r.returncode == 0, f"the fuzz child ended with code {r.returncode}:\n{tail}"
-    assert "OK: 1500 iterations" in r.stdout, tail
+    support.run_fuzz_child("ml_fuzz_child.py", seed, 1500)
 
 
 def _random_vpls(g, n, spread=20.0):

@@ -3,7 +3,6 @@ inject_indirect_sun_light ends with the emissive injection and its volumes equal
 (mesh.emissive_clouds + sah_lpv_inject_emissive) bit for bit; with it off the recorded passes are today's; the injection alone equals the
 direct calls onto cleared volumes."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -11,19 +10,15 @@ import pytest
 
 from androidrenderer_amd import _abi, images, lib, mesh
 from tests import util
+from tests.host_programs import host_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPE = (32, 32, 128, 4)
 
 
 def test_mesh_lights_through_cpp_facade(tmp_path, hip_ctx):
     import torch
-    exe = str(tmp_path / "host_lpv_mesh_lights")
-    libdir = os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "host_lpv_mesh_lights.cpp"), "-o", exe, "-L", libdir, "-lsah_hip", f"-Wl,-rpath,{libdir}"],
-                          timeout=600)
+    exe = host_program("host_lpv_mesh_lights", tmp_path)  # (not among those build() leaves: compiled here)
     arrays = mesh.atrium().arrays()
     arrays["textures"], arrays["material_textures"] = [], np.zeros((0, 4), np.uint32)
     seed, flags = 77, lib.POINT_CLOUD_ON_SURFACE

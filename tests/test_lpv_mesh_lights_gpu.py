@@ -13,6 +13,7 @@ import pytest
 
 from androidrenderer_amd import _abi, images, lib, mesh, scene
 from tests import util
+from tests.support import side_stream_context
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -284,10 +285,7 @@ def test_order_onto_filled_volumes_repeatability_and_capture(hip_ctx):
     assert [x.tobytes() for x in _inject(hip_ctx, g, records, lpv, prior)] == [x.tobytes() for x in got]
     # the call records under stream capture (no host synchronisation, no read-back) and the replay gives the same bytes
     t = [util.to_torch(v.copy()) for v in prior]
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
-    try:
-        ctx.set_stream(s.cuda_stream)
+    with side_stream_context() as (ctx, s):
         with torch.cuda.stream(s):
             ctx.lpv_inject_emissive(g, records, lpv.matrices, lpv.bounds, 4, [_vol(x) for x in t])  # grows the scratch outside the capture
         s.synchronize()
@@ -301,8 +299,6 @@ def test_order_onto_filled_volumes_repeatability_and_capture(hip_ctx):
         torch.cuda.synchronize()
         for c in range(3):
             assert np.array_equal(util.from_torch(t[c], np.uint16).reshape(SHAPE), got[c])
-    finally:
-        ctx.close()
 
 
 def test_too_many_entries_is_refused(hip_ctx):

@@ -9,6 +9,7 @@ import pytest
 
 from androidrenderer_amd import _abi, images, mesh, scene
 from tests import mip_chain_ref as ref
+from tests.host_programs import host_program
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,17 +20,6 @@ def _time_limit():
     faulthandler.dump_traceback_later(300, exit=True)  # an overrun ends the process
     yield
     faulthandler.cancel_dump_traceback_later()
-
-
-def _host_program(tmp_path):
-    built = os.path.join(ROOT, "tests", "cpp", "host_hi_z")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_mip_chain.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_hi_z"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
 
 
 def test_hi_z_of_a_rasterised_depth_plane_through_cpp_facade(tmp_path, hip_ctx):
@@ -54,7 +44,7 @@ def test_hi_z_of_a_rasterised_depth_plane_through_cpp_facade(tmp_path, hip_ctx):
     with open(inp, "wb") as f:
         f.write(np.array([W, H], np.uint32).tobytes())
         f.write(depth.tobytes())
-    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    subprocess.check_call([host_program("host_hi_z", tmp_path), str(inp), str(outp)], timeout=120)
     blob = open(outp, "rb").read()
     assert int(np.frombuffer(blob[:4], np.uint32)[0]) == n
     at = 4

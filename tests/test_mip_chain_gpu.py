@@ -9,6 +9,7 @@ import pytest
 from androidrenderer_amd import _abi, lib
 from tests import mip_chain_ref as ref
 from tests import util
+from tests.support import context_state, side_stream_context
 
 pytestmark = pytest.mark.gpu
 SENTINEL = 0xA5
@@ -280,10 +281,7 @@ def test_on_a_side_stream_without_host_sync_and_under_capture(fixtures):
     import torch
     fx = fixtures["192x136"]
     want = [fx[f"d32_level{i}"] for i in range(7)]
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
-    try:
-        ctx.set_stream(s.cuda_stream)
+    with side_stream_context() as (ctx, s):
         src = Image(D32, 192, 136, data=fx["d32_src"])
         levels = _levels(R32, (96, 68), 7)
         planes = [im.plane for im in levels]
@@ -313,9 +311,6 @@ def test_on_a_side_stream_without_host_sync_and_under_capture(fixtures):
         torch.cuda.synchronize()
         assert all(a.tobytes() == im.bytes().tobytes() for a, im in zip(first, levels))
         assert not np.array_equal(want2[6], want[6])
-    finally:
-        torch.cuda.synchronize()
-        ctx.close()
 
 
 def test_no_side_effects_on_the_context(hip_ctx, fixtures):
@@ -324,7 +319,7 @@ def test_no_side_effects_on_the_context(hip_ctx, fixtures):
     f.run_hip(hip_ctx)
 
     def state():
-        return hip_ctx.cache_epoch(), hip_ctx.lighting_dispatch(), hip_ctx.copy_rebuilds()
+        return context_state(hip_ctx)
     before = state()
     fx = fixtures["160x96"]
     got = _run(hip_ctx, D32, fx["d32_src"], (80, 48), 6)

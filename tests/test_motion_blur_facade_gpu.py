@@ -11,7 +11,9 @@ import pytest
 
 from androidrenderer_amd import _abi
 from tests import motion_blur_ref as ref
-from tests.test_motion_blur_gpu import Planes, _differs, _params, _same
+from tests.test_motion_blur_gpu import Planes, _params
+from tests.host_programs import host_program
+from tests.support import differs, same
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,17 +25,6 @@ def _time_limit():
     faulthandler.dump_traceback_later(120, exit=True)
     yield
     faulthandler.cancel_dump_traceback_later()
-
-
-def _host_program(tmp_path):
-    built = os.path.join(ROOT, "tests", "cpp", "host_motion_blur")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_motion_blur.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_motion_blur"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
 
 
 def test_three_frames_through_the_cpp_facade(tmp_path, hip_ctx):
@@ -52,7 +43,7 @@ def test_three_frames_through_the_cpp_facade(tmp_path, hip_ctx):
             f.write(np.array([W, H, w, h, dither, count], np.uint32).tobytes() + np.array(list(jitter) + [shutter], f32).tobytes())
             for a in planes:
                 f.write(np.ascontiguousarray(a).tobytes())
-    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    subprocess.check_call([host_program("host_motion_blur", tmp_path), str(inp), str(outp)], timeout=120)
     blob = open(outp, "rb").read()
     at, previous, blurred = 0, (0.0, 0.0), 0
     for i, (((W, H), (w, h), dither, count, jitter, shutter), (scene_bits, depth, mv)) in enumerate(zip(frames, arrays)):
@@ -63,9 +54,9 @@ def test_three_frames_through_the_cpp_facade(tmp_path, hip_ctx):
         assert tuple(view.previous_jitter) == tuple(f32(j) for j in previous) and f32(view.z_near) == f32(0.05)
         settings = dict(shutter=shutter, sample_count=count, flags=ref.DITHER if dither else 0, z_near=0.05, jitter=jitter, previous_jitter=previous)
         want, info = ref.motion_blur_ex(scene_bits, depth, mv, **settings)
-        assert _same(facade, want), f"frame {i}: " + _differs(facade, want)
+        assert same(facade, want), f"frame {i}: " + differs(facade, want)
         got = Planes(scene_bits, depth, mv).run(hip_ctx, _params(**settings))
-        assert _same(facade, got)
+        assert same(facade, got)
         blurred += int((~info["passed"]).sum())
         previous = jitter
     assert at == len(blob) and blurred > 3000

@@ -15,7 +15,7 @@ from androidrenderer_amd import _abi, frame, lib, mesh, scene
 from tests import layouts
 from tests import motion_blur_ref as ref
 from tests import util
-from tests.test_vrsaa_gpu import SENTINEL, Image
+from tests.support import context_state, differs, Image, resized, retyped, same, SENTINEL, side_stream_context
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -78,22 +78,13 @@ class Planes:
         return self.result()
 
 
-def _differs(got, want):
-    bad = (got != want).any(-1)
-    return f"{int(bad.sum())} of {bad.size} pixels differ, first (y, x) at {np.argwhere(bad)[:4].tolist()}"
-
-
-def _same(got, want):
-    return got.tobytes() == want.tobytes()
-
-
 def _check(hip_ctx, scene_bits, depth, mv, settings, **kw):
     """one whole-frame call against the restatement, the tile plane included; -> (got, info)"""
     p = Planes(scene_bits, depth, mv, **kw)
     got = p.run(hip_ctx, _params(**settings))
     want, info = ref.motion_blur_ex(scene_bits, depth, mv, **settings)
-    assert _same(p.tiles(), info["tiles"]), f"{settings}: tiles " + _differs(p.tiles(), info["tiles"])
-    assert _same(got, want), f"{settings}: " + _differs(got, want)
+    assert same(p.tiles(), info["tiles"]), f"{settings}: tiles " + differs(p.tiles(), info["tiles"])
+    assert same(got, want), f"{settings}: " + differs(got, want)
     return got, info
 
 
@@ -112,9 +103,9 @@ def test_fixture_bit_for_bit_and_repeatable(hip_ctx, fixture, case):
     field, settings = gen.CASES[case]
     p = Planes(fixture["scene"], fixture[f"{field}_depth"], fixture[f"{field}_mv"])
     got = p.run(hip_ctx, _params(**settings))
-    assert _same(got, fixture["out"][case]), _differs(got, fixture["out"][case])
+    assert same(got, fixture["out"][case]), differs(got, fixture["out"][case])
     again = p.run(hip_ctx, _params(**settings))  # two calls, the same bytes
-    assert _same(again, got)
+    assert same(again, got)
 
 
 # ---- extents and parameters ---------------------------------------------------------------------------------------------------------------
@@ -201,7 +192,7 @@ def test_non_finite_vectors_and_unclean_texels_on_the_device(hip_ctx):
     assert (~ref.clean(ref.h2f(got[..., :3]))).sum() == 4
     for bits in (0x7E00, 0x7C00, 0xFC00):
         got, _ = _check(hip_ctx, scene_bits, depth, np.full((h, w, 2), bits, np.uint16), dict())
-        assert _same(got, scene_bits)
+        assert same(got, scene_bits)
 
 
 def test_a_static_camera_copies_the_scene_on_either_path(hip_ctx):
@@ -211,7 +202,7 @@ def test_a_static_camera_copies_the_scene_on_either_path(hip_ctx):
     mv = ref.static_vectors(w, h, jitter, previous)
     for kw in (dict(), dict(offsets=dict(scene=8, out=4))):
         got, _ = _check(hip_ctx, scene_bits, depth, mv, dict(jitter=jitter, previous_jitter=previous), **kw)
-        assert _same(got, scene_bits)
+        assert same(got, scene_bits)
 
 
 # ---- upscale ------------------------------------------------------------------------------------------------------------------------------
@@ -233,20 +224,20 @@ def test_row_windows_cover_the_frame_and_write_nothing_else(hip_ctx, render, out
     settings = dict(flags=ref.DITHER, jitter=(0.25, 0.125), previous_jitter=(0.0, 0.0))
     want = ref.motion_blur(scene_bits, depth, mv, **settings)
     whole = Planes(scene_bits, depth, mv).run(hip_ctx, _params(**settings))
-    assert _same(whole, want)
+    assert same(whole, want)
     banded = Planes(scene_bits, depth, mv)
     for rows in ((0, 7), (7, 8), (8, 24), (24, 24), (24, 40), (40, H)):  # windows that split tile rows; a one-row and an empty window
         before = banded.result().copy()
         single = Planes(scene_bits, depth, mv)
         got = single.run(hip_ctx, _params(**settings), rows)
-        assert _same(got[rows[0]:rows[1]], want[rows[0]:rows[1]]), f"rows {rows}: " + _differs(got[rows[0]:rows[1]], want[rows[0]:rows[1]])
+        assert same(got[rows[0]:rows[1]], want[rows[0]:rows[1]]), f"rows {rows}: " + differs(got[rows[0]:rows[1]], want[rows[0]:rows[1]])
         layouts.assert_rows_untouched(np.uint16(SENTINEL * 0x101), got, rows[0], rows[1], what=f"rows {rows}")
         if rows[0] == rows[1]:
             assert single.img["tiles"].unchanged()  # an empty band writes nothing at all
         banded.run(hip_ctx, _params(**settings), rows)
         layouts.assert_rows_untouched(before, banded.result(), rows[0], rows[1], what=f"rows {rows} of the union")
     torch.cuda.synchronize()
-    assert _same(banded.result(), whole)
+    assert same(banded.result(), whole)
 
 
 # ---- layout -------------------------------------------------------------------------------------------------------------------------------
@@ -260,7 +251,7 @@ def test_pitched_offset_and_misaligned_planes_give_the_same_bytes(hip_ctx):
                dict(pitches=dict(scene=w * 8 + 16, out=w * 8 + 32, mv=w * 4 + 4, depth=w * 4 + 12, tiles=3 * 4 + 8)),
                dict(pitches=dict(scene=w * 8 + 4, out=w * 8 + 12), offsets=dict(scene=16, out=16))):
         got, _ = _check(hip_ctx, scene_bits, depth, mv, settings, **kw)
-        assert _same(got, tight), kw
+        assert same(got, tight), kw
 
 
 @pytest.mark.parametrize("spec", [dict(row_pad=8, offset=8), dict(row_pad=40, offset=16)], ids=["A", "B"])
@@ -277,7 +268,7 @@ def test_layouts_of_tests_layouts(hip_ctx, spec):
     wrapped = layouts.wrap(arrays, {n: (FORMATS[n], 2) for n in ORDER}, dict(scene=spec, out=spec, depth=small, mv=small, tiles=small))
     hip_ctx.motion_blur(*[wrapped[n].plane() for n in ORDER], _params())
     torch.cuda.synchronize()
-    assert _same(wrapped["out"].read(np.uint16), want)
+    assert same(wrapped["out"].read(np.uint16), want)
     layouts.assert_padding_intact(wrapped, what=str(spec))
     layouts.assert_inputs_unchanged({n: wrapped[n] for n in INPUTS}, what=str(spec))
 
@@ -287,17 +278,14 @@ def test_side_stream_under_capture_and_replayed_over_other_inputs(fixture):
     import torch
     fx = fixture
     field, settings = gen.CASES[2]
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
-    try:
-        ctx.set_stream(s.cuda_stream)
+    with side_stream_context() as (ctx, s):
         a = Planes(fx["scene"], fx[f"{field}_depth"], fx[f"{field}_mv"])
         params = _params(**settings)
         torch.cuda.synchronize()
         with torch.cuda.stream(s):
             ctx.motion_blur(*a.planes(), params)
         s.synchronize()
-        assert _same(a.result(), fx["out"][2])
+        assert same(a.result(), fx["out"][2])
         b = Planes(ref.textured_scene(gen.WIDTH, gen.HEIGHT, 71), fx["box_pan_depth"], fx["box_pan_mv"])
         direct = ref.motion_blur(b.img["scene"].texels(np.uint16).reshape(gen.HEIGHT, gen.WIDTH, 4), fx["box_pan_depth"], fx["box_pan_mv"], **settings)
         torch.cuda.synchronize()
@@ -309,10 +297,7 @@ def test_side_stream_under_capture_and_replayed_over_other_inputs(fixture):
         torch.cuda.synchronize()
         graph.replay()
         torch.cuda.synchronize()
-        assert _same(a.result(), direct) and not _same(direct, fx["out"][2])
-    finally:
-        torch.cuda.synchronize()
-        ctx.close()
+        assert same(a.result(), direct) and not same(direct, fx["out"][2])
 
 
 def test_no_side_effects_on_the_context(hip_ctx, fixture):
@@ -320,10 +305,10 @@ def test_no_side_effects_on_the_context(hip_ctx, fixture):
     f.run_hip(hip_ctx)
 
     def state():
-        return hip_ctx.cache_epoch(), hip_ctx.lighting_dispatch(), hip_ctx.copy_rebuilds()
+        return context_state(hip_ctx)
     before = state()
     got = Planes(fixture["scene"], fixture["dolly_depth"], fixture["dolly_mv"]).run(hip_ctx, _params())
-    assert state() == before and _same(got, fixture["out"][2])
+    assert state() == before and same(got, fixture["out"][2])
 
 
 def test_refusals_launch_nothing(hip_ctx, fixture):
@@ -333,11 +318,6 @@ def test_refusals_launch_nothing(hip_ctx, fixture):
     scene_p, depth, mv, tiles, out = p.planes()
     ok = _params()
 
-    def retyped(plane, fmt):
-        return _abi.Plane(plane.ptr, plane.width, plane.height, plane.row_pitch_bytes, fmt)
-
-    def resized(plane, width, height):
-        return _abi.Plane(plane.ptr, width, height, plane.row_pitch_bytes, plane.format)
     INVALID, FORMAT = _abi.SAH_ERR_INVALID_ARGUMENT, _abi.SAH_ERR_UNSUPPORTED_FORMAT
     nan = float("nan")
     cases = [((scene_p, depth, mv, tiles, retyped(out, _abi.FORMAT_R32_SFLOAT), ok), FORMAT),
@@ -398,8 +378,8 @@ def test_three_frames_of_a_panning_camera_on_the_rasterised_atrium(hip_ctx):
         got, depth_np, mv_np = util.from_torch(out, np.uint16), gb["depth"].cpu().numpy(), util.from_torch(mv, np.uint16)
         want, info = ref.motion_blur_ex(scene_bits, depth_np, mv_np, flags=ref.DITHER, z_near=view.near_value, jitter=jitter,
                                         previous_jitter=jitter if previous is None else previous)
-        assert _same(got, want), f"frame {n}: " + _differs(got, want)
-        assert _same(util.from_torch(blur.tiles, np.uint16), info["tiles"])
+        assert same(got, want), f"frame {n}: " + differs(got, want)
+        assert same(util.from_torch(blur.tiles, np.uint16), info["tiles"])
         assert (~info["passed"]).mean() > 0.5 and (depth_np > 0).mean() > 0.5, f"frame {n}"
         previous = jitter
     assert (blur.width, blur.height, blur.render_width, blur.render_height) == (w, h, w, h)

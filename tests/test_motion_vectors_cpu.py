@@ -11,6 +11,7 @@ import pytest
 
 from androidrenderer_amd import _abi, lib, mesh, scene
 from tests import mv_reproject
+from tests import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -41,13 +42,7 @@ def test_header_compiles_as_c_and_as_cpp(tmp_path, language):
 
 @pytest.mark.parametrize("seed", [31, 32])
 def test_malformed_calls_are_refused_and_launch_nothing(seed):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "mv_fuzz_child.py"), str(seed), "3000"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       text=True, timeout=600)
-    tail = "\n".join(r.stdout.splitlines()[-10:])
-    if "SKIP:" in r.stdout:
-        pytest.skip(r.stdout.strip().splitlines()[-1])
-    assert r.returncode == 0, f"the fuzz child ended with code {r.returncode}:\n{tail}"
-    assert "OK: 3000 iterations" in r.stdout, tail
+    support.run_fuzz_child("mv_fuzz_child.py", seed, 3000)
 
 
 def test_generator_reproduces_the_committed_fixture():

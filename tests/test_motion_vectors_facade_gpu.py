@@ -3,7 +3,6 @@
 stays as it was created and the G-buffer planes are the ones the frame writes without the feature."""
 import ctypes as C
 import faulthandler
-import os
 import subprocess
 
 import numpy as np
@@ -11,9 +10,9 @@ import pytest
 
 from androidrenderer_amd import _abi, frame, images, mesh
 from tests import util
+from tests.host_programs import host_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLANES = (("color", 4, np.uint8), ("normals", 8, np.uint16), ("data", 4, np.uint8), ("emission", 4, np.uint8), ("depth", 4, np.float32),
           ("motion_vectors", 4, np.uint16))
 
@@ -38,10 +37,7 @@ def _run_facade(exe, tmp_path, arrays, W, H, switch):
 
 def test_motion_vectors_phase_through_cpp_facade(tmp_path, hip_ctx):
     import torch
-    exe = str(tmp_path / "host_motion_vectors")
-    libdir = os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "host_motion_vectors.cpp"),
-                           "-o", exe, "-L", libdir, "-lsah_hip", f"-Wl,-rpath,{libdir}"], timeout=600)
+    exe = host_program("host_motion_vectors", tmp_path)  # (not among those build() leaves: compiled here)
     W, H = 320, 180
     arrays = mesh.random_soup(43, triangles=600, extent=8.0).arrays()
     vd_on, on = _run_facade(exe, tmp_path, arrays, W, H, 1)

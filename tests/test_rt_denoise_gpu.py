@@ -12,7 +12,8 @@ import pytest
 from androidrenderer_amd import _abi, frame, lib, scene
 from tests import rt_denoise_ref as ref
 from tests import util
-from tests.test_vrsaa_gpu import SENTINEL, Image
+from tests.host_programs import host_program
+from tests.support import context_state, differs, Image, reprojection_view_data_of, retyped, same, SENTINEL, side_stream_context
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,16 +40,6 @@ def _time_limit():
 @pytest.fixture(scope="module")
 def fixture():
     return dict(np.load(gen.FIXTURE))
-
-
-def view_data_of(view):
-    """an _abi.ViewData holding what the pass reads, from a rt_denoise_ref.View"""
-    v = _abi.ViewData()
-    for i in range(16):
-        v.inverse_view[i], v.last_frame_view[i] = float(view.inverse_view[i]), float(view.last_frame_view[i])
-    v.projection[0], v.projection[5], v.projection[8], v.projection[9], v.z_near = float(view.p00), float(view.p11), float(view.p20), float(view.p21), float(view.z_near)
-    v.projection[11] = -1.0
-    return v
 
 
 def moved_view(w, h, dolly=0.05, jitter=(0.3, -0.2)):
@@ -104,20 +95,10 @@ class Planes:
                 im["denoised"].texels(f32).reshape(self.h, self.w))
 
 
-def _differs(got, want):
-    as_bytes = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(a.shape + (-1,))  # noqa: E731
-    bad = (as_bytes(got) != as_bytes(want)).any(-1)
-    return f"{int(bad.sum())} of {bad.size} texels differ, first (y, x) at {np.argwhere(bad)[:4].tolist()}"
-
-
-def _same(got, want):
-    return np.ascontiguousarray(got).tobytes() == np.ascontiguousarray(want).tobytes()
-
-
 def assert_outputs(got, want, what=""):
     for name, g, w in zip(("accum_out", "length_out", "denoised"), got, want):
         w = w.view(np.uint16) if w.dtype == np.float16 else w
-        assert _same(g, w), f"{what} {name}: " + _differs(g, w)
+        assert same(g, w), f"{what} {name}: " + differs(g, w)
 
 
 def reference(inputs, view, settings):
@@ -132,7 +113,7 @@ def fixture_want(fx, i, passes):
 @pytest.mark.parametrize("passes", [0, 1, 2, 3])
 def test_fixture_bit_for_bit_and_repeatable(hip_ctx, fixture, passes):
     for i in range(gen.FRAMES):
-        inputs, view, params = gen.frame_of(fixture, i), view_data_of(gen.view(i)), _params(**gen.params(i, passes))
+        inputs, view, params = gen.frame_of(fixture, i), reprojection_view_data_of(gen.view(i)), _params(**gen.params(i, passes))
         got = Planes(inputs).run(hip_ctx, view, params)
         assert_outputs(got, fixture_want(fixture, i, passes), f"frame {i}")
         assert_outputs(Planes(inputs).run(hip_ctx, view, params), got, f"frame {i} again")
@@ -174,7 +155,7 @@ LAYOUTS = {"dwords: nothing 16-byte aligned": _layout(4, 4),
 def test_pitches_offsets_sentinels_and_inputs(hip_ctx, fixture, layout, passes):
     for i in (0, 1):
         p = Planes(gen.frame_of(fixture, i), LAYOUTS[layout])
-        got = p.run(hip_ctx, view_data_of(gen.view(i)), _params(**gen.params(i, passes)))  # (asserts the inputs unchanged)
+        got = p.run(hip_ctx, reprojection_view_data_of(gen.view(i)), _params(**gen.params(i, passes)))  # (asserts the inputs unchanged)
         assert_outputs(got, fixture_want(fixture, i, passes), f"frame {i}")
         assert all(p.images[n].padding_intact() for n, _ in OUTPUTS)
 
@@ -183,7 +164,7 @@ def test_pitches_offsets_sentinels_and_inputs(hip_ctx, fixture, layout, passes):
 @pytest.mark.parametrize("passes", [0, 1, 3])
 def test_row_bands_write_their_rows_and_nothing_else(hip_ctx, fixture, passes):
     W, H = gen.WIDTH, gen.HEIGHT
-    view, params = view_data_of(gen.view(1)), _params(**gen.params(1, passes))
+    view, params = reprojection_view_data_of(gen.view(1)), _params(**gen.params(1, passes))
     whole = fixture_want(fixture, 1, passes)
     assembled = [np.full((H, W), SENTINEL, np.uint8).repeat(4, 1).view(f32), np.full((H, W), SENTINEL, np.uint8).repeat(2, 1).view(np.uint16),
                  np.full((H, W), SENTINEL, np.uint8).repeat(4, 1).view(f32)]
@@ -193,7 +174,7 @@ def test_row_bands_write_their_rows_and_nothing_else(hip_ctx, fixture, passes):
         wide = ref.band_rows(rows, H, passes)
         for k, (name, _) in enumerate(OUTPUTS):
             r = rows if name == "denoised" else wide
-            assert _same(got[k][r[0]:r[1]], whole[k][r[0]:r[1]]), f"{rows} {name}: " + _differs(got[k][r[0]:r[1]], whole[k][r[0]:r[1]])
+            assert same(got[k][r[0]:r[1]], whole[k][r[0]:r[1]]), f"{rows} {name}: " + differs(got[k][r[0]:r[1]], whole[k][r[0]:r[1]])
             assert p.images[name].padding_intact(r), f"{rows}: {name} changed outside rows {r}"
             assembled[k][r[0]:r[1]] = got[k][r[0]:r[1]]
     assert_outputs(assembled, whole, "assembled")
@@ -203,25 +184,22 @@ def test_row_bands_write_their_rows_and_nothing_else(hip_ctx, fixture, passes):
 def test_refusals_launch_nothing(hip_ctx, fixture):
     import torch
     p = Planes(gen.frame_of(fixture, 1))
-    view, ok = view_data_of(gen.view(1)), _params(**gen.params(1, 3))
+    view, ok = reprojection_view_data_of(gen.view(1)), _params(**gen.params(1, 3))
     pl = {n: im.plane for n, im in p.images.items()}
-
-    def retyped(name, fmt):
-        return _abi.Plane(pl[name].ptr, pl[name].width, pl[name].height, pl[name].row_pitch_bytes, fmt)
 
     def shaped(name, **kw):
         q = _abi.Plane(pl[name].ptr, pl[name].width, pl[name].height, pl[name].row_pitch_bytes, pl[name].format)
         for k, v in kw.items():
             setattr(q, k, v)
         return q
-    bad_view = view_data_of(gen.view(1))
+    bad_view = reprojection_view_data_of(gen.view(1))
     bad_view.z_near = float("nan")
-    nan_view = view_data_of(gen.view(1))
+    nan_view = reprojection_view_data_of(gen.view(1))
     nan_view.last_frame_view[10] = float("nan")
     INVALID, FORMAT = _abi.SAH_ERR_INVALID_ARGUMENT, _abi.SAH_ERR_UNSUPPORTED_FORMAT
     P = lambda **kw: _params(**dict(gen.params(1, 3), **kw))  # noqa: E731
     inf = float("inf")
-    cases = [((view, p.desc(**{n: retyped(n, D32 if f != D32 else R32F)}), ok), FORMAT) for n, f in INPUTS + OUTPUTS]
+    cases = [((view, p.desc(**{n: retyped(pl[n], D32 if f != D32 else R32F)}), ok), FORMAT) for n, f in INPUTS + OUTPUTS]
     cases += [((view, p.desc(**{n: None}), ok), INVALID) for n in NAMES]  # a previous-frame plane may be NULL only with the flag
     cases += [((view, p.desc(), ok, (0, 22)), INVALID), ((view, p.desc(), ok, (9, 3)), INVALID),
               ((view, p.desc(), P(flags=2)), INVALID), ((view, p.desc(), P(flags=3)), INVALID),
@@ -250,7 +228,7 @@ def test_refusals_launch_nothing(hip_ctx, fixture):
 def test_history_invalid_flag_excuses_the_previous_planes(hip_ctx, fixture):
     inputs = gen.frame_of(fixture, 1)
     params = _params(**dict(gen.params(1, 3), flags=_abi.RT_DENOISE_HISTORY_INVALID))
-    view = view_data_of(gen.view(1))
+    view = reprojection_view_data_of(gen.view(1))
     without = Planes(dict(inputs, previous_depth=None, history=None, history_length=None))
     assert set(without.images) == set(NAMES) - {"previous_depth", "history", "history_length"}
     got = without.run(hip_ctx, view, params)
@@ -265,20 +243,17 @@ def test_history_invalid_flag_excuses_the_previous_planes(hip_ctx, fixture):
 
 def test_side_stream_captured_graph_replayed_twice_and_no_side_effects(fixture):
     import torch
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
-    try:
-        ctx.set_stream(s.cuda_stream)
-        view, params = view_data_of(gen.view(1)), _params(**gen.params(1, 3))
+    with side_stream_context() as (ctx, s):
+        view, params = reprojection_view_data_of(gen.view(1)), _params(**gen.params(1, 3))
         a = Planes(gen.frame_of(fixture, 1))
         desc = a.desc()
-        state = (ctx.cache_epoch(), ctx.lighting_dispatch(), ctx.copy_rebuilds())
+        state = context_state(ctx)
         torch.cuda.synchronize()
         with torch.cuda.stream(s):
             ctx.rt_denoise(view, desc, params)
         s.synchronize()
         assert_outputs(a.outputs(), fixture_want(fixture, 1, 3))
-        assert (ctx.cache_epoch(), ctx.lighting_dispatch(), ctx.copy_rebuilds()) == state
+        assert context_state(ctx) == state
         # one captured graph (temporal, then filter: a linear chain), replayed twice over other input contents
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=s):
@@ -296,9 +271,6 @@ def test_side_stream_captured_graph_replayed_twice_and_no_side_effects(fixture):
             want = ref.denoise_ex(*[inputs[k] for k in ORDER], gen.view(1), gen.params(1, 3))
             assert_outputs(a.outputs(), want[:3], f"replay with seed {seed}")
             assert want[3]["history"].sum() > 200
-    finally:
-        torch.cuda.synchronize()
-        ctx.close()
 
 
 # ---- wrappers -----------------------------------------------------------------------------------------------------------------------------------
@@ -327,23 +299,11 @@ def test_four_frames_through_the_python_wrapper(hip_ctx):
         assert out is dn.denoised
         settings = dict(max_history=8.0, jitter=jitter, previous_jitter=jitter if first else jitters[i - 1], flags=ref.HISTORY_INVALID if first else 0)
         accum, length, want, info = ref.denoise_ex(noisy, depth, base["normals"], mv, previous_depth, accum, length, ref.View(view), settings)
-        assert _same(out.cpu().numpy(), want), f"frame {i}: " + _differs(out.cpu().numpy(), want)
-        assert _same(dn.accum[dn.current].cpu().numpy(), accum) and _same(dn.length[dn.current].cpu().numpy()[:, :W], length)
+        assert same(out.cpu().numpy(), want), f"frame {i}: " + differs(out.cpu().numpy(), want)
+        assert same(dn.accum[dn.current].cpu().numpy(), accum) and same(dn.length[dn.current].cpu().numpy()[:, :W], length)
         assert info["history"].sum() == (0 if first else info["ok"].sum())
         assert float(length.max()) == (1 if first else i + 1)
         previous_depth = depth
-
-
-def _host_program(tmp_path):
-    import subprocess
-    built = os.path.join(ROOT, "tests", "cpp", "host_rt_denoise")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_rt_denoise.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_rt_denoise"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
 
 
 @pytest.mark.parametrize("passes", [3, 0])
@@ -366,7 +326,7 @@ def test_four_frames_through_the_cpp_facade(tmp_path, passes):
         f.write(np.array([len(frames), passes], np.uint32).tobytes())
         for w, h, jitter, noisy, depth, normals, mv in frames:
             f.write(np.array([w, h], np.uint32).tobytes() + np.array(jitter, f32).tobytes() + noisy.tobytes() + depth.tobytes() + normals.tobytes() + mv.tobytes())
-    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    subprocess.check_call([host_program("host_rt_denoise", tmp_path), str(inp), str(outp)], timeout=120)
     blob = open(outp, "rb").read()
     at = 0
     accum = length = previous_depth = None
@@ -380,7 +340,7 @@ def test_four_frames_through_the_cpp_facade(tmp_path, passes):
         settings = dict(passes=passes, jitter=tuple(view.jitter), previous_jitter=tuple(view.jitter) if first else tuple(view.previous_jitter),
                         flags=ref.HISTORY_INVALID if first else 0)
         accum, length, want, info = ref.denoise_ex(noisy, depth, normals, mv, previous_depth, accum, length, ref.View(view), settings)
-        assert _same(facade, want), f"frame {i}: " + _differs(facade, want)
+        assert same(facade, want), f"frame {i}: " + differs(facade, want)
         assert info["history"].sum() == (0 if first else info["ok"].sum()) and info["ok"].mean() > 0.5
         previous_depth = depth
     assert at == len(blob)
@@ -426,8 +386,8 @@ def test_atrium_rtao_denoised_over_sixteen_frames_then_lpv_lighting(hip_ctx):
         torch.cuda.synchronize()
         accum, length, want, info = ref.denoise_ex(raw, depth, normals, mv, depth, accum, length, rview, dict(flags=0 if i else ref.HISTORY_INVALID))
         got = out.cpu().numpy()
-        assert _same(got, want), f"frame {i}: " + _differs(got, want)
-        assert _same(dn.accum[dn.current].cpu().numpy(), accum) and _same(dn.length[dn.current].cpu().numpy()[:, :W], length)
+        assert same(got, want), f"frame {i}: " + differs(got, want)
+        assert same(dn.accum[dn.current].cpu().numpy(), accum) and same(dn.length[dn.current].cpu().numpy()[:, :W], length)
         assert (length[info["ok"]] <= i + 1).all() and (length[info["ok"]] == i + 1).mean() > 0.99  # (a tap across an edge may be rejected)
     covered = info["ok"]
     converged = np.zeros((H, W), np.float64)

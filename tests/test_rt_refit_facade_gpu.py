@@ -10,6 +10,7 @@ import pytest
 
 from androidrenderer_amd import mesh, synth
 from tests import rt_structure_scenes as scenes
+from tests.host_programs import host_program
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,17 +21,6 @@ def _time_limit():
     faulthandler.dump_traceback_later(300, exit=True)  # an overrun ends the process
     yield
     faulthandler.cancel_dump_traceback_later()
-
-
-def _host_program(tmp_path):
-    built = os.path.join(ROOT, "tests", "cpp", "host_rt_refit")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_rt_refit.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_rt_refit"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
 
 
 def test_a_moved_primitive_through_the_cpp_facade(tmp_path):
@@ -46,7 +36,7 @@ def test_a_moved_primitive_through_the_cpp_facade(tmp_path):
             f.write(np.ascontiguousarray(arrays[k]).tobytes())
         f.write(noise.tobytes())
         f.write(np.ascontiguousarray(model, np.float32).tobytes())
-    exe = _host_program(tmp_path)
+    exe = host_program("host_rt_refit", tmp_path)
     out = {mode: subprocess.run([exe, str(inp), mode], check=True, timeout=120, capture_output=True, text=True).stdout.splitlines() for mode in ("refit", "rebuild")}
     assert len(out["refit"]) == len(out["rebuild"]) == 2
     assert out["refit"][0] == out["rebuild"][0] and out["refit"][0].startswith("frame 0 Build TLAS depth ")

@@ -11,6 +11,7 @@ from tests import rt_structure_scenes as scenes
 from tests.rt_refit_check import check_refit, moved
 from tests.rt_structure_check import _bits
 from tests.test_rt import RtCase, _probe_ids
+from tests.support import side_stream_context
 
 W, H, PROBES = 32, 18, 6
 
@@ -256,10 +257,7 @@ def test_on_a_side_stream_without_host_sync_and_under_capture():
     b1, b2 = _case(moved(scenes.soup(1025), seed=1), a), _case(moved(scenes.soup(1025), seed=2), a)
     want1, want2 = b1.oracle_rtao(1, 4.0), b2.oracle_rtao(1, 4.0)
     assert want1.tobytes() != want2.tobytes()
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
-    try:
-        ctx.set_stream(s.cuda_stream)
+    with side_stream_context() as (ctx, s):
         dv = b1.device()  # b1's models and topology; its positions are what gets overwritten
         positions = dv["keep"][0]
         assert positions.numel() == b1.arrays["positions"].nbytes and positions.data_ptr() == dv["geo"].vertex_positions
@@ -285,6 +283,3 @@ def test_on_a_side_stream_without_host_sync_and_under_capture():
             graph.replay()
             torch.cuda.synchronize()
             assert out.cpu().numpy().tobytes() == want.tobytes()
-    finally:
-        torch.cuda.synchronize()
-        ctx.close()

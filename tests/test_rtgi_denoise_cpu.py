@@ -15,6 +15,7 @@ import pytest
 from androidrenderer_amd import _abi, lib
 from tests import rt_denoise_ref as mask_ref
 from tests import rtgi_denoise_ref as ref
+from tests import support
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -180,12 +181,9 @@ def test_every_refusal_of_the_header_on_a_context_without_a_device():
     """A malformed call answers its status; a well-formed one gets as far as selecting the device, which a detached context does not have
     (SAH_ERR_HIP) — so nothing is launched and the made-up addresses are never used."""
     L = lib.load()
-    L.sah_debug_create_detached.argtypes = [C.POINTER(C.c_void_p)]
-    h = C.c_void_p()
-    rc = L.sah_debug_create_detached(C.byref(h))
-    if rc == _abi.SAH_ERR_UNSUPPORTED:
+    h = lib.create_detached()
+    if h is None:
         pytest.skip("a HIP device is present (made-up addresses must not reach a GPU); tests/test_rtgi_denoise_gpu.py checks the refusals there")
-    assert rc == 0 and h.value
     ref_of = lambda a: None if a is None else C.byref(a)  # noqa: E731
     n = 0
     try:
@@ -203,14 +201,8 @@ def test_every_refusal_of_the_header_on_a_context_without_a_device():
 @pytest.mark.parametrize("seed", [11, 12])
 def test_argument_fuzz_in_a_child_process(seed):
     """random bits in every argument (tests/rtgi_denoise_fuzz_child.py): every call comes back with a sah_status and the process survives"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "rtgi_denoise_fuzz_child.py"), str(seed), "2000"], stdout=subprocess.PIPE,
-                       stderr=subprocess.STDOUT, text=True, timeout=600)
-    tail = "\n".join(r.stdout.splitlines()[-10:])
-    if "SKIP:" in r.stdout:
-        pytest.skip(r.stdout.strip().splitlines()[-1])
-    assert r.returncode == 0, f"the fuzz child ended with code {r.returncode}:\n{tail}"
-    assert "OK: 2000 iterations" in r.stdout, tail
-    assert " ok:" not in r.stdout and "invalid_argument:" in r.stdout and "hip:" in r.stdout  # (a detached context never launches; well-formed calls get as far as the device)
+    stdout = support.run_fuzz_child("rtgi_denoise_fuzz_child.py", seed, 2000)
+    assert " ok:" not in stdout and "invalid_argument:" in stdout and "hip:" in stdout  # (a detached context never launches; well-formed calls get as far as the device)
 
 
 # ---- the fixture ------------------------------------------------------------------------------------------------------------------------------

@@ -12,7 +12,8 @@ import pytest
 from androidrenderer_amd import _abi, frame, lib, scene
 from tests import rtgi_denoise_ref as ref
 from tests import util
-from tests.test_vrsaa_gpu import SENTINEL, Image
+from tests.host_programs import host_program
+from tests.support import context_state, differs, Image, reprojection_view_data_of, retyped, same, SENTINEL, side_stream_context
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,16 +42,6 @@ def _time_limit():
 @pytest.fixture(scope="module")
 def fixture():
     return dict(np.load(gen.FIXTURE))
-
-
-def view_data_of(view):
-    """an _abi.ViewData holding what the pass reads, from a rtgi_denoise_ref.View"""
-    v = _abi.ViewData()
-    for i in range(16):
-        v.inverse_view[i], v.last_frame_view[i] = float(view.inverse_view[i]), float(view.last_frame_view[i])
-    v.projection[0], v.projection[5], v.projection[8], v.projection[9], v.z_near = float(view.p00), float(view.p11), float(view.p20), float(view.p21), float(view.z_near)
-    v.projection[11] = -1.0
-    return v
 
 
 def moved_view(w, h, dolly=0.05, jitter=(0.3, -0.2)):
@@ -104,19 +95,9 @@ class Planes:
         return tuple(self.images[n].texels(OUT_SHAPE[n][0]).reshape(self.h, self.w, OUT_SHAPE[n][1]) for n, _ in OUTPUTS)
 
 
-def _differs(got, want):
-    as_bytes = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(a.shape[:2] + (-1,))  # noqa: E731
-    bad = (as_bytes(got) != as_bytes(want)).any(-1)
-    return f"{int(bad.sum())} of {bad.size} texels differ, first (y, x) at {np.argwhere(bad)[:4].tolist()}"
-
-
-def _same(got, want):
-    return np.ascontiguousarray(got).tobytes() == np.ascontiguousarray(want).tobytes()
-
-
 def assert_outputs(got, want, what=""):
     for (name, _), g, w in zip(OUTPUTS, got, want):
-        assert _same(g, w), f"{what} {name}: " + _differs(g, w)
+        assert same(g, w), f"{what} {name}: " + differs(g, w)
 
 
 def reference(inputs, view, settings):
@@ -130,7 +111,7 @@ def fixture_want(fx, i, passes):
     ok, _, _, N, _ = ref.surfaces(inputs["depth"], inputs["normals"], gen.view(i))
     drb = ref.pack(inputs["ray_buffer"], inputs["ray_irradiance"], ok, N, np.zeros(ok.shape + (3,), f32))[0]
     if i == 0:
-        assert _same(drb, fx["denoised_ray_buffer0"])
+        assert same(drb, fx["denoised_ray_buffer0"])
     return fx[f"accum{i}"], fx[f"moments{i}"], drb, fx[f"denoised_irradiance{i}_passes{passes}"]
 
 
@@ -138,7 +119,7 @@ def fixture_want(fx, i, passes):
 @pytest.mark.parametrize("passes", [0, 1, 2, 3])
 def test_fixture_bit_for_bit_and_repeatable(hip_ctx, fixture, passes):
     for i in range(gen.FRAMES):
-        inputs, view, params = gen.frame_of(fixture, i), view_data_of(gen.view(i)), _params(**gen.params(i, passes))
+        inputs, view, params = gen.frame_of(fixture, i), reprojection_view_data_of(gen.view(i)), _params(**gen.params(i, passes))
         got = Planes(inputs).run(hip_ctx, view, params)
         assert_outputs(got, fixture_want(fixture, i, passes), f"frame {i}")
         assert_outputs(Planes(inputs).run(hip_ctx, view, params), got, f"frame {i} again")
@@ -181,7 +162,7 @@ LAYOUTS = {"dwords: nothing 16-byte aligned": _layout(4, 4),
 def test_pitches_offsets_sentinels_and_inputs(hip_ctx, fixture, layout, passes):
     for i in (0, 1):
         p = Planes(gen.frame_of(fixture, i), LAYOUTS[layout])
-        got = p.run(hip_ctx, view_data_of(gen.view(i)), _params(**gen.params(i, passes)))  # (asserts the inputs unchanged)
+        got = p.run(hip_ctx, reprojection_view_data_of(gen.view(i)), _params(**gen.params(i, passes)))  # (asserts the inputs unchanged)
         assert_outputs(got, fixture_want(fixture, i, passes), f"frame {i}")
         assert all(p.images[n].padding_intact() for n, _ in OUTPUTS)
 
@@ -190,7 +171,7 @@ def test_pitches_offsets_sentinels_and_inputs(hip_ctx, fixture, layout, passes):
 @pytest.mark.parametrize("passes", [0, 1, 3])
 def test_row_bands_write_their_rows_and_nothing_else(hip_ctx, fixture, passes):
     W, H = gen.WIDTH, gen.HEIGHT
-    view, params = view_data_of(gen.view(1)), _params(**gen.params(1, passes))
+    view, params = reprojection_view_data_of(gen.view(1)), _params(**gen.params(1, passes))
     whole = fixture_want(fixture, 1, passes)
     assembled = [np.full((H, W, c * np.dtype(t).itemsize), SENTINEL, np.uint8).view(t) for t, c in (OUT_SHAPE[n] for n, _ in OUTPUTS)]
     for rows in ((9, 10), (0, 9), (10, H), (17, 19), (5, 5), (0, 1), (H - 1, H)):
@@ -199,7 +180,7 @@ def test_row_bands_write_their_rows_and_nothing_else(hip_ctx, fixture, passes):
         wide = ref.band_rows(rows, H, passes)
         for k, (name, _) in enumerate(OUTPUTS):
             r = rows if name.startswith("denoised") else wide
-            assert _same(got[k][r[0]:r[1]], whole[k][r[0]:r[1]]), f"{rows} {name}: " + _differs(got[k][r[0]:r[1]], whole[k][r[0]:r[1]])
+            assert same(got[k][r[0]:r[1]], whole[k][r[0]:r[1]]), f"{rows} {name}: " + differs(got[k][r[0]:r[1]], whole[k][r[0]:r[1]])
             assert p.images[name].padding_intact(r), f"{rows}: {name} changed outside rows {r}"
             assembled[k][r[0]:r[1]] = got[k][r[0]:r[1]]
     assert_outputs(assembled, whole, "assembled")
@@ -209,27 +190,24 @@ def test_row_bands_write_their_rows_and_nothing_else(hip_ctx, fixture, passes):
 def test_refusals_launch_nothing(hip_ctx, fixture):
     import torch
     p = Planes(gen.frame_of(fixture, 1))
-    view, ok = view_data_of(gen.view(1)), _params(**gen.params(1, 3))
+    view, ok = reprojection_view_data_of(gen.view(1)), _params(**gen.params(1, 3))
     pl = {n: im.plane for n, im in p.images.items()}
-
-    def retyped(name, fmt):
-        return _abi.Plane(pl[name].ptr, pl[name].width, pl[name].height, pl[name].row_pitch_bytes, fmt)
 
     def shaped(name, **kw):
         q = _abi.Plane(pl[name].ptr, pl[name].width, pl[name].height, pl[name].row_pitch_bytes, pl[name].format)
         for k, v in kw.items():
             setattr(q, k, v)
         return q
-    bad_view = view_data_of(gen.view(1))
+    bad_view = reprojection_view_data_of(gen.view(1))
     bad_view.z_near = float("nan")
-    nan_view = view_data_of(gen.view(1))
+    nan_view = reprojection_view_data_of(gen.view(1))
     nan_view.last_frame_view[10] = float("nan")
-    zero_view = view_data_of(gen.view(1))
+    zero_view = reprojection_view_data_of(gen.view(1))
     zero_view.z_near = 0.0
     INVALID, FORMAT = _abi.SAH_ERR_INVALID_ARGUMENT, _abi.SAH_ERR_UNSUPPORTED_FORMAT
     P = lambda **kw: _params(**dict(gen.params(1, 3), **kw))  # noqa: E731
     inf, nan = float("inf"), float("nan")
-    cases = [((view, p.desc(**{n: retyped(n, D32 if f != D32 else _abi.FORMAT_R32_SFLOAT)}), ok), FORMAT) for n, f in INPUTS + OUTPUTS]
+    cases = [((view, p.desc(**{n: retyped(pl[n], D32 if f != D32 else _abi.FORMAT_R32_SFLOAT)}), ok), FORMAT) for n, f in INPUTS + OUTPUTS]
     cases += [((view, p.desc(**{n: None}), ok), INVALID) for n in NAMES]  # a previous-frame plane may be NULL only with the flag
     cases += [((view, p.desc(), ok, (0, 22)), INVALID), ((view, p.desc(), ok, (9, 3)), INVALID),
               ((view, p.desc(), P(flags=2)), INVALID), ((view, p.desc(), P(flags=3)), INVALID),
@@ -262,7 +240,7 @@ def test_refusals_launch_nothing(hip_ctx, fixture):
 def test_history_invalid_flag_excuses_the_previous_planes(hip_ctx, fixture):
     inputs = gen.frame_of(fixture, 1)
     params = _params(**dict(gen.params(1, 3), flags=_abi.RTGI_DENOISE_HISTORY_INVALID))
-    view = view_data_of(gen.view(1))
+    view = reprojection_view_data_of(gen.view(1))
     cut = dict(inputs, previous_depth=None, history=None, history_moments=None)
     without = Planes(cut)
     assert set(without.images) == set(NAMES) - set(PREVIOUS)
@@ -278,20 +256,17 @@ def test_history_invalid_flag_excuses_the_previous_planes(hip_ctx, fixture):
 
 def test_side_stream_captured_graph_replayed_twice_and_no_side_effects(fixture):
     import torch
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
-    try:
-        ctx.set_stream(s.cuda_stream)
-        view, params = view_data_of(gen.view(1)), _params(**gen.params(1, 3))
+    with side_stream_context() as (ctx, s):
+        view, params = reprojection_view_data_of(gen.view(1)), _params(**gen.params(1, 3))
         a = Planes(gen.frame_of(fixture, 1))
         desc = a.desc()
-        state = (ctx.cache_epoch(), ctx.lighting_dispatch(), ctx.copy_rebuilds())
+        state = context_state(ctx)
         torch.cuda.synchronize()
         with torch.cuda.stream(s):
             ctx.rtgi_denoise(view, desc, params)
         s.synchronize()
         assert_outputs(a.outputs(), fixture_want(fixture, 1, 3))
-        assert (ctx.cache_epoch(), ctx.lighting_dispatch(), ctx.copy_rebuilds()) == state
+        assert context_state(ctx) == state
         # one captured graph (temporal, then filter: a linear chain), replayed twice over other input contents
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=s):
@@ -309,10 +284,7 @@ def test_side_stream_captured_graph_replayed_twice_and_no_side_effects(fixture):
             want = ref.denoise_ex(*[inputs[k] for k in ORDER], gen.view(1), gen.params(1, 3))
             assert_outputs(a.outputs(), want[:4], f"replay with seed {seed}")
             assert want[4]["history"].sum() > 200
-        assert (ctx.cache_epoch(), ctx.lighting_dispatch(), ctx.copy_rebuilds()) == state
-    finally:
-        torch.cuda.synchronize()
-        ctx.close()
+        assert context_state(ctx) == state
 
 
 # ---- wrappers -----------------------------------------------------------------------------------------------------------------------------------
@@ -355,25 +327,13 @@ def test_four_frames_through_the_python_wrapper(hip_ctx):
                         flags=ref.HISTORY_INVALID if first else 0)
         accum, moments, drb, dirr, info = ref.denoise_ex(rays, irr, depth, normals, mv, previous_depth, accum, moments, ref.View(view), settings)
         got = [t.cpu().numpy().view(np.uint16) for t in out]
-        assert _same(got[0], drb), f"frame {i} ray buffer: " + _differs(got[0], drb)
-        assert _same(got[1], dirr), f"frame {i} irradiance: " + _differs(got[1], dirr)
-        assert _same(dn.accum[dn.current].cpu().numpy(), accum) and _same(dn.moments[dn.current].cpu().numpy(), moments)
+        assert same(got[0], drb), f"frame {i} ray buffer: " + differs(got[0], drb)
+        assert same(got[1], dirr), f"frame {i} irradiance: " + differs(got[1], dirr)
+        assert same(dn.accum[dn.current].cpu().numpy(), accum) and same(dn.moments[dn.current].cpu().numpy(), moments)
         assert info["history"].sum() == (0 if first else info["ok"].sum())
         assert float(accum[..., 3].max()) == (1 if first else i + 1)
         assert info["filter"][0]["luminance_active"].any() == (i in (2, 3))  # min_history = 3
         previous_depth = depth
-
-
-def _host_program(tmp_path):
-    import subprocess
-    built = os.path.join(ROOT, "tests", "cpp", "host_rtgi_denoise")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_rt_denoise.h", "sah_rtgi_denoise.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_rtgi_denoise"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
 
 
 @pytest.mark.parametrize("passes", [3, 0])
@@ -388,7 +348,7 @@ def test_four_frames_through_the_cpp_facade(tmp_path, passes):
         f.write(np.array([len(frames), passes], np.uint32).tobytes())
         for w, h, jitter, rays, irr, depth, normals, mv in frames:
             f.write(np.array([w, h], np.uint32).tobytes() + np.array(jitter, f32).tobytes() + rays.tobytes() + irr.tobytes() + depth.tobytes() + normals.tobytes() + mv.tobytes())
-    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    subprocess.check_call([host_program("host_rtgi_denoise", tmp_path), str(inp), str(outp)], timeout=120)
     blob = open(outp, "rb").read()
     at = 0
     accum = moments = previous_depth = None
@@ -403,8 +363,8 @@ def test_four_frames_through_the_cpp_facade(tmp_path, passes):
         settings = dict(passes=passes, jitter=tuple(view.jitter), previous_jitter=tuple(view.jitter) if first else tuple(view.previous_jitter),
                         flags=ref.HISTORY_INVALID if first else 0)
         accum, moments, drb, dirr, info = ref.denoise_ex(rays, irr, depth, normals, mv, previous_depth, accum, moments, ref.View(view), settings)
-        assert _same(got_rb, drb), f"frame {i} ray buffer: " + _differs(got_rb, drb)
-        assert _same(got_ir, dirr), f"frame {i} irradiance: " + _differs(got_ir, dirr)
+        assert same(got_rb, drb), f"frame {i} ray buffer: " + differs(got_rb, drb)
+        assert same(got_ir, dirr), f"frame {i} irradiance: " + differs(got_ir, dirr)
         assert info["history"].sum() == (0 if first else info["ok"].sum()) and info["ok"].mean() > 0.5
         previous_depth = depth
     assert at == len(blob)
@@ -448,9 +408,9 @@ def test_atrium_rtgi_denoised_over_sixteen_frames_then_rtgi_lighting(hip_ctx):
         torch.cuda.synchronize()
         accum, moments, drb, dirr, info = ref.denoise_ex(rb, ri, depth, normals, mv, depth, accum, moments, rview, dict(flags=0 if i else ref.HISTORY_INVALID))
         got = [t.cpu().numpy().view(np.uint16) for t in out]
-        assert _same(got[0], drb), f"frame {i} ray buffer: " + _differs(got[0], drb)
-        assert _same(got[1], dirr), f"frame {i} irradiance: " + _differs(got[1], dirr)
-        assert _same(dn.accum[dn.current].cpu().numpy(), accum) and _same(dn.moments[dn.current].cpu().numpy(), moments)
+        assert same(got[0], drb), f"frame {i} ray buffer: " + differs(got[0], drb)
+        assert same(got[1], dirr), f"frame {i} irradiance: " + differs(got[1], dirr)
+        assert same(dn.accum[dn.current].cpu().numpy(), accum) and same(dn.moments[dn.current].cpu().numpy(), moments)
         n = accum[..., 3][info["ok"]]
         # (the rasteriser's motion vectors are its rounding, not 0: up to four taps, whose weighted mean of equal counts rounds; a tap across an
         # edge may be rejected)

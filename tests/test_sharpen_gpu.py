@@ -15,7 +15,8 @@ from androidrenderer_amd import _abi, frame, lib
 from tests import layouts
 from tests import sharpen_ref as ref
 from tests import util
-from tests.test_vrsaa_gpu import SENTINEL, Image
+from tests.host_programs import host_program
+from tests.support import context_state, differs, hip_runtime, Image, retyped, SENTINEL, side_stream_context
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -62,11 +63,6 @@ def _texels(img):
     return img.texels(np.uint16).reshape(img.h, img.w, 4)
 
 
-def _differs(got, want):
-    bad = (got != want).reshape(got.shape[0], got.shape[1], -1).any(-1)
-    return f"{int(bad.sum())} of {bad.size} pixels differ, first at {np.argwhere(bad)[:4].tolist()}"
-
-
 def _check(ctx, scene_np, settings=None, exposure=None, pitches=(None, None), offsets=(0, 0), rows=(0, 0)):
     """one call against the restatement: the rows of the band, the rows outside it, the guard bytes, the inputs; returns the texels of out"""
     import torch
@@ -78,7 +74,7 @@ def _check(ctx, scene_np, settings=None, exposure=None, pitches=(None, None), of
     torch.cuda.synchronize()
     got = _texels(out_img)
     want = ref.sharpen(scene_np, exposure, settings, rows, out=np.full(scene_np.shape, PATTERN, np.uint16))
-    assert got.tobytes() == want.tobytes(), f"{w} x {h}, {settings}, exposure {exposure}, rows {rows}: " + _differs(got, want)
+    assert got.tobytes() == want.tobytes(), f"{w} x {h}, {settings}, exposure {exposure}, rows {rows}: " + differs(got, want)
     assert out_img.padding_intact(ref_rows(rows, h)), "bytes outside the band's texels changed"
     assert scene_img.unchanged() and state.unchanged()
     return got
@@ -92,7 +88,7 @@ def ref_rows(rows, h):
 def test_fixture_bit_for_bit_and_repeatable(hip_ctx, fixture):
     for (exposure, settings), want in zip(gen.CASES, fixture["sharpened"]):
         got = _check(hip_ctx, fixture["scene"], settings, exposure)
-        assert got.tobytes() == want.tobytes(), f"{settings}, exposure {exposure}: " + _differs(got, want)
+        assert got.tobytes() == want.tobytes(), f"{settings}, exposure {exposure}: " + differs(got, want)
         assert _check(hip_ctx, fixture["scene"], settings, exposure).tobytes() == got.tobytes()
 
 
@@ -141,7 +137,7 @@ def test_layout_helpers_padded_planes_equal_the_tight_run(hip_ctx, spec):
         layouts.assert_padding_intact(scene_p, out_p, what=f"sharpen {layout}")
         layouts.assert_inputs_unchanged(scene_p, what=f"sharpen {layout}")
         results.append(out_p.read(np.uint16))
-    assert results[1].tobytes() == want.tobytes(), _differs(results[1], want)
+    assert results[1].tobytes() == want.tobytes(), differs(results[1], want)
     assert results[0].tobytes() == results[1].tobytes()
 
 
@@ -226,27 +222,17 @@ def test_unclean_texels_at_a_corner_an_edge_inside_and_on_a_tile_seam(hip_ctx, b
 
 
 # ---- stream capture -------------------------------------------------------------------------------------------------------------------------------
-def _hip_runtime():
-    """the HIP runtime this process already uses (the one the stream and the library live in)"""
-    paths = sorted({line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line})
-    assert len(paths) == 1, paths
-    return C.CDLL(paths[0])
-
-
 def test_captured_call_is_one_kernel_node_and_replays_to_the_same_bytes(fixture):
     import torch
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
-    try:
-        ctx.set_stream(s.cuda_stream)
+    with side_stream_context() as (ctx, s):
         W, H = gen.WIDTH, gen.HEIGHT
         exposure, settings = gen.CASES[3]
         params = _abi.SharpenParams.default(**settings)
         scene_img, out_img, state = Image(RGBA16F, W, H, None, fixture["scene"]), Image(RGBA16F, W, H), State(exposure)
-        before = (ctx.cache_epoch(), ctx.lighting_dispatch(), ctx.copy_rebuilds())
+        before = context_state(ctx)
         torch.cuda.synchronize()
         # the structure of what one call records: a single kernel node, no edges
-        hip = _hip_runtime()
+        hip = hip_runtime()
         stream, graph = C.c_void_p(s.cuda_stream), C.c_void_p()
         assert hip.hipStreamBeginCapture(stream, 1) == 0  # hipStreamCaptureModeThreadLocal
         try:
@@ -278,12 +264,9 @@ def test_captured_call_is_one_kernel_node_and_replays_to_the_same_bytes(fixture)
             replayed.replay()
             torch.cuda.synchronize()
             want = ref.sharpen(other, exposure, settings)
-            assert _texels(out_img).tobytes() == want.tobytes(), f"replay with seed {seed}: " + _differs(_texels(out_img), want)
+            assert _texels(out_img).tobytes() == want.tobytes(), f"replay with seed {seed}: " + differs(_texels(out_img), want)
             assert out_img.padding_intact() and state.unchanged()
-        assert (ctx.cache_epoch(), ctx.lighting_dispatch(), ctx.copy_rebuilds()) == before
-    finally:
-        torch.cuda.synchronize()
-        ctx.close()
+        assert context_state(ctx) == before
 
 
 # ---- refusals -------------------------------------------------------------------------------------------------------------------------------------
@@ -295,9 +278,6 @@ def test_refusals_launch_nothing(hip_ctx, fixture):
     scene_img, out_img, state = Image(RGBA16F, W, H, None, fixture["scene"]), Image(RGBA16F, W, H), State(0.5)
     sc, out, st = scene_img.plane, out_img.plane, state.ptr
     P = _abi.SharpenParams.default
-
-    def retyped(plane, fmt):
-        return _abi.Plane(plane.ptr, plane.width, plane.height, plane.row_pitch_bytes, fmt)
 
     def reshaped(plane, **kw):
         a = dict(ptr=plane.ptr, width=plane.width, height=plane.height, row_pitch_bytes=plane.row_pitch_bytes)
@@ -358,21 +338,10 @@ def test_frames_of_two_extents_through_the_python_wrapper(hip_ctx):
         torch.cuda.synchronize()
         assert out is sharpener.sharpened and tuple(out.shape) == sc.shape
         got, want = out.cpu().numpy().view(np.uint16), ref.sharpen(sc, exposure, settings)
-        assert got.tobytes() == want.tobytes(), _differs(got, want)
+        assert got.tobytes() == want.tobytes(), differs(got, want)
         planes.append(out)
     assert planes[0] is not planes[1] and planes[1] is planes[2]  # re-created for another extent, kept while it stays
     assert frame.Sharpener(hip_ctx, 8, 8, sharpness=0.5, flags=1).params.flags == 1
-
-
-def _host_program(tmp_path):
-    built = os.path.join(ROOT, "tests", "cpp", "host_sharpen")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_exposure.h", "sah_sharpen.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_sharpen"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
 
 
 def test_frames_of_two_extents_through_the_cpp_facade(tmp_path):
@@ -385,12 +354,12 @@ def test_frames_of_two_extents_through_the_cpp_facade(tmp_path):
             assert 2.0 ** -st == settings["sharpness"]
             f.write(np.array([sc.shape[1], sc.shape[0], settings["flags"] & ref.DENOISE, exposure is not None], np.uint32).tobytes())
             f.write(np.array([st, settings["pre_scale"], exposure or 0.0], f32).tobytes() + sc.tobytes())
-    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    subprocess.check_call([host_program("host_sharpen", tmp_path), str(inp), str(outp)], timeout=120)
     blob = open(outp, "rb").read()
     at = 0
     for i, (sc, settings, exposure) in enumerate(zip(frames, FRAME_SETTINGS, FRAME_EXPOSURES)):
         got = np.frombuffer(blob[at:at + sc.nbytes], np.uint16).reshape(sc.shape)
         at += sc.nbytes
         want = ref.sharpen(sc, exposure, settings)
-        assert got.tobytes() == want.tobytes(), f"frame {i}: " + _differs(got, want)
+        assert got.tobytes() == want.tobytes(), f"frame {i}: " + differs(got, want)
     assert at == len(blob)

@@ -13,7 +13,8 @@ import pytest
 from androidrenderer_amd import _abi, frame, lib, mesh, scene
 from tests import ssao_ref as ref
 from tests import util
-from tests.test_vrsaa_gpu import SENTINEL, Image
+from tests.host_programs import host_program
+from tests.support import context_state, differs, Image, retyped, same, SENTINEL, side_stream_context, view_data_of
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,16 +38,6 @@ def fixture():
     fx = np.load(gen.FIXTURE)
     return {"depth": np.ascontiguousarray(fx["depth_plane"][:, :gen.WIDTH]), "normals": np.ascontiguousarray(fx["normals_plane"][:, :gen.WIDTH]),
             "ao": [fx[f"ao_blur{b}"] for b in (0, 1, 2)]}
-
-
-def view_data_of(view):
-    """an _abi.ViewData holding what the pass reads, from a ssao_ref.View"""
-    v = _abi.ViewData()
-    for i in range(16):
-        v.view[i] = float(view.view[i])
-    v.projection[0], v.projection[5], v.projection[8], v.projection[9], v.z_near = float(view.p00), float(view.p11), float(view.p20), float(view.p21), float(view.z_near)
-    v.projection[11] = -1.0
-    return v
 
 
 def scene_view(w, h, jitter=(0.3, -0.2)):
@@ -79,28 +70,19 @@ class Planes:
         return self.out.texels(f32).reshape(self.h, self.w)
 
 
-def _differs(got, want):
-    bad = got.view(np.uint32) != want.view(np.uint32)
-    return f"{int(bad.sum())} of {bad.size} texels differ, first (y, x) at {np.argwhere(bad)[:4].tolist()}"
-
-
-def _same(got, want):
-    return got.tobytes() == want.tobytes()
-
-
 # ---- the fixture --------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("passes", [0, 1, 2])
 def test_fixture_bit_for_bit_and_repeatable(hip_ctx, fixture, passes):
     view, params = view_data_of(gen.view()), _params(**dict(gen.PARAMS, blur_passes=passes))
     p = Planes(fixture["depth"], fixture["normals"])
     got = p.run(hip_ctx, view, params)
-    assert _same(got, fixture["ao"][passes]), _differs(got, fixture["ao"][passes])
+    assert same(got, fixture["ao"][passes]), differs(got, fixture["ao"][passes])
     if passes:
-        assert _same(p.scratch.texels(f32).reshape(p.h, p.w), fixture["ao"][0])  # the scratch plane is the raw result
+        assert same(p.scratch.texels(f32).reshape(p.h, p.w), fixture["ao"][0])  # the scratch plane is the raw result
     else:
-        assert p.scratch.unchanged() and _same(Planes(fixture["depth"], fixture["normals"]).run(hip_ctx, view, params, scratch=False), got)
+        assert p.scratch.unchanged() and same(Planes(fixture["depth"], fixture["normals"]).run(hip_ctx, view, params, scratch=False), got)
     again = Planes(fixture["depth"], fixture["normals"]).run(hip_ctx, view, params)
-    assert _same(again, got)
+    assert same(again, got)
 
 
 # ---- extents --------------------------------------------------------------------------------------------------------------------------------
@@ -117,7 +99,7 @@ def test_extents_and_radius_caps(hip_ctx, extent, passes):
         settings = dict(radius=1.5, max_radius_pixels=cap, blur_passes=passes, fade_out_from=3.0, fade_out_to=9.0)
         got = p.run(hip_ctx, view, _params(**settings))
         want, info = ref.ssao_ex(depth, normals, ref.View(view), settings)
-        assert _same(got, want), f"max_radius_pixels {cap}: " + _differs(got, want)
+        assert same(got, want), f"max_radius_pixels {cap}: " + differs(got, want)
         darkened += int((want < 1).sum())
         if w * h >= 64 and cap > 2:
             assert (info["r_px"][info["live"]] > 2).any()
@@ -135,9 +117,9 @@ def test_extents_and_radius_caps(hip_ctx, extent, passes):
 def test_pitches_offsets_sentinels_and_inputs(hip_ctx, fixture, pitches, offsets, passes):
     p = Planes(fixture["depth"], fixture["normals"], pitches, offsets)
     got = p.run(hip_ctx, view_data_of(gen.view()), _params(**dict(gen.PARAMS, blur_passes=passes)))  # (asserts the inputs unchanged)
-    assert _same(got, fixture["ao"][passes]), _differs(got, fixture["ao"][passes])
+    assert same(got, fixture["ao"][passes]), differs(got, fixture["ao"][passes])
     assert p.out.padding_intact() and p.scratch.padding_intact()
-    assert p.scratch.unchanged() if passes == 0 else _same(p.scratch.texels(f32).reshape(p.h, p.w), fixture["ao"][0])
+    assert p.scratch.unchanged() if passes == 0 else same(p.scratch.texels(f32).reshape(p.h, p.w), fixture["ao"][0])
 
 
 # ---- row bands --------------------------------------------------------------------------------------------------------------------------------
@@ -150,13 +132,13 @@ def test_row_bands_write_their_rows_and_nothing_else(hip_ctx, fixture, passes):
     for rows in ((9, 10), (0, 9), (10, H), (17, 19), (5, 5), (0, 0 + 1), (H - 1, H)):
         p = Planes(fixture["depth"], fixture["normals"], (None, None, 69 * 4 + 12, 69 * 4 + 28))
         got = p.run(hip_ctx, view, params, rows)
-        assert _same(got[rows[0]:rows[1]], whole[rows[0]:rows[1]]), f"{rows}: " + _differs(got[rows[0]:rows[1]], whole[rows[0]:rows[1]])
+        assert same(got[rows[0]:rows[1]], whole[rows[0]:rows[1]]), f"{rows}: " + differs(got[rows[0]:rows[1]], whole[rows[0]:rows[1]])
         assert p.out.padding_intact(rows), f"{rows}: ao_out changed outside the band"
         raw_rows = ref.band_rows(rows, H, passes) if passes else (0, 0)  # the rows of scratch the header names
         assert p.scratch.padding_intact(raw_rows), f"{rows}: scratch changed outside rows {raw_rows}"
-        assert _same(p.scratch.texels(f32).reshape(H, W)[raw_rows[0]:raw_rows[1]], fixture["ao"][0][raw_rows[0]:raw_rows[1]])
+        assert same(p.scratch.texels(f32).reshape(H, W)[raw_rows[0]:raw_rows[1]], fixture["ao"][0][raw_rows[0]:raw_rows[1]])
         assembled[rows[0]:rows[1]] = got[rows[0]:rows[1]]
-    assert _same(assembled, whole)
+    assert same(assembled, whole)
 
 
 # ---- the call contract ----------------------------------------------------------------------------------------------------------------------
@@ -167,8 +149,6 @@ def test_refusals_launch_nothing(hip_ctx, fixture):
     view, ok = view_data_of(gen.view()), _params(**gen.PARAMS)
     depth, normals, scratch, out = p.depth.plane, p.normals.plane, p.scratch.plane, p.out.plane
 
-    def retyped(plane, fmt):
-        return _abi.Plane(plane.ptr, plane.width, plane.height, plane.row_pitch_bytes, fmt)
     bad_view = view_data_of(gen.view())
     bad_view.z_near = float("nan")
     INVALID, FORMAT = _abi.SAH_ERR_INVALID_ARGUMENT, _abi.SAH_ERR_UNSUPPORTED_FORMAT
@@ -202,20 +182,17 @@ def test_refusals_launch_nothing(hip_ctx, fixture):
 
 def test_side_stream_captured_graph_replayed_twice_and_no_side_effects(fixture):
     import torch
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
-    try:
-        ctx.set_stream(s.cuda_stream)
+    with side_stream_context() as (ctx, s):
         W, H = gen.WIDTH, gen.HEIGHT
         view, params = view_data_of(gen.view()), _params(**dict(gen.PARAMS, blur_passes=2))
         a = Planes(fixture["depth"], fixture["normals"])
-        state = (ctx.cache_epoch(), ctx.lighting_dispatch(), ctx.copy_rebuilds())
+        state = context_state(ctx)
         torch.cuda.synchronize()
         with torch.cuda.stream(s):
             ctx.ssao(view, a.depth.plane, a.normals.plane, a.scratch.plane, a.out.plane, params)
         s.synchronize()
-        assert _same(a.out.texels(f32).reshape(H, W), fixture["ao"][2])
-        assert (ctx.cache_epoch(), ctx.lighting_dispatch(), ctx.copy_rebuilds()) == state
+        assert same(a.out.texels(f32).reshape(H, W), fixture["ao"][2])
+        assert context_state(ctx) == state
         # one captured graph (raw, then blur: a linear chain), replayed twice over other input contents
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=s):
@@ -231,11 +208,8 @@ def test_side_stream_captured_graph_replayed_twice_and_no_side_effects(fixture):
             torch.cuda.synchronize()
             want = ref.ssao(depth, normals, gen.view(), dict(gen.PARAMS, blur_passes=2))
             got = a.out.texels(f32).reshape(H, W)
-            assert _same(got, want), f"replay with seed {seed}: " + _differs(got, want)
+            assert same(got, want), f"replay with seed {seed}: " + differs(got, want)
             assert (want < 1).sum() > 200
-    finally:
-        torch.cuda.synchronize()
-        ctx.close()
 
 
 # ---- the frame the pass exists for -------------------------------------------------------------------------------------------------------------
@@ -258,7 +232,7 @@ def test_atrium_rasterised_then_ssao_then_lpv_lighting(hip_ctx):
     gb_np["normals"] = gb_np["normals"].view(np.uint16)
     ao = ao_t.cpu().numpy()
     want, info = ref.ssao_ex(gb_np["depth"], gb_np["normals"], ref.View(view.gpu_data), dict(radius=2.0))
-    assert _same(ao, want), _differs(ao, want)
+    assert same(ao, want), differs(ao, want)
     covered = gb_np["depth"] > 0
     print(f"atrium {W} x {H}: {float(covered.mean()):.2f} covered, AO below 1 at {float((ao < 1).mean()):.2f} of the pixels, minimum {float(ao.min()):.3f}, "
           f"mean {float(ao[covered].mean()):.3f}")
@@ -289,24 +263,13 @@ def test_three_frames_through_the_python_wrapper(hip_ctx):
         torch.cuda.synchronize()
         assert out is ssao.ao
         want = ref.ssao(depth, normals, ref.View(view), dict(radius=1.5, fade_out_from=3.0, fade_out_to=9.0))
-        assert _same(out.cpu().numpy(), want), _differs(out.cpu().numpy(), want)
+        assert same(out.cpu().numpy(), want), differs(out.cpu().numpy(), want)
         assert (want < 1).mean() > 0.2
     unblurred = frame.ScreenSpaceAO(hip_ctx, W, H, radius=1.5, blur_passes=0, fade_out_from=3.0, fade_out_to=9.0)
     out = unblurred.generate(view, torch.from_numpy(depth).cuda(), util.to_torch(normals))
     torch.cuda.synchronize()
-    assert _same(out.cpu().numpy(), ref.ssao(depth, normals, ref.View(view), dict(radius=1.5, blur_passes=0, fade_out_from=3.0, fade_out_to=9.0)))
+    assert same(out.cpu().numpy(), ref.ssao(depth, normals, ref.View(view), dict(radius=1.5, blur_passes=0, fade_out_from=3.0, fade_out_to=9.0)))
     assert (unblurred.scratch == 1).all()  # not touched
-
-
-def _host_program(tmp_path):
-    built = os.path.join(ROOT, "tests", "cpp", "host_ssao")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_ssao.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_ssao"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
 
 
 @pytest.mark.parametrize("passes", [2, 0])
@@ -320,7 +283,7 @@ def test_three_frames_through_the_cpp_facade(tmp_path, hip_ctx, passes):
         f.write(np.array([len(frames), passes], np.uint32).tobytes() + f32(radius).tobytes())
         for w, h, jitter, depth, normals in frames:
             f.write(np.array([w, h], np.uint32).tobytes() + np.array(jitter, f32).tobytes() + depth.tobytes() + normals.tobytes())
-    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    subprocess.check_call([host_program("host_ssao", tmp_path), str(inp), str(outp)], timeout=120)
     blob = open(outp, "rb").read()
     at = 0
     for i, (w, h, jitter, depth, normals) in enumerate(frames):
@@ -330,7 +293,7 @@ def test_three_frames_through_the_cpp_facade(tmp_path, hip_ctx, passes):
         assert tuple(view.render_resolution) == (w, h) and tuple(view.jitter) == tuple(f32(j) for j in jitter) and view.projection[8] != 0 and view.projection[9] != 0
         settings = dict(radius=radius, blur_passes=passes)  # everything else: the reference's CACAO settings
         want = ref.ssao(depth, normals, ref.View(view), settings)
-        assert _same(facade, want), f"frame {i}: " + _differs(facade, want)
+        assert same(facade, want), f"frame {i}: " + differs(facade, want)
         got = Planes(depth, normals).run(hip_ctx, view, _params(**settings))
-        assert _same(facade, got) and (want < 1).mean() > 0.1
+        assert same(facade, got) and (want < 1).mean() > 0.1
     assert at == len(blob)

@@ -10,7 +10,9 @@ import pytest
 
 from androidrenderer_amd import _abi
 from tests import ssr_ref as ref
-from tests.test_ssr_gpu import INPUTS, Planes, _differs, _params, _same
+from tests.test_ssr_gpu import INPUTS, Planes, _params
+from tests.host_programs import host_program
+from tests.support import differs, same
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,17 +26,6 @@ def _time_limit():
     faulthandler.cancel_dump_traceback_later()
 
 
-def _host_program(tmp_path):
-    built = os.path.join(ROOT, "tests", "cpp", "host_ssr")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_ssr.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_ssr"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
-
-
 def test_three_frames_through_the_cpp_facade(tmp_path, hip_ctx):
     # (width, height, source is the previous output, jitter flag, reflection only, view jitter, stride, thickness)
     frames = [(80, 36, 0, 0, 0, (0.25, -0.125), 4.0, 0.5), (80, 36, 1, 1, 0, (-0.375, 0.125), 2.5, 3e38), (45, 50, 0, 0, 1, (0.125, 0.375), 1.0, 0.5)]
@@ -46,7 +37,7 @@ def test_three_frames_through_the_cpp_facade(tmp_path, hip_ctx):
             f.write(np.array([w, h, prev, jit, only], np.uint32).tobytes() + np.array(list(jitter) + [stride, thick], f32).tobytes())
             for k in ("color", "normals", "data", "depth", "lit"):
                 f.write(np.ascontiguousarray(a[k]).tobytes())
-    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    subprocess.check_call([host_program("host_ssr", tmp_path), str(inp), str(outp)], timeout=120)
     blob = open(outp, "rb").read()
     at, previous, hits = 0, None, 0
     for i, ((w, h, prev, jit, only, jitter, stride, thick), a) in enumerate(zip(frames, arrays)):
@@ -57,9 +48,9 @@ def test_three_frames_through_the_cpp_facade(tmp_path, hip_ctx):
         settings = dict(stride_pixels=stride, thickness=thick, flags=(ref.JITTER if jit else 0) | (ref.REFLECTION_ONLY if only else 0))
         inputs = dict({k: a[k] for k in INPUTS}, source=previous if prev else a["lit"])
         want, info = ref.ssr_ex(view=ref.View(view), params=settings, **inputs)
-        assert _same(facade, want), f"frame {i}: " + _differs(facade, want)
+        assert same(facade, want), f"frame {i}: " + differs(facade, want)
         got = Planes(inputs).run(hip_ctx, view, _params(**settings))
-        assert _same(facade, got)
+        assert same(facade, got)
         hits += int(info["hit"].sum())
         previous = facade
     assert at == len(blob) and hits > 300

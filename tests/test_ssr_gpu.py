@@ -11,10 +11,10 @@ import sys
 import numpy as np
 import pytest
 
-from androidrenderer_amd import _abi, frame, lib, mesh, scene
+from androidrenderer_amd import _abi, frame, mesh, scene
 from tests import ssr_ref as ref
 from tests import util
-from tests.test_vrsaa_gpu import SENTINEL, Image
+from tests.support import context_state, differs, Image, same, SENTINEL, side_stream_context, view_data_of
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,16 +39,6 @@ def _time_limit():
 def fixture():
     fx = np.load(gen.FIXTURE)
     return {k: fx[k] for k in fx.files}
-
-
-def view_data_of(view):
-    """an _abi.ViewData holding what the pass reads, from a ssao_ref.View"""
-    v = _abi.ViewData()
-    for i in range(16):
-        v.view[i] = float(view.view[i])
-    v.projection[0], v.projection[5], v.projection[8], v.projection[9], v.z_near = float(view.p00), float(view.p11), float(view.p20), float(view.p21), float(view.z_near)
-    v.projection[11] = -1.0
-    return v
 
 
 def _params(**changes):
@@ -84,21 +74,12 @@ class Planes:
         return self.out.texels(np.uint16).reshape(self.h, self.w, 4)
 
 
-def _differs(got, want):
-    bad = (got != want).any(-1)
-    return f"{int(bad.sum())} of {bad.size} pixels differ, first (y, x) at {np.argwhere(bad)[:4].tolist()}"
-
-
-def _same(got, want):
-    return got.tobytes() == want.tobytes()
-
-
 def _check(hip_ctx, frame_arrays, view, settings, **kw):
     """one call against the restatement; -> (got, info)"""
     got = Planes(frame_arrays, **kw).run(hip_ctx, view_data_of(view), _params(**settings))
     src = frame_arrays["lit"] if kw.get("same_source") else frame_arrays["source"]
     want, info = ref.ssr_ex(**dict(frame_arrays, source=src), view=view, params=settings)
-    assert _same(got, want), f"{settings}: " + _differs(got, want)
+    assert same(got, want), f"{settings}: " + differs(got, want)
     return got, info
 
 
@@ -107,9 +88,9 @@ def _check(hip_ctx, frame_arrays, view, settings, **kw):
 def test_fixture_bit_for_bit_and_repeatable(hip_ctx, fixture, case):
     view, params = view_data_of(gen.view()), _params(**gen.CASES[case])
     got = Planes(fixture).run(hip_ctx, view, params)
-    assert _same(got, fixture["out"][case]), _differs(got, fixture["out"][case])
+    assert same(got, fixture["out"][case]), differs(got, fixture["out"][case])
     again = Planes(fixture).run(hip_ctx, view, params)
-    assert _same(again, got)
+    assert same(again, got)
 
 
 # ---- extents ------------------------------------------------------------------------------------------------------------------------------
@@ -237,9 +218,9 @@ def test_identities_bit_for_bit(hip_ctx, only):
         got, info = _check(hip_ctx, frame_arrays, view, dict(settings, flags=only))
         assert set(np.unique(info["outcome"][info["surface"]])) <= outcomes | {ref.NO_SURFACE}, name
         want = np.zeros_like(got) if only else frame_arrays["lit"]
-        assert _same(got, want), f"{name}: " + _differs(got, want)
+        assert same(got, want), f"{name}: " + differs(got, want)
     got, info = _check(hip_ctx, room, ref.room_view(), dict(ref.ROOM_SETTINGS, flags=only))  # (and the room itself is no identity)
-    assert info["hit"].mean() > 0.1 and not _same(got, np.zeros_like(got) if only else room["lit"])
+    assert info["hit"].mean() > 0.1 and not same(got, np.zeros_like(got) if only else room["lit"])
 
 
 def test_unclean_source_texels_spread_no_further(hip_ctx):
@@ -254,7 +235,7 @@ def test_unclean_source_texels_spread_no_further(hip_ctx):
         got, info = _check(hip_ctx, dirty, ref.room_view(), ref.ROOM_SETTINGS)
         rejected = info["outcome"] == ref.REJECTED
         assert rejected.sum() > 100 and info["hit"].sum() > 100 and (rejected | info["hit"]).sum() == clean_info["hit"].sum()
-        assert _same(got[rejected], frame_arrays["lit"][rejected])
+        assert same(got[rejected], frame_arrays["lit"][rejected])
         assert np.isfinite(got.view(np.float16).astype(f32)).all()
 
 
@@ -266,11 +247,11 @@ def test_row_bands_write_their_rows_and_nothing_else(hip_ctx, fixture):
     for rows in ((9, 10), (0, 7), (7, 9), (10, 18), (18, 27), (27, 27), (27, H - 1), (H - 1, H)):
         p = Planes(fixture, pitches=dict(out=W * 8 + 12))
         got = p.run(hip_ctx, view, params, rows)
-        assert _same(got[rows[0]:rows[1]], whole[rows[0]:rows[1]]), f"{rows}: " + _differs(got[rows[0]:rows[1]], whole[rows[0]:rows[1]])
+        assert same(got[rows[0]:rows[1]], whole[rows[0]:rows[1]]), f"{rows}: " + differs(got[rows[0]:rows[1]], whole[rows[0]:rows[1]])
         assert p.out.padding_intact(rows), f"{rows}: out changed outside the band"
         assembled[rows[0]:rows[1]] = got[rows[0]:rows[1]]
-    assert _same(assembled, whole)
-    assert _same(Planes(fixture).run(hip_ctx, view, params, (0, H)), whole)
+    assert same(assembled, whole)
+    assert same(Planes(fixture).run(hip_ctx, view, params, (0, H)), whole)
 
 
 # ---- pitches and alignment ------------------------------------------------------------------------------------------------------------------
@@ -293,7 +274,7 @@ def test_pitches_offsets_sentinels_and_inputs(hip_ctx, fixture, pitches, offsets
     p = Planes(frame_arrays, pitches, offsets, same_source=same_source)
     got = p.run(hip_ctx, view, params)  # (asserts the inputs unchanged)
     want = ref.ssr(view=gen.view(), params=gen.CASES[0], **{k: frame_arrays[k] for k in INPUTS}) if same_source else fixture["out"][0]
-    assert _same(got, want), _differs(got, want)
+    assert same(got, want), differs(got, want)
     assert p.out.padding_intact() and p.img["scratch"].padding_intact()
     assert (got != frame_arrays["lit"]).any(-1).mean() > 0.1
 
@@ -372,20 +353,17 @@ def test_refusals_launch_nothing(hip_ctx, fixture):
 
 def test_side_stream_captured_graph_replayed_and_no_side_effects(fixture):
     import torch
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
-    try:
-        ctx.set_stream(s.cuda_stream)
+    with side_stream_context() as (ctx, s):
         view, params = view_data_of(gen.view()), _params(**gen.CASES[1])
         a = Planes(fixture)
-        state = (ctx.cache_epoch(), ctx.lighting_dispatch(), ctx.copy_rebuilds())
+        state = context_state(ctx)
         torch.cuda.synchronize()
         with torch.cuda.stream(s):
             ctx.ssr(view, *a.planes(), params)
         s.synchronize()
         direct = a.out.texels(np.uint16).reshape(H_, W_, 4)
-        assert _same(direct, fixture["out"][1])
-        assert (ctx.cache_epoch(), ctx.lighting_dispatch(), ctx.copy_rebuilds()) == state
+        assert same(direct, fixture["out"][1])
+        assert context_state(ctx) == state
         graph = torch.cuda.CUDAGraph()  # one kernel
         with torch.cuda.graph(graph, stream=s):
             ctx.ssr(view, *a.planes(), params)
@@ -403,11 +381,8 @@ def test_side_stream_captured_graph_replayed_and_no_side_effects(fixture):
             torch.cuda.synchronize()
             want = ref.ssr(view=gen.view(), params=gen.CASES[1], **{k: other[k] for k in INPUTS})
             got = a.out.texels(np.uint16).reshape(H_, W_, 4)
-            assert _same(got, want), f"replay with seed {seed}: " + _differs(got, want)
+            assert same(got, want), f"replay with seed {seed}: " + differs(got, want)
             assert (want != other["lit"]).any(-1).mean() > 0.05
-    finally:
-        torch.cuda.synchronize()
-        ctx.close()
 
 
 # ---- wrappers -----------------------------------------------------------------------------------------------------------------------------------
@@ -425,14 +400,14 @@ def test_two_frames_through_the_python_wrapper(hip_ctx):
     assert first is ssr.out and tuple(ssr.scratch.shape) == (7, 12)
     want1, info = ref.ssr_ex(**dict(arrays, source=arrays["lit"]), view=rview, params=settings)
     got1 = first.cpu().numpy().view(np.uint16)
-    assert _same(got1, want1), _differs(got1, want1)
+    assert same(got1, want1), differs(got1, want1)
     previous = first.clone()
     second = ssr(view, dev, dev["lit"], source=previous)
     torch.cuda.synchronize()
     want2 = ref.ssr(**dict(arrays, source=want1), view=rview, params=settings)
     got2 = second.cpu().numpy().view(np.uint16)
-    assert second is ssr.out and _same(got2, want2), _differs(got2, want2)
-    assert info["hit"].mean() > 0.1 and not _same(want1, want2)  # (a reflection of last frame's reflections)
+    assert second is ssr.out and same(got2, want2), differs(got2, want2)
+    assert info["hit"].mean() > 0.1 and not same(want1, want2)  # (a reflection of last frame's reflections)
     view = view_data_of(ref.room_view())
     ssr.params = _params(**ref.ROOM_SETTINGS)
     # a frame of another extent: the wrapper re-creates its planes
@@ -441,7 +416,7 @@ def test_two_frames_through_the_python_wrapper(hip_ctx):
     third = ssr(view, dev, dev["lit"], source=dev["source"])
     torch.cuda.synchronize()
     want3 = ref.ssr(**small, view=ref.room_view(), params=ref.ROOM_SETTINGS)
-    assert tuple(third.shape) == (27, 48, 4) and _same(third.cpu().numpy().view(np.uint16), want3)
+    assert tuple(third.shape) == (27, 48, 4) and same(third.cpu().numpy().view(np.uint16), want3)
 
 
 # ---- the frame the pass exists for -------------------------------------------------------------------------------------------------------------
@@ -467,7 +442,7 @@ def test_atrium_rasterised_lit_then_reflected(hip_ctx):
     torch.cuda.synchronize()
     got = out.cpu().numpy().view(np.uint16)
     want, info = ref.ssr_ex(gb_np["color"], gb_np["normals"], gb_np["data"], gb_np["depth"], lit, lit, ref.View(view.gpu_data))
-    assert _same(got, want), _differs(got, want)
+    assert same(got, want), differs(got, want)
     n = gb_np["normals"].view(np.float16)[..., :3].astype(f32)
     covered = gb_np["depth"] > 0
     floor = covered & (n[..., 1] < -0.9 * np.sqrt((n * n).sum(-1)))  # the world's y axis points down: the floor's normal is -y
@@ -476,4 +451,4 @@ def test_atrium_rasterised_lit_then_reflected(hip_ctx):
     print(f"atrium {W} x {H}: {float(covered.mean()):.2f} covered, {int(info['hit'].sum())} pixels reflect, {int((brighter & floor).sum())} of {int(floor.sum())} floor "
           f"pixels brighter")
     assert covered.mean() > 0.5 and floor.sum() > 50 and (brighter & floor).sum() >= 1 and not (a < b).any()
-    assert _same(got[~covered], lit[~covered])
+    assert same(got[~covered], lit[~covered])

@@ -11,7 +11,9 @@ import pytest
 
 from androidrenderer_amd import _abi
 from tests import sun_shafts_ref as ref
-from tests.test_sun_shafts_gpu import Map, Planes, _differs, _params, _same
+from tests.test_sun_shafts_gpu import Map, Planes, _params, _same
+from tests.host_programs import host_program
+from tests.support import differs
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,17 +25,6 @@ def _time_limit():
     faulthandler.dump_traceback_later(120, exit=True)
     yield
     faulthandler.cancel_dump_traceback_later()
-
-
-def _host_program(tmp_path):
-    built = os.path.join(ROOT, "tests", "cpp", "host_sun_shafts")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_sun_shafts.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_sun_shafts"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
 
 
 def test_four_frames_through_the_cpp_facade(tmp_path, hip_ctx):
@@ -52,7 +43,7 @@ def test_four_frames_through_the_cpp_facade(tmp_path, hip_ctx):
             for a in planes:
                 if a is not None:
                     f.write(np.ascontiguousarray(a).tobytes())
-    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    subprocess.check_call([host_program("host_sun_shafts", tmp_path), str(inp), str(outp)], timeout=120)
     blob = open(outp, "rb").read()
     at, changed, taps = 0, 0, 0
     for i, (((w, h), s, dither, steps, res, layers, d32, extinction, step_length, ambient), (depth, lit, shadow)) in enumerate(zip(frames, arrays)):
@@ -69,8 +60,8 @@ def test_four_frames_through_the_cpp_facade(tmp_path, hip_ctx):
         settings = dict(step_length=step_length, num_steps=steps, step_transmittance=float(tau), albedo=(_abi.LIGHTING_EXPOSURE,) * 3, ambient=(ambient,) * 3,
                         downscale=s, dither_offset=i & 15 if dither else 0, flags=ref.DITHER if dither else 0)  # (the pass without planes took no offset)
         want, info = ref.sun_shafts_ex(view, sun, shadow, depth, lit, **settings)
-        assert _same(march, info["bits"]), f"frame {i}: march " + _differs(march, info["bits"])
-        assert _same(facade, want), f"frame {i}: " + _differs(facade, want)
+        assert _same(march, info["bits"]), f"frame {i}: march " + differs(march, info["bits"])
+        assert _same(facade, want), f"frame {i}: " + differs(facade, want)
         got = Planes(depth, lit, s).run(hip_ctx, dict(view=view, sun=sun), None if shadow is None else Map(shadow), _params(**settings))
         assert _same(facade, got)
         changed += int((want != lit).any(-1).sum())

@@ -16,7 +16,7 @@ from androidrenderer_amd import _abi, frame, lib, mesh
 from tests import layouts
 from tests import sun_shafts_ref as ref
 from tests import util
-from tests.test_vrsaa_gpu import SENTINEL, Image
+from tests.support import context_state, differs, Image, resized, retyped, same, SENTINEL, side_stream_context
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -110,13 +110,8 @@ class Planes:
         return self.result()
 
 
-def _differs(got, want):
-    bad = (got != want).any(-1)
-    return f"{int(bad.sum())} of {bad.size} texels differ, first (y, x) at {np.argwhere(bad)[:4].tolist()}"
-
-
 def _same(got, want):
-    return got.shape == want.shape and got.tobytes() == want.tobytes()
+    return got.shape == want.shape and same(got, want)
 
 
 _MAPS = {}
@@ -135,8 +130,8 @@ def _check(hip_ctx, world, shadow, depth, lit_bits, settings, **kw):
     p = Planes(depth, lit_bits, settings.get("downscale", 1), **kw)
     got = p.run(hip_ctx, world, _device_map(shadow), _params(**settings))
     want, info = ref.sun_shafts_ex(world["view"], world["sun"], shadow, depth, lit_bits, **settings)
-    assert _same(p.march(), info["bits"]), f"{settings}: march " + _differs(p.march(), info["bits"])
-    assert _same(got, want), f"{settings}: " + _differs(got, want)
+    assert _same(p.march(), info["bits"]), f"{settings}: march " + differs(p.march(), info["bits"])
+    assert _same(got, want), f"{settings}: " + differs(got, want)
     return got, info
 
 
@@ -153,8 +148,8 @@ def test_fixture_bit_for_bit_and_repeatable(hip_ctx, fixture, case):
     p = Planes(fixture["depth"], fixture["lit"], settings.get("downscale", 1))
     shadow = _device_map(gen.shadow_map(fixture, name))
     got = p.run(hip_ctx, w, shadow, _params(**settings))
-    assert _same(p.march(), fixture[f"march{case}"]), "march " + _differs(p.march(), fixture[f"march{case}"])
-    assert _same(got, fixture["out"][case]), _differs(got, fixture["out"][case])
+    assert _same(p.march(), fixture[f"march{case}"]), "march " + differs(p.march(), fixture[f"march{case}"])
+    assert _same(got, fixture["out"][case]), differs(got, fixture["out"][case])
     again = p.run(hip_ctx, w, shadow, _params(**settings))  # two calls, the same bytes
     assert _same(again, got)
 
@@ -262,7 +257,7 @@ def test_row_windows_cover_the_frame_and_write_nothing_else(hip_ctx, world, down
         before = banded.result().copy()
         single = Planes(depth, lit, downscale)
         got = single.run(hip_ctx, world, shadow, _params(**settings), rows)
-        assert _same(got[rows[0]:rows[1]], want[rows[0]:rows[1]]), f"rows {rows}: " + _differs(got[rows[0]:rows[1]], want[rows[0]:rows[1]])
+        assert _same(got[rows[0]:rows[1]], want[rows[0]:rows[1]]), f"rows {rows}: " + differs(got[rows[0]:rows[1]], want[rows[0]:rows[1]])
         layouts.assert_rows_untouched(np.uint16(SENTINEL * 0x101), got, rows[0], rows[1], what=f"rows {rows}")
         m0, m1 = (rows if downscale == 1 else (rows[0] // 2, min((rows[1] - 1) // 2 + 2, (h + 1) // 2))) if rows[1] > rows[0] else (0, 0)
         assert _same(single.march()[m0:m1], info["bits"][m0:m1])
@@ -326,10 +321,7 @@ def test_side_stream_under_capture_and_replayed_over_other_inputs(fixture):
     name, settings = gen.CASES[1]
     view, sun = gen.structures(fx)
     shadow = _device_map(gen.shadow_map(fx, name))
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
-    try:
-        ctx.set_stream(s.cuda_stream)
+    with side_stream_context() as (ctx, s):
         a = Planes(fx["depth"], fx["lit"], settings["downscale"])
         params = _params(**settings)
         torch.cuda.synchronize()
@@ -350,9 +342,6 @@ def test_side_stream_under_capture_and_replayed_over_other_inputs(fixture):
         graph.replay()
         torch.cuda.synchronize()
         assert _same(a.result(), direct) and not _same(direct, fx["out"][1])
-    finally:
-        torch.cuda.synchronize()
-        ctx.close()
 
 
 def test_no_side_effects_on_the_context(hip_ctx, fixture):
@@ -360,7 +349,7 @@ def test_no_side_effects_on_the_context(hip_ctx, fixture):
     f.run_hip(hip_ctx)
 
     def state():
-        return hip_ctx.cache_epoch(), hip_ctx.lighting_dispatch(), hip_ctx.copy_rebuilds()
+        return context_state(hip_ctx)
     before = state()
     view, sun = gen.structures(fixture)
     got = Planes(fixture["depth"], fixture["lit"]).run(hip_ctx, dict(view=view, sun=sun), _device_map(fixture["map_d16"]), _params(**gen.CASES[0][1]))
@@ -439,12 +428,6 @@ def test_refusals_launch_nothing(hip_ctx, world, fixture):
     view, sun = world["view"], world["sun"]
     shadow = _device_map(world["maps"]["d16x4"]).volume
     ok = _params()
-
-    def retyped(plane, fmt):
-        return type(plane)(*[getattr(plane, n) for n, _ in plane._fields_[:-1]], fmt)
-
-    def resized(plane, width, height):
-        return _abi.Plane(plane.ptr, width, height, plane.row_pitch_bytes, plane.format)
 
     def relayered(volume, layers):
         return _abi.Volume(volume.ptr, volume.width, volume.height, layers, volume.row_pitch_bytes, volume.slice_pitch_bytes, volume.format)
@@ -525,7 +508,7 @@ def test_two_frames_of_the_rasterised_atrium(hip_ctx):
         got, depth_np = util.from_torch(opt["out"], np.uint16), gb["depth"].cpu().numpy()
         want, info = ref.sun_shafts_ex(view.gpu_data, sun, shadow, depth_np, lit, downscale=2, flags=ref.DITHER, dither_offset=n, ambient=(2e-6, 3e-6, 5e-6),
                                        albedo=(_abi.LIGHTING_EXPOSURE,) * 3, step_transmittance=float(shafts.params.step_transmittance))
-        assert _same(got, want), f"frame {n}: " + _differs(got, want)
+        assert _same(got, want), f"frame {n}: " + differs(got, want)
         assert _same(util.from_torch(shafts.march, np.uint16), info["bits"])
         assert (got != lit).any(-1).mean() > 0.9 and 0.05 < (depth_np > 0).mean() and info["taps"] > 0, f"frame {n}"
     assert (shafts.width, shafts.height) == (w, h)

@@ -12,7 +12,8 @@ import pytest
 from androidrenderer_amd import _abi, frame, lib, mesh, scene
 from tests import mv_reproject, util
 from tests import taa_ref as ref
-from tests.test_vrsaa_gpu import Image
+from tests.host_programs import host_program
+from tests.support import context_state, differs, Image, retyped, side_stream_context
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -65,17 +66,12 @@ class Planes:
         return self.out.texels(np.uint16).reshape(self.h, self.w, 4)
 
 
-def _differs(got, want):
-    bad = (got != want).any(-1)
-    return f"{int(bad.sum())} of {bad.size} texels differ, first (y, x) at {np.argwhere(bad)[:4].tolist()}"
-
-
 # ---- the fixture --------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("flags,key", [(0, "out_plain"), (HDR, "out_hdr")])
 def test_fixture_bit_for_bit_and_repeatable(hip_ctx, fixture, flags, key):
     fx = fixture
     got = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"]).resolve(hip_ctx, _fixture_params(fx, flags))
-    assert np.array_equal(got, fx[key]), _differs(got, fx[key])
+    assert np.array_equal(got, fx[key]), differs(got, fx[key])
     again = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"]).resolve(hip_ctx, _fixture_params(fx, flags))
     assert again.tobytes() == got.tobytes()
 
@@ -84,7 +80,7 @@ def test_without_history_the_output_is_lit(hip_ctx, fixture):
     fx = fixture
     for history in (None, fx["history"]):  # not read, given or not
         got = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], history).resolve(hip_ctx, _fixture_params(fx, NO_HISTORY | HDR))
-        assert np.array_equal(got, fx["lit"]), _differs(got, fx["lit"])
+        assert np.array_equal(got, fx["lit"]), differs(got, fx["lit"])
 
 
 # (65, 17): one tile plus one pixel in both axes; (129, 33): two tiles plus one
@@ -96,7 +92,7 @@ def test_small_extents(hip_ctx, extent, flags):
     jitter, previous = (0.3, -0.2), (-0.25, 0.4)
     got = Planes(lit, depth, mv, history).resolve(hip_ctx, _params(0.1, jitter, previous, flags))
     want, info = ref.resolve_ex(lit, depth, mv, history, 0.1, jitter, previous, flags)
-    assert np.array_equal(got, want), _differs(got, want)
+    assert np.array_equal(got, want), differs(got, want)
     if w * h >= 64:
         assert info["valid"].any() and (want[..., :3] != lit[..., :3]).any()
 
@@ -109,7 +105,7 @@ def test_pitches_offsets_sentinels_and_inputs(hip_ctx, fixture, pitches, offsets
     fx = fixture
     p = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"], pitches, offsets)
     got = p.resolve(hip_ctx, _fixture_params(fx, HDR))  # (asserts the inputs unchanged)
-    assert np.array_equal(got, fx["out_hdr"]), _differs(got, fx["out_hdr"])
+    assert np.array_equal(got, fx["out_hdr"]), differs(got, fx["out_hdr"])
     assert p.out.padding_intact()
 
 
@@ -164,24 +160,13 @@ def test_eight_frames_of_ping_pong_match_the_restatement_frame_by_frame(hip_ctx)
         out = resolver.resolve(util.to_torch(lit), torch.from_numpy(depth).cuda(), util.to_torch(mv), jitters[i])
         torch.cuda.synchronize()
         got = util.from_torch(out, np.uint16)
-        assert np.array_equal(got, want[i]), f"frame {i}: " + _differs(got, want[i])
+        assert np.array_equal(got, want[i]), f"frame {i}: " + differs(got, want[i])
     assert np.array_equal(want[0], seq[0][0]) and not np.array_equal(want[7], seq[7][0])
     # after a cut the next frame is the lit frame again
     resolver.reset()
     out = resolver.resolve(util.to_torch(seq[3][0]), torch.from_numpy(seq[3][1]).cuda(), util.to_torch(seq[3][2]), jitters[0])
     torch.cuda.synchronize()
     assert np.array_equal(util.from_torch(out, np.uint16), seq[3][0])
-
-
-def _host_program(tmp_path):
-    built = os.path.join(ROOT, "tests", "cpp", "host_taa")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_taa.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_taa"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
 
 
 def test_three_frames_through_the_cpp_facade_match_the_python_resolver(tmp_path, hip_ctx):
@@ -194,7 +179,7 @@ def test_three_frames_through_the_cpp_facade_match_the_python_resolver(tmp_path,
         f.write(np.float32(blend).tobytes())
         for lit, depth, mv in seq:
             f.write(lit.tobytes() + depth.tobytes() + mv.tobytes())
-    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    subprocess.check_call([host_program("host_taa", tmp_path), str(inp), str(outp)], timeout=120)
     blob = open(outp, "rb").read()
     size = 8 + W * H * 8
     assert len(blob) == 3 * size
@@ -207,7 +192,7 @@ def test_three_frames_through_the_cpp_facade_match_the_python_resolver(tmp_path,
         out = resolver.resolve(util.to_torch(lit), torch.from_numpy(depth).cuda(), util.to_torch(mv), jitters[i])
         torch.cuda.synchronize()
         got = util.from_torch(out, np.uint16)
-        assert np.array_equal(facade, got), f"frame {i}: " + _differs(facade, got)
+        assert np.array_equal(facade, got), f"frame {i}: " + differs(facade, got)
         assert np.array_equal(got, want[i])
 
 
@@ -215,10 +200,7 @@ def test_three_frames_through_the_cpp_facade_match_the_python_resolver(tmp_path,
 def test_side_stream_without_host_sync_and_under_capture(fixture):
     import torch
     fx = fixture
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
-    try:
-        ctx.set_stream(s.cuda_stream)
+    with side_stream_context() as (ctx, s):
         a = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"])
         second = Image(RGBA16F, 69, 21)
         p1, p2 = _fixture_params(fx, HDR), _params(float(fx["blend"]), fx["previous_jitter"], fx["jitter"], 0)
@@ -250,9 +232,6 @@ def test_side_stream_without_host_sync_and_under_capture(fixture):
         assert np.array_equal(a.out.texels(np.uint16).reshape(21, 69, 4), direct1)
         assert np.array_equal(second.texels(np.uint16).reshape(21, 69, 4), direct2)
         assert not np.array_equal(direct2, want2)
-    finally:
-        torch.cuda.synchronize()
-        ctx.close()
 
 
 def test_no_side_effects_on_the_context(hip_ctx, fixture):
@@ -261,7 +240,7 @@ def test_no_side_effects_on_the_context(hip_ctx, fixture):
     f.run_hip(hip_ctx)
 
     def state():
-        return hip_ctx.cache_epoch(), hip_ctx.lighting_dispatch(), hip_ctx.copy_rebuilds()
+        return context_state(hip_ctx)
     before = state()
     got = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"]).resolve(hip_ctx, _fixture_params(fx, 0))
     assert state() == before
@@ -276,8 +255,6 @@ def test_refusals_launch_nothing(hip_ctx, fixture):
     ok = _fixture_params(fx, 0)
     lit, depth, mv, history, out = p.lit.plane, p.depth.plane, p.mv.plane, p.history.plane, p.out.plane
 
-    def retyped(plane, fmt):
-        return _abi.Plane(plane.ptr, plane.width, plane.height, plane.row_pitch_bytes, fmt)
     INVALID, FORMAT = _abi.SAH_ERR_INVALID_ARGUMENT, _abi.SAH_ERR_UNSUPPORTED_FORMAT
     cases = [((lit, depth, mv, history, retyped(out, _abi.FORMAT_R32_SFLOAT), ok), FORMAT),
              ((lit, retyped(depth, _abi.FORMAT_R32_SFLOAT), mv, history, out, ok), FORMAT),
@@ -336,7 +313,7 @@ def test_rendered_frames_end_to_end(hip_ctx):
     (lit0, _, _, out0), (lit1, depth1, mv1, out1) = frames
     assert np.array_equal(out0, lit0)
     want, info = ref.resolve_ex(lit1, depth1, mv1, out0, blend, j1, j0, HDR)
-    assert np.array_equal(out1, want), _differs(out1, want)
+    assert np.array_equal(out1, want), differs(out1, want)
     assert info["valid"].mean() > 0.9 and (out1[..., :3] != lit1[..., :3]).any()
     solid = depth1 > 0
     assert solid.mean() > 0.5

@@ -12,7 +12,8 @@ import pytest
 from androidrenderer_amd import _abi, frame, images, lib, mesh, scene
 from tests import mv_reproject, taa_ref, util
 from tests import taa_upscale_ref as ref
-from tests.test_vrsaa_gpu import Image
+from tests.host_programs import host_program
+from tests.support import context_state, differs, Image, resized, retyped, side_stream_context
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -77,17 +78,12 @@ def _fixture_planes(fx, **kw):
     return Planes(fx["lit"], fx["depth"], fx["motion_vectors"], fx["history"], OUTPUT, **kw)
 
 
-def _differs(got, want):
-    bad = (got != want).any(-1)
-    return f"{int(bad.sum())} of {bad.size} texels differ, first (y, x) at {np.argwhere(bad)[:4].tolist()}"
-
-
 # ---- the fixture --------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("flags,key", [(0, "out_plain"), (HDR, "out_hdr")])
 def test_fixture_bit_for_bit_and_repeatable(hip_ctx, fixture, flags, key):
     fx = fixture
     got = _fixture_planes(fx).resolve(hip_ctx, _fixture_params(fx, flags))
-    assert np.array_equal(got, fx[key]), _differs(got, fx[key])
+    assert np.array_equal(got, fx[key]), differs(got, fx[key])
     again = _fixture_planes(fx).resolve(hip_ctx, _fixture_params(fx, flags))
     assert again.tobytes() == got.tobytes()
 
@@ -98,7 +94,7 @@ def test_without_history_the_output_is_the_restatements_upsample(hip_ctx, fixtur
     assert np.array_equal(want, _fixture_ref(fx, NO_HISTORY | HDR, history=None))
     for history in (None, fx["history"]):  # not read, given or not
         got = Planes(fx["lit"], fx["depth"], fx["motion_vectors"], history, OUTPUT).resolve(hip_ctx, _fixture_params(fx, NO_HISTORY | HDR))
-        assert np.array_equal(got, want), _differs(got, want)
+        assert np.array_equal(got, want), differs(got, want)
 
 
 @pytest.mark.parametrize("extents", ref.EXTENTS, ids=lambda e: f"{e[0][0]}x{e[0][1]}-{e[1][0]}x{e[1][1]}")
@@ -112,7 +108,7 @@ def test_small_extents(hip_ctx, extents, flags):
     for jitter in ((0.0, 0.0), (0.5, -0.5), (0.25, 0.25)):
         got = Planes(lit, depth, mv, history, (W, H)).resolve(hip_ctx, _params(0.1, 0.05, jitter, previous, flags))
         want, info = ref.upscale_ex(lit, depth, mv, history, (W, H), 0.1, 0.05, jitter, previous, flags)
-        assert np.array_equal(got, want), f"jitter {jitter}: " + _differs(got, want)
+        assert np.array_equal(got, want), f"jitter {jitter}: " + differs(got, want)
         blended += int((~info["fallback"]).sum())
     if W * H >= 64:
         assert blended > 0
@@ -126,7 +122,7 @@ def test_pitches_offsets_sentinels_and_inputs(hip_ctx, fixture, pitches, offsets
     fx = fixture
     p = _fixture_planes(fx, pitches=pitches, offsets=offsets)
     got = p.resolve(hip_ctx, _fixture_params(fx, HDR))  # (asserts the inputs unchanged)
-    assert np.array_equal(got, fx["out_hdr"]), _differs(got, fx["out_hdr"])
+    assert np.array_equal(got, fx["out_hdr"]), differs(got, fx["out_hdr"])
     assert p.out.padding_intact()
 
 
@@ -150,7 +146,7 @@ def test_row_bands_compose_to_the_whole_from_the_render_rows_the_header_names(hi
         body = changed[:H * pitch].reshape(H, pitch)
         assert not body[:rows[0]].any() and not body[rows[1]:].any() and not body[:, W * 8:].any() and not changed[H * pitch:].any()
     got = out.texels(np.uint16).reshape(H, W, 4)
-    assert np.array_equal(got, fx["out_hdr"]), _differs(got, fx["out_hdr"])
+    assert np.array_equal(got, fx["out_hdr"]), differs(got, fx["out_hdr"])
     before = out.bytes().copy()
     _fixture_planes(fx, out=out).resolve(hip_ctx, _fixture_params(fx, 0), (5, 5))  # an empty band writes nothing
     assert (out.bytes() == before).all()
@@ -189,7 +185,7 @@ def test_rows_beyond_2_to_28_where_a_tiles_footprint_outgrows_the_staged_cells(h
             got = out_t[band[0]:].cpu().numpy().view(np.uint16)
             want, info = ref.upscale_ex(lit, depth, mv, history, (1, H), 0.25, 0.05, jitter, previous, flags,
                                         window=(band[0], band[1] - band[0], first, h, first))
-            assert np.array_equal(got, want), f"flags {flags}: " + _differs(got, want)
+            assert np.array_equal(got, want), f"flags {flags}: " + differs(got, want)
             assert (~info["fallback"]).mean() > 0.5 and not out_t[band[0] - 64:band[0]].any()
     finally:
         del tensors, out_t, t
@@ -222,7 +218,7 @@ def test_eight_frames_of_ping_pong_match_the_restatement_frame_by_frame(hip_ctx)
         out = upscaler.resolve(util.to_torch(lit), torch.from_numpy(depth).cuda(), util.to_torch(mv), jitters[n])
         torch.cuda.synchronize()
         got = util.from_torch(out, np.uint16)
-        assert np.array_equal(got, want[n]), f"frame {n}: " + _differs(got, want[n])
+        assert np.array_equal(got, want[n]), f"frame {n}: " + differs(got, want[n])
     first = ref.upscale(*seq[0], None, (W, H), blend, mc, jitters[0], jitters[0], NO_HISTORY)
     assert np.array_equal(want[0], first) and not np.array_equal(want[7], ref.upscale(*seq[7], None, (W, H), blend, mc, jitters[7], jitters[7], NO_HISTORY))
     # after a cut the next frame is the upsample again
@@ -230,17 +226,6 @@ def test_eight_frames_of_ping_pong_match_the_restatement_frame_by_frame(hip_ctx)
     out = upscaler.resolve(util.to_torch(seq[3][0]), torch.from_numpy(seq[3][1]).cuda(), util.to_torch(seq[3][2]), jitters[0])
     torch.cuda.synchronize()
     assert np.array_equal(util.from_torch(out, np.uint16), ref.upscale(*seq[3], None, (W, H), blend, mc, jitters[0], jitters[0], NO_HISTORY))
-
-
-def _host_program(tmp_path):
-    built = os.path.join(ROOT, "tests", "cpp", "host_taa_upscale")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_taa.h", "sah_taa_upscale.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_taa_upscale"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
 
 
 def test_three_frames_through_the_cpp_facade_match_the_python_upscaler(tmp_path, hip_ctx):
@@ -255,7 +240,7 @@ def test_three_frames_through_the_cpp_facade_match_the_python_upscaler(tmp_path,
         f.write(np.array([blend, mc, scale], np.float32).tobytes())
         for lit, depth, mv in seq:
             f.write(lit.tobytes() + depth.tobytes() + mv.tobytes())
-    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    subprocess.check_call([host_program("host_taa_upscale", tmp_path), str(inp), str(outp)], timeout=120)
     blob = open(outp, "rb").read()
     assert np.frombuffer(blob[:12], np.uint32).tolist() == [w, h, len(jitters)] and len(jitters) == 18
     blob, size = blob[12:], 8 + W * H * 8
@@ -269,7 +254,7 @@ def test_three_frames_through_the_cpp_facade_match_the_python_upscaler(tmp_path,
         out = upscaler.resolve(util.to_torch(lit), torch.from_numpy(depth).cuda(), util.to_torch(mv), jitters[n])
         torch.cuda.synchronize()
         got = util.from_torch(out, np.uint16)
-        assert np.array_equal(facade, got), f"frame {n}: " + _differs(facade, got)
+        assert np.array_equal(facade, got), f"frame {n}: " + differs(facade, got)
         assert np.array_equal(got, want[n])
 
 
@@ -278,10 +263,7 @@ def test_side_stream_without_host_sync_and_under_capture(fixture):
     import torch
     fx = fixture
     (w, h), (W, H) = RENDER, OUTPUT
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
-    try:
-        ctx.set_stream(s.cuda_stream)
+    with side_stream_context() as (ctx, s):
         a = _fixture_planes(fx)
         second = Image(RGBA16F, W, H)
         blend, mc = float(fx["blend"]), float(fx["min_confidence"])
@@ -315,9 +297,6 @@ def test_side_stream_without_host_sync_and_under_capture(fixture):
         assert np.array_equal(a.out.texels(np.uint16).reshape(H, W, 4), direct1)
         assert np.array_equal(second.texels(np.uint16).reshape(H, W, 4), direct2)
         assert not np.array_equal(direct2, want2)
-    finally:
-        torch.cuda.synchronize()
-        ctx.close()
 
 
 def test_no_side_effects_on_the_context(hip_ctx, fixture):
@@ -326,7 +305,7 @@ def test_no_side_effects_on_the_context(hip_ctx, fixture):
     f.run_hip(hip_ctx)
 
     def state():
-        return hip_ctx.cache_epoch(), hip_ctx.lighting_dispatch(), hip_ctx.copy_rebuilds()
+        return context_state(hip_ctx)
     before = state()
     got = _fixture_planes(fx).resolve(hip_ctx, _fixture_params(fx, 0))
     assert state() == before
@@ -343,11 +322,6 @@ def test_refusals_launch_nothing(hip_ctx, fixture):
     lit, depth, mv, history, out = p.lit.plane, p.depth.plane, p.mv.plane, p.history.plane, p.out.plane
     blend = float(fx["blend"])
 
-    def retyped(plane, fmt):
-        return _abi.Plane(plane.ptr, plane.width, plane.height, plane.row_pitch_bytes, fmt)
-
-    def resized(plane, width, height):
-        return _abi.Plane(plane.ptr, width, height, plane.row_pitch_bytes, plane.format)
     INVALID, FORMAT = _abi.SAH_ERR_INVALID_ARGUMENT, _abi.SAH_ERR_UNSUPPORTED_FORMAT
     cases = [((lit, depth, mv, history, retyped(out, _abi.FORMAT_R32_SFLOAT), ok), FORMAT),
              ((lit, retyped(depth, _abi.FORMAT_R32_SFLOAT), mv, history, out, ok), FORMAT),
@@ -409,9 +383,9 @@ def test_rendered_frames_end_to_end(hip_ctx):
         frames.append((lit, gb_np["depth"], util.from_torch(mv, np.uint16), util.from_torch(out, np.uint16), out))
     (lit0, depth0, mv0, out0, _), (lit1, depth1, mv1, out1, out1_t) = frames
     want0 = ref.upscale(lit0, depth0, mv0, None, (W, H), blend, mc, j0, j0, HDR | NO_HISTORY)
-    assert np.array_equal(out0, want0), _differs(out0, want0)
+    assert np.array_equal(out0, want0), differs(out0, want0)
     want, info = ref.upscale_ex(lit1, depth1, mv1, out0, (W, H), blend, mc, j1, j0, HDR)
-    assert np.array_equal(out1, want), _differs(out1, want)
+    assert np.array_equal(out1, want), differs(out1, want)
     assert info["valid"].mean() > 0.9 and (~info["fallback"]).mean() > 0.9
     solid = depth1[info["j"]][:, info["i"]] > 0
     assert solid.mean() > 0.5

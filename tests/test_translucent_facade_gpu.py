@@ -12,6 +12,7 @@ import pytest
 from androidrenderer_amd import _abi, frame, mesh, scene, synth
 from tests import translucent_ref as ref
 from tests import util
+from tests.host_programs import host_program
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -83,17 +84,6 @@ def test_rasterised_frame_with_and_without_translucent(hip_ctx):
     assert util.from_torch(lit, np.uint16).tobytes() == np.concatenate([fr.lit0[:10], want[10:30], fr.lit0[30:]]).tobytes()
 
 
-def _host_program(tmp_path):
-    built = os.path.join(ROOT, "tests", "cpp", "host_translucent")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_translucent.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_translucent"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
-
-
 def test_translucency_phase_through_cpp_facade(tmp_path, hip_ctx):
     import torch
     steps = 1
@@ -108,7 +98,7 @@ def test_translucency_phase_through_cpp_facade(tmp_path, hip_ctx):
         for a in (opaque["positions"], opaque["vertex_data"], opaque["indices"], opaque["materials"], opaque["primitives"], translucent["primitives"], ao,
                   luts["transmittance"], luts["sky_view"], pattern, *vols):
             fh.write(np.ascontiguousarray(a).tobytes())
-    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    subprocess.check_call([host_program("host_translucent", tmp_path), str(inp), str(outp)], timeout=120)
     blob = open(outp, "rb").read()
     off = 0
 

@@ -16,6 +16,7 @@ from androidrenderer_amd import _abi, images, lib, mesh
 from tests import layouts
 from tests import translucent_ref as ref
 from tests import util
+from tests.support import differs
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,11 +34,6 @@ def _time_limit():
     faulthandler.dump_traceback_later(120, exit=True)  # each test under a limit of its own: an overrun ends the process
     yield
     faulthandler.cancel_dump_traceback_later()
-
-
-def _differs(got, want):
-    bad = (got != want).reshape(got.shape[0], got.shape[1], -1).any(-1)
-    return f"{int(bad.sum())} of {bad.size} pixels differ, first at {np.argwhere(bad)[:4].tolist()}"
 
 
 def device_geometry(arrays):
@@ -85,8 +81,8 @@ def _case(ctx, scene, extent, sun=CSM, gi=LPV, flags=BLEND):
 def _check(ctx, c, min_changed=0.2, min_depth=1):
     ref.assert_preconditions(c.fr, c.want, c.blended, min_changed, min_depth)
     got, stats = c.run(ctx)
-    print(f"{_differs(got, c.want)}; statistics {stats.tolist()}; the reference's deepest pixel blends {int(c.blended.max())}")
-    assert got.tobytes() == c.want.tobytes(), _differs(got, c.want)
+    print(f"{differs(got, c.want)}; statistics {stats.tolist()}; the reference's deepest pixel blends {int(c.blended.max())}")
+    assert got.tobytes() == c.want.tobytes(), differs(got, c.want)
     assert stats[7] == c.blended.max() and stats[5] == 0 and stats[6] == 0
     return got, stats
 
@@ -98,8 +94,8 @@ def test_the_fixture(hip_ctx):
     c = Case(hip_ctx, ref.scene_panes(), (gen.WIDTH, gen.HEIGHT), gen.SUN, gen.GI, compose=False)
     assert c.fr.depth.view(np.uint32).tobytes() == fx["depth"].view(np.uint32).tobytes(), "sah_gbuffer_render's depth is not the oracle's"
     got, stats = c.run(hip_ctx, lit0=fx["lit0"])
-    print(f"{_differs(got, fx['lit'])}; statistics {stats.tolist()}")
-    assert got.tobytes() == fx["lit"].tobytes(), _differs(got, fx["lit"])
+    print(f"{differs(got, fx['lit'])}; statistics {stats.tolist()}")
+    assert got.tobytes() == fx["lit"].tobytes(), differs(got, fx["lit"])
     assert stats[7] == fx["blended"].max() >= 3
 
 
@@ -124,7 +120,7 @@ def test_over_the_sky_behind_geometry_and_back_facing(hip_ctx):
         geo, keep = device_geometry(dict(c.fr.translucent, primitives=prims[k:k + 1]))
         got, stats = c.run(hip_ctx, geo=geo)
         want, blended = c.fr.compose(dict(c.fr.translucent, primitives=prims[k:k + 1]))
-        assert got.tobytes() == want.tobytes(), (k, _differs(got, want))
+        assert got.tobytes() == want.tobytes(), (k, differs(got, want))
         return got, stats, blended
     got, stats, blended = alone(0)  # behind the end wall
     assert got.tobytes() == c.fr.lit0.tobytes() and stats[3] == 2 and stats[7] == 0 and blended.max() == 0
@@ -179,7 +175,7 @@ def test_the_whole_scene_gives_what_its_translucent_half_gives(hip_ctx):
     c = _case(hip_ctx, "panes", SMALL)
     geo, keep = device_geometry(c.fr.arrays)
     got, stats = c.run(hip_ctx, geo=geo)
-    assert got.tobytes() == c.want.tobytes(), _differs(got, c.want)
+    assert got.tobytes() == c.want.tobytes(), differs(got, c.want)
     assert stats[0] == 13
 
 
@@ -222,7 +218,7 @@ def _pitched_call(ctx, c, spec, rows=(0, 0)):
 def test_pitched_and_offset_planes(hip_ctx, spec):
     c = _case(hip_ctx, "panes", SMALL)
     got = _pitched_call(hip_ctx, c, spec)
-    assert got.tobytes() == c.want.tobytes(), _differs(got, c.want)
+    assert got.tobytes() == c.want.tobytes(), differs(got, c.want)
 
 
 @pytest.mark.parametrize("rows", [(10, 30), (0, 1), (53, 54), (64, 70), (63, 65), (20, 20)])
@@ -232,7 +228,7 @@ def test_a_row_range_equals_the_same_rows_of_the_whole_frame(hip_ctx, rows):
     want = np.array(c.fr.lit0)
     want[rows[0]:rows[1]] = c.want[rows[0]:rows[1]]
     got, _ = c.run(hip_ctx, rows=rows)
-    assert got.tobytes() == want.tobytes(), f"rows {rows}: " + _differs(got, want)
+    assert got.tobytes() == want.tobytes(), f"rows {rows}: " + differs(got, want)
     layouts.assert_rows_untouched(c.fr.lit0, got, rows[0], rows[1], what=f"rows {rows}")
     if rows == (10, 30):
         assert c.fr.compose(rows=rows)[0].tobytes() == want.tobytes()
@@ -298,7 +294,7 @@ def test_a_repeated_attempt_blends_once(hip_ctx):
         two = fresh.raster_last_pass()
         print(f"first call {one}, second call {two}; statistics {stats.tolist()}")
         assert one["attempts"] >= 2 and two["attempts"] == 1
-        assert got.tobytes() == c.want.tobytes(), _differs(got, c.want)
+        assert got.tobytes() == c.want.tobytes(), differs(got, c.want)
         assert again.tobytes() == c.want.tobytes() and stats[0] == 1406 and stats[3] == 6 and stats[7] == 3
     finally:
         torch.cuda.synchronize()

@@ -11,6 +11,7 @@ import pytest
 from androidrenderer_amd import _abi, frame, images, mesh, scene
 from tests import util
 from tests import vrsaa_ref as ref
+from tests.host_programs import host_program
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,17 +24,6 @@ def _time_limit():
     faulthandler.cancel_dump_traceback_later()
 
 
-def _host_program(tmp_path):
-    built = os.path.join(ROOT, "tests", "cpp", "host_vrsaa")
-    deps = [built + ".cpp"] + [os.path.join(ROOT, "include", h) for h in ("sah_host.hpp", "sah_hip.h", "sah_vrsaa.h")]
-    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(d) for d in deps):
-        return built
-    exe, libdir = str(tmp_path / "host_vrsaa"), os.path.join(ROOT, "androidrenderer_amd")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "include"), built + ".cpp", "-o", exe, "-L", libdir, "-lsah_hip",
-                           f"-Wl,-rpath,{libdir}"], timeout=600)
-    return exe
-
-
 def test_vrsaa_through_cpp_facade(tmp_path, hip_ctx):
     import torch
     fx = np.load(os.path.join(ROOT, "tests", "golden", "vrsaa_97x61.npz"))
@@ -44,7 +34,7 @@ def test_vrsaa_through_cpp_facade(tmp_path, hip_ctx):
         f.write(np.array(ref.RATES, np.uint32).tobytes())
         f.write(fx["color"].tobytes())
         f.write(fx["depth"].tobytes())
-    subprocess.check_call([_host_program(tmp_path), str(inp), str(outp)], timeout=120)
+    subprocess.check_call([host_program("host_vrsaa", tmp_path), str(inp), str(outp)], timeout=120)
     blob = open(outp, "rb").read()
     sw, sh = (int(v) for v in np.frombuffer(blob[:8], np.uint32))
     assert (sw, sh) == scene.shading_rate_image_extent((W, H), texel) == (13, 8)

@@ -8,9 +8,9 @@ import pytest
 from androidrenderer_amd import _abi, lib, scene
 from tests import util
 from tests import vrsaa_ref as ref
+from tests.support import context_state, differs, Image, side_stream_context
 
 pytestmark = pytest.mark.gpu
-SENTINEL = 0xA5
 FIXTURE = "tests/golden/vrsaa_97x61.npz"
 
 
@@ -25,41 +25,6 @@ def _time_limit():
 def fixture():
     import os
     return np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), FIXTURE))
-
-
-class Image:
-    """A device plane of `bpp`-byte texels with a pitch of its own; bytes that belong to no texel hold SENTINEL."""
-
-    def __init__(self, fmt, w, h, pitch=None, data=None, offset=0):
-        import torch
-        self.bpp = _abi.FORMAT_BPP[fmt]
-        self.w, self.h, self.pitch, self.offset = w, h, (w * self.bpp if pitch is None else pitch), offset
-        host = np.full(self.offset + self.h * self.pitch + 64, SENTINEL, np.uint8)
-        if data is not None:
-            rows = np.ascontiguousarray(data).view(np.uint8).reshape(h, w * self.bpp)
-            host[self.offset:self.offset + h * self.pitch].reshape(h, self.pitch)[:, :w * self.bpp] = rows
-        self.host_in = host.copy()
-        self.t = torch.from_numpy(host).cuda()
-        self.plane = _abi.Plane(self.t.data_ptr() + self.offset, w, h, self.pitch, fmt)
-
-    def bytes(self):
-        return self.t.cpu().numpy()
-
-    def texels(self, dtype):
-        b = self.bytes()[self.offset:self.offset + self.h * self.pitch].reshape(self.h, self.pitch)[:, :self.w * self.bpp]
-        return np.ascontiguousarray(b).view(dtype)
-
-    def padding_intact(self, rows=None):
-        """no byte outside the texels (of `rows`, default all) changed"""
-        b = self.bytes()
-        mask = np.ones(b.shape, bool)
-        body = mask[self.offset:self.offset + self.h * self.pitch].reshape(self.h, self.pitch)
-        r0, r1 = rows if rows is not None else (0, self.h)
-        body[r0:r1, :self.w * self.bpp] = False
-        return bool((b[mask] == self.host_in[mask]).all())
-
-    def unchanged(self):
-        return bool((self.bytes() == self.host_in).all())
 
 
 def _inputs(w, h, seed, specials=True):
@@ -100,14 +65,10 @@ def _rates(ctx, contrast_bits, sri_extent, rates=ref.RATES, num=None, c_pitch=No
     return s.texels(np.uint8)
 
 
-def _differs(got, want):
-    return f"{int((got != want).sum())} of {got.size} values differ, first at {np.argwhere(got != want)[:4].tolist()}"
-
-
 # ---- contrast ---------------------------------------------------------------------------------------------------------------------------
 def test_contrast_fixture_bit_for_bit_and_repeatable(hip_ctx, fixture):
     got = _measure(hip_ctx, fixture["color"], fixture["depth"]).texels(np.uint16).reshape(61, 97, 2)
-    assert np.array_equal(got, fixture["contrast"]), _differs(got, fixture["contrast"])
+    assert np.array_equal(got, fixture["contrast"]), differs(got, fixture["contrast"])
     again = _measure(hip_ctx, fixture["color"], fixture["depth"]).texels(np.uint16).reshape(61, 97, 2)
     assert again.tobytes() == got.tobytes()
 
@@ -118,7 +79,7 @@ def test_contrast_small_extents(hip_ctx, extent):
     color, depth = _inputs(w, h, 7 + w)
     got = _measure(hip_ctx, color, depth).texels(np.uint16).reshape(h, w, 2)
     want = ref.contrast(color, depth)
-    assert np.array_equal(got, want), _differs(got, want)
+    assert np.array_equal(got, want), differs(got, want)
 
 
 @pytest.mark.parametrize("pitches,offsets", [((97 * 4 + 12, 97 * 4 + 20, 97 * 4 + 4), (4, 8, 12)),  # no plane 16-byte aligned
@@ -127,7 +88,7 @@ def test_contrast_small_extents(hip_ctx, extent):
 def test_contrast_pitches_sentinels_and_inputs(hip_ctx, fixture, pitches, offsets):
     out = _measure(hip_ctx, fixture["color"], fixture["depth"], pitches, offsets)  # (asserts the inputs unchanged)
     got = out.texels(np.uint16).reshape(61, 97, 2)
-    assert np.array_equal(got, fixture["contrast"]), _differs(got, fixture["contrast"])
+    assert np.array_equal(got, fixture["contrast"]), differs(got, fixture["contrast"])
     assert out.padding_intact()
 
 
@@ -154,7 +115,7 @@ def test_contrast_all_nan_depth_is_the_luma_term(hip_ctx):
     got = _measure(hip_ctx, color, depth).texels(np.uint16).reshape(h, w, 2)
     with np.errstate(all="ignore"):
         luma_term = (ref.gradients(ref.luma(color)) * np.float32(0.5)).astype(np.float16).view(np.uint16)
-    assert np.array_equal(got, luma_term), _differs(got, luma_term)
+    assert np.array_equal(got, luma_term), differs(got, luma_term)
     assert np.array_equal(got, ref.contrast(color, depth))
 
 
@@ -195,7 +156,7 @@ def _random_contrast(w, h, seed):
 
 def test_shading_rate_fixture(hip_ctx, fixture):
     got = _rates(hip_ctx, fixture["contrast"], (13, 8))
-    assert np.array_equal(got, fixture["shading_rate_image"]), _differs(got, fixture["shading_rate_image"])
+    assert np.array_equal(got, fixture["shading_rate_image"]), differs(got, fixture["shading_rate_image"])
 
 
 @pytest.mark.parametrize("cw,ch,sw,sh,d", [(119, 50, 8, 4, 15),   # blocks reach past the image on both axes
@@ -209,7 +170,7 @@ def test_shading_rate_block_sizes_and_out_of_range_reads(hip_ctx, cw, ch, sw, sh
     contrast[ch - 1, cw - 1] = np.array([2.0, 0.25], np.float16).view(np.uint16)  # the last texel counts where a block reaches it
     got = _rates(hip_ctx, contrast, (sw, sh))
     want = ref.shading_rate_image(contrast, (sw, sh), ref.RATES)
-    assert np.array_equal(got, want), _differs(got, want)
+    assert np.array_equal(got, want), differs(got, want)
     assert len(np.unique(want)) >= 2
 
 
@@ -223,7 +184,7 @@ def test_shading_rate_special_contrast_values(hip_ctx):
     bits = np.ascontiguousarray(contrast).view(np.uint16)
     got = _rates(hip_ctx, bits, (sw, sh))
     want = ref.shading_rate_image(bits, (sw, sh), ref.RATES)
-    assert np.array_equal(got, want), _differs(got, want)
+    assert np.array_equal(got, want), differs(got, want)
     assert want[5, 2] == 10
 
 
@@ -233,7 +194,7 @@ def test_shading_rate_counts(hip_ctx, num):
     contrast = _random_contrast(48, 24, 5)
     got = _rates(hip_ctx, contrast, (12, 6), rates, num)
     want = ref.shading_rate_image(contrast, (12, 6), rates, num_rates=num)
-    assert np.array_equal(got, want), _differs(got, want)
+    assert np.array_equal(got, want), differs(got, want)
     if num < 2:
         assert (got == ref.rate_code(2, 2)).all()  # rates[0] whether the search runs over nothing or over itself
 
@@ -265,11 +226,8 @@ def _chain_images(fixture, color=None, depth=None):
 
 def test_chain_on_a_side_stream_without_host_sync_and_under_capture(fixture):
     import torch
-    s = torch.cuda.Stream()
-    ctx = lib.Context(0)
     params = scene.shading_rate_params((97, 61), (13, 8), ref.RATES)
-    try:
-        ctx.set_stream(s.cuda_stream)
+    with side_stream_context() as (ctx, s):
         c, d, o, r = _chain_images(fixture)
         torch.cuda.synchronize()
         with torch.cuda.stream(s):
@@ -300,9 +258,6 @@ def test_chain_on_a_side_stream_without_host_sync_and_under_capture(fixture):
         assert o.bytes().tobytes() == o2.bytes().tobytes() and r.bytes().tobytes() == r2.bytes().tobytes()
         assert np.array_equal(o.texels(np.uint16).reshape(61, 97, 2), direct_o) and np.array_equal(r.texels(np.uint8), direct_r)
         assert not np.array_equal(direct_o, fixture["contrast"])
-    finally:
-        torch.cuda.synchronize()
-        ctx.close()
 
 
 def test_no_side_effects_on_the_context(hip_ctx, fixture):
@@ -311,7 +266,7 @@ def test_no_side_effects_on_the_context(hip_ctx, fixture):
     f.run_hip(hip_ctx)
 
     def state():
-        return hip_ctx.cache_epoch(), hip_ctx.lighting_dispatch(), hip_ctx.copy_rebuilds()
+        return context_state(hip_ctx)
     before = state()
     c, d, o, r = _chain_images(fixture)
     hip_ctx.vrsaa_measure_aliasing(c.plane, d.plane, o.plane)
